@@ -17,7 +17,9 @@ searches its own batches (the path shards by query: no data-path collective; sca
 rank g builds and searches shard g; every rank searches the SAME batch, one all-gather of the packed
 per-shard top-k (RCCL), then the merge kernel; a step = one batch through search + exchange + merge.
 
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+Rank 0 prints ONE JSON line. A plain run sets up (rows, graph), warms up, times the K steps, writes the last step's results
+if --dump-outputs DIR is given (DIR/ids.npy, dists.npy, counts.npy, stats.npy: what the caller of the timed path receives
+for the last timed batch) and prints the contract fields. Everything else is taken with --full only; the line then carries
   roofline      HBM roofline of the dominant kernel: algorithmic bytes per launch (SURVEY.md 8d:
                 n_dist*d*s + 4*n_adj + d*s + 8*k per query, n_dist = the reference's count of distinct nodes) /
                 mean launch duration from HIP events recorded around the kernel on its stream
@@ -124,7 +126,7 @@ def parse():
     ap.add_argument("--no-partitioned", action="store_true", help="WORLD_SIZE > 1: skip the partitioned sub-record")
     ap.add_argument("--partitioned-timeout", type=int, default=240,
                     help="WORLD_SIZE > 1: seconds the partitioned sub-record (taken after the line is printed) may take per rank")
-    ap.add_argument("--force-partitioned", action="store_true", help="take the partitioned sub-record with one rank too (tests)")
+    ap.add_argument("--force-partitioned", action="store_true", help="with --full: take the partitioned sub-record with one rank too (tests)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--sweep-ef", default="50,100,200,400,800,1600,2048,4096,8192", help="ef values of ef_sweep ('' = skip)")
     ap.add_argument("--no-recall", action="store_true")
@@ -135,6 +137,12 @@ def parse():
                     help="GRANNE_HIP_OPT_VISITED_SLOTS: LDS visited-table slots per walker (0 = auto)")
     ap.add_argument("--reorder", action="store_true",
                     help="apply Granne::reorder (src/index/reorder.rs) to the built index before searching")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (replica mode): steady, sequential and begin/end forms, "
+                         "roofline, recall and the exact scan, CPU baseline and oracle parity, max_search sweep, latency, the "
+                         "sub-records, with N > 1 the partitioned one; the full record goes to bench_extras.json and stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the last timed step returned, as DIR/<name>.npy (float64; distances float32)")
     return ap.parse_args()
 
 
@@ -310,12 +318,13 @@ class Bench:
 
     # ---- one workload on one index: the timed K steps + per-launch events + counters ----------------
     def measure(self, index, queries, dim, esize, nq, ef, k, steps, warmup, group, inflight=1, contract=False, steady_s=0.0,
-                profile_only=False):
+                profile_only=False, lean=False):
         """The K timed steps (K batches of nq fresh queries) handed to the library `group` batches per call
         (granne_hip_search_batches_device: one launch per call) on torch's current stream; or, inflight > 1, one batch per
         call on stream i % inflight (round 3's form). Then, untimed: the grouped launches again between HIP events (the
         dominant kernel's duration), the same steps one batch per call (`sequential`, with the library's own events
-        around every launch), and a counting pass with an exact visited set (the reference's n_dist)."""
+        around every launch), and a counting pass with an exact visited set (the reference's n_dist). `lean`: the timed
+        steps only. `last` holds copies of what the last timed step returned."""
         torch = self.torch
         from granne_amd.index import pointer_array
         n_batches = warmup + steps
@@ -380,6 +389,12 @@ class Bench:
             elapsed = float(t.item())
         if int(status[0].item()) != 0:
             raise RuntimeError("exact-search scratch exhausted during the timed steps")
+        b_last = warmup + steps - 1
+        last = {"ids": ids[b_last].clone(), "dists": dists[b_last].clone(), "counts": counts[b_last].clone(),
+                "stats": stats[b_last].clone()}
+        if lean:
+            return {"elapsed": elapsed, "value_local": steps * nq / elapsed, "group": group, "calls": len(timed_calls),
+                    "inflight": inflight, "slow": int(status[1].item()), "spill": int(status[2].item()), "last": last}
 
         # the same K steps again and again, back to back, until `steady_s` seconds have passed: the K-step window above
         # is a few milliseconds, this one is long enough to trust (same batches, same calls, one synchronisation)
@@ -415,7 +430,8 @@ class Bench:
         slow_n, spill_n = int(status[1].item()), int(status[2].item())  # (of the timed forms of the walk, not of the counting pass)
         if profile_only:
             return {"elapsed": elapsed, "value_local": steps * nq / elapsed, "steady": steady, "group": group,
-                    "calls": len(timed_calls), "inflight": inflight, "group_launch_ms": grp_ms, "slow": slow_n, "spill": spill_n}
+                    "calls": len(timed_calls), "inflight": inflight, "group_launch_ms": grp_ms, "slow": slow_n, "spill": spill_n,
+                    "last": last}
 
         # the same K steps strictly one after the other, ONE batch per call, twice: first bare (the wall clock of K
         # back-to-back launches: what one batch at a time costs, launch gaps included), then with one pair of HIP events
@@ -529,7 +545,7 @@ class Bench:
                                      "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default: 4)")},
                           "note": "one batch per call, granne_hip_search_begin_device / _end_device: up to `depth` calls in flight "
                                   "beside one caller stream (rank-local); depth8 = GRANNE_HIP_OPT_SEARCH_DEPTH 8"},
-            "ids": ids, "dists": dists, "counts": counts, "status": status, "inflight": inflight, "group": group,
+            "ids": ids, "dists": dists, "counts": counts, "status": status, "last": last, "inflight": inflight, "group": group,
             "calls": len(timed_calls), "slow": slow_n, "spill": spill_n,
             "alg_per_launch": alg_per_launch, "achieved": alg_per_launch / (launch_ms * 1e-3) / 1e9, "launch_ms_mean": launch_ms,
             "launch_ms_min": float(np.min(grp_ms)) if grp_ms else float(np.min(step_ms)),
@@ -927,8 +943,10 @@ def run_replica(B, args):
     if rank == 0:
         log("gen %.1fs, gpu build %.1fs, layers %s, index %.2f GB HBM" % (t_gen, t_build, layer_sizes, index.hbm_bytes() / 1e9))
 
+    lean = not (args.full or args.profile_run)
     m = B.measure(index, queries, dim, esize, nq, ef, k, args.steps, args.warmup, group, inflight=args.inflight, contract=True,
-                  steady_s=0.5, profile_only=args.profile_run)
+                  steady_s=0.5, profile_only=args.profile_run, lean=lean)
+    B.outputs = m["last"]
     value = world * args.steps * nq / m["elapsed"]
     if args.profile_run:  # rocprofv3 runs: the trace holds launches of the timed shape only
         return {"metric": "queries/sec (profile run: timed launches only)", "value": round(value, 1), "unit": "queries/s",
@@ -946,11 +964,6 @@ def run_replica(B, args):
         "ms_per_step": round(m["elapsed"] / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
         "inflight_batches": m["inflight"], "batches_per_call": m["group"] if m["inflight"] == 1 else 1, "library_calls": m["calls"],
         "slow_path_queries": m["slow"], "visited_spill_walks": m["spill"],
-        "sequential": {"value": round(args.steps * nq / m["seq_elapsed"], 1),
-                       "ms_per_step": round(m["seq_elapsed"] / args.steps * 1e3, 4),
-                       "note": "same K steps, one stream, one batch PER CALL (rank-local)"},
-        "one_batch_calls_in_flight": m["begin_end"],
-        "steady": m["steady"],
         "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
         "config": {
             "workload": workload_label(n, dim, args.dtype, args.data, nq, ef, k,
@@ -967,12 +980,21 @@ def run_replica(B, args):
                            ("replica x%d; one batch per call, %d batches in flight on HIP streams of the caller, "
                             "GPU_MAX_HW_QUEUES=%s" % (world, m["inflight"], os.environ.get("GPU_MAX_HW_QUEUES"))),
         },
-        "roofline": B.roofline(m, wl_key, value / world, nq),
         "kernel_sources_sha": csrc_sha(),
     }
     if getattr(B, "shared_devices", False):
         out["shared_devices"] = ("LOGIC TEST, not a measurement: %d ranks share %d device(s) over %s (GRANNE_BENCH_BACKEND)"
                                  % (world, torch.cuda.device_count(), B.backend))
+    if lean:  # a plain run: the headline and nothing else
+        return out
+    out.update({
+        "sequential": {"value": round(args.steps * nq / m["seq_elapsed"], 1),
+                       "ms_per_step": round(m["seq_elapsed"] / args.steps * 1e3, 4),
+                       "note": "same K steps, one stream, one batch PER CALL (rank-local)"},
+        "one_batch_calls_in_flight": m["begin_end"],
+        "steady": m["steady"],
+        "roofline": B.roofline(m, wl_key, value / world, nq),
+    })
 
     # ---- the partitioned exchange over RCCL as a sub-record: with ONE rank (--force-partitioned) here, in the line; with
     # N > 1 ranks only after the line is out (main, partitioned_after_the_line) -- a collective that one rank fails to
@@ -988,10 +1010,12 @@ def run_replica(B, args):
 def rank0_plan(world, args):
     """What rank 0 measures after the timed region. Every N: recall@10 of the timed batch and the CPU baseline (the other
     ranks wait meanwhile, without spinning: main) -- the line of an N-GPU run carries `roofline` AND `cpu_baseline` like the
-    one-GPU line. N = 1 only: the max_search sweep, the one-query latency, the other configs as sub-records."""
-    return {"recall": not args.no_recall, "ef_sweep": world == 1 and not args.no_recall and bool(args.sweep_ef),
-            "cpu_baseline": args.cpu_batches > 0, "cpu_thread_sweep": world == 1,
-            "extras": world == 1 and not args.no_extras}
+    one-GPU line. N = 1 only: the max_search sweep, the one-query latency, the other configs as sub-records. Without --full:
+    nothing."""
+    full = bool(args.full)
+    return {"recall": full and not args.no_recall, "ef_sweep": full and world == 1 and not args.no_recall and bool(args.sweep_ef),
+            "cpu_baseline": full and args.cpu_batches > 0, "cpu_thread_sweep": full and world == 1,
+            "extras": full and world == 1 and not args.no_extras}
 
 
 def rank0_after_the_timed_region(B, args, out, index, builder, elements, queries, m, order, value, group):
@@ -1410,6 +1434,7 @@ def partitioned_record(B, args, n, dim, dtype, nq, ef, k, steps, warmup, spg, se
     pick = args.driver if (args.driver in drivers and "value" in drivers[args.driver]) else "torch"
     value, ms_step = drivers[pick]["value"], drivers[pick]["ms_per_step"]  # every rank answers the same queries: the job's rate, not a sum over ranks
     out_ids, out_d = (c_ids, c_d) if (pick == "cabi" and c_ids is not None) else (t_ids, t_d)
+    B.partitioned_outputs = {"ids": out_ids[-1].clone(), "dists": out_d[-1].clone()}  # the last timed step's merged result
 
     # roofline of the dominant kernel: shard 0 of this rank, one launch at a time
     m = B.measure(indexes[0], queries, dim, esize, nq, ef, k, steps, warmup, 1)
@@ -1502,6 +1527,7 @@ def run_partitioned(B, args):
     """BASELINE.json configs[3]/[4] shape: bench.py --mode partitioned [--shards-per-gpu S]."""
     out = partitioned_record(B, args, args.n, args.dim, args.dtype, args.batch, args.ef, args.k, args.steps, args.warmup,
                              max(1, args.shards_per_gpu), seed_base=SEED + 100)
+    B.outputs = B.partitioned_outputs
     out["vs_baseline"] = None
     out["kernel_sources_sha"] = csrc_sha()
     return out
@@ -1668,6 +1694,29 @@ def compact_line(out, extras_path=None):
     return json.dumps(line, allow_nan=False)
 
 
+DUMP_LIMIT = 60 << 20  # bytes of --dump-outputs in all (64 MB with room for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array; distances as float32,
+    ids and counters as float64 (exact: ids < 2^53). One row per query; beyond DUMP_LIMIT bytes the same fixed, seeded
+    sample of rows from every array, and their row numbers as sampled_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    rows = min(a.shape[0] for a in host.values())
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in host.values())
+    if rows * row_bytes > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(SEED).choice(rows, DUMP_LIMIT // (row_bytes + 8), replace=False))
+        host = {name: a[keep] for name, a in host.items()}
+        host["sampled_rows"] = keep.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs of the last timed step: %s in %s" % (", ".join("%s %s" % (n, a.shape) for n, a in host.items()), path))
+
+
 def write_extras(out):
     """The full record: next to the script, under gpurun_out/ when that exists (it travels back from a GPU box), and on stderr."""
     text = json.dumps(_finite(out), allow_nan=False)
@@ -1759,15 +1808,18 @@ def main():
     os.dup2(2, 1)
     B = Bench(args)
     out = run_partitioned(B, args) if args.mode == "partitioned" else run_replica(B, args)
+    plain = args.mode == "replica" and not (args.full or args.profile_run)
     if B.rank == 0:
-        extras = write_extras(out)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, B.outputs)
+        extras = None if plain else write_extras(out)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(_finite(out), allow_nan=False) if args.full_line else compact_line(out, extras), flush=True)
         os.dup2(2, 1)
     if B.use_dist and B.world > 1:
         wait_for_rank0(B, "granne_bench_line_out")  # (rank 0 took recall + the CPU baseline after the timed region)
-    if args.mode == "replica" and B.world > 1 and not args.no_partitioned:
+    if args.mode == "replica" and B.world > 1 and args.full and not args.no_partitioned:
         partitioned_after_the_line(B, args, out)
     if B.use_dist:
         B.dist.barrier()

@@ -153,7 +153,7 @@ def test_the_line_of_an_n_gpu_run_carries_roofline_and_cpu_baseline():
     import numpy as np
     import torch
     saved = sys.argv
-    sys.argv = ["bench.py", "--gpus", "2"]
+    sys.argv = ["bench.py", "--gpus", "2", "--full"]
     try:
         args = bench.parse()
     finally:
@@ -212,6 +212,51 @@ def test_the_line_of_an_n_gpu_run_carries_roofline_and_cpu_baseline():
         assert key in line["roofline"], key
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in line["cpu_baseline"], key
+
+
+def test_a_plain_run_takes_nothing_after_the_timed_region():
+    """Without --full a run sets up, warms up, times the K steps and prints the line: rank 0 plans no recall, no CPU
+    baseline, no sweep and no sub-record, whatever N."""
+    saved = sys.argv
+    sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    try:
+        args = bench.parse()
+    finally:
+        sys.argv = saved
+    assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    for world in (1, 2, 8):
+        assert not any(bench.rank0_plan(world, args).values()), world
+
+
+def test_dump_outputs_writes_float_arrays_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per returned array, float32 distances, float64 ids and counters (ids exact), and beyond
+    DUMP_LIMIT the same seeded sample of rows from every array, the same from run to run."""
+    import numpy as np
+    import torch
+    nq, k = 300, 10
+    ids = torch.arange(nq * k, dtype=torch.int64).reshape(nq, k) + (1 << 40)
+    dists = torch.linspace(0, 1, nq * k, dtype=torch.float32).reshape(nq, k)
+    counts = torch.full((nq,), k, dtype=torch.int32)
+    stats = torch.arange(nq * 3, dtype=torch.int64).reshape(nq, 3)
+    arrays = {"ids": ids, "dists": dists, "counts": counts, "stats": stats}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(n + ".npy" for n in arrays)
+    assert got["dists"].dtype == np.float32 and got["dists"].tobytes() == dists.numpy().tobytes()
+    for n in ("ids", "counts", "stats"):
+        assert got[n].dtype == np.float64 and (got[n] == arrays[n].numpy()).all(), n
+    limit = 40 * (k * 8 + k * 4 + 8 + 3 * 8)  # room for 40 rows
+    monkeypatch.setattr(bench, "DUMP_LIMIT", limit)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    rows = np.load(tmp_path / "a" / "sampled_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 40 and (np.diff(rows) > 0).all()
+    total = 0
+    for n in arrays:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.tobytes() == b.tobytes() and a.tobytes() == got[n][rows].tobytes(), n
+        total += a.nbytes
+    assert total + rows.nbytes <= limit
 
 
 def test_the_secondary_generators_are_named_in_their_labels():

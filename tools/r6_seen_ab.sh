@@ -10,7 +10,7 @@ for data in "${CASES[@]}"; do
   set -- $data
   for seen in off 2048; do
     if [ "$seen" = "off" ]; then export GRANNE_HIP_SEEN_MIN=1000000000; else export GRANNE_HIP_SEEN_MIN=$seen; fi
-    python bench.py --data $1 --dtype $2 --ef $3 --dim ${4:-100} --elements ${SEEN_AB_N:-10000000} --steps 20 --warmup 3 --no-extras --cpu-batches 0 --no-recall --c5-elements 0 --build-max-search 50 --build-reinsert 0 2>/dev/null | python -c "
+    python bench.py --full --data $1 --dtype $2 --ef $3 --dim ${4:-100} --elements ${SEEN_AB_N:-10000000} --steps 20 --warmup 3 --no-extras --cpu-batches 0 --no-recall --c5-elements 0 --build-max-search 50 --build-reinsert 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']
