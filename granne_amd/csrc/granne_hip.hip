@@ -73,7 +73,7 @@ extern "C" int granne_hip_device_count(int* out_count) {
 
 // experiment knobs, read once per process
 struct EnvKnobs {
-    int visited_cap = 0, front_eighths = 0, maxc = 0, lds_pad = 0, visited = 0, tail_blocks = -1, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1;
+    int visited_cap = 0, front_eighths = 0, maxc = 0, lds_pad = 0, visited = 0, tail_blocks = -1, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1, sketch = 1;
     EnvKnobs() {
         auto geti = [](const char* name, int dflt) {
             const char* e = getenv(name);
@@ -89,6 +89,7 @@ struct EnvKnobs {
         bf_b16 = geti("GRANNE_HIP_BF_B16", 1); // 0: the exact scan of f32 rows scores on the f32 matrix path (round 5's: 5 x slower, scores to the last bits)
         seen_min = geti("GRANNE_HIP_SEEN_MIN", -1); // launches of at least this many walks skip revisits before their rows are fetched (-1: default)
         touch_max = geti("GRANNE_HIP_TOUCH_MAX", -1); // launches of up to this many queries touch rows ahead (-1: default)
+        sketch = geti("GRANNE_HIP_SKETCH", 1); // 0: no index makes row sketches, and no search uses them (A/B of GRANNE_HIP_OPT_SKETCH)
     }
 };
 static const EnvKnobs& knobs() {
@@ -155,11 +156,14 @@ struct granne_hip_index {
     uint64_t opt_visited16_lg = 0;   // 0 auto, else log2(buckets)
     uint64_t opt_inline_tails = 1;   // GRANNE_HIP_OPT_INLINE_TAILS: keep LayerDev::adjx for the shapes that have one
     uint64_t opt_seen_min = 2048;    // GRANNE_HIP_OPT_SEEN_MIN: launches of at least this many walks skip revisits before their rows are fetched
+    uint64_t opt_sketch = 1;         // GRANNE_HIP_OPT_SKETCH: the register walker rejects candidates by their row sketch (when d_sketch exists)
     std::atomic<uint64_t> last_slow_count{0};
     std::atomic<uint64_t> last_walker{0}; // GRANNE_HIP_OPT_LAST_WALKER
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
     float* d_inv_norm = nullptr;
+    // f32 rows of the sketched shapes: one SKETCH_LINE per row (search_kernel.h), made with the index, or null
+    uint8_t* d_sketch = nullptr;
     // host-pointer searches (granne_hip_search / _search_batch): a stream, a device buffer and a pinned
     // staging buffer per concurrent caller, kept for the life of the index -- the reference's API is one
     // query per call (src/index/mod.rs:140-150), so a call must not pay stream creation and hipMalloc
@@ -261,6 +265,7 @@ static void destroy_index(granne_hip_index* ix) {
     }
     if (ix->d_layers) (void)hipFree(ix->d_layers);
     if (ix->d_inv_norm) (void)hipFree(ix->d_inv_norm);
+    if (ix->d_sketch) (void)hipFree(ix->d_sketch);
     for (auto* c : ix->call_free) {
         if (c->stream) (void)hipStreamDestroy(c->stream);
         if (c->d_buf) (void)hipFree(c->d_buf);
@@ -360,12 +365,41 @@ static int make_scan_norms(granne_hip_index* ix, hipStream_t s) {
     return GRANNE_HIP_OK;
 }
 
+// The register walker's row sketches (search_kernel.h SKETCH_LINE, walk_fast.h FastWalker::sketch_rejects): made here
+// (and again after reorder: the rows moved), never inside a search, so that searches stay capturable. Like LayerDev::adjx
+// they are an accelerator, not part of the index: without room for them the index is made without (searches read every
+// row, as they would with GRANNE_HIP_OPT_SKETCH = 0), and the room is judged with headroom left for what searches allocate.
+static int make_row_sketch(granne_hip_index* ix, hipStream_t s) {
+    if (ix->dtype != GRANNE_HIP_F32 || !sketch_dim_ok(ix->dim) || ix->n_elements == 0 || !knobs().sketch) return GRANNE_HIP_OK;
+    const uint64_t n = ix->n_elements;
+    const size_t bytes = (size_t)n * SKETCH_LINE;
+    if (!ix->d_sketch) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+            (void)hipGetLastError();
+            return GRANNE_HIP_OK;
+        }
+        if ((uint64_t)free_b < (uint64_t)bytes + total_b / 32u) return GRANNE_HIP_OK;
+        if (hipMalloc((void**)&ix->d_sketch, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ix->d_sketch = nullptr;
+            return GRANNE_HIP_OK;
+        }
+        ix->hbm_bytes += bytes;
+    }
+    hipLaunchKernelGGL(row_sketch_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ix->d_elements, n, ix->row_stride, ix->dim,
+                       ix->d_sketch);
+    HIP_TRY(hipGetLastError());
+    return GRANNE_HIP_OK; // (finish_layers synchronises s before the index is handed out)
+}
+
 static int finish_layers(granne_hip_index* ix, hipStream_t s) {
     std::vector<LayerDev> h(ix->layers.size());
     ix->max_dev_width = 32;
     {
         int r = make_inline_tails(ix, s);
         if (r == 0) r = make_scan_norms(ix, s);
+        if (r == 0) r = make_row_sketch(ix, s);
         if (r) return r;
     }
     // rows that name a neighbor twice (LAYER_TWIN_ROWS, walk_fast.h): looked for once, here, on the device rows
@@ -620,6 +654,16 @@ extern "C" int granne_hip_index_get_element(const granne_hip_index* ix, uint64_t
     return GRANNE_HIP_OK;
 }
 
+extern "C" int granne_hip_index_get_sketch(const granne_hip_index* ix, uint64_t first, uint64_t count, void* out) {
+    if (!ix || (!out && count)) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
+    if (!ix->d_sketch) return fail(GRANNE_HIP_ERR_INVALID, "the index holds no row sketches");
+    if (first > ix->n_elements || count > ix->n_elements - first) return fail(GRANNE_HIP_ERR_INVALID, "rows out of range");
+    if (count == 0) return GRANNE_HIP_OK;
+    DeviceGuard g(ix->device);
+    HIP_TRY(hipMemcpy(out, ix->d_sketch + first * SKETCH_LINE, (size_t)count * SKETCH_LINE, hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
+}
+
 extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uint64_t value) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
     switch (option) {
@@ -672,6 +716,10 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
     case GRANNE_HIP_OPT_SEEN_MIN:
         ix->opt_seen_min = value > 0xFFFFFFFFull ? 0xFFFFFFFFull : value;
         return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_SKETCH:
+        if (value > 1) return fail(GRANNE_HIP_ERR_INVALID, "the sketch option is 0 or 1");
+        ix->opt_sketch = value;
+        return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_VISITED16_LG: // (retired with the bucket tables it sized: accepted, ignored)
         if (value > 12) return fail(GRANNE_HIP_ERR_INVALID, "value out of range");
         ix->opt_visited16_lg = value;
@@ -695,6 +743,7 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     case GRANNE_HIP_OPT_SEARCH_DEPTH: *value = ix->depth; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_INLINE_TAILS: *value = (!ix->layers.empty() && ix->layers.back().d_adjx) ? 1 : 0; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SEEN_MIN: *value = ix->opt_seen_min; return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_SKETCH: *value = (ix->opt_sketch && ix->d_sketch && knobs().sketch) ? 1 : 0; return GRANNE_HIP_OK;
     default: return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -720,6 +769,7 @@ struct SearchTarget {
     uint64_t opt_visited_slots, opt_force_slow, opt_slow_slots, opt_slow_blocks, opt_overflow_slots;
     uint64_t opt_visited16 = 0, opt_visited16_lg = 0;
     uint64_t opt_seen_min = 0xFFFFFFFFull; // (a builder's searches: never -- its layers change between launches, its batches are its own)
+    const uint8_t* d_sketch = nullptr;     // row sketches the register walker may use (an index's, when GRANNE_HIP_OPT_SKETCH is on)
     ScratchCache* scratch; // search_launch's per-stream scratch blocks
     std::atomic<uint64_t>* last_walker = nullptr; // which kernel the last launch took (an index's read-only option)
 };
@@ -744,6 +794,7 @@ static SearchTarget target_of(const granne_hip_index* ix) {
     T.opt_visited16 = ix->opt_visited16;
     T.opt_visited16_lg = ix->opt_visited16_lg;
     T.opt_seen_min = ix->opt_seen_min;
+    T.d_sketch = (ix->opt_sketch && knobs().sketch) ? ix->d_sketch : nullptr;
     T.scratch = &const_cast<granne_hip_index*>(ix)->scratch;
     T.last_walker = &const_cast<granne_hip_index*>(ix)->last_walker;
     return T;
@@ -1174,6 +1225,7 @@ static int search_launch(const SearchTarget* ix, const void* d_queries, int64_t 
     p.slow_list = (uint32_t*)(scratch + off_list);
     p.force_slow = 0;
     p.spec = 1;
+    p.sketch = ix->d_sketch;
     p.ovf.tables = (uint32_t*)(scratch + off_ovf);
     p.ovf.state = (uint32_t*)(scratch + SCRATCH_STATE_OFF);
     p.ovf.slots = ovf_slots;

@@ -46,6 +46,18 @@ struct LayerDev {
 };
 constexpr uint32_t LAYER_TWIN_ROWS = 1u; // some row names a neighbor twice (no builder of the reference makes such rows; a foreign file may hold them)
 
+// Row sketches (walk_fast.h, FastWalker::sketch_rejects): one 128-byte line per f32 row of the shapes whose walker reads
+// them (sketch_dim_ok), made with the index (row_sketch_kernel, util_kernels.h):
+//   bytes [0, dim)       c_i = rint(x_i / s) clamped to [-127, 127], s = (float)(max |x_i| / 127)   (s = 0: every c_i = 0)
+//   bytes [dim, 112)     zero
+//   112: s   116: R >= |x - s c|   120: X >= |s c|   124: N >= |x|   (f32; R, X, N: the smallest float whose square is at
+//                                                                       least the double sum of squares times 1 + 2^-40)
+// A row with a component that is not finite: codes 0, s = 0, R = X = N = +inf -- its bound is +inf, it is never rejected.
+constexpr uint32_t SKETCH_LINE = 128u;
+constexpr uint32_t SKETCH_META = 112u; // byte offset of s, R, X, N
+constexpr uint32_t SKETCH_MAX_DIM = 112u;
+__host__ __device__ constexpr bool sketch_dim_ok(uint32_t dim) { return dim == 100u; } // the unrolled 100-d walker (XT)
+
 // one batch of a launch that serves several (SearchParams::batch)
 constexpr uint32_t MAX_LAUNCH_BATCHES = 32;
 struct BatchIO {
@@ -84,6 +96,7 @@ struct SearchParams {
     uint32_t* slow_list;     // [nq]
     uint32_t force_slow;
     uint32_t spec;           // 1: speculative adjacency prefetch (narrow layers)
+    const uint8_t* sketch;   // [n][SKETCH_LINE] row sketches the register walker rejects candidates by before it reads their rows, or null
     OverflowPool ovf;        // global overflow tables of the visited sets (wave_prims.h)
     // trail mode (Granne::reorder, src/index/reorder.rs:180-208): instead of a search, walk layers
     // 0..trail_layers-1 with max_search 1, each from node 0, and record the ids found

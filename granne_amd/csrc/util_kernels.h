@@ -3,8 +3,67 @@
 #pragma once
 
 #include "dist.h"
+#include "search_kernel.h"
 
 namespace granne_hip {
+
+// The smallest float f with f * f >= S (1 + 2^-40) (both sides in double, where f * f is exact): an upper bound of the
+// norm whose sum of squares S is (the double sum of a row's squares is within 2^-46 of the exact one), and a canonical
+// one -- tests/test_sketch_bound.py makes the same bytes on the host. +inf beyond the float range (or S not finite).
+__device__ __forceinline__ float sketch_ceil_sqrt(double S) {
+    const double T = S * (1.0 + 0x1p-40);
+    if (!(T <= (double)3.4028234663852886e38 * (double)3.4028234663852886e38)) return __builtin_inff();
+    float f = (float)__builtin_sqrt(T);
+    while ((double)f * (double)f < T) f = __uint_as_float(__float_as_uint(f) + 1u);
+    while (f > 0.0f) {
+        const float g = __uint_as_float(__float_as_uint(f) - 1u);
+        if ((double)g * (double)g < T) break;
+        f = g;
+    }
+    return f;
+}
+
+// One row sketch per thread (layout: SKETCH_LINE, search_kernel.h). dim <= SKETCH_MAX_DIM.
+__global__ void row_sketch_kernel(const uint8_t* __restrict__ elements, uint64_t n, uint32_t row_stride, uint32_t dim,
+                                  uint8_t* __restrict__ out) {
+    for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n; row += (uint64_t)gridDim.x * blockDim.x) {
+        const float* x = reinterpret_cast<const float*>(elements + row * row_stride);
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + row * SKETCH_LINE);
+        float m = 0.0f;
+        bool finite = true;
+        for (uint32_t i = 0; i < dim; ++i) {
+            const float a = __builtin_fabsf(x[i]);
+            finite = finite && a <= 3.4028234663852886e38f;
+            m = a > m ? a : m;
+        }
+        const float s = finite ? (float)((double)m / 127.0) : 0.0f;
+        double se = 0.0, sc = 0.0, sx = 0.0;
+        for (uint32_t j = 0; j < SKETCH_META / 4u; ++j) {
+            uint32_t w = 0;
+            for (uint32_t t = 0; t < 4u; ++t) {
+                const uint32_t i = j * 4u + t;
+                if (i >= dim) break;
+                const double xd = (double)x[i];
+                double c = 0.0;
+                if (s > 0.0f) {
+                    c = __builtin_rint(xd / (double)s);
+                    c = c < -127.0 ? -127.0 : (c > 127.0 ? 127.0 : c);
+                }
+                const double pc = (double)s * c, e = xd - pc;
+                se = se + e * e;
+                sc = sc + pc * pc;
+                sx = sx + xd * xd;
+                w |= ((uint32_t)(int32_t)c & 0xFFu) << (8u * t);
+            }
+            o[j] = w;
+        }
+        const float inf = __builtin_inff();
+        o[SKETCH_META / 4u + 0u] = __float_as_uint(s);
+        o[SKETCH_META / 4u + 1u] = __float_as_uint(finite ? sketch_ceil_sqrt(se) : inf);
+        o[SKETCH_META / 4u + 2u] = __float_as_uint(finite ? sketch_ceil_sqrt(sc) : inf);
+        o[SKETCH_META / 4u + 3u] = __float_as_uint(finite ? sketch_ceil_sqrt(sx) : inf);
+    }
+}
 
 // dense [n][src_bytes] -> padded [n][dst_bytes] (zero fill); one 16-byte unit per thread
 __global__ void relayout_rows_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t n,

@@ -296,6 +296,13 @@ struct FastWalker {
     // bound by bandwidth, not by one wave's latency.
     static constexpr bool SEEN = V16 == 5;
     static_assert(!WIDE || V16 == 3, "layers of 64 ids: walked without a visited set only");
+    // SK: the launches of many walks (SEEN) on the 100-d rows reject a neighbor by its row sketch (SearchParams::sketch) when
+    // that alone proves its distance beyond theta -- its row is then not read (sketch_rejects).
+    static constexpr bool SK = SEEN && XT && sketch_dim_ok((uint32_t)DIM);
+    // SK: the query's sketch -- codes c (sk_qc, LDS), scale s, R >= |q - s c|, N >= |q|
+    int8_t* sk_qc; // (LDS: where the visited table of the walks that keep one is)
+    float sk_s, sk_r, sk_n;
+    bool sk_on; // the query is finite (else no neighbor is rejected by its sketch)
     static_assert(V16 == 0 || V16 == 3 || V16 == 4 || V16 == 5, "the exact 32-bit table, or no visited set (4: + rows touched ahead, 5: + revisits skipped before their rows are fetched)");
     typename std::conditional<V16 == 0, VisitedSet, VisitedNone>::type vis;
     List L;
@@ -330,6 +337,9 @@ struct FastWalker {
         st.n_dist = st.n_expand = st.n_adj = 0;
         bail = false;
         sy = 0.0f;
+        sk_qc = reinterpret_cast<int8_t*>(vis_tab);
+        sk_s = sk_r = sk_n = 0.0f;
+        sk_on = false;
         vis.init_walker();
     }
 
@@ -354,6 +364,7 @@ struct FastWalker {
                 for (uint32_t i = lane; i < (uint32_t)DIM; i += 64) l[i] = q[i];
                 __syncthreads();
             }
+            if constexpr (SK) load_query_sketch(q);
         } else {
             const int8_t* q = reinterpret_cast<const int8_t*>(query_io(p, qi).q);
             int8_t* l = reinterpret_cast<int8_t*>(lds_q);
@@ -371,6 +382,41 @@ struct FastWalker {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) qi8[b * 4 + k] = *reinterpret_cast<const uint4*>(lds_q + b * 128u + h * 64u + k * 16u);
         }
+    }
+
+    // SK: the query's sketch. Lane l takes components l and l + 64; the codes go to LDS (sk_qc, SKETCH_LINE bytes, zero past
+    // the dim), s, R and N to scalar registers. Any codes give a sound bound -- R and N are measured from the ones taken;
+    // the margins (x (1 + 2^-8), + 2^-58) cover the f32 sums in any order, the square root and underflow of the squares
+    // ("Row sketches").
+    __device__ __forceinline__ void load_query_sketch(const float* q) {
+        static_assert(DIM >= 64 && DIM <= (int)SKETCH_MAX_DIM, "two components per lane");
+        const float v0 = q[lane];
+        const float v1 = lane + 64u < (uint32_t)DIM ? q[lane + 64u] : 0.0f;
+        const float a0 = __builtin_fabsf(v0), a1 = __builtin_fabsf(v1);
+        const bool fin = wave_ballot(!(a0 <= 3.4028234663852886e38f && a1 <= 3.4028234663852886e38f)) == 0;
+        float m = a0 > a1 ? a0 : a1;
+        for (int o = 32; o > 0; o >>= 1) {
+            const float t = __shfl_xor(m, o, 64);
+            m = t > m ? t : m;
+        }
+        const float s = m / 127.0f;
+        const float inv = m > 0.0f ? 127.0f / m : 0.0f;
+        float c0 = __builtin_rintf(v0 * inv), c1 = __builtin_rintf(v1 * inv);
+        c0 = c0 < -127.0f ? -127.0f : (c0 > 127.0f ? 127.0f : c0);
+        c1 = c1 < -127.0f ? -127.0f : (c1 > 127.0f ? 127.0f : c1);
+        const float e0 = __builtin_fmaf(-s, c0, v0), e1 = __builtin_fmaf(-s, c1, v1);
+        float ee = __builtin_fmaf(e1, e1, e0 * e0), nn = __builtin_fmaf(v1, v1, v0 * v0);
+        for (int o = 32; o > 0; o >>= 1) {
+            ee += __shfl_xor(ee, o, 64);
+            nn += __shfl_xor(nn, o, 64);
+        }
+        sk_qc[lane] = (int8_t)(int)c0;
+        sk_qc[lane + 64u] = (int8_t)(int)c1; // (v1 = 0 past the dim: code 0)
+        asm volatile("" ::: "memory"); // one wave: LDS executes its accesses in program order
+        sk_s = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s)));
+        sk_r = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_sqrtf(ee) * (1.0f + 0x1p-8f) + 0x1p-58f)));
+        sk_n = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_sqrtf(nn) * (1.0f + 0x1p-8f) + 0x1p-58f)));
+        sk_on = fin;
     }
 
     // The element rows of one expansion in flight: lane (R,h) holds half h of row R.
@@ -431,6 +477,42 @@ struct FastWalker {
                 for (int k = 0; k < 4; ++k) rr.x[b * 4 + k] = *reinterpret_cast<const uint4*>(e + b * 128 + k * 16);
         }
         asm volatile("" ::: "memory"); // the loads are issued here, whatever follows runs under them
+    }
+
+    // SK, lanes of go (both of a pair, theta < +inf): the pairs (both lanes) whose neighbor the row sketch proves to be
+    // beyond theta. The sketch line lands where the row's first chunk will (rr.v[0]: no registers of its own); a rejected
+    // pair's row is not read and its stale registers are never looked at. With q~ = s_q c_q, x~ = s_x c_x:
+    //   q.x = q~.x~ + (q - q~).x~ + q.(x - x~) <= s_q s_x ip + R_q X + N_q R_x,  ip = c_q.c_x exact in i32 (v_dot4_i32_i8);
+    // U adds the f32 error of the walker's own dot (39 roundings per term: < 2^-18.7 N_q N_x) and of U's own operations;
+    // U >= the walker's f32 dot r, so LB = 1 - U <= 1 - r (rounding is monotone) and LB > theta proves d > theta: the
+    // candidate filter_mask would have dropped. Ties and NaN (a comparison that is false) take the exact path; so does a
+    // pair whose N_q N_x reaches 2^100 (no overflow can occur below). Proof: DESIGN.md, "Row sketches".
+    __device__ __forceinline__ uint64_t sketch_rejects(const uint32_t nb, const bool go, RowRegs& rr) {
+        if (go) {
+            const uint8_t* line = p.sketch + (size_t)nb * SKETCH_LINE + h * 64u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rr.v[0][k] = *reinterpret_cast<const float4*>(line + k * 16);
+        }
+        asm volatile("" ::: "memory");
+        int ip = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint4 qq = *reinterpret_cast<const uint4*>(sk_qc + h * 64u + k * 16);
+            ip = dot4_i8(__float_as_uint(rr.v[0][k].x), qq.x, ip);
+            ip = dot4_i8(__float_as_uint(rr.v[0][k].y), qq.y, ip);
+            ip = dot4_i8(__float_as_uint(rr.v[0][k].z), qq.z, ip);
+            ip = dot4_i8(__float_as_uint(rr.v[0][k].w), qq.w, ip);
+        }
+        ip += pair_swap(ip);
+        static_assert(SKETCH_META == 64u + 48u, "s, R, X, N: the last 16 bytes of the odd lane's half");
+        const float sx = rr.v[0][3].x, rx = rr.v[0][3].y, xx = rr.v[0][3].z, nx = rr.v[0][3].w;
+        const float t = (sk_s * sx) * (float)ip;
+        const float nqnx = sk_n * nx;
+        const float b = (sk_r * xx + sk_n * rx) + nqnx * 0x1p-17f;
+        const float U = t + ((__builtin_fabsf(t) * 0x1p-20f + b * 1.0001f) + 0x1p-20f);
+        const float lb = 1.0f - U;
+        const uint64_t rm = wave_ballot(go && h != 0u && nqnx < 0x1p100f && lb > __uint_as_float(theta));
+        return rm | (rm >> 1);
     }
 
     // Distances of the rows in rr to the query: valid in ODD lanes.
@@ -1183,6 +1265,7 @@ struct FastWalker {
             const uint32_t nvalid = unused ? ((uint32_t)__builtin_ctzll(unused) >> 1) : 32u;
             st.n_adj += nvalid;
             [[maybe_unused]] uint64_t seenm = 0; // SEEN: the pairs whose id the walk has evaluated before (both lanes of a pair)
+            [[maybe_unused]] uint64_t skipm = 0; // SK: the pairs (both lanes) the row sketch rejected -- evaluated, no candidate
             if constexpr (SEEN) {
                 const bool seen = vcache[vcache_slot(nb)] == nb; // (the entry point is in the cache; UNUSED never is)
                 seenm = wave_ballot(seen);
@@ -1192,12 +1275,21 @@ struct FastWalker {
                     const uint64_t newm = wave_ballot(!seen && nb != ID_EMPTY);
                     const uint32_t fill = newm ? readlane32(nb, (uint32_t)__builtin_ctzll(newm)) : xid;
                     issue_rows((!seen && nb != ID_EMPTY) ? nb : fill, rr);
-                } else if (!seen && nb != ID_EMPTY) { // rows of new ids only: a revisit's -- and an empty pair's -- loads are not issued
-                    const uint8_t* tails = nullptr;
-                    if constexpr (XT) {
-                        if (adjx) tails = adjx + (size_t)xid * Ly.adjx_stride + 128u + R * XTAILB;
+                } else {
+                    bool go = !seen && nb != ID_EMPTY; // rows of new ids only: a revisit's -- and an empty pair's -- loads are not issued
+                    if constexpr (SK) {
+                        if (p.sketch && sk_on && theta < 0x7F800000u) { // (theta finite: the list holds max_search entries)
+                            skipm = sketch_rejects(nb, go, rr);
+                            go = go && ((skipm >> lane) & 1ull) == 0ull;
+                        }
                     }
-                    issue_rows(nb, rr, tails);
+                    if (go) {
+                        const uint8_t* tails = nullptr;
+                        if constexpr (XT) {
+                            if (adjx) tails = adjx + (size_t)xid * Ly.adjx_stride + 128u + R * XTAILB;
+                        }
+                        issue_rows(nb, rr, tails);
+                    }
                 }
             } else {
                 // pairs past the row's end re-read its first neighbor (the same lines as pair 0: no traffic of their own; an
@@ -1267,6 +1359,7 @@ struct FastWalker {
             const uint32_t dbits = __float_as_uint(d);
             uint64_t candm = fm << 1; // odd lanes whose even partner holds a new id
             if constexpr (NOVIS) candm &= ~wave_ballot(cached == nb); // entered the list before: visited (a pair past the row's end is no candidate anyway)
+            if constexpr (SK) candm &= ~skipm;
             uint64_t passm = filter_mask(candm, dbits, ef);
             PT_ADD(6, (uint32_t)__popcll(passm));
             PT_MARK(10); // cache look-up, filter
@@ -1494,7 +1587,9 @@ __host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t d
     const bool lng = walk_list_is_long((int)S, wide);
     // [query][the list's image][lists of up to 17 slots: the cache of entered ids][visited]
     // (lists beyond 1024 keys: M's image, then F's of 128 keys)
-    return fast_query_bytes(i8, gen, dim, row_bytes, S) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + (seen ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS) * 4u + visited_slots * 4u;
+    // (+ the launches that skip revisits on the sketched shapes: the query's sketch codes where the visited table would be)
+    const uint32_t sk = (seen && !i8 && !gen && !wide && sketch_dim_ok(dim)) ? SKETCH_LINE : 0u;
+    return fast_query_bytes(i8, gen, dim, row_bytes, S) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + (seen ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS) * 4u + visited_slots * 4u + sk;
 }
 
 } // namespace granne_hip

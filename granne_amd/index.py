@@ -210,6 +210,14 @@ class Granne:
     def hbm_bytes(self):
         return int(lib().granne_hip_index_hbm_bytes(self._h))
 
+    def get_sketch(self, first=0, count=None):
+        """The row sketches of OPT_SKETCH (uint8 [count][128]), or None when the index holds none."""
+        count = len(self) - first if count is None else count
+        out = np.empty((count, 128), np.uint8)
+        if lib().granne_hip_index_get_sketch(self._h, first, count, _p(out)) != 0:
+            return None
+        return out
+
     # ---- reorder (src/index/reorder.rs) --------------------------------------------------------------
     def reorder(self):
         """Granne::reorder: places similar elements closer together, in place. Returns the permutation

@@ -106,6 +106,9 @@ int granne_hip_index_get_neighbors(const granne_hip_index* index, uint64_t node,
                                    uint32_t* out_ids, uint32_t cap, uint32_t* out_count);
 /* Granne::get_element (src/index/mod.rs:153-155): copies dim scalars of element `idx`. */
 int granne_hip_index_get_element(const granne_hip_index* index, uint64_t idx, void* out);
+/* The row sketches of GRANNE_HIP_OPT_SKETCH: copies the 128-byte lines of elements first .. first + count - 1 to out.
+ * GRANNE_HIP_ERR_INVALID when the index holds none (get_option(GRANNE_HIP_OPT_SKETCH) says whether searches use them). */
+int granne_hip_index_get_sketch(const granne_hip_index* index, uint64_t first, uint64_t count, void* out);
 
 /* ---- search -----------------------------------------------------------------------------------
  * granne_hip_search_batch: `nq` independent `Granne::search(&query, max_search, num_neighbors)`
@@ -515,7 +518,7 @@ enum {
                                          (re)makes or frees the copy: not while a search of the index is running. An index
                                          whose copy does not fit in HBM is made without it (no error).
                                          get_option returns 1 only when the index actually holds the copy */
-    GRANNE_HIP_OPT_SEEN_MIN = 11      /* f32 walks (every dim) of max_search up to 252 on layers of 32 ids: launches of at least this many
+    GRANNE_HIP_OPT_SEEN_MIN = 11,     /* f32 walks (every dim) of max_search up to 252 on layers of 32 ids: launches of at least this many
                                          walks (queries x batches) consult a cache of the ids the walk has EVALUATED before
                                          they fetch a neighbor's row, and skip a hit -- the reference's `!visited.insert(n)`
                                          (src/index/mod.rs:1026) for the recent part of the visited set; a miss means nothing
@@ -523,6 +526,14 @@ enum {
                                          rows of revisits (3.6 % of a walk's rows on i.i.d.-uniform data, 40-70 % on clustered
                                          data) and costs an LDS round trip before the row loads, which only pays where the
                                          launch is bound by bandwidth: [2048]; 0 = every launch, 0xFFFFFFFF = never */
+    GRANNE_HIP_OPT_SKETCH = 12        /* f32 indexes of 100 dimensions keep a 128-byte sketch of every row (int8 codes, scale and
+                                         norm bounds: 1.28 GB at 10M rows) from which the register walker bounds a neighbor's
+                                         distance from below; a neighbor whose bound is already beyond the list's max_search-th
+                                         distance is rejected without its row being read (it would have been rejected after).
+                                         Results are the same bits. 1 = use it [default], 0 = read every row. The sketch is
+                                         made with the index (and again after reorder), not when this is set; an index without
+                                         room for it, or made with GRANNE_HIP_SKETCH=0 in the environment, has none.
+                                         get_option returns 1 only when searches of the index use a sketch */
 };
 enum {
     GRANNE_HIP_WALKER_NONE = 0,          /* no search yet */

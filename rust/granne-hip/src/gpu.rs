@@ -52,6 +52,7 @@ extern "C" {
     fn granne_hip_index_get_neighbors(index: *const granne_hip_index, node: u64, layer: u32,
         out_ids: *mut u32, cap: u32, out_count: *mut u32) -> c_int;
     fn granne_hip_index_get_element(index: *const granne_hip_index, idx: u64, out: *mut c_void) -> c_int;
+    fn granne_hip_index_get_sketch(index: *const granne_hip_index, first: u64, count: u64, out: *mut c_void) -> c_int;
     // ---- search
     fn granne_hip_search(index: *const granne_hip_index, query: *const c_void, max_search: u32,
         num_neighbors: u32, out_ids: *mut u64, out_dists: *mut f32, out_count: *mut u32) -> c_int;
@@ -96,6 +97,7 @@ extern "C" {
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
 pub const GRANNE_HIP_OPT_SEEN_MIN: c_int = 11;
+pub const GRANNE_HIP_OPT_SKETCH: c_int = 12;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
 pub const GRANNE_HIP_SHARDED_EXCHANGE_PEER: u64 = 0;
