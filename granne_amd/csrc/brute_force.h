@@ -46,6 +46,12 @@ constexpr uint32_t BF_THREADS = 512;
 constexpr uint32_t BF_EXTRA = 6;   // candidates selected beyond k, re-ranked by the exact distance
 constexpr uint32_t BF_KMAX = 16;   // longest per-lane list (k + BF_EXTRA <= BF_KMAX)
 
+// A scan kernel's launch (granne_hip_brute_force_device): rows per tile, queries per block, threads per block and dynamic LDS
+// bytes, from the kernel's own constants (ET, STRIDE, STRIDE_B, SUB, KG). Each kernel's is next to it.
+struct BfGeometry {
+    uint32_t rows, qt, threads, lds;
+};
+
 struct BruteParams {
     const uint8_t* elements; // device rows: row_bytes of (zero padded) data every row_stride bytes
     uint64_t n;
@@ -343,6 +349,12 @@ __global__ __launch_bounds__(BF_THREADS) void bf_f32_kernel(const BruteParams P)
     else bf_write_list(P, L, blk.range, q, qlive, h);
 }
 
+template <int KH, int R>
+constexpr BfGeometry bf_f32_geometry() {
+    constexpr uint32_t ET = 32u * R, STRIDE = 2u * KH + 4u;
+    return {ET, BF_QT, BF_THREADS, ET * STRIDE * 4u}; // the tile
+}
+
 // f32 rows scored on the bf16 matrix path (round 6): the f32 scan above is MFMA-bound at 0.76 of the f32 matrix peak
 // (157 TFLOP/s: 17.2 ms per 1024 x 10M x 100) while the bf16 path is 16 x as wide. A scan only SELECTS candidates (their
 // distances are recomputed exactly afterwards), so its score needs to be accurate to a small fraction of the gap between
@@ -499,6 +511,12 @@ __global__ __launch_bounds__(BF_B16_THREADS) void bf_b16_kernel(const BruteParam
     else bf_write_list(P, L, blk.range, q, qlive, h);
 }
 
+template <int KG, int R>
+constexpr BfGeometry bf_b16_geometry() {
+    constexpr uint32_t ET = 32u * R, COMPS = 16u * KG, STRIDE_B = 2u * COMPS + 16u;
+    return {ET, BF_B16_QT, BF_B16_THREADS, 2u * ET * STRIDE_B}; // tile_hi, tile_lo
+}
+
 // f32 rows of ANY length on the bf16 path (round 6: bf_b16_kernel keeps a lane's half of its query in registers for the
 // whole scan, which ends at 256 dims). Here the vector is walked in chunks of 128 components: the accumulators of a
 // tile of 64 rows stay in registers across the chunks, a chunk of the tile goes HBM -> registers -> LDS as in
@@ -644,6 +662,12 @@ __global__ __launch_bounds__(BF_B16_THREADS) void bf_b16_chunked_kernel(const Br
     }
     if constexpr (PRIME) bf_write_max(P, best, blk.range, q, qlive, h);
     else bf_write_list(P, L, blk.range, q, qlive, h);
+}
+
+template <int R>
+constexpr BfGeometry bf_b16_chunked_geometry() {
+    constexpr uint32_t KG = 8, ET = 32u * R, COMPS = 16u * KG, STRIDE_B = 2u * COMPS + 16u;
+    return {ET, BF_B16_QT, BF_B16_THREADS, 2u * ET * STRIDE_B}; // tile_hi, tile_lo
 }
 
 // int8: device rows of up to 128 bytes (dims up to 128; the scan refuses longer rows). K = 32 per MFMA
@@ -852,6 +876,12 @@ __global__ __launch_bounds__(BF_THREADS) void bf_i8_kernel(const BruteParams P) 
     else bf_write_list(P, L, blk.range, q, qlive, h, qinv);
 }
 
+template <int R>
+constexpr BfGeometry bf_i8_geometry() {
+    constexpr uint32_t ET = 32u * R, SUB = BF_I8_SUB, ST = ET * SUB, STRIDE = 128u + 16u;
+    return {ET, BF_QT, BF_THREADS, ST * STRIDE + ST * 4u + SUB * 2u * R * 4u}; // tiles, inv [ST], gm [SUB][2][R]
+}
+
 // int8 rows of MORE than 128 bytes (round 6; bf_i8_kernel and the ring keep a lane's part of its query in registers for the
 // whole scan: 128 bytes). The row is walked in chunks of 128 bytes: the integer accumulators of a tile of 32 R rows stay in
 // registers across the chunks, a chunk of the tile goes HBM -> registers -> LDS as in bf_i8_kernel, and a wave reads its 32
@@ -1015,6 +1045,12 @@ __global__ __launch_bounds__(BF_THREADS) void bf_i8_chunked_kernel(const BrutePa
     }
     if constexpr (PRIME) bf_write_max(P, best * qinv, blk.range, q, qlive, h);
     else bf_write_list(P, L, blk.range, q, qlive, h, qinv);
+}
+
+template <int R>
+constexpr BfGeometry bf_i8_chunked_geometry() {
+    constexpr uint32_t ET = 32u * R, STRIDE = 128u + 16u;
+    return {ET, BF_QT, BF_THREADS, ET * STRIDE + ET * 4u + 2u * R * 4u}; // tile, inv [ET], gm [2][R]
 }
 
 // ---- int8 rows of 128 bytes: the tiles travel HBM -> LDS by LDS-DMA into a ring, two query sets per wave (round 6) ----
@@ -1220,6 +1256,19 @@ struct BfSets {
     }
 };
 
+// What bf_i8_ring_kernel relies on and the compiler cannot see. Its LDS, in the order and at the offsets it uses: the tile
+// ring (NS x TB), the sets at NS x TB (sets.at), the norm ring at NS x TB + BF_SET_BYTES (norms0), NS slots of NB bytes.
+constexpr uint32_t BF_RING_NORM_BYTES = 8u * 80u; // NB: per tile, 8 waves x ([16] 1 / |x|, [2] inv_gmax, [2] unused)
+static_assert(BF_SET_BYTES == BF_KMAX * BF_SET_QT * 4u * 2u + BF_SET_QT * 4u * 2u, "BfSets::at: scores, ids, worst, place");
+static_assert(BF_RING_LDS == BF_RING_STAGES * BF_RING_TILE_BYTES + BF_SET_BYTES + BF_RING_STAGES * BF_RING_NORM_BYTES,
+              "the ring's LDS: tiles, then the sets, then the norms");
+static_assert(BF_RING_LDS <= 160u * 1024u, "the ring's LDS fits a CU");
+// A wave's part of a tile is three LDS-DMA instructions: two of 64 x 16 bytes (rows) and one of 4 bytes per lane (norms). The
+// loop's s_waitcnt vmcnt(6 / 3 / 0) counts them: the wave's transfers of the (at most) two tiles issued after tile t.
+constexpr uint32_t BF_RING_DMA_PER_TILE = 3;
+static_assert(BF_RING_THREADS / 64u * 2u * 64u * 16u == BF_RING_TILE_BYTES, "two 16-byte transfers per lane and wave cover a tile");
+static_assert(BF_RING_STAGES - 1u == 3u && 2u * BF_RING_DMA_PER_TILE == 6u && 1u * BF_RING_DMA_PER_TILE == 3u,
+              "vmcnt(6) / vmcnt(3): three tiles in flight, three transfers per wave and tile");
 __global__ __launch_bounds__(BF_RING_THREADS) void bf_i8_ring_kernel(const BruteParams P) {
     extern __shared__ __align__(16) uint8_t smem_bf[];
     constexpr uint32_t NS = BF_RING_STAGES, TR = BF_RING_ROWS, TB = BF_RING_TILE_BYTES;
@@ -1371,6 +1420,9 @@ __global__ __launch_bounds__(BF_RING_THREADS) void bf_i8_ring_kernel(const Brute
     for (int s = 0; s < 2; ++s)
         if (qlive[s] && h == 0u) sets.write(P, ql[s], blk.range, q[s], qinv[s]);
 }
+
+// bf_i8_ring_kernel's launch: 64 queries per wave, the ring's tiles of BF_RING_ROWS rows
+constexpr BfGeometry bf_ring_geometry() { return {BF_RING_ROWS, BF_RING_QT, BF_RING_THREADS, BF_RING_LDS}; }
 
 // 1 / |x| of every int8 row (0 for a zero row), once per index: eight lanes per 128-byte row
 __global__ void inv_norm_rows_kernel(const uint8_t* __restrict__ elements, uint64_t n, uint32_t row_bytes, float* __restrict__ out) {

@@ -261,23 +261,14 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
         HIP_TRY(hipFuncSetAttribute((const void*)K.final_prune, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
 
-    SearchTarget T;
-    T.device = b->device;
-    T.d_elements = b->d_elements;
-    T.n_elements = b->n_elements;
-    T.dim = b->dim;
-    T.dtype = b->dtype;
-    T.row_bytes = b->row_bytes;
-    T.row_stride = b->row_stride;
-    T.d_layers = S.d_layers;
-    T.n_layers = last + 1;
-    T.max_dev_width = b->W;
-    T.opt_visited_slots = 0;
-    T.opt_force_slow = 0;
-    T.opt_slow_slots = 1u << 18;
-    T.opt_slow_blocks = 16;
-    T.opt_overflow_slots = 0;
-    T.scratch = &b->scratch;
+    const SearchTarget T(b, S.d_layers, last + 1);
+    SearchCall call; // phase A's searches: max_search neighbors of each batch's rows, from the rows themselves
+    call.ef = call.k = max_search;
+    call.ids = S.s_ids;
+    call.dists = S.s_dists;
+    call.counts = S.s_counts;
+    call.status = S.counters + 1;
+    call.stream = s;
 
     BuildParams P;
     P.elements = b->d_elements;
@@ -325,9 +316,10 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
         const int64_t step = reinsert ? -1 : 1;
 
         // phase A: entry search through the previous layers + search_for_neighbors on this layer
-        int rc = search_launch(&T, b->d_elements + (size_t)first * b->row_stride, step * (int64_t)b->row_stride, (uint32_t)B,
-                               max_search, max_search, S.s_ids, S.s_dists, S.s_counts, nullptr, S.counters + 1, s,
-                               nullptr);
+        call.queries = b->d_elements + (size_t)first * b->row_stride;
+        call.q_stride = step * (int64_t)b->row_stride;
+        call.nq = (uint32_t)B;
+        int rc = search_launch(T, call);
         if (rc) return rc;
         dbg("search", pos, B);
         P.first_idx = first;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/granne_hip.h"
@@ -73,16 +74,12 @@ extern "C" int granne_hip_device_count(int* out_count) {
 
 // experiment knobs, read once per process
 struct EnvKnobs {
-    int visited_cap = 0, front_eighths = 0, maxc = 0, lds_pad = 0, visited = 0, tail_blocks = -1, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1, sketch = 1;
+    int visited = 0, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1, sketch = 1;
     EnvKnobs() {
         auto geti = [](const char* name, int dflt) {
             const char* e = getenv(name);
             return e ? atoi(e) : dflt;
         };
-        visited_cap = geti("GRANNE_HIP_VISITED_CAP", 0);
-        front_eighths = geti("GRANNE_HIP_FRONT_EIGHTHS", 0);
-        maxc = geti("GRANNE_HIP_MAXC", 0);
-        lds_pad = geti("GRANNE_HIP_LDS_PAD", 0);
         visited = geti("GRANNE_HIP_VISITED", 0); // GRANNE_HIP_OPT_VISITED16's values, where the option says auto
         inline_tails = geti("GRANNE_HIP_INLINE_TAILS", 1); // 0: no index keeps LayerDev::adjx (experiments: the layout before round 6)
         bf_ring = geti("GRANNE_HIP_BF_RING", 1); // 0: the exact scan of 128-byte int8 rows stages its tiles through registers (round 5's bf_i8_kernel)
@@ -755,259 +752,6 @@ extern "C" uint64_t granne_hip_index_last_slow_count(const granne_hip_index* ix)
 // ------------------------------------------------------------------------------------------------
 // search
 // ------------------------------------------------------------------------------------------------
-// what a search launch needs to know about the graph it walks (an index, or a builder's layers)
-struct SearchTarget {
-    int device;
-    const uint8_t* d_elements;
-    uint64_t n_elements;
-    uint32_t dim;
-    int dtype;
-    uint32_t row_bytes, row_stride;
-    const LayerDev* d_layers;
-    uint32_t n_layers;
-    uint32_t max_dev_width;
-    uint64_t opt_visited_slots, opt_force_slow, opt_slow_slots, opt_slow_blocks, opt_overflow_slots;
-    uint64_t opt_visited16 = 0, opt_visited16_lg = 0;
-    uint64_t opt_seen_min = 0xFFFFFFFFull; // (a builder's searches: never -- its layers change between launches, its batches are its own)
-    const uint8_t* d_sketch = nullptr;     // row sketches the register walker may use (an index's, when GRANNE_HIP_OPT_SKETCH is on)
-    ScratchCache* scratch; // search_launch's per-stream scratch blocks
-    std::atomic<uint64_t>* last_walker = nullptr; // which kernel the last launch took (an index's read-only option)
-};
-
-static SearchTarget target_of(const granne_hip_index* ix) {
-    SearchTarget T;
-    T.device = ix->device;
-    T.d_elements = ix->d_elements;
-    T.n_elements = ix->n_elements;
-    T.dim = ix->dim;
-    T.dtype = ix->dtype;
-    T.row_bytes = ix->row_bytes;
-    T.row_stride = ix->row_stride;
-    T.d_layers = ix->d_layers;
-    T.n_layers = (uint32_t)ix->layers.size();
-    T.max_dev_width = ix->max_dev_width;
-    T.opt_visited_slots = ix->opt_visited_slots;
-    T.opt_force_slow = ix->opt_force_slow;
-    T.opt_slow_slots = ix->opt_slow_slots;
-    T.opt_slow_blocks = ix->opt_slow_blocks;
-    T.opt_overflow_slots = ix->opt_overflow_slots;
-    T.opt_visited16 = ix->opt_visited16;
-    T.opt_visited16_lg = ix->opt_visited16_lg;
-    T.opt_seen_min = ix->opt_seen_min;
-    T.d_sketch = (ix->opt_sketch && knobs().sketch) ? ix->d_sketch : nullptr;
-    T.scratch = &const_cast<granne_hip_index*>(ix)->scratch;
-    T.last_walker = &const_cast<granne_hip_index*>(ix)->last_walker;
-    return T;
-}
-
-typedef void (*search_fn)(const SlowParams);
-
-
-template <int DT, int DIM>
-static search_fn pick_s(uint32_t ef) {
-    if (ef <= 64) return search_kernel<DT, DIM, 1>;
-    if (ef <= 128) return search_kernel<DT, DIM, 2>;
-    return search_kernel<DT, DIM, 4>;
-}
-
-// the general walker (search_kernel.h): run-time dims, any row width
-static search_fn pick_trail_kernel(int dtype) { // Granne::reorder's trail walks (max_search 1)
-    return dtype == GRANNE_HIP_I8 ? (search_fn)search_kernel<DT_I8, 0, 1, true> : (search_fn)search_kernel<DT_F32, 0, 1, true>;
-}
-static search_fn pick_kernel(int dtype, uint32_t ef) {
-    return dtype == GRANNE_HIP_I8 ? pick_s<DT_I8, 0>(ef) : pick_s<DT_F32, 0>(ef);
-}
-
-// the walker of the common shapes (walk_fast.h): every layer 32 ids wide on the device, ids within 31
-// bits, f32 rows of an instantiated dim or int8 rows of 128 bytes. The list holds 64*S keys and must
-// hold max_search of them plus a few spare places: two distances of a walk tie surprisingly often (4000
-// candidates share 2^23 float values), and a tie between entry max_search-1 and an entry pushed off the
-// end hands the walk over -- with spare places that takes a run of ties.
-constexpr uint32_t FAST_MAX_SEARCH = 8192; // f32 rows of 100 / 200 dims and int8 rows of 128 bytes: two-level lists of up to 129 x 64 keys
-static uint32_t fast_list_slots(uint32_t ef) {
-    return ef <= 60 ? 1u : ef <= 124 ? 2u : ef <= 252 ? 4u : ef <= 508 ? 8u : ef <= 1024 ? 17u : ef <= 2048 ? 33u : ef <= 4096 ? 65u : 129u;
-}
-// v16: the form of the visited set (FastWalker's V16): 0 = the exact 32-bit table, 3 = none, 4 = none + rows touched ahead
-template <int DT, int DIM, int S>
-static search_fn pick_fast_v(int v16) {
-    if constexpr (S == 1 && !(DT == DT_F32 && DIM == 0) && !(DT == DT_I8 && DIM >= 256)) {
-        if (v16 == 4) return fast_kernel<DT, DIM, S, false, 4>; // no visited set + rows touched ahead (few queries)
-    }
-    if constexpr (DT == DT_F32 && S <= 4) {
-        if (v16 == 5) return fast_kernel<DT, DIM, S, false, 5>; // no visited set + revisits skipped before their rows are fetched (many walks)
-    }
-    if (v16 >= 3) return fast_kernel<DT, DIM, S, false, 3>;
-    return fast_kernel<DT, DIM, S>;
-}
-template <int DT, int DIM>
-static search_fn pick_fast_s(uint32_t S, bool trail, int v16) {
-    if (trail) return fast_kernel<DT, DIM, 1, true>;
-    switch (S) {
-    case 1: return pick_fast_v<DT, DIM, 1>(v16);
-    case 2: return pick_fast_v<DT, DIM, 2>(v16);
-    case 4: return pick_fast_v<DT, DIM, 4>(v16);
-    case 8: return v16 >= 3 ? fast_kernel<DT, DIM, 8, false, 3> : fast_kernel<DT, DIM, 8>;
-    default:
-        if constexpr ((DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256)) {
-            // streamed f32 dims and int8 rows of 256 / 512 bytes: lists of up to 17 x 64 keys (max_search 1024)
-            if constexpr (walk_list_is_long(17, false)) return fast_kernel<DT, DIM, 17, false, 3>; // (a two-level list: no exact set)
-            else return v16 >= 3 ? fast_kernel<DT, DIM, 17, false, 3> : fast_kernel<DT, DIM, 17>;
-        } else {
-            // lists of 33 / 65 slots (max_search up to 2048 / 4096) exist without a visited set only: plan_launch sends
-            // such a search there whatever the option says (an exact set of ~40 x max_search ids fits no LDS)
-            if (S == 33) return fast_kernel<DT, DIM, 33, false, 3>;
-            if (S == 65) return fast_kernel<DT, DIM, 65, false, 3>;
-            if (S == 129) return fast_kernel<DT, DIM, 129, false, 3>;
-            if constexpr (walk_list_is_long(17, false)) return fast_kernel<DT, DIM, 17, false, 3>;
-            else return v16 >= 3 ? fast_kernel<DT, DIM, 17, false, 3> : fast_kernel<DT, DIM, 17>;
-        }
-    }
-}
-// Layers of up to 64 ids per node (graphs with num_neighbors 33..63: the GPU builder makes them, BuildConfig::num_neighbors
-// src/index/mod.rs:242) are walked in two passes of 32 pairs per expansion (FastWalker's WIDE) -- instantiated for lists of
-// up to 17 x 64 keys, without a visited set, not for Granne::reorder's trail walks, and for int8 rows of 128 bytes only.
-static bool fast_wide(const SearchTarget* ix) { return ix->max_dev_width == 64; }
-static bool fast_shape(const SearchTarget* ix) {
-    // (ids: 31 bits. A 2^31-element index needs 275 GB for its bottom layer's 128-byte adjacency rows alone, so the
-    //  reference's 2^32 - 2 capacity, src/index/mod.rs:27-28, is out of one device's reach whatever the key layout)
-    if (ix->max_dev_width > 64 || ix->n_elements > WALK_MAX_ELEMENTS) return false;
-    if (ix->dtype == GRANNE_HIP_I8)
-        return ix->row_bytes == 128 || (!fast_wide(ix) && (ix->row_bytes == 256 || ix->row_bytes == 512)); // dims <= 512
-    return true; // f32: 100 and 200 fully unrolled, any other dim streamed (dims below 32: the tail alone)
-}
-static bool fast_generic(const SearchTarget* ix) { return ix->dtype == GRANNE_HIP_F32 && ix->dim != 100 && ix->dim != 200; }
-// the longest max_search the register walker is instantiated for, by shape
-static uint32_t fast_max_search(const SearchTarget* ix) {
-    if (fast_wide(ix)) return 1024u;                                                        // layers of 64 ids: lists of up to 17 x 64 keys
-    if (ix->dtype == GRANNE_HIP_I8) return ix->row_bytes == 128 ? FAST_MAX_SEARCH : 1024u; // wide int8 rows: lists of up to 17 x 64 keys
-    return fast_generic(ix) ? 1024u : FAST_MAX_SEARCH;                                      // streamed f32 dims: up to 17 x 64 keys
-}
-// int8 rows of 256 / 512 bytes (dims 129..512, e.g. the 200- and 300-d rows of benches/distance_computation.rs:29-39)
-template <int ROWB>
-static search_fn pick_fast_i8_wide(uint32_t S, bool trail, int v16) {
-    return pick_fast_s<DT_I8, ROWB>(S, trail, v16);
-}
-template <int DT, int DIM>
-static search_fn pick_fast_wide(uint32_t S) {
-    switch (S) {
-    case 1: return fast_kernel<DT, DIM, 1, false, 3, true>;
-    case 2: return fast_kernel<DT, DIM, 2, false, 3, true>;
-    case 4: return fast_kernel<DT, DIM, 4, false, 3, true>;
-    case 8: return fast_kernel<DT, DIM, 8, false, 3, true>;
-    default: return fast_kernel<DT, DIM, 17, false, 3, true>;
-    }
-}
-static search_fn pick_fast_kernel(const SearchTarget* ix, uint32_t S, bool trail, int v16) {
-    if (fast_wide(ix)) { // (search_launch sends trail walks and longer lists of such graphs to the general walker)
-        if (ix->dtype == GRANNE_HIP_I8) return pick_fast_wide<DT_I8, 0>(S);
-        if (ix->dim == 100) return pick_fast_wide<DT_F32, 100>(S);
-        if (ix->dim == 200) return pick_fast_wide<DT_F32, 200>(S);
-        return pick_fast_wide<DT_F32, 0>(S);
-    }
-    if (ix->dtype == GRANNE_HIP_I8 && ix->row_bytes == 256) return pick_fast_i8_wide<256>(S, trail, v16);
-    if (ix->dtype == GRANNE_HIP_I8 && ix->row_bytes == 512) return pick_fast_i8_wide<512>(S, trail, v16);
-    if (ix->dtype == GRANNE_HIP_I8) return pick_fast_s<DT_I8, 0>(S, trail, v16);
-    if (ix->dim == 100) return pick_fast_s<DT_F32, 100>(S, trail, v16);
-    if (ix->dim == 200) return pick_fast_s<DT_F32, 200>(S, trail, v16);
-    return pick_fast_s<DT_F32, 0>(S, trail, v16);
-}
-
-struct LaunchPlan {
-    uint32_t visited_slots, upper_slots, maxc, lrow_bytes, stage_bytes, adjspec_bytes, lds_bytes;
-    int v16; // FastWalker's V16: 0 = the exact 32-bit table, 3 = no visited set, 4 = none + rows touched ahead
-};
-
-// LDS plan. The visited table dominates; the f32 stage gets what keeps four walkers per CU
-// (160 KiB / 4) when that leaves it at least 16 rows, else up to 32 rows within 64 KiB, else
-// whatever fits in the CU's 160 KiB. GRANNE_HIP_MAXC overrides the stage rows (experiments).
-static LaunchPlan plan_launch(const SearchTarget* ix, uint32_t ef, uint32_t nq, uint32_t fastS /* 0: general walker */,
-                              bool trail) {
-    LaunchPlan P;
-    P.v16 = 0;
-    // The register walkers walk without a visited set by default (VisitedNone, wave_prims.h: the list itself is searched for
-    // a candidate's id): no table in LDS, only the query's staging area and what a tail block needs, so the registers
-    // alone bound the walkers per CU. GRANNE_HIP_OPT_VISITED16 = 1..3 switches the exact set on (a 32-bit open-addressing
-    // table in LDS + a global overflow table): n_dist is then the reference's count of distinct evaluated nodes.
-    const int vmode = ix->opt_visited16 ? ix->opt_visited16 : knobs().visited;
-    const bool none = vmode == 4 || vmode == 0;
-    const bool longest = walk_list_is_long((int)fastS, fast_wide(ix)) || fast_wide(ix); // (lists of 33 / 65 slots, and 64-id layers: instantiated without a set only, whatever the options say)
-    if (fastS >= 1 && !trail && ((none && !ix->opt_visited_slots) || longest) && ix->n_elements <= WALK_MAX_ELEMENTS) { // (fast_shape's bound)
-        // a launch of a few queries leaves the chip idle: its walkers touch the next node's rows ahead (walk_fast.h, TOUCH)
-        const uint32_t touch_max = knobs().touch_max >= 0 ? (uint32_t)knobs().touch_max : 256u; // (round 5: +4 % at 256 queries, -10 % at 1024: profiles/r5_touch.txt)
-        const bool touch_shape = fastS == 1 && !fast_generic(ix) && !(ix->dtype == GRANNE_HIP_I8 && ix->row_bytes != 128);
-        P.v16 = (touch_shape && nq <= touch_max) ? 4 : 3;
-        // launches of many walks are bound by bandwidth: their walkers skip revisits BEFORE the rows are fetched (walk_fast.h, SEEN)
-        const uint64_t seen_min = knobs().seen_min >= 0 ? (uint64_t)knobs().seen_min : ix->opt_seen_min; // (GRANNE_HIP_SEEN_MIN overrides the option: experiments)
-        // (f32 rows: the walkers per CU are bound by registers there, 8 KB of cache each fit; int8 walkers are four times as many
-        //  and lose more to the look-up than the few revisits of their rows cost: measured, profiles/r6_seen_ab.txt)
-        if (fastS <= 4 && !fast_wide(ix) && ix->dtype == GRANNE_HIP_F32 && nq >= seen_min) P.v16 = 5; // (every f32 dim: unrolled and streamed)
-        P.visited_slots = P.upper_slots = 0;
-        P.maxc = 0;
-        P.lrow_bytes = 16;
-        P.stage_bytes = 0;
-        P.adjspec_bytes = 0;
-        P.lds_bytes = fast_lds_bytes(ix->dtype == GRANNE_HIP_I8, fast_generic(ix), ix->dim, ix->row_bytes, fastS, 0u, P.v16 == 5, fast_wide(ix));
-        const uint32_t least = lds_query_bytes(ix->row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
-        if (P.lds_bytes < least) P.lds_bytes = least;
-        return P;
-    }
-    // The front table must hold the walk's visited ids (~40 x max_search on 10M uniform points) below its 7/8
-    // load limit: 4096 slots at max_search 50. (Tables of 3 * 2^k slots are accepted as an option; 3072 slots --
-    // 12 KB, twelve walkers per CU instead of nine -- measured no faster: 0.5 % of the walks spill to the
-    // overflow table and a launch lasts as long as its slowest walk.)
-    uint32_t want = ix->opt_visited_slots ? (uint32_t)ix->opt_visited_slots : next_pow2(ef * 64u);
-    if (!ix->opt_visited_slots) {
-        if (want < 1024) want = 1024;
-        // larger walks spill to the global overflow table. A launch with more walkers than the chip
-        // holds is better off with small tables (more walkers per CU; measured on the 10M build:
-        // 37.7 s vs 45.4 s), one batch of a thousand queries with fewer spills (ef 200: 508k vs 421k q/s)
-        uint32_t cap = nq >= 4096 ? 4096u : 8192u;
-        // long lists (max_search > 252) walk ~20x max_search nodes: most inserts land in the overflow table
-        // whatever the front table's size, and a 32 KB front table beside the list's LDS mirror leaves room
-        // for only three walkers per CU (768 of a batch of 1024 resident: the batch runs in two rounds)
-        if (fastS >= 8) cap = 4096u;
-        if (knobs().visited_cap) cap = next_pow2((uint32_t)knobs().visited_cap); // experiments
-        if (cap < 1024) cap = 1024;
-        if (cap > 32768) cap = 32768;
-        if (want > cap) want = cap;
-    }
-    P.visited_slots = want;
-    P.upper_slots = want < 1024 ? want : 1024;
-    if (fastS) { // walk_fast.h: [query][S >= 8: 64*S keys][visited front table]
-        P.maxc = 0;
-        P.lrow_bytes = 16;
-        P.stage_bytes = 0;
-        P.adjspec_bytes = 0;
-        P.lds_bytes = fast_lds_bytes(ix->dtype == GRANNE_HIP_I8, fast_generic(ix), ix->dim, ix->row_bytes, fastS, P.visited_slots, false, fast_wide(ix));
-        return P;
-    }
-    // the general walker (search_kernel.h): int8 keeps its speculative adjacency rows in registers (Walker::REGSPEC),
-    // run-time-dim f32 parks them in LDS
-    P.adjspec_bytes = ix->dtype == GRANNE_HIP_I8 ? 0u : LDS_ADJSPEC_BYTES;
-    uint32_t fixed = lds_query_bytes(ix->row_bytes) + LDS_FIXED_BYTES + P.adjspec_bytes;
-    if (ix->dtype == GRANNE_HIP_F32) {
-        uint32_t row16 = ix->row_bytes / 16;
-        P.lrow_bytes = (row16 | 1u) * 16u; // odd number of 16-byte units: conflict-free ds_read_b128
-        uint32_t wmax = ix->max_dev_width < 64 ? ix->max_dev_width : 64;
-        uint32_t used = fixed + P.visited_slots * 4u;
-        auto rows_in = [&](uint32_t budget) { return budget > used ? (budget - used) / P.lrow_bytes : 0u; };
-        uint32_t maxc = rows_in(40u * 1024u);
-        if (maxc < 16) maxc = rows_in(64u * 1024u) < 32u ? rows_in(64u * 1024u) : 32u;
-        if (maxc < 16) maxc = rows_in(160u * 1024u) < 32u ? rows_in(160u * 1024u) : 32u;
-        if (maxc > wmax) maxc = wmax;
-        if (knobs().maxc >= 1 && knobs().maxc <= 64) maxc = (uint32_t)knobs().maxc;
-        if (maxc < 1) maxc = 1;
-        P.maxc = maxc;
-        P.stage_bytes = P.maxc * P.lrow_bytes;
-    } else {
-        P.maxc = 0;
-        P.lrow_bytes = 16;
-        P.stage_bytes = 0;
-    }
-    P.lds_bytes = fixed + P.stage_bytes + P.visited_slots * 4u;
-    return P;
-}
-
 // A search's scratch block (control words, overflow-region states, hand-over list, overflow tables, the exact
 // walker's containers) is kept per (index, stream) for the life of the index: launches on one stream run in
 // order, so they can share a block, and the kernels leave its control words and region states zeroed -- no
@@ -1080,93 +824,370 @@ static int scratch_for(ScratchCache* cache, hipStream_t s, size_t total, uint8_t
     return GRANNE_HIP_OK;
 }
 
-static int search_launch(const SearchTarget* ix, const void* d_queries, int64_t q_stride, uint32_t nq, uint32_t ef,
-                         uint32_t k, uint64_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t* d_stats,
-                         uint32_t* d_status, hipStream_t s, uint32_t* h_slow_count /* optional, syncs */,
-                         uint32_t* d_trail = nullptr /* [nq][8]: trail mode, no search outputs */,
-                         uint32_t trail_layers = 0, hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,
-                         uint32_t* host_status = nullptr /* u32[2], host-mapped: hand-over count and exhaustion flag, plain stores */,
-                         const BatchIO* batches = nullptr, uint32_t n_batches = 0 /* > 0: `nq` queries in EACH of these, one launch */) {
-    if (ef == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_search must be > 0 (the reference panics, src/index/mod.rs:1019)");
-    if (nq == 0) return GRANNE_HIP_OK;
-    if (n_batches > MAX_LAUNCH_BATCHES) return fail(GRANNE_HIP_ERR_INVALID, "at most %u batches per launch", MAX_LAUNCH_BATCHES);
-    if (n_batches && (uint64_t)n_batches * nq > 0x7FFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many queries in one launch");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
-    const uint32_t batch_nq = nq;
-    if (n_batches) {
-        for (uint32_t b = 0; b < n_batches; ++b)
-            if (!batches[b].queries || !batches[b].out_counts || (k && (!batches[b].out_ids || !batches[b].out_dists)))
-                return fail(GRANNE_HIP_ERR_INVALID, "null buffer (batch %u)", b);
-        if (k == 0) {
-            for (uint32_t b = 0; b < n_batches; ++b) HIP_TRY(hipMemsetAsync(batches[b].out_counts, 0, (size_t)nq * 4, s));
-            return GRANNE_HIP_OK;
-        }
-        d_queries = batches[0].queries;
-        d_ids = batches[0].out_ids;
-        d_dists = batches[0].out_dists;
-        d_counts = batches[0].out_counts;
-        d_stats = batches[0].out_stats;
-        nq *= n_batches; // walkers of the launch
-    }
-    if (k == 0 && !d_trail) { // .take(0): every result is empty (src/index/mod.rs:974-977)
-        if (!d_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 4, s));
-        return GRANNE_HIP_OK;
-    }
-    if (!d_queries || (!d_trail && (!d_ids || !d_dists || !d_counts))) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+namespace { // (the planners' types stay out of the library's exports)
+// what a search launch needs to know about the graph it walks: an index's, or the layers a builder has so far
+struct SearchTarget {
+    int device;
+    const uint8_t* d_elements;
+    uint64_t n_elements;
+    uint32_t dim;
+    int dtype;
+    uint32_t row_bytes, row_stride;
+    const LayerDev* d_layers;
+    uint32_t n_layers;
+    uint32_t max_dev_width;
+    uint64_t opt_visited_slots = 0, opt_force_slow = 0, opt_slow_slots = 1u << 18, opt_slow_blocks = 16, opt_overflow_slots = 0;
+    uint64_t opt_visited16 = 0;
+    uint64_t opt_seen_min = 0xFFFFFFFFull;
+    const uint8_t* d_sketch = nullptr; // row sketches the register walker may use (an index's, when GRANNE_HIP_OPT_SKETCH is on)
+    ScratchCache* scratch;             // search_launch's per-stream scratch blocks
+    std::atomic<uint64_t>* last_walker = nullptr; // which walker the last launch took (an index's read-only option)
 
-    // (the streamed run-time-dim walker is instantiated up to 8 x 64 keys: beyond that the exact walker)
-    const bool fast = fast_shape(ix) && ef <= fast_max_search(ix) && !(fast_wide(ix) && d_trail);
-    const uint32_t fastS = fast ? fast_list_slots(ef) : 0u;
-    const uint32_t ef_walk = fast ? ef : (ef > 256 ? 256 : ef); // what the register/LDS walker is sized for
-    const bool all_slow = ix->opt_force_slow || (!fast && ef > 256);
-    LaunchPlan plan = plan_launch(ix, ef_walk, nq, fastS, d_trail != nullptr);
-    if (plan.lds_bytes > 160u * 1024u) return fail(GRANNE_HIP_ERR_INVALID, "dimension too large for the LDS stage");
+    // G: granne_hip_index, or granne_hip_builder (builder_host.h) searching its `layers`. A builder's searches differ in
+    // these ways only: no row sketches, seen_min never reached (its layers change between launches, its batches are its
+    // own), its own scratch cache, its row width W as the widest layer's; every other option keeps its default.
+    template <class G>
+    SearchTarget(const G* g, const LayerDev* layers, uint32_t n_layers)
+        : device(g->device), d_elements(g->d_elements), n_elements(g->n_elements), dim(g->dim), dtype(g->dtype),
+          row_bytes(g->row_bytes), row_stride(g->row_stride), d_layers(layers), n_layers(n_layers),
+          scratch(&const_cast<G*>(g)->scratch) {
+        if constexpr (std::is_same<G, granne_hip_index>::value) {
+            max_dev_width = g->max_dev_width;
+            opt_visited_slots = g->opt_visited_slots;
+            opt_force_slow = g->opt_force_slow;
+            opt_slow_slots = g->opt_slow_slots;
+            opt_slow_blocks = g->opt_slow_blocks;
+            opt_overflow_slots = g->opt_overflow_slots;
+            opt_visited16 = g->opt_visited16;
+            opt_seen_min = g->opt_seen_min;
+            d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch : nullptr;
+            last_walker = &const_cast<G*>(g)->last_walker;
+        } else {
+            max_dev_width = g->W;
+        }
+    }
+};
+} // namespace
+
+// One search launch. Every caller sets the queries, nq, ef, k and the stream; of the rest only what it uses.
+struct SearchCall {
+    const void* queries = nullptr;
+    int64_t q_stride = 0; // bytes from one query to the next (0: the target's row length, dim x element size)
+    uint32_t nq = 0, ef = 0, k = 0;
+    uint64_t* ids = nullptr;
+    float* dists = nullptr;
+    uint32_t* counts = nullptr;
+    uint64_t* stats = nullptr;
+    uint32_t* status = nullptr; // the caller's status words (d_status of the C ABI), or null
+    hipStream_t stream = nullptr;
+    uint32_t* slow_count = nullptr;  // u32[2] on the host: hand-overs and exhaustion (the call waits for the launch)
+    uint32_t* trail = nullptr;       // [nq][8]: trail mode (Granne::reorder), no search outputs
+    uint32_t trail_layers = 0;
+    hipEvent_t ev_before = nullptr, ev_after = nullptr;
+    uint32_t* host_status = nullptr; // u32[2], host-mapped: hand-over count and exhaustion flag, plain stores
+    const BatchIO* batches = nullptr;
+    uint32_t n_batches = 0;          // > 0: `nq` queries in EACH of these, one launch
+};
+
+typedef void (*search_fn)(const SlowParams);
+
+// The general walker (search_kernel.h): run-time dims, any row width. nullptr: not instantiated.
+template <int DT>
+static search_fn general_kernel_s(uint32_t S) {
+    switch (S) {
+    case 1: return search_kernel<DT, 0, 1>;
+    case 2: return search_kernel<DT, 0, 2>;
+    case 4: return search_kernel<DT, 0, 4>;
+    }
+    return nullptr;
+}
+static search_fn general_kernel_of(int dtype, uint32_t S, bool trail) {
+    const bool i8 = dtype == GRANNE_HIP_I8;
+    if (trail) // Granne::reorder's trail walks (max_search 1)
+        return S != 1 ? nullptr : i8 ? (search_fn)search_kernel<DT_I8, 0, 1, true> : (search_fn)search_kernel<DT_F32, 0, 1, true>;
+    return i8 ? general_kernel_s<DT_I8>(S) : general_kernel_s<DT_F32>(S);
+}
+
+// The register walkers instantiated (walk_fast.h), by the values their LDS is sized from: the row shape DT, DIM (f32 rows of
+// 100 / 200 dims unrolled, 0: any other f32 dim streamed; int8 rows of 128 bytes as DIM 0, of 256 / 512 bytes as DIM 256 /
+// 512), the list slots S, the visited form V16, trail mode and 64-id layers (WIDE). nullptr: not instantiated.
+template <int DT, int DIM, int S>
+static search_fn fast_kernel_v(int v16) {
+    constexpr bool streamed = (DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256);
+    if constexpr (S == 1 && !streamed) {
+        if (v16 == 4) return fast_kernel<DT, DIM, S, false, 4>;
+    }
+    if constexpr (DT == DT_F32 && S <= 4) {
+        if (v16 == 5) return fast_kernel<DT, DIM, S, false, 5>;
+    }
+    if (v16 == 3) return fast_kernel<DT, DIM, S, false, 3>;
+    if constexpr (S <= 17 && !walk_list_is_long(S, false)) { // (longer lists: an exact set of ~40 x max_search ids fits no LDS)
+        if (v16 == 0) return fast_kernel<DT, DIM, S>;
+    }
+    return nullptr;
+}
+template <int DT, int DIM>
+static search_fn fast_kernel_s(uint32_t S, bool trail, int v16) {
+    if (trail) return S == 1 && v16 == 0 ? fast_kernel<DT, DIM, 1, true> : nullptr;
+    switch (S) {
+    case 1: return fast_kernel_v<DT, DIM, 1>(v16);
+    case 2: return fast_kernel_v<DT, DIM, 2>(v16);
+    case 4: return fast_kernel_v<DT, DIM, 4>(v16);
+    case 8: return fast_kernel_v<DT, DIM, 8>(v16);
+    }
+    if constexpr (!((DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256))) { // (streamed f32 dims, wide int8 rows: up to 17 slots)
+        switch (S) {
+        case 33: return fast_kernel_v<DT, DIM, 33>(v16);
+        case 65: return fast_kernel_v<DT, DIM, 65>(v16);
+        case 129: return fast_kernel_v<DT, DIM, 129>(v16);
+        }
+    }
+    return S == 17 ? fast_kernel_v<DT, DIM, 17>(v16) : nullptr;
+}
+template <int DT, int DIM>
+static search_fn fast_wide_kernel_s(uint32_t S) {
+    switch (S) {
+    case 1: return fast_kernel<DT, DIM, 1, false, 3, true>;
+    case 2: return fast_kernel<DT, DIM, 2, false, 3, true>;
+    case 4: return fast_kernel<DT, DIM, 4, false, 3, true>;
+    case 8: return fast_kernel<DT, DIM, 8, false, 3, true>;
+    case 17: return fast_kernel<DT, DIM, 17, false, 3, true>;
+    }
+    return nullptr;
+}
+static search_fn fast_kernel_of(const SearchTarget& T, uint32_t S, bool trail, int v16, bool wide) {
+    const bool i8 = T.dtype == GRANNE_HIP_I8;
+    if (wide) { // (64-id layers: no visited set, no trail walks, int8 rows of 128 bytes)
+        if (trail || v16 != 3 || (i8 && T.row_bytes != 128)) return nullptr;
+        if (i8) return fast_wide_kernel_s<DT_I8, 0>(S);
+        return T.dim == 100 ? fast_wide_kernel_s<DT_F32, 100>(S) : T.dim == 200 ? fast_wide_kernel_s<DT_F32, 200>(S) : fast_wide_kernel_s<DT_F32, 0>(S);
+    }
+    if (i8 && T.row_bytes == 256) return fast_kernel_s<DT_I8, 256>(S, trail, v16);
+    if (i8 && T.row_bytes == 512) return fast_kernel_s<DT_I8, 512>(S, trail, v16);
+    if (i8) return T.row_bytes == 128 ? fast_kernel_s<DT_I8, 0>(S, trail, v16) : nullptr;
+    return T.dim == 100 ? fast_kernel_s<DT_F32, 100>(S, trail, v16) : T.dim == 200 ? fast_kernel_s<DT_F32, 200>(S, trail, v16) : fast_kernel_s<DT_F32, 0>(S, trail, v16);
+}
+
+// which walker serves a launch, its kernel, and how the launch is sized
+struct WalkPlan {
+    uint64_t walker = GRANNE_HIP_WALKER_GENERAL; // what GRANNE_HIP_OPT_LAST_WALKER reports
+    uint32_t S = 0;         // list slots of 64 keys
+    int v16 = 0;            // FastWalker's V16: 0 = the exact 32-bit table, 3 = no visited set, 4 = none + rows touched
+                            // ahead, 5 = none + revisits skipped before their rows are fetched
+    search_fn fn = nullptr; // null: the launch cannot be planned (the error is set)
+    uint32_t lds_bytes = 0; // the launch's dynamic LDS
+    uint32_t grid = 0;      // blocks of 64 lanes: the walkers, then the tail blocks; or the exact walker's blocks alone
+    uint32_t visited_slots = 0, upper_slots = 0, front_eighths = 7;
+    uint32_t maxc = 0, lrow_bytes = 16, stage_bytes = 0, adjspec_bytes = 0;
+    uint32_t ovf_slots = 0, ovf_regions = 0; // visited-set overflow tables
+    uint32_t slow_blocks = 0, tail_blocks = 0; // the exact walker's containers; its blocks behind the walkers
+};
+
+// The register walker (walk_fast.h) serves the common shapes: every layer up to 64 ids wide on the device, ids within 31
+// bits, f32 rows of any dim or int8 rows of 128 / 256 / 512 bytes. Its list holds 64*S keys and must hold max_search of
+// them plus a few spare places: two distances of a walk tie surprisingly often (4000 candidates share 2^23 float values),
+// and a tie between entry max_search-1 and an entry pushed off the end hands the walk over -- with spare places that takes
+// a run of ties.
+constexpr uint32_t FAST_MAX_SEARCH = 8192; // f32 rows of 100 / 200 dims and int8 rows of 128 bytes: two-level lists of up to 129 x 64 keys
+
+static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool trail) {
+    WalkPlan P;
+    const bool i8 = T.dtype == GRANNE_HIP_I8;
+    const bool streamed = !i8 && T.dim != 100 && T.dim != 200; // f32: 100 and 200 fully unrolled, any other dim streamed (dims below 32: the tail alone)
+    // Layers of up to 64 ids per node (graphs with num_neighbors 33..63: the GPU builder makes them, BuildConfig::num_neighbors
+    // src/index/mod.rs:242) are walked in two passes of 32 pairs per expansion (FastWalker's WIDE) -- instantiated for lists of
+    // up to 17 x 64 keys, without a visited set, not for Granne::reorder's trail walks, and for int8 rows of 128 bytes only.
+    const bool wide = T.max_dev_width == 64;
+    // (ids: 31 bits. A 2^31-element index needs 275 GB for its bottom layer's 128-byte adjacency rows alone, so the
+    //  reference's 2^32 - 2 capacity, src/index/mod.rs:27-28, is out of one device's reach whatever the key layout)
+    const bool shape = T.max_dev_width <= 64 && T.n_elements <= WALK_MAX_ELEMENTS &&
+                       (!i8 || T.row_bytes == 128 || (!wide && (T.row_bytes == 256 || T.row_bytes == 512))); // (int8 dims <= 512)
+    // the longest max_search the register walker is instantiated for: lists of up to 17 x 64 keys for 64-id layers, int8
+    // rows of 256 / 512 bytes and streamed f32 dims, else two-level lists of up to 129 x 64 keys
+    const uint32_t fast_max = (wide || (i8 ? T.row_bytes != 128 : streamed)) ? 1024u : FAST_MAX_SEARCH;
+    const bool fast = shape && ef <= fast_max && !(wide && trail);
+    const uint32_t ef_walk = fast ? ef : (ef > 256 ? 256 : ef); // what the register / general walker is sized for
+    const bool all_slow = T.opt_force_slow || (!fast && ef > 256);
+    P.walker = all_slow ? GRANNE_HIP_WALKER_EXACT
+                        : fast ? (wide ? GRANNE_HIP_WALKER_REGISTER_WIDE : GRANNE_HIP_WALKER_REGISTER) : GRANNE_HIP_WALKER_GENERAL;
+    if (fast)
+        P.S = ef <= 60 ? 1u : ef <= 124 ? 2u : ef <= 252 ? 4u : ef <= 508 ? 8u : ef <= 1024 ? 17u : ef <= 2048 ? 33u : ef <= 4096 ? 65u : 129u;
+    else
+        P.S = ef_walk <= 64 ? 1u : ef_walk <= 128 ? 2u : 4u;
+
+    // The register walkers walk without a visited set by default (VisitedNone, wave_prims.h: the list itself is searched for
+    // a candidate's id): no table in LDS, only the query's staging area and what a tail block needs, so the registers
+    // alone bound the walkers per CU. GRANNE_HIP_OPT_VISITED16 = 1..3 switches the exact set on (a 32-bit open-addressing
+    // table in LDS + a global overflow table): n_dist is then the reference's count of distinct evaluated nodes.
+    const int vmode = T.opt_visited16 ? (int)T.opt_visited16 : knobs().visited;
+    const bool none = vmode == 4 || vmode == 0;
+    const bool longest = walk_list_is_long((int)P.S, wide) || wide; // (lists of 33 / 65 / 129 slots, and 64-id layers: instantiated without a set only, whatever the options say)
+    uint32_t walk_lds;
+    if (fast && !trail && ((none && !T.opt_visited_slots) || longest)) {
+        // a launch of a few queries leaves the chip idle: its walkers touch the next node's rows ahead (walk_fast.h, TOUCH)
+        const uint32_t touch_max = knobs().touch_max >= 0 ? (uint32_t)knobs().touch_max : 256u; // (round 5: +4 % at 256 queries, -10 % at 1024: profiles/r5_touch.txt)
+        const bool touch_shape = P.S == 1 && !wide && !streamed && !(i8 && T.row_bytes != 128);
+        P.v16 = (touch_shape && nq <= touch_max) ? 4 : 3;
+        // launches of many walks are bound by bandwidth: their walkers skip revisits BEFORE the rows are fetched (walk_fast.h, SEEN)
+        const uint64_t seen_min = knobs().seen_min >= 0 ? (uint64_t)knobs().seen_min : T.opt_seen_min; // (GRANNE_HIP_SEEN_MIN overrides the option: experiments)
+        // (f32 rows: the walkers per CU are bound by registers there, 8 KB of cache each fit; int8 walkers are four times as many
+        //  and lose more to the look-up than the few revisits of their rows cost: measured, profiles/r6_seen_ab.txt)
+        if (P.S <= 4 && !wide && !i8 && nq >= seen_min) P.v16 = 5; // (every f32 dim: unrolled and streamed)
+        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, 0u, P.v16 == 5, wide);
+        const uint32_t least = lds_query_bytes(T.row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
+        if (walk_lds < least) walk_lds = least;
+    } else {
+        // The front table must hold the walk's visited ids (~40 x max_search on 10M uniform points) below its 7/8
+        // load limit: 4096 slots at max_search 50. (Tables of 3 * 2^k slots are accepted as an option; 3072 slots --
+        // 12 KB, twelve walkers per CU instead of nine -- measured no faster: 0.5 % of the walks spill to the
+        // overflow table and a launch lasts as long as its slowest walk.)
+        uint32_t want = T.opt_visited_slots ? (uint32_t)T.opt_visited_slots : next_pow2(ef_walk * 64u);
+        if (!T.opt_visited_slots) {
+            if (want < 1024) want = 1024;
+            // larger walks spill to the global overflow table. A launch with more walkers than the chip
+            // holds is better off with small tables (more walkers per CU; measured on the 10M build:
+            // 37.7 s vs 45.4 s), one batch of a thousand queries with fewer spills (ef 200: 508k vs 421k q/s)
+            uint32_t cap = nq >= 4096 ? 4096u : 8192u;
+            // long lists (max_search > 252) walk ~20x max_search nodes: most inserts land in the overflow table
+            // whatever the front table's size, and a 32 KB front table beside the list's LDS mirror leaves room
+            // for only three walkers per CU (768 of a batch of 1024 resident: the batch runs in two rounds)
+            if (fast && P.S >= 8) cap = 4096u;
+            if (want > cap) want = cap;
+        }
+        P.visited_slots = want;
+        P.upper_slots = want < 1024 ? want : 1024;
+        if (fast) { // walk_fast.h: [query][S >= 8: 64*S keys][visited front table]
+            walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, P.visited_slots, false, wide);
+        } else {
+            // the general walker (search_kernel.h): int8 keeps its speculative adjacency rows in registers (Walker::REGSPEC),
+            // run-time-dim f32 parks them in LDS. LDS plan: the visited table dominates; the f32 stage gets what keeps four
+            // walkers per CU (160 KiB / 4) when that leaves it at least 16 rows, else up to 32 rows within 64 KiB, else
+            // whatever fits in the CU's 160 KiB.
+            P.adjspec_bytes = i8 ? 0u : LDS_ADJSPEC_BYTES;
+            const uint32_t fixed = lds_query_bytes(T.row_bytes) + LDS_FIXED_BYTES + P.adjspec_bytes;
+            if (!i8) {
+                P.lrow_bytes = ((T.row_bytes / 16) | 1u) * 16u; // odd number of 16-byte units: conflict-free ds_read_b128
+                const uint32_t wmax = T.max_dev_width < 64 ? T.max_dev_width : 64;
+                const uint32_t used = fixed + P.visited_slots * 4u;
+                auto rows_in = [&](uint32_t budget) { return budget > used ? (budget - used) / P.lrow_bytes : 0u; };
+                uint32_t maxc = rows_in(40u * 1024u);
+                if (maxc < 16) maxc = rows_in(64u * 1024u) < 32u ? rows_in(64u * 1024u) : 32u;
+                if (maxc < 16) maxc = rows_in(160u * 1024u) < 32u ? rows_in(160u * 1024u) : 32u;
+                if (maxc > wmax) maxc = wmax;
+                if (maxc < 1) maxc = 1;
+                P.maxc = maxc;
+                P.stage_bytes = P.maxc * P.lrow_bytes;
+            }
+            walk_lds = fixed + P.stage_bytes + P.visited_slots * 4u;
+        }
+    }
+    if (walk_lds > 160u * 1024u) {
+        fail(GRANNE_HIP_ERR_INVALID, "dimension too large for the LDS stage");
+        return P;
+    }
+    // A walk that will outgrow the front table anyway (it visits ~40 x max_search nodes) freezes it at 5/8 load
+    // instead of 7/8: every later lookup of a new id runs to an empty slot of the frozen table, 8 probes on average
+    // at 7/8 load with the wave waiting for its slowest lane, 2.7 at 5/8 (C5-like int8 walk at max_search 200:
+    // launch 2.70 -> 2.44 ms; f32 at 800: 7.75 -> 6.5 ms).
+    P.front_eighths = (!P.v16 && (uint64_t)ef * 40u > (uint64_t)P.visited_slots) ? 5u : 7u;
 
     // visited-set overflow pool: one table per walker that can be resident at once (bounded by
     // LDS: 160 KiB per CU, and by 32 waves per CU), at most one per query
-    uint32_t ovf_slots = 0, ovf_regions = 0;
-    if (!all_slow && ix->opt_overflow_slots != 1 && plan.v16 < 3) { // (no visited set, no overflow)
-        ovf_slots = ix->opt_overflow_slots ? next_pow2((uint32_t)ix->opt_overflow_slots) : next_pow2(ef_walk * 64u);
-        if (!ix->opt_overflow_slots && ovf_slots < 4096) ovf_slots = 4096;
-        if (ovf_slots < 512) ovf_slots = 512;
-        if (ovf_slots > (1u << 20)) ovf_slots = 1u << 20;
-        uint32_t per_cu = (160u * 1024u) / (plan.lds_bytes ? plan.lds_bytes : 1u);
+    if (!all_slow && T.opt_overflow_slots != 1 && P.v16 < 3) { // (no visited set, no overflow)
+        P.ovf_slots = T.opt_overflow_slots ? next_pow2((uint32_t)T.opt_overflow_slots) : next_pow2(ef_walk * 64u);
+        if (!T.opt_overflow_slots && P.ovf_slots < 4096) P.ovf_slots = 4096;
+        if (P.ovf_slots < 512) P.ovf_slots = 512;
+        if (P.ovf_slots > (1u << 20)) P.ovf_slots = 1u << 20;
+        uint32_t per_cu = (160u * 1024u) / (walk_lds ? walk_lds : 1u);
         if (per_cu > 32) per_cu = 32;
         if (per_cu < 1) per_cu = 1;
-        ovf_regions = 256u * per_cu * 2u; // 2x the residency bound keeps the region probe short
-        if (ovf_regions > nq) ovf_regions = nq;
-        if (ovf_regions > SCRATCH_MAX_REGIONS) ovf_regions = SCRATCH_MAX_REGIONS;
+        P.ovf_regions = 256u * per_cu * 2u; // 2x the residency bound keeps the region probe short
+        if (P.ovf_regions > nq) P.ovf_regions = nq;
+        if (P.ovf_regions > SCRATCH_MAX_REGIONS) P.ovf_regions = SCRATCH_MAX_REGIONS;
     }
 
-    // scratch: [control words][region states] (zero between launches) [hand-over list][overflow tables][exact walker]
     // The exact walker's blocks: a few as the tail of a register-walker launch (hand-overs are rare), many when the whole
     // batch is its to walk (max_search beyond the register lists, GRANNE_HIP_OPT_FORCE_SLOW): one block per query up to
-    // 32x the option (512 at its default of 16) -- each block owns 12 bytes x slow_slots of global scratch.
-    // Every block owns 12 bytes x slow_slots + 8 x max_search of global scratch (3 MB at the default 2^18 slots), and the
-    // scratch block is kept per (index, stream): the many-block form is bounded by SLOW_SCRATCH_BUDGET bytes (never below
-    // the option itself), so that a handful of streams searching beyond the register lists hold a few GB, not tens.
-    uint32_t slow_blocks = (uint32_t)ix->opt_slow_blocks;
-    const uint32_t slots = (uint32_t)ix->opt_slow_slots;
-    if (all_slow) {
-        uint32_t most = slow_blocks * 32u;
-        const size_t per_block = (size_t)slots * 12 + (size_t)ef * 8;
+    // 32x the option (512 at its default of 16). Every block owns 12 bytes x slow_slots + 8 x max_search of global scratch
+    // (3 MB at the default 2^18 slots), and the scratch block is kept per (index, stream): the many-block form is bounded
+    // by SLOW_SCRATCH_BUDGET bytes (never below the option itself), so that a handful of streams searching beyond the
+    // register lists hold a few GB, not tens.
+    P.slow_blocks = (uint32_t)T.opt_slow_blocks;
+    const uint32_t slow_lds = lds_query_bytes(T.row_bytes) + 64 * 8;
+    if (all_slow) { // every query on the exact walker: its kernel alone
+        uint32_t most = P.slow_blocks * 32u;
+        const size_t per_block = (size_t)T.opt_slow_slots * 12 + (size_t)ef * 8;
         const size_t fit = SLOW_SCRATCH_BUDGET / per_block;
-        if (most > fit) most = fit > slow_blocks ? (uint32_t)fit : slow_blocks;
-        slow_blocks = nq < most ? (nq > slow_blocks ? nq : slow_blocks) : most;
+        if (most > fit) most = fit > P.slow_blocks ? (uint32_t)fit : P.slow_blocks;
+        P.slow_blocks = nq < most ? (nq > P.slow_blocks ? nq : P.slow_blocks) : most;
+        P.fn = !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
+        P.lds_bytes = slow_lds;
+        P.grid = P.slow_blocks;
+        return P;
     }
-    const uint32_t n_tail = all_slow ? 0u : (slow_blocks < nq ? slow_blocks : nq);
+    if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
+    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide) : general_kernel_of(T.dtype, P.S, trail);
+    if (!P.fn) {
+        fail(GRANNE_HIP_ERR_INVALID, "no walker is instantiated for this launch (list slots %u, visited form %d, trail %d, 64-id layers %d)",
+             P.S, P.v16, (int)trail, (int)wide);
+        return P;
+    }
+    P.lds_bytes = walk_lds > slow_lds ? walk_lds : slow_lds; // the tail blocks stage a query too
+    if (P.lds_bytes > 160u * 1024u) {
+        P.fn = nullptr;
+        fail(GRANNE_HIP_ERR_INVALID, "dimension too large for the LDS stage");
+        return P;
+    }
+    P.tail_blocks = P.slow_blocks < nq ? P.slow_blocks : nq;
+    P.grid = nq + P.tail_blocks;
+    return P;
+}
+
+static int search_launch(const SearchTarget& T, SearchCall c) {
+    if (c.ef == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_search must be > 0 (the reference panics, src/index/mod.rs:1019)");
+    if (c.nq == 0) return GRANNE_HIP_OK;
+    if (c.n_batches > MAX_LAUNCH_BATCHES) return fail(GRANNE_HIP_ERR_INVALID, "at most %u batches per launch", MAX_LAUNCH_BATCHES);
+    if (c.n_batches && (uint64_t)c.n_batches * c.nq > 0x7FFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many queries in one launch");
+    DeviceGuard g(T.device);
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", T.device);
+    hipStream_t s = c.stream;
+    const uint32_t batch_nq = c.nq;
+    uint32_t nq = c.nq; // walkers of the launch
+    if (c.n_batches) {
+        for (uint32_t b = 0; b < c.n_batches; ++b)
+            if (!c.batches[b].queries || !c.batches[b].out_counts || (c.k && (!c.batches[b].out_ids || !c.batches[b].out_dists)))
+                return fail(GRANNE_HIP_ERR_INVALID, "null buffer (batch %u)", b);
+        if (c.k == 0) {
+            for (uint32_t b = 0; b < c.n_batches; ++b) HIP_TRY(hipMemsetAsync(c.batches[b].out_counts, 0, (size_t)nq * 4, s));
+            return GRANNE_HIP_OK;
+        }
+        c.queries = c.batches[0].queries;
+        c.ids = c.batches[0].out_ids;
+        c.dists = c.batches[0].out_dists;
+        c.counts = c.batches[0].out_counts;
+        c.stats = c.batches[0].out_stats;
+        nq *= c.n_batches;
+    }
+    if (c.k == 0 && !c.trail) { // .take(0): every result is empty (src/index/mod.rs:974-977)
+        if (!c.counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+        HIP_TRY(hipMemsetAsync(c.counts, 0, (size_t)nq * 4, s));
+        return GRANNE_HIP_OK;
+    }
+    if (!c.queries || (!c.trail && (!c.ids || !c.dists || !c.counts))) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+    const WalkPlan W = plan_walk(T, c.ef, nq, c.trail != nullptr);
+    if (!W.fn) return GRANNE_HIP_ERR_INVALID;
+
+    // scratch: [control words][region states] (zero between launches) [hand-over list][overflow tables][exact walker]
+    const uint32_t slots = (uint32_t)T.opt_slow_slots;
     const size_t list_bytes = ((size_t)nq * 4 + 15) & ~(size_t)15;
     size_t off_list = SCRATCH_FIXED;
     size_t off_ovf = off_list + list_bytes;
-    const uint32_t ovf_stride = ovf_slots;
-    size_t off_vis = off_ovf + (size_t)ovf_regions * ovf_stride * 4;
-    size_t off_pq = off_vis + (size_t)slow_blocks * slots * 4;
-    size_t off_res = off_pq + (size_t)slow_blocks * slots * 8;
-    size_t total = off_res + (size_t)slow_blocks * ef * 8;
+    size_t off_vis = off_ovf + (size_t)W.ovf_regions * W.ovf_slots * 4;
+    size_t off_pq = off_vis + (size_t)W.slow_blocks * slots * 4;
+    size_t off_res = off_pq + (size_t)W.slow_blocks * slots * 8;
+    size_t total = off_res + (size_t)W.slow_blocks * c.ef * 8;
     // The cache's mutex covers finding (or growing) this stream's block and the enqueue -- host work of microseconds.
-    // Whatever waits for the GPU (the synchronisation behind h_slow_count) happens after it is released: host threads
+    // Whatever waits for the GPU (the synchronisation behind slow_count) happens after it is released: host threads
     // searching one index on streams of their own do not queue behind each other's kernels.
     struct Bury { // (declared before the lock: destroyed after it is released)
         std::vector<uint8_t*> blocks;
@@ -1174,12 +1195,12 @@ static int search_launch(const SearchTarget* ix, const void* d_queries, int64_t 
             for (auto* b : blocks) (void)hipFree(b); // waits for the device: whatever still used an evicted block is over
         }
     } bury;
-    std::unique_lock<std::mutex> cache_lock(ix->scratch->mu);
+    std::unique_lock<std::mutex> cache_lock(T.scratch->mu);
     uint8_t* scratch = nullptr;
     bool transient = false;
     {
-        int r = scratch_for(ix->scratch, s, total, &scratch, &transient);
-        bury.blocks.swap(ix->scratch->graveyard);
+        int r = scratch_for(T.scratch, s, total, &scratch, &transient);
+        bury.blocks.swap(T.scratch->graveyard);
         if (r) return r;
     }
     struct FreeTransient { // a block of the stream-ordered allocator goes back after the launch's last use of it
@@ -1193,95 +1214,88 @@ static int search_launch(const SearchTarget* ix, const void* d_queries, int64_t 
 
     SlowParams sp;
     SearchParams& p = sp.sp;
-    p.elements = ix->d_elements;
-    p.n_elements = ix->n_elements;
-    p.dim = ix->dim;
-    p.row_bytes = ix->row_bytes;
-    p.row_stride = ix->row_stride;
-    p.layers = ix->d_layers;
-    p.n_layers = ix->n_layers;
-    p.queries = (const uint8_t*)d_queries;
-    p.q_stride = q_stride;
+    p.elements = T.d_elements;
+    p.n_elements = T.n_elements;
+    p.dim = T.dim;
+    p.row_bytes = T.row_bytes;
+    p.row_stride = T.row_stride;
+    p.layers = T.d_layers;
+    p.n_layers = T.n_layers;
+    p.queries = (const uint8_t*)c.queries;
+    p.q_stride = c.q_stride ? c.q_stride : (int64_t)T.dim * elem_size(T.dtype);
     p.nq = nq;
-    p.ef = ef;
-    p.k = k;
-    p.out_ids = d_ids;
-    p.out_dists = d_dists;
-    p.out_counts = d_counts;
-    p.out_stats = d_stats;
-    p.visited_slots = plan.visited_slots;
-    p.upper_slots = plan.upper_slots;
-    // A walk that will outgrow the front table anyway (it visits ~40 x max_search nodes) freezes it at 5/8 load
-    // instead of 7/8: every later lookup of a new id runs to an empty slot of the frozen table, 8 probes on average
-    // at 7/8 load with the wave waiting for its slowest lane, 2.7 at 5/8 (C5-like int8 walk at max_search 200:
-    // launch 2.70 -> 2.44 ms; f32 at 800: 7.75 -> 6.5 ms).
-    p.front_eighths = (!plan.v16 && (uint64_t)ef * 40u > (uint64_t)plan.visited_slots) ? 5u : 7u;
-    if (knobs().front_eighths >= 1 && knobs().front_eighths <= 7) p.front_eighths = (uint32_t)knobs().front_eighths;
-    p.maxc = plan.maxc;
-    p.lrow_bytes = plan.lrow_bytes;
-    p.stage_bytes = plan.stage_bytes;
-    p.adjspec_bytes = plan.adjspec_bytes;
+    p.ef = c.ef;
+    p.k = c.k;
+    p.out_ids = c.ids;
+    p.out_dists = c.dists;
+    p.out_counts = c.counts;
+    p.out_stats = c.stats;
+    p.visited_slots = W.visited_slots;
+    p.upper_slots = W.upper_slots;
+    p.front_eighths = W.front_eighths;
+    p.maxc = W.maxc;
+    p.lrow_bytes = W.lrow_bytes;
+    p.stage_bytes = W.stage_bytes;
+    p.adjspec_bytes = W.adjspec_bytes;
     p.slow_count = ctl + CTL_SLOW_COUNT;
     p.slow_list = (uint32_t*)(scratch + off_list);
     p.force_slow = 0;
     p.spec = 1;
-    p.sketch = ix->d_sketch;
+    p.sketch = T.d_sketch;
     p.ovf.tables = (uint32_t*)(scratch + off_ovf);
     p.ovf.state = (uint32_t*)(scratch + SCRATCH_STATE_OFF);
-    p.ovf.slots = ovf_slots;
-    p.ovf.stride = ovf_stride;
-    p.ovf.regions = ovf_regions;
-    p.ovf.spilled = d_status ? d_status + 2 : ctl + CTL_SPILLED;
-    p.trail_out = d_trail;
-    p.trail_layers = trail_layers;
-    p.n_batches = n_batches;
+    p.ovf.slots = W.ovf_slots;
+    p.ovf.stride = W.ovf_slots;
+    p.ovf.regions = W.ovf_regions;
+    p.ovf.spilled = c.status ? c.status + 2 : ctl + CTL_SPILLED;
+    p.trail_out = c.trail;
+    p.trail_layers = c.trail_layers;
+    p.n_batches = c.n_batches;
     p.batch_nq = batch_nq;
-    for (uint32_t b = 0; b < n_batches; ++b) p.batch[b] = batches[b];
+    for (uint32_t b = 0; b < c.n_batches; ++b) p.batch[b] = c.batches[b];
     sp.ctl = ctl;
     sp.vis = (uint32_t*)(scratch + off_vis);
     sp.pq = (uint64_t*)(scratch + off_pq);
     sp.res = (uint64_t*)(scratch + off_res);
     sp.slots = slots;
-    sp.all = all_slow ? 1u : 0u;
-    sp.status2 = d_status;
-    sp.host_status = host_status;
+    sp.all = W.walker == GRANNE_HIP_WALKER_EXACT ? 1u : 0u;
+    sp.status2 = c.status;
+    sp.host_status = c.host_status;
 
-    if (ix->last_walker)
-        ix->last_walker->store(all_slow ? GRANNE_HIP_WALKER_EXACT
-                                        : fast ? (fast_wide(ix) ? GRANNE_HIP_WALKER_REGISTER_WIDE : GRANNE_HIP_WALKER_REGISTER)
-                                               : GRANNE_HIP_WALKER_GENERAL);
-    const uint32_t slow_lds = lds_query_bytes(ix->row_bytes) + 64 * 8;
-    if (all_slow) { // every query on the exact walker: its kernel alone
-        if (ev_before) HIP_TRY(hipEventRecord(ev_before, s));
-        if (ix->dtype == GRANNE_HIP_F32)
-            hipLaunchKernelGGL(slow_kernel<DT_F32>, dim3(slow_blocks), dim3(64), slow_lds, s, sp);
-        else
-            hipLaunchKernelGGL(slow_kernel<DT_I8>, dim3(slow_blocks), dim3(64), slow_lds, s, sp);
-        HIP_TRY(hipGetLastError());
-        if (ev_after) HIP_TRY(hipEventRecord(ev_after, s));
-    } else {
-        search_fn fn = fast ? pick_fast_kernel(ix, fastS, d_trail != nullptr, plan.v16)
-                            : (d_trail ? pick_trail_kernel(ix->dtype) : pick_kernel(ix->dtype, ef_walk));
-        uint32_t lds = plan.lds_bytes > slow_lds ? plan.lds_bytes : slow_lds; // the tail blocks stage a query too
-        lds += (uint32_t)knobs().lds_pad; // occupancy experiments
-        if (lds > 160u * 1024u) return fail(GRANNE_HIP_ERR_INVALID, "dimension too large for the LDS stage");
-        if (lds > 32u * 1024u)
-            HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (ev_before) HIP_TRY(hipEventRecord(ev_before, s));
-        hipLaunchKernelGGL(fn, dim3(nq + n_tail), dim3(64), lds, s, sp);
-        HIP_TRY(hipGetLastError());
-        if (ev_after) HIP_TRY(hipEventRecord(ev_after, s));
-    }
+    if (T.last_walker) T.last_walker->store(W.walker);
+    if (W.walker != GRANNE_HIP_WALKER_EXACT && W.lds_bytes > 32u * 1024u)
+        HIP_TRY(hipFuncSetAttribute((const void*)W.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W.lds_bytes));
+    if (c.ev_before) HIP_TRY(hipEventRecord(c.ev_before, s));
+    hipLaunchKernelGGL(W.fn, dim3(W.grid), dim3(64), W.lds_bytes, s, sp);
+    HIP_TRY(hipGetLastError());
+    if (c.ev_after) HIP_TRY(hipEventRecord(c.ev_after, s));
 
-    if (h_slow_count) {
+    if (c.slow_count) {
         uint32_t hs[2] = {0, 0};
         HIP_TRY(hipMemcpyAsync(hs, ctl + CTL_LAST_SLOW, 8, hipMemcpyDeviceToHost, s)); // enqueued under the lock, ...
         cache_lock.unlock();
         HIP_TRY(hipStreamSynchronize(s));                                               // ... waited for outside it
-        h_slow_count[0] = hs[0]; // queries served by the global-memory walker
-        h_slow_count[1] = hs[1]; // its containers ran out
+        c.slow_count[0] = hs[0]; // queries served by the global-memory walker
+        c.slow_count[1] = hs[1]; // its containers ran out
     }
     return GRANNE_HIP_OK;
+}
+
+// a search of the C ABI's device-pointer entry points on an index
+static SearchCall index_call(const void* d_queries, uint32_t nq, uint32_t max_search, uint32_t num_neighbors, uint64_t* d_out_ids,
+                             float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats, uint32_t* d_status, void* stream) {
+    SearchCall c;
+    c.queries = d_queries;
+    c.nq = nq;
+    c.ef = max_search;
+    c.k = num_neighbors;
+    c.ids = d_out_ids;
+    c.dists = d_out_dists;
+    c.counts = d_out_counts;
+    c.stats = d_out_stats;
+    c.status = d_status;
+    c.stream = (hipStream_t)stream;
+    return c;
 }
 
 extern "C" int granne_hip_search_batch_device(const granne_hip_index* ix, const void* d_queries, uint32_t nq,
@@ -1289,9 +1303,8 @@ extern "C" int granne_hip_search_batch_device(const granne_hip_index* ix, const 
                                               float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats,
                                               uint32_t* d_status, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    SearchTarget T = target_of(ix);
-    return search_launch(&T, d_queries, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors,
-                         d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, (hipStream_t)stream, nullptr);
+    return search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()),
+                         index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, stream));
 }
 
 extern "C" int granne_hip_search_batch_device_timed(const granne_hip_index* ix, const void* d_queries, uint32_t nq,
@@ -1299,10 +1312,10 @@ extern "C" int granne_hip_search_batch_device_timed(const granne_hip_index* ix, 
                                                     float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats,
                                                     uint32_t* d_status, void* stream, void* ev_before, void* ev_after) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    SearchTarget T = target_of(ix);
-    return search_launch(&T, d_queries, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors,
-                         d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, (hipStream_t)stream, nullptr,
-                         nullptr, 0, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
+    SearchCall c = index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, stream);
+    c.ev_before = (hipEvent_t)ev_before;
+    c.ev_after = (hipEvent_t)ev_after;
+    return search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()), c);
 }
 
 // A batch in flight beside the caller's stream. begin: the search is ordered after what `stream` holds (an event), runs on
@@ -1350,9 +1363,8 @@ extern "C" int granne_hip_search_begin_device(const granne_hip_index* cix, const
     }
     HIP_TRY(hipEventRecord(F.ready, (hipStream_t)stream));
     HIP_TRY(hipStreamWaitEvent(F.stream, F.ready, 0));
-    SearchTarget T = target_of(ix);
-    int rc = search_launch(&T, d_queries, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors, d_out_ids,
-                           d_out_dists, d_out_counts, d_out_stats, d_status, F.stream, nullptr);
+    int rc = search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()),
+                           index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, F.stream));
     if (rc) {
         (void)hipStreamSynchronize(F.stream); // an error return leaves nothing running
         return rc;
@@ -1392,7 +1404,7 @@ extern "C" int granne_hip_search_batches_device(const granne_hip_index* ix, uint
     if (n_batches == 0 || nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_out_counts || (num_neighbors && (!d_out_ids || !d_out_dists)))
         return fail(GRANNE_HIP_ERR_INVALID, "null pointer array");
-    SearchTarget T = target_of(ix);
+    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
     // as many batches per launch as keep the launch's walker count within 31 bits (and the kernel argument table)
     uint32_t per = MAX_LAUNCH_BATCHES;
     while (per > 1 && (uint64_t)per * nq > 0x7FFFFFFFull) per >>= 1;
@@ -1406,9 +1418,10 @@ extern "C" int granne_hip_search_batches_device(const granne_hip_index* ix, uint
             io[b].out_counts = d_out_counts[b0 + b];
             io[b].out_stats = d_out_stats ? d_out_stats[b0 + b] : nullptr;
         }
-        int rc = search_launch(&T, nullptr, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors, nullptr,
-                               nullptr, nullptr, nullptr, d_status, (hipStream_t)stream, nullptr, nullptr, 0, nullptr, nullptr,
-                               nullptr, io, nb);
+        SearchCall c = index_call(nullptr, nq, max_search, num_neighbors, nullptr, nullptr, nullptr, nullptr, d_status, stream);
+        c.batches = io;
+        c.n_batches = nb;
+        int rc = search_launch(T, c);
         if (rc) return rc;
     }
     return GRANNE_HIP_OK;
@@ -1562,7 +1575,8 @@ extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* 
         c->h_cap = 256u << 10;
     }
     hipStream_t s = c->stream;
-    SearchTarget T = target_of(ix);
+    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+    SearchCall call = index_call(nullptr, nq, max_search, num_neighbors, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     uint32_t slow[2] = {0, 0};
     if (staged) {
         // Small calls (one query per call is the reference's own shape, src/index/mod.rs:140-150): no copy
@@ -1576,9 +1590,13 @@ extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* 
         uint32_t* hst = (uint32_t*)(c->h_pin + total);
         memcpy(c->h_pin, queries, qb);
         hst[0] = hst[1] = hst[2] = hst[3] = 0;
-        int r = search_launch(&T, dp, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors,
-                              (uint64_t*)(dp + o_ids), (float*)(dp + o_d), (uint32_t*)(dp + o_c), (uint64_t*)(dp + o_s),
-                              nullptr, s, nullptr, nullptr, 0, nullptr, nullptr, (uint32_t*)(dp + total));
+        call.queries = dp;
+        call.ids = (uint64_t*)(dp + o_ids);
+        call.dists = (float*)(dp + o_d);
+        call.counts = (uint32_t*)(dp + o_c);
+        call.stats = (uint64_t*)(dp + o_s);
+        call.host_status = (uint32_t*)(dp + total);
+        int r = search_launch(T, call);
         hipError_t e = hipStreamSynchronize(s);
         if (r) return r;
         if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
@@ -1601,9 +1619,13 @@ extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* 
     }
     uint8_t* buf = c->d_buf;
     HIP_TRY(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));
-    int r = search_launch(&T, buf, (int64_t)ix->dim * elem_size(ix->dtype), nq, max_search, num_neighbors,
-                          (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), (uint64_t*)(buf + o_s),
-                          nullptr, s, slow);
+    call.queries = buf;
+    call.ids = (uint64_t*)(buf + o_ids);
+    call.dists = (float*)(buf + o_d);
+    call.counts = (uint32_t*)(buf + o_c);
+    call.stats = (uint64_t*)(buf + o_s);
+    call.slow_count = slow;
+    int r = search_launch(T, call);
     if (r) {
         (void)hipStreamSynchronize(s);
         return r;
@@ -1698,6 +1720,87 @@ static int merge_launch(const uint8_t* ids, const uint8_t* dists, const uint8_t*
                         uint32_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         int device_id, void* stream);
 
+// which scan kernel serves an index's rows (brute_force.h), and how it is launched
+struct ScanPlan {
+    void (*fn)(const BruteParams);
+    void (*prime)(const BruteParams); // the same scan keeping only the best score per (range, query)
+    BfGeometry geo, prime_geo;
+    uint64_t max_ranges = 64; // element ranges: their lists are merged (a range is a whole number of tiles)
+};
+static ScanPlan plan_scan(const granne_hip_index* ix, uint32_t nq) {
+    if (ix->dtype == GRANNE_HIP_I8) {
+        if (ix->row_bytes > 128u) // rows of any length: in chunks of 128 bytes (brute_force.h, bf_i8_chunked_kernel)
+            return {bf_i8_chunked_kernel<4>, bf_i8_chunked_kernel<4, true>, bf_i8_chunked_geometry<4>(), bf_i8_chunked_geometry<4>()};
+        if (knobs().bf_ring && ix->row_bytes == 128u && ix->row_stride == 128u && ix->n_elements < (1ull << 29)) {
+            // tiles by LDS-DMA into a ring, 64 queries per wave (brute_force.h, bf_i8_ring_kernel); the priming pass stays
+            ScanPlan P{bf_i8_ring_kernel, bf_i8_kernel<4, true>, bf_ring_geometry(), bf_i8_geometry<4>()};
+            // 512 queries per block: half as many blocks per range, so twice the ranges fill the chip (merged in two steps)
+            if ((uint64_t)((nq + P.geo.qt - 1) / P.geo.qt) * 64u < 256u) P.max_ranges = 128;
+            return P;
+        }
+        return {bf_i8_kernel<4>, bf_i8_kernel<4, true>, bf_i8_geometry<4>(), bf_i8_geometry<4>()};
+    }
+    // f32 rows on the bf16 matrix path, three instructions per product (brute_force.h)
+    if (knobs().bf_b16 && ix->dim <= 112) return {bf_b16_kernel<7, 4>, bf_b16_kernel<7, 4, true>, bf_b16_geometry<7, 4>(), bf_b16_geometry<7, 4>()};
+    if (knobs().bf_b16 && ix->dim <= 208) return {bf_b16_kernel<13, 2>, bf_b16_kernel<13, 2, true>, bf_b16_geometry<13, 2>(), bf_b16_geometry<13, 2>()};
+    // rows of any length: the vector in chunks of 128 components (brute_force.h, bf_b16_chunked_kernel; tiles of 64 rows:
+    // 128 take 256 registers and spill)
+    if (ix->dim > 256) return {bf_b16_chunked_kernel<2>, bf_b16_chunked_kernel<2, true>, bf_b16_chunked_geometry<2>(), bf_b16_chunked_geometry<2>()};
+    if (knobs().bf_b16) return {bf_b16_kernel<16, 1>, bf_b16_kernel<16, 1, true>, bf_b16_geometry<16, 1>(), bf_b16_geometry<16, 1>()};
+    if (ix->dim <= 104) return {bf_f32_kernel<52, 4>, bf_f32_kernel<52, 4, true>, bf_f32_geometry<52, 4>(), bf_f32_geometry<52, 4>()};
+    if (ix->dim <= 200) return {bf_f32_kernel<100, 2>, bf_f32_kernel<100, 2, true>, bf_f32_geometry<100, 2>(), bf_f32_geometry<100, 2>()};
+    return {bf_f32_kernel<128, 1>, bf_f32_kernel<128, 1, true>, bf_f32_geometry<128, 1>(), bf_f32_geometry<128, 1>()};
+}
+
+// the scan's scratch: the ranges' lists, the merged lists, the candidates and their exact distances, the thresholds, what
+// the ranges of a query have seen per score bucket, and the zero-padded queries (int8 rows of more than 128 bytes)
+namespace {
+struct ScanScratch {
+    size_t pid, pd, pc, mid, md, mc, cand, ex, tau, share, qpad, total = 0;
+    ScanScratch(uint64_t ranges, uint32_t nq, uint32_t kk, size_t share_bytes, size_t qpad_bytes) {
+        auto take = [&](size_t bytes, size_t align) {
+            total = (total + align - 1) & ~(align - 1);
+            total += bytes;
+            return total - bytes;
+        };
+        const size_t lists = (size_t)ranges * nq;
+        pid = take(lists * kk * 8, 1), pd = take(lists * kk * 4, 1), pc = take(lists * 4, 1);
+        mid = take((size_t)nq * kk * 8, 16), md = take((size_t)nq * kk * 4, 1), mc = take((size_t)nq * 4, 1);
+        cand = take((size_t)nq * kk * 4, 16), ex = take((size_t)nq * kk * 4, 1);
+        tau = take((size_t)nq * 4, 16);
+        share = take(share_bytes, 16);
+        qpad = take(qpad_bytes, 16);
+    }
+};
+} // namespace
+
+// The lists of G ranges ([G][nq][kk] ids, dists; [G][nq] counts) merged into one per query. More lists than the merge has
+// lanes (G > 64): ranges 0..63 and 64.. are merged into two lists of their own, then those two.
+static int merge_ranges(const BruteParams& P, uint32_t G, uint32_t nq, uint32_t kk, uint64_t* ids, float* dists, uint32_t* counts,
+                        int device, void* stream) {
+    const uint8_t* pi = (const uint8_t*)P.part_ids;
+    const uint8_t* pd = (const uint8_t*)P.part_d;
+    const uint8_t* pc = (const uint8_t*)P.part_c;
+    const uint64_t si = (uint64_t)nq * kk * 8, sd = (uint64_t)nq * kk * 4, sc = (uint64_t)nq * 4;
+    uint64_t zeros[64];
+    memset(zeros, 0, sizeof(zeros)); // the lists hold global ids already
+    if (G <= 64) return merge_launch(pi, pd, pc, si, sd, sc, zeros, G, nq, kk, ids, dists, counts, device, stream);
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* half = nullptr; // [2] x (ids, dists, counts)
+    const size_t hi = 0, hd = 2 * si, hc = hd + 2 * sd, hbytes = hc + 2 * sc;
+    HIP_TRY(hipMallocAsync((void**)&half, hbytes, s));
+    int rc = 0;
+    for (uint32_t part = 0; part < 2 && rc == 0; ++part) {
+        const uint32_t first = part * 64u, count = part == 0 ? 64u : G - 64u;
+        rc = merge_launch(pi + first * si, pd + first * sd, pc + first * sc, si, sd, sc, zeros, count, nq, kk,
+                          (uint64_t*)(half + hi + part * si), (float*)(half + hd + part * sd), (uint32_t*)(half + hc + part * sc),
+                          device, stream);
+    }
+    if (rc == 0) rc = merge_launch(half + hi, half + hd, half + hc, si, sd, sc, zeros, 2, nq, kk, ids, dists, counts, device, stream);
+    (void)hipFreeAsync(half, s);
+    return rc;
+}
+
 // exact k nearest elements by a scan of all of them on the matrix cores (brute_force.h)
 extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k,
                                              uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, void* stream) {
@@ -1710,89 +1813,19 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
     hipStream_t s = (hipStream_t)stream;
     const uint64_t n = ix->n_elements;
     const uint32_t kk = k + BF_EXTRA < BF_KMAX ? k + BF_EXTRA : BF_KMAX;
-    // element ranges: the lists of up to 64 ranges are merged; a range is a whole number of tiles
-    uint32_t R = 4, lds = 0, qt = BF_QT, threads = BF_THREADS;
-    uint32_t prime_lds = 0, prime_qt = 0, prime_threads = 0; // 0: the scan's own
-    uint64_t max_ranges = 64;
-    void (*fn)(const BruteParams) = nullptr;
-    void (*fn_prime)(const BruteParams) = nullptr; // the same scan keeping only the best score per (range, query)
-    if (ix->dtype == GRANNE_HIP_I8) {
-        R = 4;
-        fn = bf_i8_kernel<4>;
-        fn_prime = bf_i8_kernel<4, true>;
-        lds = BF_I8_SUB * (32u * R * (128u + 16u) + 32u * R * 4u + 2u * R * 4u);
-        if (ix->row_bytes > 128u) { // rows of any length: in chunks of 128 bytes (brute_force.h, bf_i8_chunked_kernel)
-            fn = bf_i8_chunked_kernel<4>;
-            fn_prime = bf_i8_chunked_kernel<4, true>;
-            lds = 32u * R * (128u + 16u) + 32u * R * 4u + 2u * R * 4u;
-        } else if (knobs().bf_ring && ix->row_bytes == 128u && ix->row_stride == 128u && n < (1ull << 29)) {
-            // tiles by LDS-DMA into a ring, 64 queries per wave (brute_force.h, bf_i8_ring_kernel); the priming pass stays
-            prime_lds = lds, prime_qt = qt, prime_threads = threads;
-            fn = bf_i8_ring_kernel;
-            lds = BF_RING_LDS;
-            qt = BF_RING_QT, threads = BF_RING_THREADS;
-            // 512 queries per block: half as many blocks per range, so twice the ranges fill the chip (merged in two steps)
-            if ((uint64_t)((nq + qt - 1) / qt) * 64u < 256u) max_ranges = 128;
-        }
-    } else if (knobs().bf_b16 && ix->dim <= 112) { // f32 rows on the bf16 matrix path, three instructions per product (brute_force.h)
-        R = 4;
-        fn = bf_b16_kernel<7, 4>;
-        fn_prime = bf_b16_kernel<7, 4, true>;
-        lds = 2u * 32u * R * (2u * 16u * 7u + 16u);
-        qt = BF_B16_QT, threads = BF_B16_THREADS;
-    } else if (knobs().bf_b16 && ix->dim <= 208) {
-        R = 2;
-        fn = bf_b16_kernel<13, 2>;
-        fn_prime = bf_b16_kernel<13, 2, true>;
-        lds = 2u * 32u * R * (2u * 16u * 13u + 16u);
-        qt = BF_B16_QT, threads = BF_B16_THREADS;
-    } else if (ix->dim > 256) { // rows of any length: the vector in chunks of 128 components (brute_force.h, bf_b16_chunked_kernel)
-        R = 2; // (tiles of 64 rows: 128 take 256 registers and spill)
-        fn = bf_b16_chunked_kernel<2>;
-        fn_prime = bf_b16_chunked_kernel<2, true>;
-        lds = 2u * 32u * R * (2u * 16u * 8u + 16u);
-        qt = BF_B16_QT, threads = BF_B16_THREADS;
-    } else if (knobs().bf_b16) {
-        R = 1;
-        fn = bf_b16_kernel<16, 1>;
-        fn_prime = bf_b16_kernel<16, 1, true>;
-        lds = 2u * 32u * R * (2u * 16u * 16u + 16u);
-        qt = BF_B16_QT, threads = BF_B16_THREADS;
-    } else if (ix->dim <= 104) {
-        R = 4;
-        fn = bf_f32_kernel<52, 4>;
-        fn_prime = bf_f32_kernel<52, 4, true>;
-        lds = 32u * R * (2u * 52u + 4u) * 4u;
-    } else if (ix->dim <= 200) {
-        R = 2;
-        fn = bf_f32_kernel<100, 2>;
-        fn_prime = bf_f32_kernel<100, 2, true>;
-        lds = 32u * R * (2u * 100u + 4u) * 4u;
-    } else {
-        R = 1;
-        fn = bf_f32_kernel<128, 1>;
-        fn_prime = bf_f32_kernel<128, 1, true>;
-        lds = 32u * R * (2u * 128u + 4u) * 4u;
-    }
-    const uint64_t tile = 32ull * R;
+    const ScanPlan S = plan_scan(ix, nq);
+    const uint64_t tile = S.geo.rows;
     uint64_t G = (n + tile - 1) / tile;
-    if (G > max_ranges) G = max_ranges;
+    if (G > S.max_ranges) G = S.max_ranges;
     if (G < 1) G = 1;
     uint64_t per_range = (n + G - 1) / G;
     per_range = (per_range + tile - 1) / tile * tile;
     if (per_range < tile) per_range = tile;
-    const size_t lists = (size_t)G * nq;
-    const size_t o_pid = 0, o_pd = o_pid + lists * kk * 8, o_pc = o_pd + lists * kk * 4;
-    const size_t o_mid = (o_pc + lists * 4 + 15) & ~(size_t)15, o_md = o_mid + (size_t)nq * kk * 8, o_mc = o_md + (size_t)nq * kk * 4;
-    const size_t o_cand = (o_mc + (size_t)nq * 4 + 15) & ~(size_t)15, o_ex = o_cand + (size_t)nq * kk * 4;
-    const size_t o_tau = (o_ex + (size_t)nq * kk * 4 + 15) & ~(size_t)15;
-    const size_t o_share = (o_tau + (size_t)nq * 4 + 15) & ~(size_t)15; // what the ranges of a query have seen, per score bucket
     const size_t share_bytes = (size_t)nq * BF_SHARE_BUCKETS * 4;
-    const size_t o_qpad = (o_share + share_bytes + 15) & ~(size_t)15; // int8 rows of more than 128 bytes: the queries, zero padded
     const size_t qpad_bytes = (ix->dtype == GRANNE_HIP_I8 && ix->row_bytes > 128u) ? (size_t)nq * ix->row_bytes : 0;
-    const size_t total = o_qpad + qpad_bytes;
+    const ScanScratch o(G, nq, kk, share_bytes, qpad_bytes);
     uint8_t* scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
+    HIP_TRY(hipMallocAsync((void**)&scratch, o.total, s));
     struct Release {
         void* p;
         hipStream_t s;
@@ -1829,21 +1862,19 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
     P.nq = nq;
     P.kk = kk;
     P.per_range = per_range;
-    P.part_ids = (uint64_t*)(scratch + o_pid);
-    P.part_d = (float*)(scratch + o_pd);
-    P.part_c = (uint32_t*)(scratch + o_pc);
-    if (lds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    P.part_ids = (uint64_t*)(scratch + o.pid);
+    P.part_d = (float*)(scratch + o.pd);
+    P.part_c = (uint32_t*)(scratch + o.pc);
+    if (S.geo.lds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)S.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.geo.lds));
     P.tau_in = nullptr;
     P.share_hist = nullptr;
     P.qpad = nullptr;
     if (qpad_bytes) {
         hipLaunchKernelGGL(bf_pad_queries_kernel, dim3(grid_for(qpad_bytes, 256)), dim3(256), 0, s, (const uint8_t*)d_queries, nq, ix->dim,
-                           ix->row_bytes, scratch + o_qpad);
+                           ix->row_bytes, scratch + o.qpad);
         HIP_TRY(hipGetLastError());
-        P.qpad = scratch + o_qpad;
+        P.qpad = scratch + o.qpad;
     }
-    uint64_t zeros[64];
-    memset(zeros, 0, sizeof(zeros)); // the lists hold global ids already
     if (G >= 32) {
         // the priming pass (brute_force.h, bf_tau_kernel): the first range alone, cut into up to 64 sub-ranges so that the
         // whole chip scans it (1/64 of the scan proper, without its lists: the best score per sub-range and query)
@@ -1854,57 +1885,34 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
         Q.per_range = ((Q.n + Gs - 1) / Gs + tile - 1) / tile * tile;
         Gs = (Q.n + Q.per_range - 1) / Q.per_range;
         if (Gs >= kk) {
-            const uint32_t plds = prime_qt ? prime_lds : lds, pqt = prime_qt ? prime_qt : qt, pthreads = prime_qt ? prime_threads : threads;
-            if (plds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)fn_prime, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-            hipLaunchKernelGGL(fn_prime, dim3((nq + pqt - 1) / pqt, (uint32_t)Gs), dim3(pthreads), plds, s, Q);
+            const BfGeometry& pg = S.prime_geo;
+            if (pg.lds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)S.prime, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg.lds));
+            hipLaunchKernelGGL(S.prime, dim3((nq + pg.qt - 1) / pg.qt, (uint32_t)Gs), dim3(pg.threads), pg.lds, s, Q);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(bf_tau_kernel, dim3(nq), dim3(64), 0, s, (const float*)P.part_d, (uint32_t)Gs, nq, kk,
-                               (float*)(scratch + o_tau));
+                               (float*)(scratch + o.tau));
             HIP_TRY(hipGetLastError());
-            P.tau_in = (const float*)(scratch + o_tau);
+            P.tau_in = (const float*)(scratch + o.tau);
             // the ranges of a query tell each other what they have seen (brute_force.h, BfShare)
-            HIP_TRY(hipMemsetAsync(scratch + o_share, 0, share_bytes, s));
-            P.share_hist = (uint32_t*)(scratch + o_share);
+            HIP_TRY(hipMemsetAsync(scratch + o.share, 0, share_bytes, s));
+            P.share_hist = (uint32_t*)(scratch + o.share);
         }
     }
-    hipLaunchKernelGGL(fn, dim3((nq + qt - 1) / qt, (uint32_t)G), dim3(threads), lds, s, P);
+    hipLaunchKernelGGL(S.fn, dim3((nq + S.geo.qt - 1) / S.geo.qt, (uint32_t)G), dim3(S.geo.threads), S.geo.lds, s, P);
     HIP_TRY(hipGetLastError());
-    int rc = 0;
-    if (G > 64) {
-        // more lists than the merge has lanes: ranges 0..63 and 64.. are merged into two lists of their own, then those two
-        const uint8_t* pi = (const uint8_t*)P.part_ids;
-        const uint8_t* pd = (const uint8_t*)P.part_d;
-        const uint8_t* pc = (const uint8_t*)P.part_c;
-        const uint64_t si = (uint64_t)nq * kk * 8, sd = (uint64_t)nq * kk * 4, sc = (uint64_t)nq * 4;
-        uint8_t* half = nullptr; // [2] x (ids, dists, counts)
-        const size_t hi = 0, hd = 2 * si, hc = hd + 2 * sd, hbytes = hc + 2 * sc;
-        HIP_TRY(hipMallocAsync((void**)&half, hbytes, s));
-        Release release_half{half, s};
-        for (uint32_t part = 0; part < 2 && rc == 0; ++part) {
-            const uint32_t first = part * 64u, count = part == 0 ? 64u : (uint32_t)G - 64u;
-            rc = merge_launch(pi + first * si, pd + first * sd, pc + first * sc, si, sd, sc, zeros, count, nq, kk,
-                              (uint64_t*)(half + hi + part * si), (float*)(half + hd + part * sd),
-                              (uint32_t*)(half + hc + part * sc), ix->device, stream);
-        }
-        if (rc == 0)
-            rc = merge_launch(half + hi, half + hd, half + hc, si, sd, sc, zeros, 2, nq, kk, (uint64_t*)(scratch + o_mid),
-                              (float*)(scratch + o_md), (uint32_t*)(scratch + o_mc), ix->device, stream);
-    } else {
-        rc = merge_launch((const uint8_t*)P.part_ids, (const uint8_t*)P.part_d, (const uint8_t*)P.part_c, (uint64_t)nq * kk * 8,
-                          (uint64_t)nq * kk * 4, (uint64_t)nq * 4, zeros, (uint32_t)G, nq, kk, (uint64_t*)(scratch + o_mid),
-                          (float*)(scratch + o_md), (uint32_t*)(scratch + o_mc), ix->device, stream);
-    }
+    int rc = merge_ranges(P, (uint32_t)G, nq, kk, (uint64_t*)(scratch + o.mid), (float*)(scratch + o.md), (uint32_t*)(scratch + o.mc),
+                          ix->device, stream);
     if (rc) return rc;
     // the candidates' distances in the reference's own arithmetic, then the k best by (distance, id)
     const uint32_t pairs = nq * kk;
-    hipLaunchKernelGGL(bf_narrow_ids_kernel, dim3((pairs + 255) / 256), dim3(256), 0, s, (const uint64_t*)(scratch + o_mid),
-                       (const uint32_t*)(scratch + o_mc), nq, kk, (uint32_t*)(scratch + o_cand));
+    hipLaunchKernelGGL(bf_narrow_ids_kernel, dim3((pairs + 255) / 256), dim3(256), 0, s, (const uint64_t*)(scratch + o.mid),
+                       (const uint32_t*)(scratch + o.mc), nq, kk, (uint32_t*)(scratch + o.cand));
     HIP_TRY(hipGetLastError());
-    rc = dists_launch(ix, d_queries, nullptr, kk, (const uint32_t*)(scratch + o_cand), (uint64_t)pairs, (float*)(scratch + o_ex),
+    rc = dists_launch(ix, d_queries, nullptr, kk, (const uint32_t*)(scratch + o.cand), (uint64_t)pairs, (float*)(scratch + o.ex),
                       nullptr, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(bf_final_kernel, dim3((pairs + 255) / 256), dim3(256), 0, s, (const uint32_t*)(scratch + o_cand),
-                       (const float*)(scratch + o_ex), nq, kk, k, d_out_ids, d_out_dists, d_out_counts);
+    hipLaunchKernelGGL(bf_final_kernel, dim3((pairs + 255) / 256), dim3(256), 0, s, (const uint32_t*)(scratch + o.cand),
+                       (const float*)(scratch + o.ex), nq, kk, k, d_out_ids, d_out_dists, d_out_counts);
     HIP_TRY(hipGetLastError());
     return GRANNE_HIP_OK;
 }

@@ -37,12 +37,6 @@ __global__ void scatter_inverse_kernel(const uint32_t* __restrict__ order, uint6
         inv[order[t]] = lo + (uint32_t)t;
 }
 
-__global__ void gather_u64_kernel(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint64_t n,
-                                  uint64_t* __restrict__ out) {
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x)
-        out[t] = src[idx[t]];
-}
-
 __global__ void widen_u32_kernel(const uint32_t* __restrict__ src, uint64_t n, uint64_t* __restrict__ out) {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x)
         out[t] = src[t];
@@ -243,14 +237,22 @@ extern "C" int granne_hip_index_reorder(granne_hip_index* ix, uint64_t* out_orde
         HIP_TRY(hipGetLastError());
         void* tmp = nullptr;
         size_t tmp_bytes = 0;
-        SearchTarget T = target_of(ix);
+        const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+        SearchCall call; // the trail walks: max_search 1
+        call.q_stride = ix->row_stride;
+        call.ef = call.k = 1;
+        call.status = d_overflow;
+        call.stream = s;
+        call.trail = d_trail;
         for (uint32_t layer = 1; layer < n_layers; ++layer) { // :149
             const uint64_t lo = ix->layers[layer - 1].len, hi = ix->layers[layer].len;
             const uint64_t m = hi - lo;
             if (m == 0) continue;
             // find_entrypoint_trail for every idx in [lo, hi); the element rows are the queries
-            int r = search_launch(&T, ix->d_elements + (size_t)lo * ix->row_stride, (int64_t)ix->row_stride, (uint32_t)m, 1, 1,
-                                  nullptr, nullptr, nullptr, nullptr, d_overflow, s, nullptr, d_trail, layer);
+            call.queries = ix->d_elements + (size_t)lo * ix->row_stride;
+            call.nq = (uint32_t)m;
+            call.trail_layers = layer;
+            int r = search_launch(T, call);
             if (r) return r;
             // (eps, idx) ascending: LSD over the column pairs, starting from idx order
             uint32_t* perm = d_order + lo; // holds lo..hi-1 from the iota

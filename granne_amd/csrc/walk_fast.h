@@ -104,11 +104,6 @@ __device__ __forceinline__ float from_lower_f(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111 /* row_shr:1 */, 0xf, 0xf, false));
 }
 
-// lane i receives lane i-1's value, lane 0 receives 0
-__device__ __forceinline__ uint32_t from_prev_lane_or_zero(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-}
-
 // From how many slots on a list is the two-level list of FastWalker::search_layer_long (M in LDS only, F in registers).
 #ifndef GRANNE_HIP_LONG_MIN
 #define GRANNE_HIP_LONG_MIN 33
@@ -239,7 +234,7 @@ __host__ __device__ inline uint32_t fast_query_bytes(bool i8, bool gen, uint32_t
 
 // V16: the form of the visited set. 3 = none (the default; 4 = none + rows touched ahead, for launches of a few
 // queries); 0 = the exact set: 32-bit open addressing in LDS + a global overflow table (VisitedSet, wave_prims.h) --
-// kept so that n_dist can be counted the way the reference counts it. The host picks (plan_launch, granne_hip.hip).
+// kept so that n_dist can be counted the way the reference counts it. The host picks (plan_walk, granne_hip.hip).
 // WIDE: layers of up to 64 ids per node (graphs built with num_neighbors 33..63): an expansion takes the row's ids in two
 // passes of 32 pairs -- rows, distances, filter, insert for ids 0..31, then for ids 32..63 when the row goes that far.
 // `res` does not change within an expansion (mod.rs:1025-1033 pushes to pq only), so the reference's filter gives every
