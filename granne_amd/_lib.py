@@ -21,6 +21,7 @@ SEARCH_DEPTH = 3  # GRANNE_HIP_SEARCH_DEPTH (the default of OPT_SEARCH_DEPTH)
 SEARCH_DEPTH_MAX = 16  # GRANNE_HIP_SEARCH_DEPTH_MAX
 SHARDED_OPT_DEPTH, SHARDED_OPT_EXCHANGE = 1, 2
 SHARDED_EXCHANGE_PEER, SHARDED_EXCHANGE_RCCL = 0, 1
+SE_MATERIALIZED, SE_COMPACT = 0, 1  # GRANNE_HIP_SE_*: the two forms of an index over a SumEmbeddings container
 
 
 class GranneHipError(RuntimeError):
@@ -142,6 +143,27 @@ SIGNATURES = {
     "granne_hip_index_set_option": (i32, [vp, i32, u64]),
     "granne_hip_index_get_option": (i32, [vp, i32, C.POINTER(u64)]),
     "granne_hip_index_last_slow_count": (u64, [vp]),
+    "granne_hip_sum_embeddings_create": (i32, [C.POINTER(vp), vp, u64, u32, vp, vp, u64, i32]),
+    "granne_hip_sum_embeddings_create_device": (i32, [C.POINTER(vp), vp, u64, u32, vp, vp, u64, i32, vp]),
+    "granne_hip_sum_embeddings_load_files": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, i32]),
+    "granne_hip_sum_embeddings_load": (i32, [C.POINTER(vp), vp, u64, u32, vp, u64, i32]),
+    "granne_hip_sum_embeddings_save_elements": (i32, [vp, C.c_char_p]),
+    "granne_hip_sum_embeddings_save_embeddings": (i32, [vp, C.c_char_p]),
+    "granne_hip_sum_embeddings_destroy": (None, [vp]),
+    "granne_hip_sum_embeddings_len": (u64, [vp]),
+    "granne_hip_sum_embeddings_num_embeddings": (u64, [vp]),
+    "granne_hip_sum_embeddings_dim": (u32, [vp]),
+    "granne_hip_sum_embeddings_hbm_bytes": (u64, [vp]),
+    "granne_hip_sum_embeddings_get_terms": (i32, [vp, u64, vp, u32, C.POINTER(u32)]),
+    "granne_hip_sum_embeddings_append": (i32, [vp, vp, vp, u64]),
+    "granne_hip_sum_embeddings_materialize_device": (i32, [vp, u64, u64, i32, vp, u64, vp]),
+    "granne_hip_sum_embeddings_materialize": (i32, [vp, u64, u64, i32, vp]),
+    "granne_hip_sum_embeddings_embed_device": (i32, [vp, vp, vp, u64, i32, vp, u64, vp]),
+    "granne_hip_sum_embeddings_embed": (i32, [vp, vp, vp, u64, i32, vp]),
+    "granne_hip_index_create_sum_embeddings": (i32, [C.POINTER(vp), vp, u32, vp, vp, vp, i32]),
+    "granne_hip_index_load_files_sum_embeddings": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, i32, i32]),
+    "granne_hip_builder_create_sum_embeddings": (i32, [C.POINTER(vp), vp, vp]),
+    "granne_hip_builder_get_index_compact": (i32, [vp, C.POINTER(vp)]),
 }
 
 

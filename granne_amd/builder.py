@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import BUILD_ALL, BuildConfig, check, lib
-from .index import _ELEMENT_TYPES, Granne, _p, normalize, quantize
+from ._lib import BUILD_ALL, F32, BuildConfig, check, lib
+from .index import _ELEMENT_TYPES, EMBEDDINGS, Granne, _p, normalize, quantize
 
 
 class GranneBuilder:
@@ -17,10 +17,13 @@ class GranneBuilder:
         num_neighbors 30, max_search 200). batch_max / batch_div tune the GPU insertion schedule
         (include/granne_hip.h)."""
         et = element_type.lower()
-        if et not in _ELEMENT_TYPES:
+        self._se = None
+        if et == EMBEDDINGS:  # elements: a granne_amd.SumEmbeddings; the build runs over its normalised rows
+            self._se, elements, device = elements, None, elements.device
+        elif et not in _ELEMENT_TYPES:
             raise ValueError("Invalid element type")
         self.element_type = et
-        self.dtype_code, self.np_dtype = _ELEMENT_TYPES[et]
+        self.dtype_code, self.np_dtype = _ELEMENT_TYPES.get(et, (F32, np.float32))
         self.device = device
         cfg = BuildConfig()
         lib().granne_hip_build_config_default(C.byref(cfg))
@@ -43,6 +46,10 @@ class GranneBuilder:
         self._prepared = prepared
         self._h = None
         self.dim = None
+        if self._se is not None:
+            h = C.c_void_p()
+            check(lib().granne_hip_builder_create_sum_embeddings(C.byref(h), C.byref(cfg), self._se._h))
+            self._h, self.dim = h, self._se.dim
         if elements is not None:
             el = np.asarray(elements)
             if el.ndim != 2:
@@ -68,6 +75,8 @@ class GranneBuilder:
 
     def append(self, element):
         """GranneBuilder.append (py/src/lib.rs:487-489): the element is indexed by the next build()."""
+        if self._se is not None:
+            raise ValueError("push new elements into the SumEmbeddings container and make a new builder from it")
         row = np.asarray(element).reshape(1, -1)
         if self.dim is None:
             self.dim = row.shape[1]
@@ -141,12 +150,17 @@ class GranneBuilder:
         row = self.get_layer(layer)[idx]
         return [int(x) for x in row if x != 0xFFFFFFFF]
 
-    def get_index(self):
-        """GranneBuilder::get_index (src/index/mod.rs:483-488): a searchable Granne on the same device."""
+    def get_index(self, compact=False):
+        """GranneBuilder::get_index (src/index/mod.rs:483-488): a searchable Granne on the same device. compact=True
+        (builders over a SumEmbeddings): an index that keeps the container instead of dense rows."""
         self._ensure()
         h = C.c_void_p()
-        check(lib().granne_hip_builder_get_index(self._h, C.byref(h)))
+        if compact:
+            check(lib().granne_hip_builder_get_index_compact(self._h, C.byref(h)))
+        else:
+            check(lib().granne_hip_builder_get_index(self._h, C.byref(h)))
         ix = Granne.__new__(Granne)
+        ix._se, ix.compact = self._se, bool(compact)
         ix.element_type = self.element_type
         ix.dtype_code, ix.np_dtype = self.dtype_code, self.np_dtype
         ix.device = self.device

@@ -28,6 +28,7 @@ struct granne_hip_builder {
     std::vector<BuilderLayer> layers;
     uint64_t hbm_bytes = 0;
     ScratchCache scratch; // the build's searches (search_launch)
+    std::shared_ptr<SeDev> se; // made by granne_hip_builder_create_sum_embeddings: the container d_elements was materialised from
 };
 
 extern "C" void granne_hip_build_config_default(granne_hip_build_config* c) {

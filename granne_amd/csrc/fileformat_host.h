@@ -451,6 +451,7 @@ extern "C" int granne_hip_index_save(const granne_hip_index* ix, const char* ind
         if (!granne_file::write_file(index_path, buf.data(), buf.size(), nullptr, 0)) return fail(GRANNE_HIP_ERR_IO, "Could not write %s", index_path);
     }
     if (elements_path) {
+        GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "save_elements (write the container's own files with granne_hip_sum_embeddings_save_*)");
         size_t dense = (size_t)ix->dim * elem_size(ix->dtype);
         std::vector<uint8_t> el((size_t)ix->n_elements * dense);
         if (!el.empty())

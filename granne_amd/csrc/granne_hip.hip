@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -122,6 +123,29 @@ struct ScratchCache {
     }
 };
 
+// A SumEmbeddings container's device copy (sum_embeddings_host.h): immutable once made, shared by the container and by
+// every compact index and builder made from it, freed with the last of them.
+struct SeDev {
+    int device = 0;
+    uint32_t dim = 0, tstride = 0; // floats per table row; floats from one row to the next (rows padded to 16 bytes)
+    uint64_t n_embeddings = 0, n = 0, n_terms = 0;
+    float* d_table = nullptr;
+    uint64_t* d_offsets = nullptr;
+    uint32_t* d_terms = nullptr;
+    uint64_t bytes() const { return n_embeddings * tstride * 4u + (n + 1) * 8u + n_terms * 4u; }
+    ~SeDev() {
+        DeviceGuard g(device);
+        if (d_table) (void)hipFree(d_table);
+        if (d_offsets) (void)hipFree(d_offsets);
+        if (d_terms) (void)hipFree(d_terms);
+    }
+};
+#define GRANNE_HIP_COMPACT_UNSUPPORTED(ix, what)                                                                        \
+    do {                                                                                                                \
+        if ((ix) && (ix)->se)                                                                                           \
+            return fail(GRANNE_HIP_ERR_INVALID, what " needs dense rows: make the index with GRANNE_HIP_SE_MATERIALIZED (a compact SumEmbeddings index keeps none)"); \
+    } while (0)
+
 struct LayerHost {
     uint64_t len = 0;
     uint32_t width = 0;     // caller's row width
@@ -139,6 +163,7 @@ struct granne_hip_index {
     uint32_t row_bytes = 0;  // data bytes of a device row (zero padded to 16)
     uint32_t row_stride = 0; // bytes from one device row to the next
     uint8_t* d_elements = nullptr;
+    std::shared_ptr<SeDev> se; // a compact SumEmbeddings index: no d_elements, vectors are made from the term lists
     std::vector<LayerHost> layers;
     LayerDev* d_layers = nullptr;
     uint64_t hbm_bytes = 0;
@@ -252,6 +277,9 @@ static int validate_common(granne_hip_index** out, uint64_t n_elements, uint32_t
     return GRANNE_HIP_OK;
 }
 
+// rows first .. first + count - 1 of a container as dense host rows [count][dim] (sum_embeddings_host.h)
+static int se_rows_to_host(const SeDev& se, uint64_t first, uint64_t count, int normalised, float* out);
+
 static void destroy_index(granne_hip_index* ix) {
     if (!ix) return;
     DeviceGuard g(ix->device);
@@ -309,7 +337,7 @@ static int make_inline_tails(granne_hip_index* ix, hipStream_t s) {
             L.adjx_stride = 0;
         }
     }
-    const uint32_t tu = inline_tail_units(ix->dim, ix->dtype);
+    const uint32_t tu = ix->se ? 0u : inline_tail_units(ix->dim, ix->dtype);
     if (!tu || !ix->opt_inline_tails || !knobs().inline_tails) return GRANNE_HIP_OK;
     for (auto& L : ix->layers)
         if (L.dev_width != 32u) return GRANNE_HIP_OK; // layers of up to 64 ids (WIDE) read their tails from the rows
@@ -367,7 +395,7 @@ static int make_scan_norms(granne_hip_index* ix, hipStream_t s) {
 // they are an accelerator, not part of the index: without room for them the index is made without (searches read every
 // row, as they would with GRANNE_HIP_OPT_SKETCH = 0), and the room is judged with headroom left for what searches allocate.
 static int make_row_sketch(granne_hip_index* ix, hipStream_t s) {
-    if (ix->dtype != GRANNE_HIP_F32 || !sketch_dim_ok(ix->dim) || ix->n_elements == 0 || !knobs().sketch) return GRANNE_HIP_OK;
+    if (ix->se || ix->dtype != GRANNE_HIP_F32 || !sketch_dim_ok(ix->dim) || ix->n_elements == 0 || !knobs().sketch) return GRANNE_HIP_OK;
     const uint64_t n = ix->n_elements;
     const size_t bytes = (size_t)n * SKETCH_LINE;
     if (!ix->d_sketch) {
@@ -645,6 +673,7 @@ extern "C" int granne_hip_index_get_neighbors(const granne_hip_index* ix, uint64
 extern "C" int granne_hip_index_get_element(const granne_hip_index* ix, uint64_t idx, void* out) {
     if (!ix || !out) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
     if (idx >= ix->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "element index out of range");
+    if (ix->se) return se_rows_to_host(*ix->se, idx, 1, 1, (float*)out); // ElementContainer::get: the normalised vector
     DeviceGuard g(ix->device);
     HIP_TRY(hipMemcpy(out, ix->d_elements + idx * ix->row_stride, (size_t)ix->dim * elem_size(ix->dtype),
                       hipMemcpyDeviceToHost));
@@ -653,6 +682,7 @@ extern "C" int granne_hip_index_get_element(const granne_hip_index* ix, uint64_t
 
 extern "C" int granne_hip_index_get_sketch(const granne_hip_index* ix, uint64_t first, uint64_t count, void* out) {
     if (!ix || (!out && count)) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "get_sketch");
     if (!ix->d_sketch) return fail(GRANNE_HIP_ERR_INVALID, "the index holds no row sketches");
     if (first > ix->n_elements || count > ix->n_elements - first) return fail(GRANNE_HIP_ERR_INVALID, "rows out of range");
     if (count == 0) return GRANNE_HIP_OK;
@@ -840,6 +870,7 @@ struct SearchTarget {
     uint64_t opt_visited16 = 0;
     uint64_t opt_seen_min = 0xFFFFFFFFull;
     const uint8_t* d_sketch = nullptr; // row sketches the register walker may use (an index's, when GRANNE_HIP_OPT_SKETCH is on)
+    const SeDev* se = nullptr;         // a compact SumEmbeddings index: no dense rows (d_elements is null)
     ScratchCache* scratch;             // search_launch's per-stream scratch blocks
     std::atomic<uint64_t>* last_walker = nullptr; // which walker the last launch took (an index's read-only option)
 
@@ -862,6 +893,7 @@ struct SearchTarget {
             opt_seen_min = g->opt_seen_min;
             d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch : nullptr;
             last_walker = &const_cast<G*>(g)->last_walker;
+            se = g->se.get();
         } else {
             max_dev_width = g->W;
         }
@@ -898,6 +930,15 @@ static search_fn general_kernel_s(uint32_t S) {
     case 1: return search_kernel<DT, 0, 1>;
     case 2: return search_kernel<DT, 0, 2>;
     case 4: return search_kernel<DT, 0, 4>;
+    }
+    return nullptr;
+}
+// the general walker of a compact SumEmbeddings index (sum_embeddings.h): f32, run-time dim, no trail walks
+static search_fn compact_kernel_s(uint32_t S) {
+    switch (S) {
+    case 1: return search_kernel<DT_F32, 0, 1, false, true>;
+    case 2: return search_kernel<DT_F32, 0, 2, false, true>;
+    case 4: return search_kernel<DT_F32, 0, 4, false, true>;
     }
     return nullptr;
 }
@@ -1005,7 +1046,14 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
     // the longest max_search the register walker is instantiated for: lists of up to 17 x 64 keys for 64-id layers, int8
     // rows of 256 / 512 bytes and streamed f32 dims, else two-level lists of up to 129 x 64 keys
     const uint32_t fast_max = (wide || (i8 ? T.row_bytes != 128 : streamed)) ? 1024u : FAST_MAX_SEARCH;
-    const bool fast = shape && ef <= fast_max && !(wide && trail);
+    // a compact SumEmbeddings index has no rows, sketches or inline tails for the register walker to read: every walk of
+    // it is the general walker's (max_search up to 256) or the exact walker's
+    const bool compact = T.se != nullptr;
+    if (compact && (trail || i8)) {
+        fail(GRANNE_HIP_ERR_INVALID, "a compact SumEmbeddings index serves searches only: make the index with GRANNE_HIP_SE_MATERIALIZED");
+        return P;
+    }
+    const bool fast = !compact && shape && ef <= fast_max && !(wide && trail);
     const uint32_t ef_walk = fast ? ef : (ef > 256 ? 256 : ef); // what the register / general walker is sized for
     const bool all_slow = T.opt_force_slow || (!fast && ef > 256);
     P.walker = all_slow ? GRANNE_HIP_WALKER_EXACT
@@ -1120,13 +1168,13 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         const size_t fit = SLOW_SCRATCH_BUDGET / per_block;
         if (most > fit) most = fit > P.slow_blocks ? (uint32_t)fit : P.slow_blocks;
         P.slow_blocks = nq < most ? (nq > P.slow_blocks ? nq : P.slow_blocks) : most;
-        P.fn = !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
+        P.fn = compact ? (search_fn)slow_kernel<DT_F32, true> : !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
         P.lds_bytes = slow_lds;
         P.grid = P.slow_blocks;
         return P;
     }
     if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
-    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide) : general_kernel_of(T.dtype, P.S, trail);
+    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide) : compact ? compact_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
     if (!P.fn) {
         fail(GRANNE_HIP_ERR_INVALID, "no walker is instantiated for this launch (list slots %u, visited form %d, trail %d, 64-id layers %d)",
              P.S, P.v16, (int)trail, (int)wide);
@@ -1185,7 +1233,8 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     size_t off_vis = off_ovf + (size_t)W.ovf_regions * W.ovf_slots * 4;
     size_t off_pq = off_vis + (size_t)W.slow_blocks * slots * 4;
     size_t off_res = off_pq + (size_t)W.slow_blocks * slots * 8;
-    size_t total = off_res + (size_t)W.slow_blocks * c.ef * 8;
+    size_t off_sex = (off_res + (size_t)W.slow_blocks * c.ef * 8 + 15) & ~(size_t)15; // compact indexes: a vector per lane of the exact walker
+    size_t total = off_sex + (T.se ? (size_t)W.slow_blocks * 64u * T.dim * 4u : 0u);
     // The cache's mutex covers finding (or growing) this stream's block and the enqueue -- host work of microseconds.
     // Whatever waits for the GPU (the synchronisation behind slow_count) happens after it is released: host threads
     // searching one index on streams of their own do not queue behind each other's kernels.
@@ -1261,6 +1310,10 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     sp.all = W.walker == GRANNE_HIP_WALKER_EXACT ? 1u : 0u;
     sp.status2 = c.status;
     sp.host_status = c.host_status;
+    p.se_table = T.se ? T.se->d_table : nullptr;
+    p.se_offsets = T.se ? T.se->d_offsets : nullptr;
+    p.se_terms = T.se ? T.se->d_terms : nullptr;
+    sp.se_x = T.se ? (float*)(scratch + off_sex) : nullptr;
 
     if (T.last_walker) T.last_walker->store(W.walker);
     if (W.walker != GRANNE_HIP_WALKER_EXACT && W.lds_bytes > 32u * 1024u)
@@ -1682,6 +1735,7 @@ extern "C" int granne_hip_quantize_f32_device(const float* d_rows, int8_t* d_out
 static int dists_launch(const granne_hip_index* ix, const void* d_queries, const uint32_t* d_qidx, uint32_t m,
                         const uint32_t* d_ids, uint64_t n_pairs, float* d_out, uint32_t* d_status, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "dists");
     if (n_pairs == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_ids || !d_out) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     DeviceGuard g(ix->device);
@@ -1805,6 +1859,7 @@ static int merge_ranges(const BruteParams& P, uint32_t G, uint32_t nq, uint32_t 
 extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k,
                                              uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "brute_force");
     if (nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
@@ -1921,6 +1976,7 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
 extern "C" int granne_hip_brute_force(const granne_hip_index* ix, const void* queries, uint32_t nq, uint32_t k,
                                       uint64_t* out_ids, float* out_dists, uint32_t* out_counts) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "brute_force");
     if (nq == 0) return GRANNE_HIP_OK;
     if (!queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
@@ -2083,6 +2139,7 @@ extern "C" int granne_hip_quantize_f32(const float* rows, int8_t* out, uint64_t 
 extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* queries, uint32_t nq, const uint32_t* qidx,
                                      const uint32_t* ids, uint64_t n_pairs, float* out) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "dist_pairs");
     if (n_pairs == 0) return GRANNE_HIP_OK;
     if (!queries || !qidx || !ids || !out) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     for (uint64_t i = 0; i < n_pairs; ++i) {
@@ -2136,3 +2193,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // partitioned indexes driven by one host process
 // ------------------------------------------------------------------------------------------------
 #include "sharded_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// embeddings::SumEmbeddings: the container, its files, materialised and compact indexes
+// ------------------------------------------------------------------------------------------------
+#include "sum_embeddings_host.h"

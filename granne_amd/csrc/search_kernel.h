@@ -24,6 +24,7 @@
 
 #include "dist.h"
 #include "wave_prims.h"
+#include "sum_embeddings.h"
 
 namespace granne_hip {
 
@@ -108,6 +109,11 @@ struct SearchParams {
     uint32_t n_batches;
     uint32_t batch_nq;
     BatchIO batch[MAX_LAUNCH_BATCHES];
+    // A compact SumEmbeddings index (sum_embeddings.h) keeps no dense rows: `elements` is null and an element's vector
+    // is made from these where a walker needs it. The table's rows are row_bytes apart. Null for dense indexes.
+    const float* se_table;      // [V][row_bytes / 4]
+    const uint64_t* se_offsets; // [n_elements + 1]
+    const uint32_t* se_terms;
 };
 constexpr uint32_t TRAIL_WIDTH = 8; // NUM_LAYERS, reorder.rs:177
 
@@ -167,7 +173,8 @@ __device__ __forceinline__ void hand_over(const SearchParams& p, uint32_t qi) {
     }
 }
 
-template <int DT, int DIM, int S>
+// SE: the walker of a compact SumEmbeddings index (f32, run-time dim): step 3 sums term rows instead of staging dense ones
+template <int DT, int DIM, int S, bool SE = false>
 struct Walker {
     // ---- immutable per-launch state
     const SearchParams& p;
@@ -234,6 +241,27 @@ struct Walker {
             const uint32_t lrow16 = p.lrow_bytes >> 4;
             for (uint32_t g0 = 0; g0 < m; g0 += p.maxc) {
                 uint32_t gm = min(p.maxc, m - g0);
+                if constexpr (SE) {
+                    // three dependent loads deep: the offsets of the group's candidates together (one lane each), then per
+                    // candidate its term ids and their rows, summed by the wave into the candidate's stage slot
+                    uint64_t o0 = 0, o1 = 0;
+                    if (lane < gm) {
+                        const uint32_t id = cand[g0 + lane];
+                        o0 = p.se_offsets[id];
+                        o1 = p.se_offsets[(size_t)id + 1];
+                    }
+                    for (uint32_t c = 0; c < gm; ++c) {
+                        const uint64_t b = readlane64(o0, c), e = readlane64(o1, c);
+                        se_sum_row(p.se_table, p.row_bytes >> 2, 0xFFFFFFFFu, p.se_terms + b, (uint32_t)(e - b), p.dim,
+                                   reinterpret_cast<float*>(stage + (size_t)c * p.lrow_bytes), lane);
+                    }
+                    __syncthreads();
+                    if (lane >= g0 && lane < g0 + gm)
+                        d = se_finish_dist(reinterpret_cast<float*>(stage + (size_t)(lane - g0) * p.lrow_bytes),
+                                           reinterpret_cast<const float*>(lds_q), p.dim);
+                    __syncthreads();
+                    continue;
+                }
                 uint32_t total = gm * row16;
                 // gather: 64 lanes x 16 bytes per step, 8 steps in flight before the first LDS write
                 for (uint32_t f0 = 0; f0 < total; f0 += 64 * 8) {
@@ -527,7 +555,7 @@ struct Walker {
     }
 };
 
-template <int DT, int DIM, int S, bool TRAIL>
+template <int DT, int DIM, int S, bool TRAIL, bool SE = false>
 __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t qi, uint8_t* smem) {
     const uint32_t lane = threadIdx.x;
     if (p.force_slow) {
@@ -535,7 +563,7 @@ __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t q
         return;
     }
 
-    Walker<DT, DIM, S> w(p, smem);
+    Walker<DT, DIM, S, SE> w(p, smem);
     w.load_query(qi);
 
     if constexpr (TRAIL) { // find_entrypoint_trail: `ep` reads the still-zero eps[i], every walk starts at node 0

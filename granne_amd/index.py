@@ -18,6 +18,7 @@ DEFAULT_MAX_SEARCH = 200   # py/src/lib.rs:14
 DEFAULT_NUM_ELEMENTS = 10  # py/src/lib.rs:15
 
 _ELEMENT_TYPES = {"angular": (F32, np.float32), "angular_int": (I8, np.int8)}
+EMBEDDINGS = "embeddings"  # embeddings::SumEmbeddings: `elements` is a granne_amd.SumEmbeddings, vectors are f32
 
 
 def _p(a):
@@ -43,17 +44,32 @@ def quantize(rows, device=0):
     return out.reshape(a.shape)
 
 
+def _is_term_lists(x):
+    """A batch of queries for an "embeddings" index: sequences of term ids (True) or float rows (False)."""
+    if isinstance(x, np.ndarray):
+        return x.dtype.kind in "iu"
+    for t in x:
+        a = np.asarray(t)
+        if a.size:
+            return a.dtype.kind in "iu"
+    return True  # nothing but empty lists
+
+
 class Granne:
     """An HNSW index resident in the HBM of one MI355X."""
 
-    def __init__(self, element_type, elements, layers, device=0, prepared=True):
-        """element_type: "angular" (f32) or "angular_int" (int8).
+    def __init__(self, element_type, elements, layers, device=0, prepared=True, compact=False):
+        """element_type: "angular" (f32), "angular_int" (int8) or "embeddings" (`elements` is a SumEmbeddings; with
+        compact=True the index keeps the container instead of dense rows and makes vectors as it walks).
         elements: [n, dim] array. With prepared=True (default) rows are taken as stored in a
         Vectors file (already normalised / quantised); with prepared=False raw float rows go
         through Vector::from first.
         layers: list of [layer_len, width] uint32 arrays (UNUSED padded), top layer first --
         what GranneBuilder::get_index hands to Granne (src/index/mod.rs:483-488)."""
         et = element_type.lower()
+        if et == EMBEDDINGS:
+            self._init_embeddings(elements, layers, compact)
+            return
         if et not in _ELEMENT_TYPES:
             raise ValueError("Invalid element type")  # the reference panics (py/src/lib.rs:210)
         self.element_type = et
@@ -74,6 +90,20 @@ class Granne:
                                             rows, widths, device))
         self._h = h
         self.dim = el.shape[1]
+
+    def _init_embeddings(self, se, layers, compact):
+        self.element_type = EMBEDDINGS
+        self.dtype_code, self.np_dtype = F32, np.float32
+        self.device, self.compact, self._se = se.device, bool(compact), se
+        layers = [np.ascontiguousarray(l, dtype=np.uint32) for l in layers]
+        n = len(layers)
+        lens = (C.c_uint64 * max(n, 1))(*[l.shape[0] for l in layers])
+        widths = (C.c_uint32 * max(n, 1))(*[l.shape[1] for l in layers])
+        rows = (C.c_void_p * max(n, 1))(*[l.ctypes.data for l in layers])
+        h = C.c_void_p()
+        check(lib().granne_hip_index_create_sum_embeddings(C.byref(h), se._h, n, lens, rows, widths, int(bool(compact))))
+        self._h = h
+        self.dim = se.dim
 
     @classmethod
     def from_csr(cls, element_type, elements, offsets, ids, device=0):
@@ -100,11 +130,26 @@ class Granne:
         return self
 
     @classmethod
-    def from_files(cls, index_path, element_type, elements_path, device=0):
+    def from_files(cls, index_path, element_type, elements_path, device=0, embeddings_path=None, compact=False):
         """Granne(index_path, element_type, elements_path) of the reference's binding
-        (py/src/lib.rs:177-214): an index file written by write_index + a Vectors file."""
+        (py/src/lib.rs:177-214): an index file written by write_index + a Vectors file -- or, for "embeddings", an
+        elements file of term lists + embeddings_path (the table), materialised or compact."""
         self = cls.__new__(cls)
         et = element_type.lower()
+        if et == EMBEDDINGS:
+            from .embeddings import SumEmbeddings
+            if embeddings_path is None:
+                raise ValueError("embeddings_path is required")  # the reference panics (py/src/lib.rs:199-202)
+            self.element_type = EMBEDDINGS
+            self.dtype_code, self.np_dtype = F32, np.float32
+            self.device, self.compact = device, bool(compact)
+            self._se = SumEmbeddings.from_files(embeddings_path, elements_path, device)  # term-id queries embed through it
+            h = C.c_void_p()
+            check(lib().granne_hip_index_load_files_sum_embeddings(C.byref(h), os.fsencode(index_path), os.fsencode(embeddings_path),
+                                                                   os.fsencode(elements_path), int(bool(compact)), device))
+            self._h = h
+            self.dim = int(lib().granne_hip_index_dim(h))
+            return self
         if et not in _ELEMENT_TYPES:
             raise ValueError("Invalid element type")
         self.element_type = et
@@ -250,6 +295,14 @@ class Granne:
 
     # ---- search -----------------------------------------------------------------------------------
     def _prepare(self, element, prepared):
+        if self.element_type == EMBEDDINGS:
+            # term-id lists are embedded and normalised on the device (py/src/lib.rs:260-268: create_embedding +
+            # Vector::from); float rows are taken like "angular" queries
+            if _is_term_lists(element):
+                if getattr(self, "_se", None) is None:
+                    raise ValueError("term-id queries need the index's SumEmbeddings container")
+                return self._se.create_embeddings(element, normalized=True)
+            return np.ascontiguousarray(element, np.float32) if prepared else normalize(element, self.device)
         if prepared:
             return np.ascontiguousarray(element, dtype=self.np_dtype)
         return normalize(element, self.device) if self.element_type == "angular" else quantize(element, self.device)
@@ -257,7 +310,9 @@ class Granne:
     def search(self, element, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS, prepared=True):
         """Granne.search (py/src/lib.rs:227-233): [(id, distance)] ascending by (distance, id).
         prepared=False applies Vector::from to `element` first, as the reference's binding does."""
-        ids, dists, counts = self.search_batch(np.asarray(element).reshape(1, -1), max_search, num_elements, prepared)
+        terms = self.element_type == EMBEDDINGS and (len(element) == 0 or np.asarray(element).dtype.kind in "iu")
+        one = [list(element)] if terms else np.asarray(element).reshape(1, -1)
+        ids, dists, counts = self.search_batch(one, max_search, num_elements, prepared)
         return [(int(ids[0, i]), float(dists[0, i])) for i in range(int(counts[0]))]
 
     def search_batch(self, elements, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS, prepared=True,

@@ -326,4 +326,75 @@ private:
     std::shared_ptr<granne_hip_builder> b_;
 };
 
+// granne::embeddings::SumEmbeddings (src/elements/embeddings/mod.rs:41-216): elements are lists of term ids, their
+// vectors sums of rows of an embedding table. index() makes a searchable index over given layers: materialised (dense
+// normalised rows on the device) or compact (the container in place of rows; search only).
+namespace embeddings {
+class SumEmbeddings {
+public:
+    SumEmbeddings(const std::vector<float>& table, uint32_t dim, const std::vector<std::vector<uint32_t>>& elements, int device = 0) {
+        std::vector<uint64_t> off(1, 0);
+        std::vector<uint32_t> terms;
+        for (const auto& e : elements) {
+            terms.insert(terms.end(), e.begin(), e.end());
+            off.push_back(terms.size());
+        }
+        granne_hip_sum_embeddings* h = nullptr;
+        check(granne_hip_sum_embeddings_create(&h, table.data(), dim ? table.size() / dim : 0, dim, off.data(), terms.data(),
+                                               elements.size(), device));
+        h_.reset(h, granne_hip_sum_embeddings_destroy);
+    }
+    static SumEmbeddings from_files(const std::string& embeddings_path, const std::string& elements_path, int device = 0) {
+        granne_hip_sum_embeddings* h = nullptr;
+        check(granne_hip_sum_embeddings_load_files(&h, embeddings_path.c_str(), elements_path.c_str(), device));
+        return SumEmbeddings(h);
+    }
+    size_t len() const { return granne_hip_sum_embeddings_len(h_.get()); }
+    size_t num_embeddings() const { return granne_hip_sum_embeddings_num_embeddings(h_.get()); }
+    size_t dim() const { return granne_hip_sum_embeddings_dim(h_.get()); }
+    void push(const std::vector<uint32_t>& element) {
+        const uint64_t off[2] = {0, element.size()};
+        check(granne_hip_sum_embeddings_append(h_.get(), off, element.data(), 1));
+    }
+    std::vector<size_t> get_terms(size_t idx) const {
+        uint32_t n = 0;
+        check(granne_hip_sum_embeddings_get_terms(h_.get(), idx, nullptr, 0, &n));
+        std::vector<uint32_t> t(n);
+        check(granne_hip_sum_embeddings_get_terms(h_.get(), idx, t.data(), n, &n));
+        return std::vector<size_t>(t.begin(), t.end());
+    }
+    std::vector<float> get_embedding(size_t idx) const { // the raw sum
+        std::vector<float> v(dim());
+        check(granne_hip_sum_embeddings_materialize(h_.get(), idx, 1, 0, v.data()));
+        return v;
+    }
+    std::vector<float> create_embedding(const std::vector<uint32_t>& terms, bool normalised = false) const {
+        const uint64_t off[2] = {0, terms.size()};
+        std::vector<float> v(dim());
+        check(granne_hip_sum_embeddings_embed(h_.get(), off, terms.data(), 1, normalised ? 1 : 0, v.data()));
+        return v;
+    }
+    void save_elements(const std::string& path) const { check(granne_hip_sum_embeddings_save_elements(h_.get(), path.c_str())); }
+    void save_embeddings(const std::string& path) const { check(granne_hip_sum_embeddings_save_embeddings(h_.get(), path.c_str())); }
+    // the C handles of an index / a builder over this container (owned by the caller: granne_hip_index_destroy / _builder_destroy)
+    granne_hip_index* index(uint32_t n_layers, const uint64_t* layer_len, const uint32_t* const* layer_rows,
+                            const uint32_t* layer_width, bool compact) const {
+        granne_hip_index* ix = nullptr;
+        check(granne_hip_index_create_sum_embeddings(&ix, h_.get(), n_layers, layer_len, layer_rows, layer_width,
+                                                     compact ? GRANNE_HIP_SE_COMPACT : GRANNE_HIP_SE_MATERIALIZED));
+        return ix;
+    }
+    granne_hip_builder* builder(const granne_hip_build_config& config) const {
+        granne_hip_builder* b = nullptr;
+        check(granne_hip_builder_create_sum_embeddings(&b, &config, h_.get()));
+        return b;
+    }
+    granne_hip_sum_embeddings* handle() const { return h_.get(); }
+
+private:
+    explicit SumEmbeddings(granne_hip_sum_embeddings* h) : h_(h, granne_hip_sum_embeddings_destroy) {}
+    std::shared_ptr<granne_hip_sum_embeddings> h_;
+};
+} // namespace embeddings
+
 } // namespace granne

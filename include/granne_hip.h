@@ -486,6 +486,88 @@ int granne_hip_sharded_build(granne_hip_sharded** out, const granne_hip_build_co
                              uint64_t n_elements, uint32_t dim, int dtype, uint32_t n_shards,
                              const int* device_ids, uint32_t n_devices);
 
+/* ---- embeddings::SumEmbeddings (src/elements/embeddings/mod.rs:41-216) ----------------------------
+ * The reference's third element container: an element is a list of term ids (3 bytes each on disk), its vector the sum
+ * of those terms' rows of an f32 embedding table, in list order (create_embedding :124-143), normalised when it is asked
+ * for (ElementContainer::get :164-166 -> angular::Vector::from). A walk over such a container is, value for value, a
+ * walk over the dense rows normalize(sum); this library computes those rows with the reference's operation order.
+ * The handle holds table [n_embeddings][dim] and the elements as CSR (offsets[n + 1] u64 counted in ids, term ids u32).
+ * Creating, loading, saving, get_terms and append are host work and need no device; the container is uploaded to
+ * device_id when an entry point below first needs it there.
+ * Invalid input -- a term id >= n_embeddings, offsets that do not start at 0 or decrease, a truncated file; on write
+ * more than 2^24 embeddings (3-byte ids) or 2^40 ids (5-byte offsets) -- is GRANNE_HIP_ERR_INVALID with a message. */
+typedef struct granne_hip_sum_embeddings granne_hip_sum_embeddings;
+int granne_hip_sum_embeddings_create(granne_hip_sum_embeddings** out, const float* table, uint64_t n_embeddings,
+                                     uint32_t dim, const uint64_t* offsets, const uint32_t* terms, uint64_t n_elements,
+                                     int device_id);
+/* the same from device buffers on device_id (copied; the term lists are checked on the host) */
+int granne_hip_sum_embeddings_create_device(granne_hip_sum_embeddings** out, const float* d_table, uint64_t n_embeddings,
+                                            uint32_t dim, const uint64_t* d_offsets, const uint32_t* d_terms,
+                                            uint64_t n_elements, int device_id, void* stream);
+/* SumEmbeddings from its two files: an f32 Vectors file ([u64 dim][rows], not normalised) and an elements file
+ * ([u64 LE n][n + 1 offsets of 5 bytes LE][ids of 3 bytes LE], src/slice_vector/mod.rs:623-634, 660-676) */
+int granne_hip_sum_embeddings_load_files(granne_hip_sum_embeddings** out, const char* embeddings_path,
+                                         const char* elements_path, int device_id);
+/* the bytes of an elements file over a table the caller holds (SumEmbeddings::from_bytes, :56-87) */
+int granne_hip_sum_embeddings_load(granne_hip_sum_embeddings** out, const float* table, uint64_t n_embeddings, uint32_t dim,
+                                   const void* elements_bytes, uint64_t elements_len, int device_id);
+int granne_hip_sum_embeddings_save_elements(const granne_hip_sum_embeddings* se, const char* path);
+int granne_hip_sum_embeddings_save_embeddings(const granne_hip_sum_embeddings* se, const char* path);
+void granne_hip_sum_embeddings_destroy(granne_hip_sum_embeddings* se);
+uint64_t granne_hip_sum_embeddings_len(const granne_hip_sum_embeddings* se);
+uint64_t granne_hip_sum_embeddings_num_embeddings(const granne_hip_sum_embeddings* se);
+uint32_t granne_hip_sum_embeddings_dim(const granne_hip_sum_embeddings* se);
+/* bytes of the container's device copy: n_embeddings rows padded to 16 bytes + 8 (n + 1) + 4 per term id */
+uint64_t granne_hip_sum_embeddings_hbm_bytes(const granne_hip_sum_embeddings* se);
+/* SumEmbeddings::get_terms (:108-110): copies up to cap ids of element idx, *out_count = how many it has */
+int granne_hip_sum_embeddings_get_terms(const granne_hip_sum_embeddings* se, uint64_t idx, uint32_t* out_terms, uint32_t cap,
+                                        uint32_t* out_count);
+/* ExtendableElementContainer::push (:180-182) for n_new elements: offsets[n_new + 1] starting at 0, their term ids.
+ * Indexes and builders made before keep the container as it was. */
+int granne_hip_sum_embeddings_append(granne_hip_sum_embeddings* se, const uint64_t* offsets, const uint32_t* terms,
+                                     uint64_t n_new);
+/* get_embedding (:113-115; normalised = 0) or ElementContainer::get (:164-166; normalised = 1) of elements first ..
+ * first + count - 1 as dense f32 rows, `stride` floats (>= dim) from one to the next; the bits are the reference's.
+ * _device: d_out on the container's device, asynchronous on `stream`. */
+int granne_hip_sum_embeddings_materialize_device(const granne_hip_sum_embeddings* se, uint64_t first, uint64_t count,
+                                                 int normalised, float* d_out, uint64_t stride, void* stream);
+int granne_hip_sum_embeddings_materialize(const granne_hip_sum_embeddings* se, uint64_t first, uint64_t count, int normalised,
+                                          float* out);
+/* create_embedding (:118-120) for nq caller-supplied term lists -- query batches: offsets[nq + 1] starting at 0. The
+ * host form checks the ids; in the device form an id >= n_embeddings contributes nothing. */
+int granne_hip_sum_embeddings_embed_device(const granne_hip_sum_embeddings* se, const uint64_t* d_offsets,
+                                           const uint32_t* d_terms, uint64_t nq, int normalised, float* d_out, uint64_t stride,
+                                           void* stream);
+int granne_hip_sum_embeddings_embed(const granne_hip_sum_embeddings* se, const uint64_t* offsets, const uint32_t* terms,
+                                    uint64_t nq, int normalised, float* out);
+
+/* An index over a container, in one of two forms (layers: host rows as in granne_hip_index_create; dtype is f32):
+ *   GRANNE_HIP_SE_MATERIALIZED  the normalised rows are made on the device and the index is from there on exactly what
+ *                               granne_hip_index_create_device makes of them: sketches, inline tails, the register
+ *                               walker, the exact scan, reorder.
+ *   GRANNE_HIP_SE_COMPACT       only the table, the offsets, the term ids and the layers stay in HBM (18 GB instead of
+ *                               400 GB for 10^9 elements of six terms at 100 dimensions). Every walk is the general
+ *                               walker's (max_search <= 256) or the exact walker's, which make a candidate's vector from
+ *                               its terms where they need it; results are the materialised index's, bit for bit.
+ *                               search*, search_begin/end, packed results, use as a shard, get_neighbors, get_element (the
+ *                               normalised vector), encode and save of the index file work. brute_force*, dists*,
+ *                               dist_pairs*, reorder*, get_sketch and save of an elements file return
+ *                               GRANNE_HIP_ERR_INVALID: they need the dense rows of the materialised form.
+ * The index shares the container's device copy; the container may be destroyed before it. */
+enum { GRANNE_HIP_SE_MATERIALIZED = 0, GRANNE_HIP_SE_COMPACT = 1 };
+int granne_hip_index_create_sum_embeddings(granne_hip_index** out, const granne_hip_sum_embeddings* se, uint32_t n_layers,
+                                           const uint64_t* layer_len, const uint32_t* const* layer_rows,
+                                           const uint32_t* layer_width, int mode);
+/* Granne::from_file over a container: index file, embeddings file, elements file */
+int granne_hip_index_load_files_sum_embeddings(granne_hip_index** out, const char* index_path, const char* embeddings_path,
+                                               const char* elements_path, int mode, int device_id);
+/* GranneBuilder::new(config, sum_embeddings): the GPU builder over the container's normalised rows.
+ * granne_hip_builder_get_index gives a materialised index, granne_hip_builder_get_index_compact a compact one over the
+ * same layers (the builder stays usable; INVALID for a builder not made by this call, or after builder_append). */
+int granne_hip_builder_create_sum_embeddings(granne_hip_builder** out, const granne_hip_build_config* config,
+                                             const granne_hip_sum_embeddings* se);
+int granne_hip_builder_get_index_compact(const granne_hip_builder* builder, granne_hip_index** out);
+
 /* ---- options (per index) ---------------------------------------------------------------------- */
 enum {
     GRANNE_HIP_OPT_VISITED_SLOTS = 1, /* LDS visited-table slots per query: 2^k or 3 * 2^k in [256, 32768]; 0 = auto */

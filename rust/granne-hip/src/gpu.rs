@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct granne_hip_index { _private: [u8; 0] }
 #[repr(C)] pub struct granne_hip_builder { _private: [u8; 0] }
 #[repr(C)] pub struct granne_hip_sharded { _private: [u8; 0] }
+#[repr(C)] pub struct granne_hip_sum_embeddings { _private: [u8; 0] }
 
 pub const GRANNE_HIP_F32: c_int = 0;
 pub const GRANNE_HIP_I8: c_int = 1;
@@ -93,6 +94,43 @@ extern "C" {
     fn granne_hip_sharded_build(out: *mut *mut granne_hip_sharded, config: *const granne_hip_build_config,
         elements: *const c_void, n_elements: u64, dim: u32, dtype: c_int, n_shards: u32, device_ids: *const c_int,
         n_devices: u32) -> c_int;
+    // ---- embeddings::SumEmbeddings: the container, its files, materialised and compact indexes
+    fn granne_hip_sum_embeddings_create(out: *mut *mut granne_hip_sum_embeddings, table: *const f32,
+        n_embeddings: u64, dim: u32, offsets: *const u64, terms: *const u32, n_elements: u64, device_id: c_int) -> c_int;
+    fn granne_hip_sum_embeddings_create_device(out: *mut *mut granne_hip_sum_embeddings, d_table: *const f32,
+        n_embeddings: u64, dim: u32, d_offsets: *const u64, d_terms: *const u32, n_elements: u64, device_id: c_int,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_sum_embeddings_load_files(out: *mut *mut granne_hip_sum_embeddings,
+        embeddings_path: *const c_char, elements_path: *const c_char, device_id: c_int) -> c_int;
+    fn granne_hip_sum_embeddings_load(out: *mut *mut granne_hip_sum_embeddings, table: *const f32,
+        n_embeddings: u64, dim: u32, elements_bytes: *const c_void, elements_len: u64, device_id: c_int) -> c_int;
+    fn granne_hip_sum_embeddings_save_elements(se: *const granne_hip_sum_embeddings, path: *const c_char) -> c_int;
+    fn granne_hip_sum_embeddings_save_embeddings(se: *const granne_hip_sum_embeddings, path: *const c_char) -> c_int;
+    fn granne_hip_sum_embeddings_destroy(se: *mut granne_hip_sum_embeddings);
+    fn granne_hip_sum_embeddings_len(se: *const granne_hip_sum_embeddings) -> u64;
+    fn granne_hip_sum_embeddings_num_embeddings(se: *const granne_hip_sum_embeddings) -> u64;
+    fn granne_hip_sum_embeddings_dim(se: *const granne_hip_sum_embeddings) -> u32;
+    fn granne_hip_sum_embeddings_hbm_bytes(se: *const granne_hip_sum_embeddings) -> u64;
+    fn granne_hip_sum_embeddings_get_terms(se: *const granne_hip_sum_embeddings, idx: u64, out_terms: *mut u32,
+        cap: u32, out_count: *mut u32) -> c_int;
+    fn granne_hip_sum_embeddings_append(se: *mut granne_hip_sum_embeddings, offsets: *const u64, terms: *const u32,
+        n_new: u64) -> c_int;
+    fn granne_hip_sum_embeddings_materialize_device(se: *const granne_hip_sum_embeddings, first: u64, count: u64,
+        normalised: c_int, d_out: *mut f32, stride: u64, stream: *mut c_void) -> c_int;
+    fn granne_hip_sum_embeddings_materialize(se: *const granne_hip_sum_embeddings, first: u64, count: u64,
+        normalised: c_int, out: *mut f32) -> c_int;
+    fn granne_hip_sum_embeddings_embed_device(se: *const granne_hip_sum_embeddings, d_offsets: *const u64,
+        d_terms: *const u32, nq: u64, normalised: c_int, d_out: *mut f32, stride: u64, stream: *mut c_void) -> c_int;
+    fn granne_hip_sum_embeddings_embed(se: *const granne_hip_sum_embeddings, offsets: *const u64,
+        terms: *const u32, nq: u64, normalised: c_int, out: *mut f32) -> c_int;
+    fn granne_hip_index_create_sum_embeddings(out: *mut *mut granne_hip_index,
+        se: *const granne_hip_sum_embeddings, n_layers: u32, layer_len: *const u64, layer_rows: *const *const u32,
+        layer_width: *const u32, mode: c_int) -> c_int;
+    fn granne_hip_index_load_files_sum_embeddings(out: *mut *mut granne_hip_index, index_path: *const c_char,
+        embeddings_path: *const c_char, elements_path: *const c_char, mode: c_int, device_id: c_int) -> c_int;
+    fn granne_hip_builder_create_sum_embeddings(out: *mut *mut granne_hip_builder,
+        config: *const granne_hip_build_config, se: *const granne_hip_sum_embeddings) -> c_int;
+    fn granne_hip_builder_get_index_compact(builder: *const granne_hip_builder, out: *mut *mut granne_hip_index) -> c_int;
 }
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
