@@ -208,24 +208,26 @@ struct WalkList : SortedList<S> {
     }
 };
 
-#ifndef GRANNE_HIP_QUERY_IN_LDS
-#define GRANNE_HIP_QUERY_IN_LDS 0 // experiments: 1 = the short list reads an f32 query from LDS too
-#endif
 // A query that lives in registers needs no LDS of its own: int8 rows (64 bytes per lane; staged once through the
 // start of the walker's LDS) and, for the short list, f32 rows of the unrolled
 // dims (this lane's pieces in VGPRs; longer lists need the registers and read the query from LDS, 13 ds_read_b128
 // per expansion at 100-d, issued under the row loads). Without a visited table the walker's LDS is that staging area
 // (and the mirror of lists of S >= 8): the registers bound the walkers per CU.
-__host__ __device__ constexpr bool fast_query_in_regs(bool i8, bool gen, uint32_t dim, uint32_t S) {
+// seen: the launches of many walks (FastWalker's V16 == 5). Their expansions are three dependent trips to memory that
+// each carry little (adjacency row, sketch lines, the survivors' rows), so they wait on latency and want walks in
+// flight more than they want the 52 registers of a 100-d query: the short list reads its query from LDS there too and
+// fits four waves per SIMD (fast_waves_per_simd). The launches of a few walks are bound by one wave's instruction
+// issue and keep the query in registers.
+__host__ __device__ constexpr bool fast_query_in_regs(bool i8, bool gen, uint32_t dim, uint32_t S, bool seen) {
     if (i8) return true;
-    if (gen || S != 1u || GRANNE_HIP_QUERY_IN_LDS) return false;
+    if (gen || S != 1u || seen) return false;
     return (dim / 32u) * 16u + ((dim % 32u) / 4u) * 4u <= 64u;
 }
 // LDS bytes of the query. f32 rows of a compile-time dim: the row itself. Run-time f32 dims (DIM == 0): full
 // 32-float chunks padded with zero chunks to a whole number of groups of three, then one 128-byte tail block.
 constexpr uint32_t GEN_GROUP = 3; // chunks whose loads are in flight together (12 x 16 bytes per lane)
-__host__ __device__ inline uint32_t fast_query_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S) {
-    if (fast_query_in_regs(i8, gen, dim, S)) return 0u;
+__host__ __device__ inline uint32_t fast_query_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S, bool seen) {
+    if (fast_query_in_regs(i8, gen, dim, S, seen)) return 0u;
     if (!gen) return lds_query_bytes(row_bytes);
     const uint32_t nbk = dim / 32u;
     const uint32_t ngroups = (nbk + GEN_GROUP - 1u) / GEN_GROUP;
@@ -248,7 +250,7 @@ struct FastWalker {
     static constexpr bool GEN = F32 && DIM == 0;
     static constexpr int NB = F32 ? (GEN ? (int)GEN_GROUP : DIM / 32) : 0; // full 32-float chunks (GEN: per group)
     static constexpr int TU = F32 ? (DIM % 32) / 4 : 0;  // 16-byte units of the tail
-    static constexpr bool QREG = F32 && fast_query_in_regs(false, GEN, (uint32_t)DIM, (uint32_t)S);
+    static constexpr bool QREG = F32 && fast_query_in_regs(false, GEN, (uint32_t)DIM, (uint32_t)S, V16 == 5);
     static constexpr int NBI = F32 ? 1 : (DIM ? DIM / 128 : 1); // int8: 128-byte blocks per row (DIM = row bytes; 0 = 128)
     static constexpr uint32_t ROWB = F32 ? (uint32_t)DIM * 4u : 128u * NBI;
     // bytes from one row to the next (device_row_stride, granne_hip.hip): f32 rows of 256 bytes and more start on a line
@@ -314,7 +316,7 @@ struct FastWalker {
         lane = threadIdx.x;
         h = lane & 1u;
         R = lane >> 1;
-        const uint32_t qb = fast_query_bytes(!F32, GEN, p.dim, p.row_bytes, (uint32_t)S);
+        const uint32_t qb = fast_query_bytes(!F32, GEN, p.dim, p.row_bytes, (uint32_t)S, V16 == 5);
         g_nbk = p.dim / 32u;
         g_ngroups = (g_nbk + GEN_GROUP - 1u) / GEN_GROUP;
         g_tu = ((p.dim & 31u) + 3u) / 4u;
@@ -1550,7 +1552,7 @@ __device__ __forceinline__ void fast_walk_one(const SearchParams& p, const uint3
 // waves per SIMD the register allocator is asked to keep possible (__launch_bounds__'s second argument is
 // per SIMD on AMD; 5 waves = 96 VGPRs, 4 = 128, 3 = 168, 2 = 256). Chosen from the unconstrained
 // allocation of each instantiation so that none spills (tools/isa_report.py prints both).
-constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false) {
+constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, bool SEEN = false) {
 #if GRANNE_HIP_PHASE_TIMERS
     return 1; // the phase clocks live in registers too: no cap, the diagnostics run is one wave per SIMD anyway
 #endif
@@ -1563,12 +1565,13 @@ constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false) {
     if (DIM == 0) return 2; // the streamed walker keeps a group of chunks, the tail and the accumulators: ~210 VGPRs
     if (DIM > 128) return S == 1 ? 3 : 2;
     if (WIDE && S == 2) return 3; // (the second half of the row is one register too many for 128)
-    return S == 1 ? (GRANNE_HIP_QUERY_IN_LDS ? 4 : 3) : S == 2 ? 4 : S <= 8 ? 3 : 2;
+    // (the short list with its 100-d query in registers: 159; with the query in LDS, fast_query_in_regs: within 128)
+    return S == 1 ? (SEEN ? 4 : 3) : S == 2 ? 4 : S <= 8 ? 3 : 2;
 }
 
 // Blocks nq.. are the tail (slow_kernel.h): they serve the hand-over list inside the same launch.
 template <int DT, int DIM, int S, bool TRAIL = false, int V16 = 0, bool WIDE = false>
-__global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE)) void fast_kernel(const SlowParams P) {
+__global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE, V16 == 5)) void fast_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
     if (blockIdx.x < P.sp.nq) {
         fast_walk_one<DT, DIM, S, TRAIL, V16, WIDE>(P.sp, blockIdx.x, smem);
@@ -1584,7 +1587,7 @@ __host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t d
     // (lists beyond 1024 keys: M's image, then F's of 128 keys)
     // (+ the launches that skip revisits on the sketched shapes: the query's sketch codes where the visited table would be)
     const uint32_t sk = (seen && !i8 && !gen && !wide && sketch_dim_ok(dim)) ? SKETCH_LINE : 0u;
-    return fast_query_bytes(i8, gen, dim, row_bytes, S) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + (seen ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS) * 4u + visited_slots * 4u + sk;
+    return fast_query_bytes(i8, gen, dim, row_bytes, S, seen) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + (seen ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS) * 4u + visited_slots * 4u + sk;
 }
 
 } // namespace granne_hip
