@@ -7,5 +7,6 @@ from ._lib import F32, I8, UNUSED, GranneHipError  # noqa: F401
 from .index import Granne, compute_distance, normalize, quantize  # noqa: F401
 from .builder import GranneBuilder  # noqa: F401
 from .embeddings import SumEmbeddings  # noqa: F401
+from .rw_builder import RwGranneBuilder  # noqa: F401
 
-__all__ = ["Granne", "GranneBuilder", "SumEmbeddings", "compute_distance", "normalize", "quantize", "GranneHipError", "F32", "I8", "UNUSED"]
+__all__ = ["Granne", "GranneBuilder", "RwGranneBuilder", "SumEmbeddings", "compute_distance", "normalize", "quantize", "GranneHipError", "F32", "I8", "UNUSED"]

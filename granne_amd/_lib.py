@@ -21,6 +21,8 @@ SEARCH_DEPTH = 3  # GRANNE_HIP_SEARCH_DEPTH (the default of OPT_SEARCH_DEPTH)
 SEARCH_DEPTH_MAX = 16  # GRANNE_HIP_SEARCH_DEPTH_MAX
 SHARDED_OPT_DEPTH, SHARDED_OPT_EXCHANGE = 1, 2
 SHARDED_EXCHANGE_PEER, SHARDED_EXCHANGE_RCCL = 0, 1
+RW_OPT_SMALL_OPS, RW_OPT_SMALL_LAUNCHES, RW_OPT_SORTED_LAUNCHES = 1, 2, 3  # GRANNE_HIP_RW_OPT_*
+RW_SMALL_OPS = 2048  # GRANNE_HIP_RW_SMALL_OPS
 SE_MATERIALIZED, SE_COMPACT = 0, 1  # GRANNE_HIP_SE_*: the two forms of an index over a SumEmbeddings container
 
 
@@ -164,6 +166,21 @@ SIGNATURES = {
     "granne_hip_index_load_files_sum_embeddings": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, i32, i32]),
     "granne_hip_builder_create_sum_embeddings": (i32, [C.POINTER(vp), vp, vp]),
     "granne_hip_builder_get_index_compact": (i32, [vp, C.POINTER(vp)]),
+    "granne_hip_rw_builder_create": (i32, [C.POINTER(vp), vp, u64]),
+    "granne_hip_rw_builder_destroy": (None, [vp]),
+    "granne_hip_rw_builder_insert_batch": (i32, [vp, vp, u64, vp, C.POINTER(u64)]),
+    "granne_hip_rw_builder_search_batch": (i32, [vp, vp, u32, u32, u32, vp, vp, vp, vp]),
+    "granne_hip_rw_builder_search": (i32, [vp, vp, u32, u32, vp, vp, C.POINTER(u32)]),
+    "granne_hip_rw_builder_len": (u64, [vp]),
+    "granne_hip_rw_builder_max_elements": (u64, [vp]),
+    "granne_hip_rw_builder_num_layers": (u32, [vp]),
+    "granne_hip_rw_builder_layer_len": (u64, [vp, u32]),
+    "granne_hip_rw_builder_get_layer": (i32, [vp, u32, vp]),
+    "granne_hip_rw_builder_get_element": (i32, [vp, u64, vp]),
+    "granne_hip_rw_builder_save": (i32, [vp, C.c_char_p, C.c_char_p]),
+    "granne_hip_rw_builder_get_index": (i32, [vp, C.POINTER(vp)]),
+    "granne_hip_rw_builder_set_option": (i32, [vp, i32, u64]),
+    "granne_hip_rw_builder_get_option": (i32, [vp, i32, C.POINTER(u64)]),
 }
 
 

@@ -231,14 +231,16 @@ struct BuildScratch {
     }
 };
 
-static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t max_search, bool reinsert,
-                               uint64_t already, BuildScratch& S, hipStream_t s) {
-    const uint32_t last = (uint32_t)b->layers.size() - 1;
-    BuilderLayer& L = b->layers[last];
-    const uint64_t layer_len = L.len;
+// What every launch of the three build kernels over one layer shares: the kernels of the row shape, the LDS carve-up
+// and its sizes, and the BuildParams that do not change from one batch to the next.
+struct BuildPlan {
+    BuildKernels K;
+    uint32_t lds = 0, lds_rows = 0; // dynamic LDS of select_kernel; of apply_kernel / final_prune_kernel (<= lds)
+    BuildParams P;
+};
+static int make_build_plan(const granne_hip_builder* b, const BuilderLayer& L, uint32_t m_layer, uint32_t max_search,
+                           const BuildScratch& S, uint8_t* selected, BuildPlan* out) {
     const uint32_t cap = b->cfg.num_neighbors;
-    const uint64_t total = reinsert ? layer_len : layer_len - already;
-    const uint32_t bmax = b->cfg.batch_max;
     const uint32_t lrow = ((b->row_bytes / 16) | 1u) * 16u;
     const BuildKernels K = pick_build_kernels(b->dtype, b->dim);
     // (apply / final_prune only ever see cap + 1 candidates: their arrays keep the minimum size)
@@ -261,17 +263,10 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
         HIP_TRY(hipFuncSetAttribute((const void*)K.apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_TRY(hipFuncSetAttribute((const void*)K.final_prune, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-
-    const SearchTarget T(b, S.d_layers, last + 1);
-    SearchCall call; // phase A's searches: max_search neighbors of each batch's rows, from the rows themselves
-    call.ef = call.k = max_search;
-    call.ids = S.s_ids;
-    call.dists = S.s_dists;
-    call.counts = S.s_counts;
-    call.status = S.counters + 1;
-    call.stream = s;
-
-    BuildParams P;
+    out->K = K;
+    out->lds = lds;
+    out->lds_rows = lds_rows;
+    BuildParams& P = out->P;
     P.elements = b->d_elements;
     P.row_bytes = b->row_bytes;
     P.row_stride = b->row_stride;
@@ -281,7 +276,7 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
     P.W = b->W;
     P.cap = cap;
     P.m_layer = m_layer;
-    P.layer_len = layer_len;
+    P.layer_len = L.len;
     P.efc = max_search;
     P.s_ids = S.s_ids;
     P.s_dists = S.s_dists;
@@ -292,10 +287,39 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
     P.sorted_vals = S.sorted_vals;
     P.seg_start = S.seg_start;
     P.n_seg = S.counters;
-    P.selected = S.selected;
+    P.selected = selected;
     P.cand_cap = cand_cap;
     P.chunk = chunk;
     P.sel_lds = sel_lds;
+    return GRANNE_HIP_OK;
+}
+
+static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t max_search, bool reinsert,
+                               uint64_t already, BuildScratch& S, hipStream_t s) {
+    const uint32_t last = (uint32_t)b->layers.size() - 1;
+    BuilderLayer& L = b->layers[last];
+    const uint64_t layer_len = L.len;
+    const uint32_t cap = b->cfg.num_neighbors;
+    const uint64_t total = reinsert ? layer_len : layer_len - already;
+    const uint32_t bmax = b->cfg.batch_max;
+    BuildPlan plan;
+    {
+        int rc = make_build_plan(b, L, m_layer, max_search, S, S.selected, &plan);
+        if (rc) return rc;
+    }
+    const BuildKernels K = plan.K;
+    const uint32_t lds = plan.lds, lds_rows = plan.lds_rows;
+    BuildParams& P = plan.P;
+
+    const SearchTarget T(b, S.d_layers, last + 1);
+    SearchCall call; // phase A's searches: max_search neighbors of each batch's rows, from the rows themselves
+    call.ef = call.k = max_search;
+    call.ids = S.s_ids;
+    call.dists = S.s_dists;
+    call.counts = S.s_counts;
+    call.status = S.counters + 1;
+    call.stream = s;
+
     HIP_TRY(hipMemsetAsync(S.selected, 0, layer_len ? layer_len : 1, s)); // nothing is known about the rows of a pass
 
     const bool debug = getenv("GRANNE_HIP_DEBUG") != nullptr;

@@ -479,6 +479,61 @@ __global__ void mark_heads_kernel(const uint64_t* __restrict__ keys, uint32_t n_
     }
 }
 
+// ---- phase B for a small sub-batch (RwGranneBuilder's inserts: one element, or tens): the radix sort, the counter
+// memset and mark_heads_kernel in one launch of one workgroup. The ops are sorted in LDS as (key, position) pairs
+// by a bitonic network over the next power of two (pads and invalid ops carry OP_INVALID, the largest key, so the
+// n_ops first sorted entries hold every valid op; valid keys are unique, the order among invalid ones decides
+// nothing); values are fetched by position when the result is written. Two elements per thread and stage: the
+// exchange partners i and i + j are read and written by the same thread, so a stage needs one barrier, and with
+// 8-byte keys a wave's accesses at a stride of j elements fall on distinct banks for j >= 32 and pair up below
+// (2-way at most) -- 66 stages at 2,048 ops, 21 for the 60 ops of a single insert at 30 neighbors, which one wave runs.
+// Segment heads go to seg_start in the order of an LDS counter (as free as mark_heads_kernel's atomic order).
+constexpr uint32_t RW_SMALL_OPS = 2048; // 2,048 x (8-byte key + 4-byte position) = 24 KB of LDS
+__global__ __launch_bounds__(1024) void sort_ops_small_kernel(const uint64_t* __restrict__ op_keys,
+                                                              const uint64_t* __restrict__ op_vals, uint32_t n_ops,
+                                                              uint64_t* __restrict__ sorted_keys,
+                                                              uint64_t* __restrict__ sorted_vals,
+                                                              uint32_t* __restrict__ seg_start, uint32_t* __restrict__ n_seg) {
+    __shared__ uint64_t key[RW_SMALL_OPS];
+    __shared__ uint32_t src[RW_SMALL_OPS];
+    __shared__ uint32_t heads;
+    const uint32_t tid = threadIdx.x;
+    if (n_ops > RW_SMALL_OPS) return; // (the host never launches this: nothing is read or written out of bounds)
+    uint32_t n = 64;
+    while (n < n_ops) n <<= 1;
+    for (uint32_t i = tid; i < n; i += blockDim.x) {
+        key[i] = i < n_ops ? op_keys[i] : OP_INVALID;
+        src[i] = i;
+    }
+    if (tid == 0) heads = 0;
+    __syncthreads();
+    for (uint32_t k = 2; k <= n; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = tid; t < (n >> 1); t += blockDim.x) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)); // bit j of i is 0
+                const uint32_t l = i | j;
+                const uint64_t a = key[i], b = key[l];
+                if ((a > b) == ((i & k) == 0u)) {
+                    key[i] = b;
+                    key[l] = a;
+                    const uint32_t sa = src[i];
+                    src[i] = src[l];
+                    src[l] = sa;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = tid; i < n_ops; i += blockDim.x) {
+        const uint64_t kk = key[i];
+        sorted_keys[i] = kk;
+        sorted_vals[i] = op_vals[src[i]];
+        if (kk != OP_INVALID && (i == 0 || op_target(key[i - 1]) != op_target(kk))) seg_start[atomicAdd(&heads, 1u)] = i;
+    }
+    __syncthreads();
+    if (tid == 0) *n_seg = heads;
+}
+
 // ---- phase B: replay one target row's ops in order (initialize_node / connect_nodes) --------------
 template <int DT, int DIM>
 __global__ __launch_bounds__(64) void apply_kernel(const BuildParams P) {

@@ -2198,3 +2198,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // embeddings::SumEmbeddings: the container, its files, materialised and compact indexes
 // ------------------------------------------------------------------------------------------------
 #include "sum_embeddings_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// RwGranneBuilder on the GPU: insert into and search a live graph
+// ------------------------------------------------------------------------------------------------
+#include "rw_builder_host.h"

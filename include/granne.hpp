@@ -32,6 +32,11 @@ inline void check(int rc) {
 }
 
 namespace detail {
+// a GranneBuilder's handle, until an RwGranneBuilder takes it over
+struct BuilderDeleter {
+    bool armed = true;
+    void operator()(granne_hip_builder* b) const { if (armed) granne_hip_builder_destroy(b); }
+};
 template <class Scalar> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = GRANNE_HIP_F32; };
 template <> struct dtype_of<int8_t> { static constexpr int value = GRANNE_HIP_I8; };
@@ -294,7 +299,7 @@ public:
         using Scalar = typename decltype(Elements::Element::data)::value_type;
         check(granne_hip_builder_create(&b, &config.raw(), elements.as_slice(), elements.len(),
                                         (uint32_t)(elements.dim() ? elements.dim() : 1), detail::dtype_of<Scalar>::value, device));
-        b_.reset(b, granne_hip_builder_destroy);
+        b_.reset(b, detail::BuilderDeleter{});
     }
     // GranneBuilder::from_bytes (mod.rs:430-461): a builder resuming from a written index
     static GranneBuilder from_bytes(const BuildConfig& config, const void* index, size_t index_len, const Elements& elements,
@@ -323,7 +328,75 @@ public:
     }
 
 private:
+    template <class> friend class RwGranneBuilder;
+    // hands the handle over (RwGranneBuilder consumes it); every copy of this GranneBuilder is empty afterwards
+    granne_hip_builder* release() {
+        std::get_deleter<detail::BuilderDeleter>(b_)->armed = false;
+        granne_hip_builder* p = b_.get();
+        b_.reset();
+        return p;
+    }
     std::shared_ptr<granne_hip_builder> b_;
+};
+
+// RwGranneBuilder (src/index/rw/mod.rs:15-224): inserts and searches on one live graph. Member functions are const as
+// the reference's take &self: the library serialises inserts against searches with a reader-writer lock held per call
+// (a search sees the graph after a whole number of insert calls). Without a previous layer search returns nothing
+// (rw/mod.rs:198-206).
+template <class Elements>
+class RwGranneBuilder {
+public:
+    using Element = typename Elements::Element;
+    // RwGranneBuilder::new(builder, max_elements, _) (rw/mod.rs:32-61): consumes the builder (no other copy of it may
+    // be in use)
+    RwGranneBuilder(GranneBuilder<Elements>&& builder, size_t max_elements) {
+        granne_hip_rw_builder* h = nullptr;
+        check(granne_hip_rw_builder_create(&h, builder.b_.get(), max_elements));
+        builder.release();
+        h_.reset(h, granne_hip_rw_builder_destroy);
+    }
+    // insert (rw/mod.rs:99-101): the element's id, or -1 when the builder is full
+    long long insert(const Element& element) const {
+        uint64_t id = 0, count = 0;
+        check(granne_hip_rw_builder_insert_batch(h_.get(), element.as_slice(), 1, &id, &count));
+        return count ? (long long)id : -1;
+    }
+    // insert_batch (rw/mod.rs:103-182)
+    std::vector<size_t> insert_batch(const Elements& elements) const {
+        std::vector<uint64_t> ids(elements.len());
+        uint64_t count = 0;
+        check(granne_hip_rw_builder_insert_batch(h_.get(), elements.as_slice(), elements.len(), ids.data(), &count));
+        return std::vector<size_t>(ids.begin(), ids.begin() + count);
+    }
+    // search (rw/mod.rs:184-207)
+    std::vector<std::pair<size_t, float>> search(const Element& element, size_t max_search, size_t num_neighbors) const {
+        std::vector<uint64_t> ids(num_neighbors);
+        std::vector<float> dists(num_neighbors);
+        uint32_t count = 0;
+        check(granne_hip_rw_builder_search(h_.get(), element.as_slice(), (uint32_t)max_search, (uint32_t)num_neighbors,
+                                           ids.data(), dists.data(), &count));
+        std::vector<std::pair<size_t, float>> out(count);
+        for (uint32_t i = 0; i < count; ++i) out[i] = {(size_t)ids[i], dists[i]};
+        return out;
+    }
+    size_t len() const { return granne_hip_rw_builder_len(h_.get()); }
+    bool is_empty() const { return len() == 0; }
+    size_t max_elements() const { return granne_hip_rw_builder_max_elements(h_.get()); }
+    size_t num_layers() const { return granne_hip_rw_builder_num_layers(h_.get()); }
+    size_t layer_len(size_t layer) const { return granne_hip_rw_builder_layer_len(h_.get(), (uint32_t)layer); }
+    // save_index_and_elements_to_disk (rw/mod.rs:63-68)
+    void save_index_and_elements_to_disk(const std::string& index_path, const std::string& elements_path) const {
+        check(granne_hip_rw_builder_save(h_.get(), index_path.c_str(), elements_path.c_str()));
+    }
+    Granne<Elements> get_index() const {
+        granne_hip_index* h = nullptr;
+        check(granne_hip_rw_builder_get_index(h_.get(), &h));
+        return Granne<Elements>(h);
+    }
+    void set_option(int option, uint64_t value) const { check(granne_hip_rw_builder_set_option(h_.get(), option, value)); }
+
+private:
+    std::shared_ptr<granne_hip_rw_builder> h_;
 };
 
 // granne::embeddings::SumEmbeddings (src/elements/embeddings/mod.rs:41-216): elements are lists of term ids, their

@@ -568,6 +568,73 @@ int granne_hip_builder_create_sum_embeddings(granne_hip_builder** out, const gra
                                              const granne_hip_sum_embeddings* se);
 int granne_hip_builder_get_index_compact(const granne_hip_builder* builder, granne_hip_index** out);
 
+/* ---- RwGranneBuilder on the GPU (src/index/rw/mod.rs:15-224) ---------------------------------------
+ * The builder that takes inserts while it answers searches. The handle keeps what the reference's keeps: the previous
+ * layers, a CURRENT layer allocated for the size its level will have at max_elements, and element storage for
+ * max_elements rows, allocated once -- an insert writes its rows and links in place, nothing is reallocated or copied.
+ * Per element the work is the bulk builder's (index_element, src/index/mod.rs:805-846) with the three differences
+ * rw/mod.rs:159-169 makes: num_neighbors is the config's on every layer, never halved; no final per-row limit pass
+ * (mod.rs:795-797); no reinsertion. The SCHEDULE is the batched one of granne_hip_builder_build (the reference's rayon
+ * loop over per-node locks is nondeterministic): the rows an insert call puts into the current layer are indexed in
+ * sub-batches of clamp(nodes in the layer / batch_div, 1, batch_max) members, each member searches the graph as it stood
+ * when its sub-batch began, then the sub-batch's link updates are applied in id order; a sub-batch never spans a layer
+ * promotion. A single insert is a sub-batch of one: the reference's sequential result.
+ * Threads: any number of host threads may search; insert, save and get_index may be called from any thread. The handle
+ * serialises them with ONE reader-writer lock held for the whole call (inserts exclusive, everything else shared), so a
+ * search sees the graph after a whole number of insert calls, never a half-applied one. That is coarser than the
+ * reference's per-node locks, under which a search may run between two elements of one insert_batch.
+ * Dense f32 / int8 builders only: a builder made by granne_hip_builder_create_sum_embeddings is rejected (Rw over a
+ * SumEmbeddings container is out of scope). Host pointers, synchronous calls; there are no device-pointer entries. */
+typedef struct granne_hip_rw_builder granne_hip_rw_builder;
+/* RwGranneBuilder::new(builder, max_elements, _) (rw/mod.rs:32-61): expected_num_elements = max_elements, build() over all
+ * the builder's elements under its own config, pop the last layer as the current one and give it
+ * max(len, compute_num_elements_in_layer(max_elements, multiplier, previous layers)) rows. CONSUMES `builder` on success:
+ * the caller must neither use nor destroy it afterwards. GRANNE_HIP_ERR_INVALID (max_elements 0 or >= 2^32 - 1, a
+ * SumEmbeddings builder) leaves the builder untouched; after a device failure it is still the caller's (and may have been
+ * built further). */
+int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_hip_builder* builder, uint64_t max_elements);
+void granne_hip_rw_builder_destroy(granne_hip_rw_builder* rw);
+/* RwGranneBuilder::insert_batch (rw/mod.rs:103-182); insert (:99-101) is n_new = 1. rows: host, dense [n_new][dim],
+ * prepared like a Vectors file. Nothing is inserted once len >= max_elements; when the current layer is full it becomes
+ * the last previous layer and a clone of it, resized to the next level's size, the current one; as many rows as fit get
+ * the ids len, len + 1, ..., the rest go round again; rows beyond max_elements are dropped. out_ids: [n_new] (host),
+ * *out_count = how many were written. */
+int granne_hip_rw_builder_insert_batch(granne_hip_rw_builder* rw, const void* rows, uint64_t n_new, uint64_t* out_ids,
+                                       uint64_t* out_count);
+/* RwGranneBuilder::search (rw/mod.rs:184-207) for nq queries; arguments and outputs as granne_hip_search_batch (host
+ * pointers). Walks the previous layers and rows 0..len of the current one where they are. WITHOUT A PREVIOUS LAYER THE
+ * RESULT IS EMPTY (counts 0), also when the current layer holds elements: the reference's index.search(..).first() is
+ * None there (:198-206). */
+int granne_hip_rw_builder_search_batch(granne_hip_rw_builder* rw, const void* queries, uint32_t nq, uint32_t max_search,
+                                       uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                       uint64_t* out_stats);
+int granne_hip_rw_builder_search(granne_hip_rw_builder* rw, const void* query, uint32_t max_search, uint32_t num_neighbors,
+                                 uint64_t* out_ids, float* out_dists, uint32_t* out_count);
+/* len (rw/mod.rs:217-219), max_elements, layers = previous layers + the current one (always at least 1), rows of a layer
+ * (the current layer reports len rows), a layer as a host [layer_len][num_neighbors] u32 matrix, get_element (:213-215) */
+uint64_t granne_hip_rw_builder_len(granne_hip_rw_builder* rw);
+uint64_t granne_hip_rw_builder_max_elements(granne_hip_rw_builder* rw);
+uint32_t granne_hip_rw_builder_num_layers(granne_hip_rw_builder* rw);
+uint64_t granne_hip_rw_builder_layer_len(granne_hip_rw_builder* rw, uint32_t layer);
+int granne_hip_rw_builder_get_layer(granne_hip_rw_builder* rw, uint32_t layer, uint32_t* out_rows);
+int granne_hip_rw_builder_get_element(granne_hip_rw_builder* rw, uint64_t idx, void* out);
+/* save_index_and_elements_to_disk / write (rw/mod.rs:63-97): an elements file and an index file of the previous layers +
+ * the current layer's first len rows; a builder without elements writes zero layers (:85-93). Inserts wait, searches go on. */
+int granne_hip_rw_builder_save(granne_hip_rw_builder* rw, const char* index_path, const char* elements_path);
+/* a static snapshot of the graph as it is now (device-to-device copy, as granne_hip_builder_get_index) */
+int granne_hip_rw_builder_get_index(granne_hip_rw_builder* rw, granne_hip_index** out);
+enum {
+    GRANNE_HIP_RW_OPT_SMALL_OPS = 1,      /* sub-batches of up to this many link-update ops (2 x members x num_neighbors) sort
+                                             them in one workgroup's LDS (sort_ops_small_kernel) instead of the device-wide
+                                             radix sort: 0 = never, 1 = the default (GRANNE_HIP_RW_SMALL_OPS), any other value
+                                             = that threshold, capped at the default. Results do not depend on it */
+    GRANNE_HIP_RW_OPT_SMALL_LAUNCHES = 2, /* read-only: sub-batches that took the small path so far */
+    GRANNE_HIP_RW_OPT_SORTED_LAUNCHES = 3 /* read-only: sub-batches that took the radix-sorted path so far */
+};
+#define GRANNE_HIP_RW_SMALL_OPS 2048
+int granne_hip_rw_builder_set_option(granne_hip_rw_builder* rw, int option, uint64_t value);
+int granne_hip_rw_builder_get_option(granne_hip_rw_builder* rw, int option, uint64_t* value);
+
 /* ---- options (per index) ---------------------------------------------------------------------- */
 enum {
     GRANNE_HIP_OPT_VISITED_SLOTS = 1, /* LDS visited-table slots per query: 2^k or 3 * 2^k in [256, 32768]; 0 = auto */

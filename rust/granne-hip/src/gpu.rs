@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct granne_hip_builder { _private: [u8; 0] }
 #[repr(C)] pub struct granne_hip_sharded { _private: [u8; 0] }
 #[repr(C)] pub struct granne_hip_sum_embeddings { _private: [u8; 0] }
+#[repr(C)] pub struct granne_hip_rw_builder { _private: [u8; 0] }
 
 pub const GRANNE_HIP_F32: c_int = 0;
 pub const GRANNE_HIP_I8: c_int = 1;
@@ -131,11 +132,34 @@ extern "C" {
     fn granne_hip_builder_create_sum_embeddings(out: *mut *mut granne_hip_builder,
         config: *const granne_hip_build_config, se: *const granne_hip_sum_embeddings) -> c_int;
     fn granne_hip_builder_get_index_compact(builder: *const granne_hip_builder, out: *mut *mut granne_hip_index) -> c_int;
+    // ---- RwGranneBuilder (src/index/rw/mod.rs:15-224)
+    fn granne_hip_rw_builder_create(out: *mut *mut granne_hip_rw_builder, builder: *mut granne_hip_builder,
+        max_elements: u64) -> c_int;
+    fn granne_hip_rw_builder_destroy(rw: *mut granne_hip_rw_builder);
+    fn granne_hip_rw_builder_insert_batch(rw: *mut granne_hip_rw_builder, rows: *const c_void, n_new: u64,
+        out_ids: *mut u64, out_count: *mut u64) -> c_int;
+    fn granne_hip_rw_builder_search_batch(rw: *mut granne_hip_rw_builder, queries: *const c_void, nq: u32,
+        max_search: u32, num_neighbors: u32, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_stats: *mut u64) -> c_int;
+    fn granne_hip_rw_builder_search(rw: *mut granne_hip_rw_builder, query: *const c_void, max_search: u32,
+        num_neighbors: u32, out_ids: *mut u64, out_dists: *mut f32, out_count: *mut u32) -> c_int;
+    fn granne_hip_rw_builder_len(rw: *mut granne_hip_rw_builder) -> u64;
+    fn granne_hip_rw_builder_max_elements(rw: *mut granne_hip_rw_builder) -> u64;
+    fn granne_hip_rw_builder_num_layers(rw: *mut granne_hip_rw_builder) -> u32;
+    fn granne_hip_rw_builder_layer_len(rw: *mut granne_hip_rw_builder, layer: u32) -> u64;
+    fn granne_hip_rw_builder_get_layer(rw: *mut granne_hip_rw_builder, layer: u32, out_rows: *mut u32) -> c_int;
+    fn granne_hip_rw_builder_get_element(rw: *mut granne_hip_rw_builder, idx: u64, out: *mut c_void) -> c_int;
+    fn granne_hip_rw_builder_save(rw: *mut granne_hip_rw_builder, index_path: *const c_char,
+        elements_path: *const c_char) -> c_int;
+    fn granne_hip_rw_builder_get_index(rw: *mut granne_hip_rw_builder, out: *mut *mut granne_hip_index) -> c_int;
+    fn granne_hip_rw_builder_set_option(rw: *mut granne_hip_rw_builder, option: c_int, value: u64) -> c_int;
+    fn granne_hip_rw_builder_get_option(rw: *mut granne_hip_rw_builder, option: c_int, value: *mut u64) -> c_int;
 }
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
 pub const GRANNE_HIP_OPT_SEEN_MIN: c_int = 11;
 pub const GRANNE_HIP_OPT_SKETCH: c_int = 12;
+pub const GRANNE_HIP_RW_OPT_SMALL_OPS: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
 pub const GRANNE_HIP_SHARDED_EXCHANGE_PEER: u64 = 0;
@@ -654,6 +678,70 @@ impl<E: GpuElements> GpuGranneBuilder<E> {
     }
 }
 impl<E: GpuElements> Drop for GpuGranneBuilder<E> { fn drop(&mut self) { unsafe { granne_hip_builder_destroy(self.handle) } } }
+
+/// `RwGranneBuilder` (src/index/rw/mod.rs:15-224) on the GPU: inserts and searches on one live graph. Methods take `&self`
+/// as the reference's do; the library serialises inserts against searches with a reader-writer lock held per call
+/// (coarser than the reference's per-node locks: a search sees the graph after a whole number of insert calls). Inserts
+/// follow the deterministic batched schedule of the GPU builder. Without a previous layer `search` returns nothing, as
+/// the reference's does (rw/mod.rs:198-206).
+pub struct GpuRwGranneBuilder<E: GpuElements> { handle: *mut granne_hip_rw_builder, dim: usize, _e: PhantomData<E> }
+unsafe impl<E: GpuElements> Send for GpuRwGranneBuilder<E> {}
+unsafe impl<E: GpuElements> Sync for GpuRwGranneBuilder<E> {}
+
+impl<E: GpuElements> GpuRwGranneBuilder<E> {
+    /// `RwGranneBuilder::new(builder, max_elements, _)` (rw/mod.rs:32-61): consumes the builder. `dim`: the width of
+    /// the builder's elements (a builder without elements has none of its own).
+    pub fn new(builder: GpuGranneBuilder<E>, max_elements: usize, dim: usize) -> std::io::Result<Self> {
+        let mut h = std::ptr::null_mut();
+        check(unsafe { granne_hip_rw_builder_create(&mut h, builder.handle, max_elements as u64) })?;
+        std::mem::forget(builder); // the handle owns it now
+        Ok(Self { handle: h, dim, _e: PhantomData })
+    }
+    /// `insert` (rw/mod.rs:99-101)
+    pub fn insert(&self, element: &E::Vector) -> Option<usize> {
+        assert_eq!(E::query_len(element), self.dim);
+        let (mut id, mut count) = (0u64, 0u64);
+        check(unsafe { granne_hip_rw_builder_insert_batch(self.handle, E::query_scalars(element), 1, &mut id, &mut count) })
+            .expect("insert");
+        if count == 1 { Some(id as usize) } else { None }
+    }
+    /// `insert_batch` (rw/mod.rs:103-182): the ids of the elements that found a place
+    pub fn insert_batch(&self, elements: &[E::Vector]) -> Vec<usize> {
+        let mut rows = Vec::new();
+        for e in elements {
+            assert_eq!(E::query_len(e), self.dim);
+            E::append_query(&mut rows, e);
+        }
+        let mut ids = vec![0u64; elements.len()];
+        let mut count = 0u64;
+        check(unsafe { granne_hip_rw_builder_insert_batch(self.handle, rows.as_ptr() as *const c_void, elements.len() as u64,
+            ids.as_mut_ptr(), &mut count) }).expect("insert_batch");
+        ids[..count as usize].iter().map(|&i| i as usize).collect()
+    }
+    /// `search` (rw/mod.rs:184-207)
+    pub fn search(&self, element: &E::Vector, max_search: usize, num_neighbors: usize) -> Vec<(usize, f32)> {
+        assert_eq!(E::query_len(element), self.dim);
+        let mut ids = vec![0u64; num_neighbors];
+        let mut dists = vec![0f32; num_neighbors];
+        let mut count = 0u32;
+        check(unsafe { granne_hip_rw_builder_search(self.handle, E::query_scalars(element), max_search as u32,
+            num_neighbors as u32, ids.as_mut_ptr(), dists.as_mut_ptr(), &mut count) }).expect("search");
+        (0..count as usize).map(|i| (ids[i] as usize, dists[i])).collect()
+    }
+    pub fn len(&self) -> usize { unsafe { granne_hip_rw_builder_len(self.handle) as usize } }
+    pub fn is_empty(&self) -> bool { self.len() == 0 }
+    /// `save_index_and_elements_to_disk` (rw/mod.rs:63-68)
+    pub fn save_index_and_elements_to_disk(&self, index_path: &str, elements_path: &str) -> std::io::Result<()> {
+        let ip = std::ffi::CString::new(index_path).map_err(|e| std::io::Error::new(std::io::ErrorKind::InvalidInput, e))?;
+        let ep = std::ffi::CString::new(elements_path).map_err(|e| std::io::Error::new(std::io::ErrorKind::InvalidInput, e))?;
+        check(unsafe { granne_hip_rw_builder_save(self.handle, ip.as_ptr(), ep.as_ptr()) })
+    }
+    /// sub-batches of up to this many link-update ops sort them in one workgroup (0: never, 1: the default)
+    pub fn set_small_ops(&self, value: u64) -> std::io::Result<()> {
+        check(unsafe { granne_hip_rw_builder_set_option(self.handle, GRANNE_HIP_RW_OPT_SMALL_OPS, value) })
+    }
+}
+impl<E: GpuElements> Drop for GpuRwGranneBuilder<E> { fn drop(&mut self) { unsafe { granne_hip_rw_builder_destroy(self.handle) } } }
 
 /// A partitioned index: shard `s` is a `GpuGranne` of its own (on the device it was created on) over the
 /// elements `[offsets[s], offsets[s] + shard.len())` of the whole set -- how the reference's own shard helper
