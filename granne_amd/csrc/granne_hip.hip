@@ -20,8 +20,13 @@
 #include "slow_kernel.h"
 #include "util_kernels.h"
 #include "brute_force.h"
+#include "combiner.h"
 
 using namespace granne_hip;
+
+static_assert(Combiner::DEPTH <= GRANNE_HIP_SEARCH_DEPTH && Combiner::CALL_MAX == GRANNE_HIP_COALESCE_CALL_MAX &&
+                  Combiner::CAP_MAX == GRANNE_HIP_COALESCE_MAX,
+              "combiner.h and granne_hip.h disagree");
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -198,6 +203,12 @@ struct granne_hip_index {
     };
     std::mutex call_mu;
     std::vector<HostCall*> call_free;
+    // GRANNE_HIP_OPT_COALESCE: host-pointer calls of up to GRANNE_HIP_COALESCE_CALL_MAX queries that are inside the
+    // library at the same moment share launches (combiner.h); each of the combiner's slots has a context of its own,
+    // whose pinned block grows to what its largest group needed
+    uint64_t opt_coalesce = 0;
+    Combiner combiner;
+    HostCall* group_call[Combiner::DEPTH] = {};
     ScratchCache scratch;
     // granne_hip_search_begin_device / _end_device: batches in flight on streams of the index's own
     struct Flight {
@@ -291,6 +302,8 @@ static void destroy_index(granne_hip_index* ix) {
     if (ix->d_layers) (void)hipFree(ix->d_layers);
     if (ix->d_inv_norm) (void)hipFree(ix->d_inv_norm);
     if (ix->d_sketch) (void)hipFree(ix->d_sketch);
+    for (auto* c : ix->group_call)
+        if (c) ix->call_free.push_back(c);
     for (auto* c : ix->call_free) {
         if (c->stream) (void)hipStreamDestroy(c->stream);
         if (c->d_buf) (void)hipFree(c->d_buf);
@@ -751,6 +764,20 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
         if (value > 12) return fail(GRANNE_HIP_ERR_INVALID, "value out of range");
         ix->opt_visited16_lg = value;
         return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE:
+        if (value > 1) return fail(GRANNE_HIP_ERR_INVALID, "the coalesce option is 0 or 1");
+        ix->opt_coalesce = value;
+        return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE_MAX:
+        if (value < 1 || value > GRANNE_HIP_COALESCE_MAX) return fail(GRANNE_HIP_ERR_INVALID, "the coalesce cap must be in [1, %d]", GRANNE_HIP_COALESCE_MAX);
+        ix->combiner.set_cap((uint32_t)value);
+        return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE_WAIT_US:
+        ix->combiner.set_wait_us(value);
+        return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCED_LAUNCHES:
+    case GRANNE_HIP_OPT_COALESCED_QUERIES:
+        return fail(GRANNE_HIP_ERR_INVALID, "option %d is read-only", option);
     default:
         return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
@@ -771,6 +798,11 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     case GRANNE_HIP_OPT_INLINE_TAILS: *value = (!ix->layers.empty() && ix->layers.back().d_adjx) ? 1 : 0; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SEEN_MIN: *value = ix->opt_seen_min; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SKETCH: *value = (ix->opt_sketch && ix->d_sketch && knobs().sketch) ? 1 : 0; return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE: *value = ix->opt_coalesce; return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE_MAX: *value = ix->combiner.cap(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCE_WAIT_US: *value = ix->combiner.wait_us(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCED_LAUNCHES: *value = ix->combiner.launches(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_COALESCED_QUERIES: *value = ix->combiner.queries(); return GRANNE_HIP_OK;
     default: return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -1583,32 +1615,32 @@ static void host_call_release(granne_hip_index* ix, granne_hip_index::HostCall* 
     ix->call_free.push_back(c);
 }
 
-extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* queries, uint32_t nq, uint32_t max_search,
-                                       uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
-                                       uint64_t* out_stats) {
-    if (!cix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    granne_hip_index* ix = const_cast<granne_hip_index*>(cix);
-    if (max_search == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_search must be > 0 (the reference panics, src/index/mod.rs:1019)");
-    if (nq == 0) return GRANNE_HIP_OK;
-    if (num_neighbors == 0) { // .take(0), src/index/mod.rs:974-977
-        if (!out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-        memset(out_counts, 0, (size_t)nq * 4);
-        return GRANNE_HIP_OK;
+// where a host-pointer call's queries and results lie in its block: [queries][ids][dists][counts][stats]; the four
+// outputs are contiguous so that a small batch comes back in one copy
+struct HostLayout {
+    size_t qb, o_ids, o_d, o_c, o_s, total;
+    HostLayout(const granne_hip_index* ix, size_t nq, size_t k) {
+        qb = nq * ix->dim * elem_size(ix->dtype);
+        o_ids = (qb + 255) & ~(size_t)255;
+        o_d = o_ids + nq * k * 8;
+        o_c = o_d + ((nq * k * 4 + 15) & ~(size_t)15);
+        o_s = o_c + ((nq * 4 + 15) & ~(size_t)15);
+        total = o_s + nq * 24;
     }
-    if (!queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+};
+constexpr size_t HOST_PIN_BYTES = 256u << 10; // the pinned block of a call context (a group's grows beyond it)
+
+// A host-pointer search on its own (the arguments are checked): one launch of nq walkers on a stream of the call's.
+static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32_t nq, uint32_t max_search,
+                               uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                               uint64_t* out_stats) {
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
 
-    // device layout: [queries][ids][dists][counts][stats]; the four outputs are contiguous so that a
-    // small batch comes back in one copy
     const size_t k = num_neighbors;
-    const size_t qb = (size_t)nq * ix->dim * elem_size(ix->dtype);
-    const size_t o_ids = (qb + 255) & ~(size_t)255;
-    const size_t o_d = o_ids + (size_t)nq * k * 8;
-    const size_t o_c = o_d + (((size_t)nq * k * 4 + 15) & ~(size_t)15);
-    const size_t o_s = o_c + (((size_t)nq * 4 + 15) & ~(size_t)15);
-    const size_t total = o_s + (size_t)nq * 24;
-    const bool staged = total <= (256u << 10); // small calls go through the pinned buffer: two DMA copies per call
+    const HostLayout L(ix, nq, k);
+    const size_t qb = L.qb, o_ids = L.o_ids, o_d = L.o_d, o_c = L.o_c, o_s = L.o_s, total = L.total;
+    const bool staged = total <= HOST_PIN_BYTES; // small calls go through the pinned buffer: two DMA copies per call
 
     granne_hip_index::HostCall* c = host_call_acquire(ix);
     if (!c) return fail(GRANNE_HIP_ERR_HIP, "cannot create a stream");
@@ -1624,8 +1656,8 @@ extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* 
         if (c->h_pin) (void)hipHostFree(c->h_pin);
         c->h_pin = nullptr;
         c->h_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->h_pin, (256u << 10) + 64, hipHostMallocMapped));
-        c->h_cap = 256u << 10;
+        HIP_TRY(hipHostMalloc((void**)&c->h_pin, HOST_PIN_BYTES + 64, hipHostMallocMapped));
+        c->h_cap = HOST_PIN_BYTES;
     }
     hipStream_t s = c->stream;
     const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
@@ -1691,6 +1723,103 @@ extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* 
     if (out_stats) HIP_TRY(hipMemcpyAsync(out_stats, buf + o_s, (size_t)nq * 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return GRANNE_HIP_OK;
+}
+
+// The combiner's launch step (combiner.h): the n requests of one key that leader `slot` collected, nq queries in all, as
+// ONE launch over the slot's pinned, device-mapped block -- what search_batch_direct does for a small call, with the
+// block sized for the group: the walker reads the queries from it and writes results and status words into it. Scratch
+// is search_launch's, sized there for the launch's nq (the group's) and kept for the slot's stream. Any non-zero return
+// sends every member to the direct path; the slot's stream is idle when this returns.
+static int search_batch_group(granne_hip_index* ix, unsigned slot, const CombineRequest* const* m, size_t n, uint32_t nq) {
+    DeviceGuard g(ix->device);
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    const size_t k = m[0]->num_neighbors;
+    const size_t row = (size_t)ix->dim * elem_size(ix->dtype);
+    const HostLayout L(ix, nq, k);
+    granne_hip_index::HostCall*& c = ix->group_call[slot]; // (the slot is this leader's alone until it returns)
+    if (!c) {
+        c = new granne_hip_index::HostCall();
+        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+            delete c;
+            c = nullptr;
+            return fail(GRANNE_HIP_ERR_HIP, "cannot create a stream");
+        }
+    }
+    if (c->h_cap < L.total) {
+        if (c->h_pin) (void)hipHostFree(c->h_pin);
+        c->h_pin = nullptr;
+        c->h_cap = 0;
+        size_t want = HOST_PIN_BYTES;
+        while (want < L.total) want <<= 1;
+        HIP_TRY(hipHostMalloc((void**)&c->h_pin, want + 64, hipHostMallocMapped));
+        c->h_cap = want;
+    }
+    void* dev_pin = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dev_pin, c->h_pin, 0));
+    uint8_t* dp = (uint8_t*)dev_pin;
+    uint32_t* hst = (uint32_t*)(c->h_pin + L.total);
+    size_t q0 = 0;
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(c->h_pin + q0 * row, m[i]->queries, m[i]->nq * row);
+        q0 += m[i]->nq;
+    }
+    hst[0] = hst[1] = hst[2] = hst[3] = 0;
+    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+    SearchCall call = index_call(dp, nq, m[0]->max_search, (uint32_t)k, (uint64_t*)(dp + L.o_ids), (float*)(dp + L.o_d),
+                                 (uint32_t*)(dp + L.o_c), (uint64_t*)(dp + L.o_s), nullptr, c->stream);
+    call.host_status = (uint32_t*)(dp + L.total);
+    int r = search_launch(T, call);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (r) return r;
+    if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    ix->last_slow_count.store(hst[1]); // (the group's count)
+    if (hst[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact-search scratch exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
+    q0 = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t mq = m[i]->nq;
+        memcpy(m[i]->ids, c->h_pin + L.o_ids + q0 * k * 8, mq * k * 8);
+        memcpy(m[i]->dists, c->h_pin + L.o_d + q0 * k * 4, mq * k * 4);
+        memcpy(m[i]->counts, c->h_pin + L.o_c + q0 * 4, mq * 4);
+        if (m[i]->stats) memcpy(m[i]->stats, c->h_pin + L.o_s + q0 * 24, mq * 24);
+        q0 += mq;
+    }
+    return GRANNE_HIP_OK;
+}
+
+extern "C" int granne_hip_search_batch(const granne_hip_index* cix, const void* queries, uint32_t nq, uint32_t max_search,
+                                       uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                       uint64_t* out_stats) {
+    if (!cix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
+    granne_hip_index* ix = const_cast<granne_hip_index*>(cix);
+    if (max_search == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_search must be > 0 (the reference panics, src/index/mod.rs:1019)");
+    if (nq == 0) return GRANNE_HIP_OK;
+    if (num_neighbors == 0) { // .take(0), src/index/mod.rs:974-977
+        if (!out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+        memset(out_counts, 0, (size_t)nq * 4);
+        return GRANNE_HIP_OK;
+    }
+    if (!queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+    // GRANNE_HIP_OPT_COALESCE: a small call shares a launch with the calls of its key that are in here at the same moment
+    if (ix->opt_coalesce && ix->combiner.takes(nq)) {
+        CombineRequest req;
+        req.queries = queries;
+        req.nq = nq;
+        req.ids = out_ids;
+        req.dists = out_dists;
+        req.counts = out_counts;
+        req.stats = out_stats;
+        req.max_search = max_search;
+        req.num_neighbors = num_neighbors;
+        return ix->combiner.submit(
+            req,
+            [ix](unsigned slot, const CombineRequest* const* m, size_t n, uint32_t group_nq) {
+                return search_batch_group(ix, slot, m, n, group_nq);
+            },
+            [ix](const CombineRequest& r) {
+                return search_batch_direct(ix, r.queries, r.nq, r.max_search, r.num_neighbors, r.ids, r.dists, r.counts, r.stats);
+            });
+    }
+    return search_batch_direct(ix, queries, nq, max_search, num_neighbors, out_ids, out_dists, out_counts, out_stats);
 }
 
 extern "C" int granne_hip_search(const granne_hip_index* ix, const void* query, uint32_t max_search,

@@ -58,9 +58,10 @@ def _is_term_lists(x):
 class Granne:
     """An HNSW index resident in the HBM of one MI355X."""
 
-    def __init__(self, element_type, elements, layers, device=0, prepared=True, compact=False):
+    def __init__(self, element_type, elements, layers, device=0, prepared=True, compact=False, coalesce=False):
         """element_type: "angular" (f32), "angular_int" (int8) or "embeddings" (`elements` is a SumEmbeddings; with
         compact=True the index keeps the container instead of dense rows and makes vectors as it walks).
+        coalesce=True: concurrent `search` calls of host threads share launches (the `coalesce` property).
         elements: [n, dim] array. With prepared=True (default) rows are taken as stored in a
         Vectors file (already normalised / quantised); with prepared=False raw float rows go
         through Vector::from first.
@@ -69,6 +70,8 @@ class Granne:
         et = element_type.lower()
         if et == EMBEDDINGS:
             self._init_embeddings(elements, layers, compact)
+            if coalesce:
+                self.coalesce = True
             return
         if et not in _ELEMENT_TYPES:
             raise ValueError("Invalid element type")  # the reference panics (py/src/lib.rs:210)
@@ -90,6 +93,8 @@ class Granne:
                                             rows, widths, device))
         self._h = h
         self.dim = el.shape[1]
+        if coalesce:
+            self.coalesce = True
 
     def _init_embeddings(self, se, layers, compact):
         self.element_type = EMBEDDINGS
@@ -292,6 +297,19 @@ class Granne:
 
     def last_slow_count(self):
         return int(lib().granne_hip_index_last_slow_count(self._h))
+
+    @property
+    def coalesce(self):
+        """OPT_COALESCE: `search` / `search_batch` calls of up to 64 queries that host threads make at the same moment
+        share search launches (the reference's par_iter over Granne::search). Off by default; results do not depend on
+        it. It gains nothing for one thread or for a caller that already batches."""
+        from ._lib import OPT_COALESCE
+        return bool(self.get_option(OPT_COALESCE))
+
+    @coalesce.setter
+    def coalesce(self, on):
+        from ._lib import OPT_COALESCE
+        self.set_option(OPT_COALESCE, 1 if on else 0)
 
     # ---- search -----------------------------------------------------------------------------------
     def _prepare(self, element, prepared):

@@ -221,6 +221,21 @@ public:
     void set_inline_tails(bool keep) { check(granne_hip_index_set_option(h_.get(), GRANNE_HIP_OPT_INLINE_TAILS, keep ? 1 : 0)); }
     // from how many walks per launch revisits are skipped before their rows are fetched (f32; 0 = always)
     void set_seen_min(uint64_t walks) { check(granne_hip_index_set_option(h_.get(), GRANNE_HIP_OPT_SEEN_MIN, walks)); }
+    // search() calls that host threads make at the same moment share search launches (GRANNE_HIP_OPT_COALESCE: the
+    // reference's par_iter over Granne::search). Off by default; results do not depend on it; nothing for one thread
+    void set_coalesce(bool on) { check(granne_hip_index_set_option(h_.get(), GRANNE_HIP_OPT_COALESCE, on ? 1 : 0)); }
+    bool coalesce() const { return get_option(GRANNE_HIP_OPT_COALESCE) != 0; }
+    // the cap of queries per grouped launch (1..1024) and how long a new leader waits for its group to fill (0 = never)
+    void set_coalesce_max(uint64_t queries) { check(granne_hip_index_set_option(h_.get(), GRANNE_HIP_OPT_COALESCE_MAX, queries)); }
+    void set_coalesce_wait_us(uint64_t us) { check(granne_hip_index_set_option(h_.get(), GRANNE_HIP_OPT_COALESCE_WAIT_US, us)); }
+    // launches made for groups since the index was created, and the queries they served
+    uint64_t coalesced_launches() const { return get_option(GRANNE_HIP_OPT_COALESCED_LAUNCHES); }
+    uint64_t coalesced_queries() const { return get_option(GRANNE_HIP_OPT_COALESCED_QUERIES); }
+    uint64_t get_option(int option) const {
+        uint64_t v = 0;
+        check(granne_hip_index_get_option(h_.get(), option, &v));
+        return v;
+    }
     granne_hip_index* raw() const { return h_.get(); }
 
 private:

@@ -675,7 +675,7 @@ enum {
                                          rows of revisits (3.6 % of a walk's rows on i.i.d.-uniform data, 40-70 % on clustered
                                          data) and costs an LDS round trip before the row loads, which only pays where the
                                          launch is bound by bandwidth: [2048]; 0 = every launch, 0xFFFFFFFF = never */
-    GRANNE_HIP_OPT_SKETCH = 12        /* f32 indexes of 100 dimensions keep a 128-byte sketch of every row (int8 codes, scale and
+    GRANNE_HIP_OPT_SKETCH = 12,       /* f32 indexes of 100 dimensions keep a 128-byte sketch of every row (int8 codes, scale and
                                          norm bounds: 1.28 GB at 10M rows) from which the register walker bounds a neighbor's
                                          distance from below; a neighbor whose bound is already beyond the list's max_search-th
                                          distance is rejected without its row being read (it would have been rejected after).
@@ -683,7 +683,31 @@ enum {
                                          made with the index (and again after reorder), not when this is set; an index without
                                          room for it, or made with GRANNE_HIP_SKETCH=0 in the environment, has none.
                                          get_option returns 1 only when searches of the index use a sketch */
+    GRANNE_HIP_OPT_COALESCE = 13,     /* 0 [default] / 1: host-pointer calls (granne_hip_search, granne_hip_search_batch) of up to
+                                         GRANNE_HIP_COALESCE_CALL_MAX queries that are inside the library at the same moment --
+                                         the reference's par_iter over Granne::search -- share search launches: one of the
+                                         callers leads, takes the waiting calls of its own (max_search, num_neighbors) in
+                                         arrival order, runs ONE launch over the sum of their queries and hands every call its
+                                         rows (granne_amd/csrc/combiner.h). While a launch is on the GPU new arrivals queue up
+                                         and the next launch takes them all: the group follows the load, no timer. Up to 2
+                                         such launches are in flight per index (<= GRANNE_HIP_SEARCH_DEPTH). Results, counts,
+                                         stats and statuses are those of the calls made alone, bit for bit: argument errors
+                                         stay the caller's own, and when a group's launch reports GRANNE_HIP_ERR_OVERFLOW or a
+                                         HIP error every member runs its own call again alone and returns what that returns.
+                                         granne_hip_index_last_slow_count after a grouped call is the GROUP's count. Larger
+                                         calls and every other entry point (_device, begin/end, packed, sharded, Rw builder)
+                                         are untouched. For one thread, or a caller that already batches, it gains nothing.
+                                         Like every option here: not to be changed while a search of the index is running */
+    GRANNE_HIP_OPT_COALESCE_MAX = 14, /* cap of queries per grouped launch: 1..GRANNE_HIP_COALESCE_MAX [GRANNE_HIP_COALESCE_MAX]; a
+                                         call of more queries than the cap does not take part */
+    GRANNE_HIP_OPT_COALESCE_WAIT_US = 15, /* [0]: a leader never waits. Non-zero: a new leader waits until its group has reached the
+                                         cap, or this many microseconds have passed since it took the lead, whichever comes
+                                         first -- a throughput knob (and what makes tests of grouping deterministic) */
+    GRANNE_HIP_OPT_COALESCED_LAUNCHES = 16, /* read-only: launches made for groups (that served them) since the index was created */
+    GRANNE_HIP_OPT_COALESCED_QUERIES = 17   /* read-only: queries those launches served */
 };
+#define GRANNE_HIP_COALESCE_CALL_MAX 64 /* calls of more queries than this never take part in GRANNE_HIP_OPT_COALESCE */
+#define GRANNE_HIP_COALESCE_MAX 1024    /* the largest (and default) GRANNE_HIP_OPT_COALESCE_MAX */
 enum {
     GRANNE_HIP_WALKER_NONE = 0,          /* no search yet */
     GRANNE_HIP_WALKER_REGISTER = 1,      /* walk_fast.h: layers of up to 32 ids, max_search up to 8192 (1024 for f32 dims other
@@ -694,7 +718,8 @@ enum {
 };
 int granne_hip_index_set_option(granne_hip_index* index, int option, uint64_t value);
 int granne_hip_index_get_option(const granne_hip_index* index, int option, uint64_t* value);
-/* number of queries of the last search_batch (host variant) that took the slow exact path */
+/* number of queries of the last search_batch (host variant) that took the slow exact path; with GRANNE_HIP_OPT_COALESCE
+ * on, of the last grouped launch: the count of the whole group a call travelled in */
 uint64_t granne_hip_index_last_slow_count(const granne_hip_index* index);
 
 #ifdef __cplusplus

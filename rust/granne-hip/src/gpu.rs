@@ -159,6 +159,11 @@ pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
 pub const GRANNE_HIP_OPT_SEEN_MIN: c_int = 11;
 pub const GRANNE_HIP_OPT_SKETCH: c_int = 12;
+pub const GRANNE_HIP_OPT_COALESCE: c_int = 13;
+pub const GRANNE_HIP_OPT_COALESCE_MAX: c_int = 14;
+pub const GRANNE_HIP_OPT_COALESCE_WAIT_US: c_int = 15;
+pub const GRANNE_HIP_OPT_COALESCED_LAUNCHES: c_int = 16;
+pub const GRANNE_HIP_OPT_COALESCED_QUERIES: c_int = 17;
 pub const GRANNE_HIP_RW_OPT_SMALL_OPS: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
@@ -449,6 +454,27 @@ impl<E: GpuElements> GpuGranne<E> {
     /// 2048; 0 = every launch; `u32::MAX as u64` = never.
     pub fn set_seen_min(&mut self, walks: u64) -> std::io::Result<()> {
         check(unsafe { granne_hip_index_set_option(self.handle, GRANNE_HIP_OPT_SEEN_MIN, walks) })
+    }
+    /// `GRANNE_HIP_OPT_COALESCE`: `search` calls that are inside the library at the same moment -- a rayon `par_iter` over
+    /// `search`, the reference's way to throughput -- share search launches: one caller leads, takes the waiting calls of
+    /// its own `(max_search, num_neighbors)`, runs one launch over all their queries and hands every call its rows.
+    /// Off by default. Results and errors are those of the calls made alone. It gains nothing for one thread, or for a
+    /// caller that already batches (`search_batch`, the `_device` entries). Not while a search is running.
+    pub fn set_coalesce(&mut self, on: bool) -> std::io::Result<()> {
+        check(unsafe { granne_hip_index_set_option(self.handle, GRANNE_HIP_OPT_COALESCE, on as u64) })
+    }
+    /// `GRANNE_HIP_OPT_COALESCE_MAX` (queries per grouped launch, 1..=1024) and `GRANNE_HIP_OPT_COALESCE_WAIT_US` (how long a
+    /// new leader waits for its group to fill; 0 = never, the default).
+    pub fn set_coalesce_limits(&mut self, max_queries: u64, wait_us: u64) -> std::io::Result<()> {
+        check(unsafe { granne_hip_index_set_option(self.handle, GRANNE_HIP_OPT_COALESCE_MAX, max_queries) })?;
+        check(unsafe { granne_hip_index_set_option(self.handle, GRANNE_HIP_OPT_COALESCE_WAIT_US, wait_us) })
+    }
+    /// `(launches, queries)` of `GRANNE_HIP_OPT_COALESCED_LAUNCHES` / `_QUERIES`: their quotient is the mean group size.
+    pub fn coalesced(&self) -> std::io::Result<(u64, u64)> {
+        let (mut launches, mut queries) = (0u64, 0u64);
+        check(unsafe { granne_hip_index_get_option(self.handle, GRANNE_HIP_OPT_COALESCED_LAUNCHES, &mut launches) })?;
+        check(unsafe { granne_hip_index_get_option(self.handle, GRANNE_HIP_OPT_COALESCED_QUERIES, &mut queries) })?;
+        Ok((launches, queries))
     }
     // ---- the Index trait's accessors (src/index/mod.rs:54-71); `impl Index for GpuGranne` below forwards to them
     pub fn len(&self) -> usize { unsafe { granne_hip_index_len(self.handle) as usize } }
