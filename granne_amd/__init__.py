@@ -8,5 +8,6 @@ from .index import Granne, compute_distance, normalize, quantize  # noqa: F401
 from .builder import GranneBuilder  # noqa: F401
 from .embeddings import SumEmbeddings  # noqa: F401
 from .rw_builder import RwGranneBuilder  # noqa: F401
+from .refined import RefinedGranne  # noqa: F401
 
-__all__ = ["Granne", "GranneBuilder", "RwGranneBuilder", "SumEmbeddings", "compute_distance", "normalize", "quantize", "GranneHipError", "F32", "I8", "UNUSED"]
+__all__ = ["Granne", "GranneBuilder", "RwGranneBuilder", "RefinedGranne", "SumEmbeddings", "compute_distance", "normalize", "quantize", "GranneHipError", "F32", "I8", "UNUSED"]

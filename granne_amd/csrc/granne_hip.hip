@@ -2332,3 +2332,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // RwGranneBuilder on the GPU: insert into and search a live graph
 // ------------------------------------------------------------------------------------------------
 #include "rw_builder_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// refined search: walk one index, re-rank by another's rows
+// ------------------------------------------------------------------------------------------------
+#include "refine_host.h"

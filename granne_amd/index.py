@@ -422,6 +422,48 @@ class Granne:
         check(lib().granne_hip_dists_device(self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_ids), int(m),
                                             C.c_void_p(d_out), C.c_void_p(d_status), C.c_void_p(stream)))
 
+    def refine_device(self, d_queries, nq, d_cand_ids, d_cand_counts, m, k, d_ids, d_dists, d_counts, d_refine_status=0,
+                      stream=0):
+        """granne_hip_refine_device: re-rank u64 candidate lists [nq, m] by this index's rows. Raw device pointers (int;
+        d_cand_counts and d_refine_status may be 0), asynchronous on `stream`."""
+        check(lib().granne_hip_refine_device(self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_cand_ids),
+                                             C.c_void_p(d_cand_counts), int(m), int(k), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                             C.c_void_p(d_counts), C.c_void_p(d_refine_status), C.c_void_p(stream)))
+
+    def refine(self, queries, ids, counts=None, k=DEFAULT_NUM_ELEMENTS, prepared=True, dropped=False):
+        """Host convenience over refine_device (torch moves the buffers): the candidates ids [nq, m] (query q's list: its
+        first counts[q] entries; None = all m) by THIS index's distances to queries [nq, dim], the k best ascending by
+        (distance, id): ids [nq, k] u64, dists [nq, k] f32, counts [nq] u32 -- and, with dropped=True, how many candidates
+        were out of range. prepared=False applies Vector::from to the queries first, as `search` does."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        ii = np.ascontiguousarray(ids, dtype=np.uint64)
+        if q.ndim != 2 or q.shape[1] != self.dim or ii.ndim != 2 or ii.shape[0] != q.shape[0]:
+            raise ValueError("queries must be [nq, %d] and ids [nq, m]" % self.dim)
+        nq, m, k = q.shape[0], ii.shape[1], int(k)
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, -1)).to(dev)
+        ti = torch.from_numpy(ii.view(np.int64)).to(dev)
+        tc = None
+        if counts is not None:
+            cc = np.ascontiguousarray(counts, dtype=np.uint32)
+            if cc.shape != (nq,):
+                raise ValueError("counts must be [nq]")
+            tc = torch.from_numpy(cc.view(np.int32)).to(dev)
+        out_ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+        out_d = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+        out_c = torch.zeros(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            self.refine_device(tq.data_ptr(), nq, ti.data_ptr(), tc.data_ptr() if tc is not None else 0, m, k,
+                               out_ids.data_ptr(), out_d.data_ptr(), out_c.data_ptr(), st.data_ptr(),
+                               torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        res = (out_ids.cpu().numpy().view(np.uint64), out_d.cpu().numpy(), out_c.cpu().numpy().view(np.uint32))
+        return res + (int(st.cpu().numpy().view(np.uint32)[0]),) if dropped else res
+
     def dists_many(self, queries, ids):
         """ElementContainer::dists for a batch: queries [nq, dim] (prepared), ids [nq, m] -> [nq, m] f32
         (+inf where an id is out of range)."""

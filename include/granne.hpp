@@ -179,6 +179,14 @@ public:
         return out;
     }
 
+    // A handle over the rows alone (no layers): what RefinedGranne re-ranks by; get_element and the distance operators work
+    static Granne from_elements(const Elements& elements, int device = 0) {
+        granne_hip_index* h = nullptr;
+        check(granne_hip_index_create(&h, elements.as_slice(), elements.len(), (uint32_t)(elements.dim() ? elements.dim() : 1), dtype(),
+                                      0, nullptr, nullptr, nullptr, device));
+        return Granne(h);
+    }
+
     // Index trait (mod.rs:54-71)
     size_t len() const { return granne_hip_index_len(h_.get()); }
     size_t num_layers() const { return granne_hip_index_num_layers(h_.get()); }
@@ -241,6 +249,49 @@ public:
 private:
     static constexpr int dtype() { return detail::dtype_of<typename decltype(Element::data)::value_type>::value; }
     std::shared_ptr<granne_hip_index> h_;
+};
+
+// Refined search (granne_hip_search_refined_batch): walk one index, give the walk's refine_from best candidates their
+// distances under ANOTHER index's rows -- the same elements under the same ids, e.g. int8 rows walked and f32 rows
+// re-ranked -- and return the num_neighbors best by (distance, id). Both handles are shared with the Grannes they came from.
+template <class WalkElements, class RefineElements>
+class RefinedGranne {
+public:
+    using WalkElement = typename WalkElements::Element;
+    using RefineElement = typename RefineElements::Element;
+    RefinedGranne(const Granne<WalkElements>& walk, const Granne<RefineElements>& refine) : walk_(walk), refine_(refine) {}
+
+    // refine_from = 0 means max_search; 1 <= refine_from <= min(max_search, 1024)
+    std::vector<std::pair<size_t, float>> search(const WalkElement& walk_element, const RefineElement& refine_element, size_t max_search,
+                                                 size_t num_neighbors, size_t refine_from = 0) const {
+        return std::move(search_batch(&walk_element, &refine_element, 1, max_search, num_neighbors, refine_from)[0]);
+    }
+    std::vector<std::vector<std::pair<size_t, float>>> search_batch(const WalkElement* walk_elements, const RefineElement* refine_elements,
+                                                                    size_t nq, size_t max_search, size_t num_neighbors,
+                                                                    size_t refine_from = 0) const {
+        const size_t wdim = granne_hip_index_dim(walk_.raw()), rdim = granne_hip_index_dim(refine_.raw());
+        std::vector<typename decltype(WalkElement::data)::value_type> qw(nq * wdim);
+        std::vector<typename decltype(RefineElement::data)::value_type> qr(nq * rdim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (walk_elements[i].len() != wdim || refine_elements[i].len() != rdim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(qw.data() + i * wdim, walk_elements[i].as_slice(), wdim * sizeof(qw[0]));
+            std::memcpy(qr.data() + i * rdim, refine_elements[i].as_slice(), rdim * sizeof(qr[0]));
+        }
+        std::vector<uint64_t> ids(nq * num_neighbors);
+        std::vector<float> ds(nq * num_neighbors);
+        std::vector<uint32_t> counts(nq);
+        check(granne_hip_search_refined_batch(walk_.raw(), refine_.raw(), qw.data(), qr.data(), (uint32_t)nq, (uint32_t)max_search,
+                                              (uint32_t)(refine_from ? refine_from : max_search), (uint32_t)num_neighbors, ids.data(),
+                                              ds.data(), counts.data(), nullptr, nullptr));
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * num_neighbors + j], ds[i * num_neighbors + j]);
+        return out;
+    }
+
+private:
+    Granne<WalkElements> walk_;
+    Granne<RefineElements> refine_;
 };
 
 // A partitioned index: shard s is a Granne of its own over the elements [offsets[s], offsets[s] + shard.len()) of the

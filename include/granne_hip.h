@@ -206,6 +206,43 @@ int granne_hip_stream_synchronize(void* stream, int device_id);
 int granne_hip_search(const granne_hip_index* index, const void* query, uint32_t max_search,
                       uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_count);
 
+/* ---- refined search: walk one index, re-rank by another's rows --------------------------------------
+ * refine(R, q, cand[0..c), k): d = R.dist_to_element(id, q) for every candidate id -- R's own arithmetic
+ * (src/math.rs:5-52 + src/elements/angular.rs:63-74 for f32 rows, math.rs:59-89 + angular_int.rs:47-60 for int8), the
+ * bits of granne_hip_dists_device and of the walks -- then the candidates ascending by (d, id), the walk's result order
+ * (src/index/mod.rs:1036), the first min(k, c) of them. One kernel: no [nq][m] distance array, no sort of the caller's.
+ * `refine_index` is any dense index (f32 or int8 rows, any dim; n_layers == 0 -- rows only -- is enough); a compact
+ * SumEmbeddings index keeps no rows and is GRANNE_HIP_ERR_INVALID.
+ * d_queries: [nq][dim] scalars of refine_index's dtype, prepared. d_cand_ids: u64 [nq][m], 1 <= m <= 1024, ids of ANY
+ * origin (a walk of another index over the same elements, a partitioned search's global ids): query q's list is its first
+ * d_cand_counts[q] entries (u32 [nq], clamped to m; NULL = all m). An id >= the index's number of elements -- UINT64_MAX,
+ * the padding of search results, included -- is dropped and counted in *d_refine_status (u32[1], optional, zeroed by the
+ * caller); an id named twice is kept twice. Outputs as granne_hip_search_batch_device: [nq][k] ids and distances, unused
+ * slots UINT64_MAX / +inf, d_out_counts[q] = min(k, kept candidates); k may exceed m. Asynchronous on `stream`. */
+int granne_hip_refine_device(const granne_hip_index* refine_index, const void* d_queries, uint32_t nq,
+                             const uint64_t* d_cand_ids, const uint32_t* d_cand_counts, uint32_t m, uint32_t k,
+                             uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_refine_status,
+                             void* stream);
+/* search_refined(W, R, qW, qR, max_search, refine_from = m, k) = refine(R, qR, W.search(qW, max_search, m), k): the walk of
+ * granne_hip_search_batch_device on walk_index with num_neighbors = refine_from, then the kernel above over
+ * refine_index's rows, on one stream; the candidate lists live in stream-ordered scratch. The two indexes hold the same
+ * elements under the same ids, on one device; their dtypes and dims need not agree (int8 rows walked, f32 rows re-ranked;
+ * a projection walked, the full rows re-ranked): d_walk_queries are [nq][walk dim] in walk_index's dtype,
+ * d_refine_queries [nq][refine dim] in refine_index's, both prepared. 1 <= refine_from <= min(max_search, 1024).
+ * d_out_stats and d_status are the walk's, as in granne_hip_search_batch_device; d_refine_status as above. walk_index may
+ * be a compact SumEmbeddings index, refine_index may not. */
+int granne_hip_search_refined_batch_device(const granne_hip_index* walk_index, const granne_hip_index* refine_index,
+                                           const void* d_walk_queries, const void* d_refine_queries, uint32_t nq,
+                                           uint32_t max_search, uint32_t refine_from, uint32_t k, uint64_t* d_out_ids,
+                                           float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats,
+                                           uint32_t* d_status, uint32_t* d_refine_status, void* stream);
+/* the same with host buffers in and out (synchronous); out_stats and out_refine_status (u32[1], set by the call) may be
+ * NULL. GRANNE_HIP_ERR_OVERFLOW as granne_hip_search_batch. */
+int granne_hip_search_refined_batch(const granne_hip_index* walk_index, const granne_hip_index* refine_index,
+                                    const void* walk_queries, const void* refine_queries, uint32_t nq, uint32_t max_search,
+                                    uint32_t refine_from, uint32_t k, uint64_t* out_ids, float* out_dists,
+                                    uint32_t* out_counts, uint64_t* out_stats, uint32_t* out_refine_status);
+
 /* ---- Granne::reorder (src/index/reorder.rs) ----------------------------------------------------- */
 /* Granne::reorder(&mut self) -> Vec<usize> (reorder.rs:59-85): computes the entry-point-trail order
  * (compute_order :135-175, find_entrypoint_trail :180-208) on the device, rewrites every layer

@@ -61,6 +61,19 @@ extern "C" {
     fn granne_hip_search_batch(index: *const granne_hip_index, queries: *const c_void, nq: u32,
         max_search: u32, num_neighbors: u32, out_ids: *mut u64, out_dists: *mut f32,
         out_counts: *mut u32, out_stats: *mut u64) -> c_int;
+    // ---- refined search: walk one index, re-rank the candidates by another's rows
+    fn granne_hip_refine_device(refine_index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        d_cand_ids: *const u64, d_cand_counts: *const u32, m: u32, k: u32, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_refine_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_search_refined_batch_device(walk_index: *const granne_hip_index,
+        refine_index: *const granne_hip_index, d_walk_queries: *const c_void, d_refine_queries: *const c_void,
+        nq: u32, max_search: u32, refine_from: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_out_stats: *mut u64, d_status: *mut u32, d_refine_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_search_refined_batch(walk_index: *const granne_hip_index, refine_index: *const granne_hip_index,
+        walk_queries: *const c_void, refine_queries: *const c_void, nq: u32, max_search: u32, refine_from: u32,
+        k: u32, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_stats: *mut u64,
+        out_refine_status: *mut u32) -> c_int;
     // ---- Granne::reorder / reorder_by_keys (src/index/reorder.rs:59-133)
     fn granne_hip_index_reorder(index: *mut granne_hip_index, out_order: *mut u64) -> c_int;
     fn granne_hip_index_reorder_by_keys(index: *mut granne_hip_index, keys: *const u64, out_order: *mut u64) -> c_int;
@@ -391,6 +404,26 @@ impl<E: GpuElements> GpuGranne<E> {
             counts.as_mut_ptr(), std::ptr::null_mut()) }).expect("granne_hip_search_batch");
         (0..nq).map(|i| (0..counts[i] as usize)
             .map(|j| (ids[i * num_neighbors + j] as usize, ds[i * num_neighbors + j])).collect()).collect()
+    }
+    /// `granne_hip_search_refined_batch`: walk `self` (say, int8 rows and their graph), give the walk's `refine_from` best
+    /// candidates their distances under `refine`'s rows (say, the f32 rows of the same elements; a handle made with no
+    /// layers is enough) and keep the `num_neighbors` best by (distance, id). `walk_elements[i]` and `refine_elements[i]`
+    /// are query i prepared for each index. `1 <= refine_from <= min(max_search, 1024)`.
+    pub fn refined<R: GpuElements>(&self, refine: &GpuGranne<R>, walk_elements: &[E::Vector], refine_elements: &[R::Vector],
+                                   max_search: usize, refine_from: usize, num_neighbors: usize)
+                                   -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = walk_elements.len();
+        assert_eq!(nq, refine_elements.len());
+        let (mut qw, mut qr) = (Vec::new(), Vec::new());
+        for e in walk_elements { assert_eq!(E::query_len(e), self.dim); E::append_query(&mut qw, e); }
+        for e in refine_elements { assert_eq!(R::query_len(e), refine.dim); R::append_query(&mut qr, e); }
+        let (mut ids, mut ds) = (vec![0u64; nq * num_neighbors], vec![0f32; nq * num_neighbors]);
+        let mut counts = vec![0u32; nq];
+        check(unsafe { granne_hip_search_refined_batch(self.handle, refine.handle, qw.as_ptr() as *const c_void,
+            qr.as_ptr() as *const c_void, nq as u32, max_search as u32, refine_from as u32, num_neighbors as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        Ok((0..nq).map(|i| (0..counts[i] as usize)
+            .map(|j| (ids[i * num_neighbors + j] as usize, ds[i * num_neighbors + j])).collect()).collect())
     }
     // ---- the device-resident entries, safe: buffers and streams are owned types (below), a batch in flight BORROWS its
     // buffers until it is ended, so the compiler keeps them alive and unaliased for exactly as long as the GPU uses them
