@@ -80,7 +80,7 @@ extern "C" int granne_hip_device_count(int* out_count) {
 
 // experiment knobs, read once per process
 struct EnvKnobs {
-    int visited = 0, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1, sketch = 1;
+    int visited = 0, touch_max = -1, inline_tails = 1, seen_min = -1, bf_b16 = 1, bf_ring = 1, sketch = 1, compact_rows = 1;
     EnvKnobs() {
         auto geti = [](const char* name, int dflt) {
             const char* e = getenv(name);
@@ -92,6 +92,7 @@ struct EnvKnobs {
         bf_b16 = geti("GRANNE_HIP_BF_B16", 1); // 0: the exact scan of f32 rows scores on the f32 matrix path (round 5's: 5 x slower, scores to the last bits)
         seen_min = geti("GRANNE_HIP_SEEN_MIN", -1); // launches of at least this many walks skip revisits before their rows are fetched (-1: default)
         touch_max = geti("GRANNE_HIP_TOUCH_MAX", -1); // launches of up to this many queries touch rows ahead (-1: default)
+        compact_rows = geti("GRANNE_HIP_COMPACT_ROWS", 1); // 0: the sketched launches keep two lanes per neighbor slot (A/B of walk_fast.h's CR)
         sketch = geti("GRANNE_HIP_SKETCH", 1); // 0: no index makes row sketches, and no search uses them (A/B of GRANNE_HIP_OPT_SKETCH)
     }
 };
@@ -186,6 +187,7 @@ struct granne_hip_index {
     uint64_t opt_sketch = 1;         // GRANNE_HIP_OPT_SKETCH: the register walker rejects candidates by their row sketch (when d_sketch exists)
     std::atomic<uint64_t> last_slow_count{0};
     std::atomic<uint64_t> last_walker{0}; // GRANNE_HIP_OPT_LAST_WALKER
+    std::atomic<uint64_t> last_compact{0}; // GRANNE_HIP_OPT_LAST_COMPACT_ROWS
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
     float* d_inv_norm = nullptr;
@@ -777,6 +779,7 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
         return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_COALESCED_LAUNCHES:
     case GRANNE_HIP_OPT_COALESCED_QUERIES:
+    case GRANNE_HIP_OPT_LAST_COMPACT_ROWS:
         return fail(GRANNE_HIP_ERR_INVALID, "option %d is read-only", option);
     default:
         return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
@@ -803,6 +806,7 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     case GRANNE_HIP_OPT_COALESCE_WAIT_US: *value = ix->combiner.wait_us(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_COALESCED_LAUNCHES: *value = ix->combiner.launches(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_COALESCED_QUERIES: *value = ix->combiner.queries(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_LAST_COMPACT_ROWS: *value = ix->last_compact.load(); return GRANNE_HIP_OK;
     default: return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -905,6 +909,7 @@ struct SearchTarget {
     const SeDev* se = nullptr;         // a compact SumEmbeddings index: no dense rows (d_elements is null)
     ScratchCache* scratch;             // search_launch's per-stream scratch blocks
     std::atomic<uint64_t>* last_walker = nullptr; // which walker the last launch took (an index's read-only option)
+    std::atomic<uint64_t>* last_compact = nullptr; // ... and whether it ran the compacted row stage
 
     // G: granne_hip_index, or granne_hip_builder (builder_host.h) searching its `layers`. A builder's searches differ in
     // these ways only: no row sketches, seen_min never reached (its layers change between launches, its batches are its
@@ -925,6 +930,7 @@ struct SearchTarget {
             opt_seen_min = g->opt_seen_min;
             d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch : nullptr;
             last_walker = &const_cast<G*>(g)->last_walker;
+            last_compact = &const_cast<G*>(g)->last_compact;
             se = g->se.get();
         } else {
             max_dev_width = g->W;
@@ -985,8 +991,11 @@ static search_fn general_kernel_of(int dtype, uint32_t S, bool trail) {
 // 100 / 200 dims unrolled, 0: any other f32 dim streamed; int8 rows of 128 bytes as DIM 0, of 256 / 512 bytes as DIM 256 /
 // 512), the list slots S, the visited form V16, trail mode and 64-id layers (WIDE). nullptr: not instantiated.
 template <int DT, int DIM, int S>
-static search_fn fast_kernel_v(int v16) {
+static search_fn fast_kernel_v(int v16, bool cr) {
     constexpr bool streamed = (DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256);
+    if constexpr (DT == DT_F32 && sketch_dim_ok((uint32_t)DIM) && S <= 4) { // the sketched launches: survivors' rows only (walk_fast.h, CR)
+        if (v16 == 5 && cr) return fast_kernel<DT, DIM, S, false, 5, false, GRANNE_HIP_CR_G>;
+    }
     if constexpr (S == 1 && !streamed) {
         if (v16 == 4) return fast_kernel<DT, DIM, S, false, 4>;
     }
@@ -1000,22 +1009,22 @@ static search_fn fast_kernel_v(int v16) {
     return nullptr;
 }
 template <int DT, int DIM>
-static search_fn fast_kernel_s(uint32_t S, bool trail, int v16) {
+static search_fn fast_kernel_s(uint32_t S, bool trail, int v16, bool cr) {
     if (trail) return S == 1 && v16 == 0 ? fast_kernel<DT, DIM, 1, true> : nullptr;
     switch (S) {
-    case 1: return fast_kernel_v<DT, DIM, 1>(v16);
-    case 2: return fast_kernel_v<DT, DIM, 2>(v16);
-    case 4: return fast_kernel_v<DT, DIM, 4>(v16);
-    case 8: return fast_kernel_v<DT, DIM, 8>(v16);
+    case 1: return fast_kernel_v<DT, DIM, 1>(v16, cr);
+    case 2: return fast_kernel_v<DT, DIM, 2>(v16, cr);
+    case 4: return fast_kernel_v<DT, DIM, 4>(v16, cr);
+    case 8: return fast_kernel_v<DT, DIM, 8>(v16, cr);
     }
     if constexpr (!((DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256))) { // (streamed f32 dims, wide int8 rows: up to 17 slots)
         switch (S) {
-        case 33: return fast_kernel_v<DT, DIM, 33>(v16);
-        case 65: return fast_kernel_v<DT, DIM, 65>(v16);
-        case 129: return fast_kernel_v<DT, DIM, 129>(v16);
+        case 33: return fast_kernel_v<DT, DIM, 33>(v16, cr);
+        case 65: return fast_kernel_v<DT, DIM, 65>(v16, cr);
+        case 129: return fast_kernel_v<DT, DIM, 129>(v16, cr);
         }
     }
-    return S == 17 ? fast_kernel_v<DT, DIM, 17>(v16) : nullptr;
+    return S == 17 ? fast_kernel_v<DT, DIM, 17>(v16, cr) : nullptr;
 }
 template <int DT, int DIM>
 static search_fn fast_wide_kernel_s(uint32_t S) {
@@ -1028,17 +1037,17 @@ static search_fn fast_wide_kernel_s(uint32_t S) {
     }
     return nullptr;
 }
-static search_fn fast_kernel_of(const SearchTarget& T, uint32_t S, bool trail, int v16, bool wide) {
+static search_fn fast_kernel_of(const SearchTarget& T, uint32_t S, bool trail, int v16, bool wide, bool cr) {
     const bool i8 = T.dtype == GRANNE_HIP_I8;
     if (wide) { // (64-id layers: no visited set, no trail walks, int8 rows of 128 bytes)
         if (trail || v16 != 3 || (i8 && T.row_bytes != 128)) return nullptr;
         if (i8) return fast_wide_kernel_s<DT_I8, 0>(S);
         return T.dim == 100 ? fast_wide_kernel_s<DT_F32, 100>(S) : T.dim == 200 ? fast_wide_kernel_s<DT_F32, 200>(S) : fast_wide_kernel_s<DT_F32, 0>(S);
     }
-    if (i8 && T.row_bytes == 256) return fast_kernel_s<DT_I8, 256>(S, trail, v16);
-    if (i8 && T.row_bytes == 512) return fast_kernel_s<DT_I8, 512>(S, trail, v16);
-    if (i8) return T.row_bytes == 128 ? fast_kernel_s<DT_I8, 0>(S, trail, v16) : nullptr;
-    return T.dim == 100 ? fast_kernel_s<DT_F32, 100>(S, trail, v16) : T.dim == 200 ? fast_kernel_s<DT_F32, 200>(S, trail, v16) : fast_kernel_s<DT_F32, 0>(S, trail, v16);
+    if (i8 && T.row_bytes == 256) return fast_kernel_s<DT_I8, 256>(S, trail, v16, cr);
+    if (i8 && T.row_bytes == 512) return fast_kernel_s<DT_I8, 512>(S, trail, v16, cr);
+    if (i8) return T.row_bytes == 128 ? fast_kernel_s<DT_I8, 0>(S, trail, v16, cr) : nullptr;
+    return T.dim == 100 ? fast_kernel_s<DT_F32, 100>(S, trail, v16, cr) : T.dim == 200 ? fast_kernel_s<DT_F32, 200>(S, trail, v16, cr) : fast_kernel_s<DT_F32, 0>(S, trail, v16, cr);
 }
 
 // which walker serves a launch, its kernel, and how the launch is sized
@@ -1047,6 +1056,7 @@ struct WalkPlan {
     uint32_t S = 0;         // list slots of 64 keys
     int v16 = 0;            // FastWalker's V16: 0 = the exact 32-bit table, 3 = no visited set, 4 = none + rows touched
                             // ahead, 5 = none + revisits skipped before their rows are fetched
+    bool cr = false;        // FastWalker's CR: the sketched launches evaluate the surviving neighbors only, several lanes to a row
     search_fn fn = nullptr; // null: the launch cannot be planned (the error is set)
     uint32_t lds_bytes = 0; // the launch's dynamic LDS
     uint32_t grid = 0;      // blocks of 64 lanes: the walkers, then the tail blocks; or the exact walker's blocks alone
@@ -1113,7 +1123,9 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         // (f32 rows: the walkers per CU are bound by registers there, 8 KB of cache each fit; int8 walkers are four times as many
         //  and lose more to the look-up than the few revisits of their rows cost: measured, profiles/r6_seen_ab.txt)
         if (P.S <= 4 && !wide && !i8 && nq >= seen_min) P.v16 = 5; // (every f32 dim: unrolled and streamed)
-        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, 0u, P.v16 == 5, wide);
+        // ... and, where they reject neighbors by the index's row sketch, read the rows of the survivors only (walk_fast.h, CR)
+        P.cr = P.v16 == 5 && !i8 && sketch_dim_ok(T.dim) && T.d_sketch != nullptr && knobs().compact_rows != 0;
+        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, 0u, P.v16 == 5, wide, P.cr ? GRANNE_HIP_CR_G : 0);
         const uint32_t least = lds_query_bytes(T.row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
         if (walk_lds < least) walk_lds = least;
     } else {
@@ -1205,8 +1217,9 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         P.grid = P.slow_blocks;
         return P;
     }
+    if (!fast || wide) P.cr = false;
     if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
-    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide) : compact ? compact_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
+    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
     if (!P.fn) {
         fail(GRANNE_HIP_ERR_INVALID, "no walker is instantiated for this launch (list slots %u, visited form %d, trail %d, 64-id layers %d)",
              P.S, P.v16, (int)trail, (int)wide);
@@ -1348,6 +1361,7 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     sp.se_x = T.se ? (float*)(scratch + off_sex) : nullptr;
 
     if (T.last_walker) T.last_walker->store(W.walker);
+    if (T.last_compact) T.last_compact->store(W.cr ? 1 : 0);
     if (W.walker != GRANNE_HIP_WALKER_EXACT && W.lds_bytes > 32u * 1024u)
         HIP_TRY(hipFuncSetAttribute((const void*)W.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W.lds_bytes));
     if (c.ev_before) HIP_TRY(hipEventRecord(c.ev_before, s));

@@ -91,6 +91,19 @@ constexpr uint32_t WPOS_NONE = 0xFFFFFFFFu;
 constexpr uint32_t VCACHE_SLOTS = 512; // FastWalker::vcache (power of two, 2 KB of LDS per walker)
 constexpr uint32_t VCACHE_SLOTS_SEEN = 2048; // ... of the walkers that skip revisits before their rows are fetched (SEEN: 8 KB; f32 rows -- 12 walkers per CU)
 constexpr uint64_t WALK_MAX_ELEMENTS = 1ull << 31; // ids must fit 31 bits
+// CR (FastWalker's compacted row stage): lanes per surviving row (8 or 4), and the waves per SIMD its launches are built
+// for -- five of them leave a walker 8 KB of LDS, so its cache of evaluated ids halves (a miss means nothing).
+#ifndef GRANNE_HIP_CR_G
+#define GRANNE_HIP_CR_G 8
+#endif
+#ifndef GRANNE_HIP_CR_WAVES
+#define GRANNE_HIP_CR_WAVES 4
+#endif
+static_assert(GRANNE_HIP_CR_G == 8 || GRANNE_HIP_CR_G == 4, "a surviving row is held by 8 or by 4 lanes");
+static_assert(GRANNE_HIP_CR_WAVES == 4 || GRANNE_HIP_CR_WAVES == 5, "four or five waves per SIMD");
+__host__ __device__ constexpr uint32_t fast_vcache_slots(bool seen, int cr) {
+    return seen ? ((cr && GRANNE_HIP_CR_WAVES == 5) ? 1024u : VCACHE_SLOTS_SEEN) : VCACHE_SLOTS;
+}
 
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t m) { // set bits of m below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -242,7 +255,9 @@ __host__ __device__ inline uint32_t fast_query_bytes(bool i8, bool gen, uint32_t
 // `res` does not change within an expansion (mod.rs:1025-1033 pushes to pq only), so the reference's filter gives every
 // neighbor of the row the same answer whichever pass it is in; the list's own bookkeeping (dead candidates beyond entry
 // max_search-1, the tie test after a pass's last insert) is per insert group and does not care where a group ends.
-template <int DT, int DIM, int S, int V16 = 0, bool WIDE = false>
+// CR (0: off; else G = 8 or 4): the sketched launches evaluate only the neighbors that survive the SEEN look-up and the
+// sketch, G lanes to a row (compact_rows) -- the other shapes keep two lanes per neighbor slot.
+template <int DT, int DIM, int S, int V16 = 0, bool WIDE = false, int CR = 0>
 struct FastWalker {
     static constexpr bool F32 = (DT == DT_F32);
     // DIM == 0: any f32 dim, known at run time (below 32 the row is its tail only). The chunks stream through the registers in groups of
@@ -296,6 +311,7 @@ struct FastWalker {
     // SK: the launches of many walks (SEEN) on the 100-d rows reject a neighbor by its row sketch (SearchParams::sketch) when
     // that alone proves its distance beyond theta -- its row is then not read (sketch_rejects).
     static constexpr bool SK = SEEN && XT && sketch_dim_ok((uint32_t)DIM);
+    static_assert(CR == 0 || (SK && (CR == 8 || CR == 4) && S <= 4), "the compacted row stage: the sketched launches, 8 or 4 lanes per row");
     // SK: the query's sketch -- codes c (sk_qc, LDS), scale s, R >= |q - s c|, N >= |q|
     int8_t* sk_qc; // (LDS: where the visited table of the walks that keep one is)
     float sk_s, sk_r, sk_n;
@@ -619,6 +635,113 @@ struct FastWalker {
         return d;
     }
 
+    // ---- CR: the row stage of the sketched launches, on the surviving neighbors only -----------------------------------
+    // After the SEEN look-up and the sketch about 4 of an expansion's ~27 new neighbors are left, and in
+    // the layout above 8 of 64 lanes do the work of finish_rows. Here every survivor (odd lane of its pair) takes a rank
+    // (mbcnt over the survivors' mask) and leaves (id, slot R) at that rank in the spare places of the list's image, which
+    // are dead between two merges. Group g of G lanes then holds the survivor of rank base + g: lane t of the group
+    // loads 128 / G bytes of each 128-byte chunk (one group reads one whole line) and owns the reference's accumulators
+    // 32 t / G .. 32 (t + 1) / G - 1 (math.rs:17-26), fed in chunk order by the same fused multiply-adds. The ordered sum
+    // (math.rs:27-30) walks up the group: step k hands lane k - 1's partial sum to lane k (DPP row_shr:1; the group's
+    // first lane takes +0.0 instead, whatever its lower neighbor holds) which adds its accumulators in order -- every lane
+    // runs every step, lane t is right from step t on, the last lane after step G - 1. That lane applies the tail
+    // (math.rs:32-39; from the expanded node's record via R when the layer carries tails, else from the row) and the
+    // distance goes back to the survivor's own lane by one ds_bpermute. Two passes (2 x 64 / G survivors) have their loads
+    // in flight together, in a register set each; more survivors (the first expansions of a layer, while theta is
+    // +inf) loop. The distances are the bits finish_rows gives: tests/test_compact_rows_model.py replays the schedule.
+    static constexpr int CG = CR ? CR : 8;         // lanes per row
+    static constexpr int CU = 8 / CG;              // 16-byte units of a chunk per lane
+    static constexpr uint32_t CNG = 64u / CG;      // rows per pass
+    struct CRows {
+        float4 v[NB ? NB : 1][CU];
+        float4 vt[TU ? TU : 1];
+    };
+    __device__ __forceinline__ uint64_t* cr_slots() const { return mslot + CAP; } // 32 x (R << 32 | id)
+    // the loads of one register set: the row named by e = (id, R), for the lanes of act
+    __device__ __forceinline__ void cr_issue(CRows& c, const uint64_t e, const bool act, const uint32_t ct, const uint8_t* xtails) const {
+        if (act) {
+            const uint8_t* row = p.elements + (size_t)(uint32_t)e * RSTRIDE;
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int u = 0; u < CU; ++u) c.v[b][u] = *reinterpret_cast<const float4*>(row + b * 128 + (ct * CU + u) * 16u);
+            const uint8_t* tp = xtails ? xtails + (uint32_t)(e >> 32) * XTAILB : row + NB * 128;
+#pragma unroll
+            for (int u = 0; u < TU; ++u) {
+                const uint4 t = load_global_u4((gptr_u32)(tp + u * 16));
+                c.vt[u] = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
+            }
+        }
+    }
+    // distance of the row in c to the query: valid in the LAST lane of every group (every lane runs it)
+    __device__ __forceinline__ float cr_finish(const CRows& c, const uint32_t ct) const {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        f32x2 acc2[2 * CU];
+#pragma unroll
+        for (int j = 0; j < 2 * CU; ++j) acc2[j] = f32x2{0.0f, 0.0f};
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+#pragma unroll
+            for (int u = 0; u < CU; ++u) {
+                const float4 qq = *reinterpret_cast<const float4*>(lds_q + b * 128 + (ct * CU + u) * 16u);
+                acc2[u * 2 + 0] = __builtin_elementwise_fma(f32x2{c.v[b][u].x, c.v[b][u].y}, f32x2{qq.x, qq.y}, acc2[u * 2 + 0]);
+                acc2[u * 2 + 1] = __builtin_elementwise_fma(f32x2{c.v[b][u].z, c.v[b][u].w}, f32x2{qq.z, qq.w}, acc2[u * 2 + 1]);
+            }
+        }
+        float acc[4 * CU];
+#pragma unroll
+        for (int j = 0; j < 2 * CU; ++j) { acc[2 * j] = acc2[j].x; acc[2 * j + 1] = acc2[j].y; }
+        const uint32_t keep = ct ? 0xFFFFFFFFu : 0u; // a group's first lane starts from +0.0
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4 * CU; ++j) s = s + acc[j];
+#pragma unroll
+        for (int k = 1; k < CG; ++k) {
+            // (bound_ctrl: a DPP row's first lane reads 0 and needs no `old` operand)
+            s = __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x111 /* row_shr:1 */, 0xf, 0xf, true) & keep);
+#pragma unroll
+            for (int j = 0; j < 4 * CU; ++j) s = s + acc[j];
+        }
+        float r = s;
+#pragma unroll
+        for (int u = 0; u < TU; ++u) {
+            const float4 qq = *reinterpret_cast<const float4*>(lds_q + NB * 128 + u * 16);
+            r = __builtin_fmaf(c.vt[u].x, qq.x, r);
+            r = __builtin_fmaf(c.vt[u].y, qq.y, r);
+            r = __builtin_fmaf(c.vt[u].z, qq.z, r);
+            r = __builtin_fmaf(c.vt[u].w, qq.w, r);
+        }
+        return angular_from_dot(r);
+    }
+    // Distances of the ns >= 1 survivors whose (id, R) stand in cr_slots(): each in its survivor's own lane (surv: this
+    // lane is one, of rank srank). xtails: the expanded node's tails (LayerDev::adjx), or null = every row's own.
+    __device__ __forceinline__ float compact_rows(const uint32_t ns, const uint32_t srank, const bool surv, const uint8_t* xtails) const {
+        const uint32_t ct = lane & (uint32_t)(CG - 1), g = lane / (uint32_t)CG;
+        const uint64_t* cs = cr_slots();
+        float d = 0.0f;
+        uint32_t base = 0;
+        CRows ra, rb;
+        do {
+            const uint32_t sa = base + g, sb = base + CNG + g; // (below 32: stale places are read, never used)
+            const uint64_t ea = cs[sa], eb = cs[sb];
+            cr_issue(ra, ea, sa < ns, ct, xtails);
+            cr_issue(rb, eb, sb < ns, ct, xtails);
+            asm volatile("" ::: "memory"); // both sets' loads are in flight here
+            const uint32_t rel = srank - base; // (a rank below base: beyond every pass of this trip)
+            const int from = (int)(((rel & (CNG - 1u)) * (uint32_t)CG + (uint32_t)(CG - 1)) * 4u);
+            const float da = cr_finish(ra, ct);
+            const float ba = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(da)));
+            d = (surv && rel < CNG) ? ba : d;
+            if (base + CNG < ns) {
+                const float db = cr_finish(rb, ct);
+                const float bb = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(db)));
+                d = (surv && rel >= CNG && rel < 2u * CNG) ? bb : d;
+            }
+            base += 2u * CNG;
+        } while (2u * CNG < 32u && base < ns);
+        return d;
+    }
+
     // ---- lists of 33 / 65 / 129 slots (max_search 1025 .. 8192): the TWO-LEVEL list ---------------------------------------
     // Round 4 kept one sorted array of 64 S keys (registers + an LDS image) and merged every expansion's candidates into
     // it: O(S) per expansion with a large constant (13.7 k of 25.4 k clocks per expansion at max_search 4096,
@@ -870,7 +993,7 @@ struct FastWalker {
     // loop: a hit means "this node entered the list earlier in this walk of the layer", i.e. the reference's visited set
     // holds it and skips it (mod.rs:1026); a miss (never entered, or evicted by a colliding id) means nothing -- the
     // candidate goes the exact way. Results do not depend on the cache.
-    static constexpr uint32_t VSLOTS = (V16 == 5) ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS;
+    static constexpr uint32_t VSLOTS = fast_vcache_slots(V16 == 5, CR);
     __device__ __forceinline__ static uint32_t vcache_slot(uint32_t id) {
         if constexpr (V16 == 5) return (id ^ (id >> 11) ^ (id >> 22)) & (VSLOTS - 1u);
         else return (id ^ (id >> 9)) & (VSLOTS - 1u);
@@ -1219,6 +1342,12 @@ struct FastWalker {
         uint64_t xkey;
         if (d0_known) {
             xkey = wkey(d0_value, entrypoint) | 1ull;
+        } else if constexpr (CR != 0) { // (one group's worth of registers, not the 13 x 16 bytes per lane of RowRegs)
+            CRows r0;
+            const uint32_t ct = lane & (uint32_t)(CG - 1);
+            cr_issue(r0, (uint64_t)entrypoint, true, ct, nullptr);
+            const float d0 = cr_finish(r0, ct);
+            xkey = readlane64(wkey(d0, entrypoint), (uint32_t)(CG - 1)) | 1ull;
         } else {
             RowRegs r0;
             issue_rows(entrypoint, r0);
@@ -1263,6 +1392,8 @@ struct FastWalker {
             st.n_adj += nvalid;
             [[maybe_unused]] uint64_t seenm = 0; // SEEN: the pairs whose id the walk has evaluated before (both lanes of a pair)
             [[maybe_unused]] uint64_t skipm = 0; // SK: the pairs (both lanes) the row sketch rejected -- evaluated, no candidate
+            [[maybe_unused]] uint32_t cr_ns = 0, cr_rank = 0; // CR: the survivors of this expansion, this lane's rank among them
+            [[maybe_unused]] bool cr_surv = false;            // CR: this (odd) lane's neighbor is one
             if constexpr (SEEN) {
                 const bool seen = vcache[vcache_slot(nb)] == nb; // (the entry point is in the cache; UNUSED never is)
                 seenm = wave_ballot(seen);
@@ -1280,7 +1411,13 @@ struct FastWalker {
                             go = go && ((skipm >> lane) & 1ull) == 0ull;
                         }
                     }
-                    if (go) {
+                    if constexpr (CR != 0) { // the survivors leave (id, R) at their ranks; their rows are read by compact_rows
+                        const uint64_t sm = wave_ballot(go) & 0xAAAAAAAAAAAAAAAAull;
+                        cr_ns = (uint32_t)__popcll(sm);
+                        cr_rank = mbcnt64(sm);
+                        cr_surv = go && h != 0u;
+                        if (cr_surv) cr_slots()[cr_rank] = ((uint64_t)R << 32) | nb;
+                    } else if (go) {
                         const uint8_t* tails = nullptr;
                         if constexpr (XT) {
                             if (adjx) tails = adjx + (size_t)xid * Ly.adjx_stride + 128u + R * XTAILB;
@@ -1328,7 +1465,13 @@ struct FastWalker {
             PT_MARK(2); // visited set (under the loads)
             PT_WAIT_VM();
             PT_MARK(3); // what is left of the wait for the rows
-            const float d = finish_rows(rr);
+            float d = 0.0f;
+            if constexpr (CR != 0) {
+                // (the slots were written before the fetch-ahead: its scalar work covers their LDS round trip)
+                if (cr_ns) d = compact_rows(cr_ns, cr_rank, cr_surv, adjx ? adjx + (size_t)xid * Ly.adjx_stride + 128u : nullptr);
+            } else {
+                d = finish_rows(rr);
+            }
             if constexpr (TOUCH) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(touched[j])); // (arrived before the rows did)
@@ -1429,14 +1572,14 @@ struct FastWalker {
     }
 };
 
-template <int DT, int DIM, int S, bool TRAIL, int V16, bool WIDE = false>
+template <int DT, int DIM, int S, bool TRAIL, int V16, bool WIDE = false, int CR = 0>
 __device__ __forceinline__ void fast_walk_one(const SearchParams& p, const uint32_t qi, uint8_t* smem) {
     const uint32_t lane = threadIdx.x;
     if (p.force_slow) {
         hand_over(p, qi);
         return;
     }
-    FastWalker<DT, DIM, S, V16, WIDE> w(p, smem);
+    FastWalker<DT, DIM, S, V16, WIDE, CR> w(p, smem);
     w.load_query(qi);
 
     if constexpr (TRAIL) { // find_entrypoint_trail (reorder.rs:180-208): every walk starts at node 0
@@ -1481,7 +1624,7 @@ __device__ __forceinline__ void fast_walk_one(const SearchParams& p, const uint3
         // res = the first max_search expanded entries; .take(num_neighbors), mod.rs:974-977
         uint32_t count;
         const QueryIO io = query_io(p, qi);
-        if constexpr (FastWalker<DT, DIM, S, V16, WIDE>::LONG) { // the list is M (flushed at the layer's end), in LDS
+        if constexpr (FastWalker<DT, DIM, S, V16, WIDE, CR>::LONG) { // the list is M (flushed at the layer's end), in LDS
             const uint32_t want = min(p.ef, p.k);
             uint32_t total = 0;
             const uint32_t nm = p.n_layers > 0 ? w.nM : 0u;
@@ -1552,10 +1695,11 @@ __device__ __forceinline__ void fast_walk_one(const SearchParams& p, const uint3
 // waves per SIMD the register allocator is asked to keep possible (__launch_bounds__'s second argument is
 // per SIMD on AMD; 5 waves = 96 VGPRs, 4 = 128, 3 = 168, 2 = 256). Chosen from the unconstrained
 // allocation of each instantiation so that none spills (tools/isa_report.py prints both).
-constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, bool SEEN = false) {
+constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, bool SEEN = false, int CR = 0) {
 #if GRANNE_HIP_PHASE_TIMERS
     return 1; // the phase clocks live in registers too: no cap, the diagnostics run is one wave per SIMD anyway
 #endif
+    if (CR && S == 1) return GRANNE_HIP_CR_WAVES; // (the compacted row stage: two sets of 128 / G bytes per chunk instead of one of 64)
     // lists of 2112 / 4160 keys: 2 registers per 64 keys + the merge's bookkeeping; 17 / 33 KB of LDS mirror each. Two
     // walkers per SIMD for the 33-slot lists (256 registers: measured 137 k against 97 k queries/s at max_search 1600 when the
     // allocation crept to 259), one for the 65-slot ones
@@ -1570,24 +1714,24 @@ constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, boo
 }
 
 // Blocks nq.. are the tail (slow_kernel.h): they serve the hand-over list inside the same launch.
-template <int DT, int DIM, int S, bool TRAIL = false, int V16 = 0, bool WIDE = false>
-__global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE, V16 == 5)) void fast_kernel(const SlowParams P) {
+template <int DT, int DIM, int S, bool TRAIL = false, int V16 = 0, bool WIDE = false, int CR = 0>
+__global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE, V16 == 5, CR)) void fast_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
     if (blockIdx.x < P.sp.nq) {
-        fast_walk_one<DT, DIM, S, TRAIL, V16, WIDE>(P.sp, blockIdx.x, smem);
+        fast_walk_one<DT, DIM, S, TRAIL, V16, WIDE, CR>(P.sp, blockIdx.x, smem);
         walker_done(P);
     } else {
         tail_block<DT>(P, smem);
     }
 }
 
-__host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S, uint32_t visited_slots, bool seen = false, bool wide = false) {
+__host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S, uint32_t visited_slots, bool seen = false, bool wide = false, int cr = 0) {
     const bool lng = walk_list_is_long((int)S, wide);
     // [query][the list's image][lists of up to 17 slots: the cache of entered ids][visited]
     // (lists beyond 1024 keys: M's image, then F's of 128 keys)
     // (+ the launches that skip revisits on the sketched shapes: the query's sketch codes where the visited table would be)
     const uint32_t sk = (seen && !i8 && !gen && !wide && sketch_dim_ok(dim)) ? SKETCH_LINE : 0u;
-    return fast_query_bytes(i8, gen, dim, row_bytes, S, seen) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + (seen ? VCACHE_SLOTS_SEEN : VCACHE_SLOTS) * 4u + visited_slots * 4u + sk;
+    return fast_query_bytes(i8, gen, dim, row_bytes, S, seen) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + fast_vcache_slots(seen, cr) * 4u + visited_slots * 4u + sk;
 }
 
 } // namespace granne_hip

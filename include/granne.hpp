@@ -239,6 +239,8 @@ public:
     // launches made for groups since the index was created, and the queries they served
     uint64_t coalesced_launches() const { return get_option(GRANNE_HIP_OPT_COALESCED_LAUNCHES); }
     uint64_t coalesced_queries() const { return get_option(GRANNE_HIP_OPT_COALESCED_QUERIES); }
+    // whether the last search launch ran the compacted row stage of the sketched walkers (GRANNE_HIP_OPT_LAST_COMPACT_ROWS)
+    bool last_compact_rows() const { return get_option(GRANNE_HIP_OPT_LAST_COMPACT_ROWS) != 0; }
     uint64_t get_option(int option) const {
         uint64_t v = 0;
         check(granne_hip_index_get_option(h_.get(), option, &v));

@@ -741,7 +741,10 @@ enum {
                                          cap, or this many microseconds have passed since it took the lead, whichever comes
                                          first -- a throughput knob (and what makes tests of grouping deterministic) */
     GRANNE_HIP_OPT_COALESCED_LAUNCHES = 16, /* read-only: launches made for groups (that served them) since the index was created */
-    GRANNE_HIP_OPT_COALESCED_QUERIES = 17   /* read-only: queries those launches served */
+    GRANNE_HIP_OPT_COALESCED_QUERIES = 17,  /* read-only: queries those launches served */
+    GRANNE_HIP_OPT_LAST_COMPACT_ROWS = 18   /* read-only: 1 when the index's last search launch ran the register walker's compacted
+                                               row stage -- the launches that use the row sketch (GRANNE_HIP_OPT_SKETCH) read
+                                               and evaluate only the neighbors that survive it, several lanes to a row; same bits */
 };
 #define GRANNE_HIP_COALESCE_CALL_MAX 64 /* calls of more queries than this never take part in GRANNE_HIP_OPT_COALESCE */
 #define GRANNE_HIP_COALESCE_MAX 1024    /* the largest (and default) GRANNE_HIP_OPT_COALESCE_MAX */
