@@ -6,7 +6,7 @@ import os
 
 from . import build as _build
 
-F32, I8 = 0, 1
+F32, I8, F16 = 0, 1, 2  # GRANNE_HIP_F32 / _I8 / _F16 (rows of halves, normalised on read: "angular_f16")
 UNUSED = 0xFFFFFFFF
 BUILD_ALL = 0xFFFFFFFFFFFFFFFF  # GRANNE_HIP_BUILD_ALL: Builder::build()
 
@@ -93,6 +93,8 @@ SIGNATURES = {
     "granne_hip_search": (i32, [vp, vp, u32, u32, vp, vp, C.POINTER(u32)]),
     "granne_hip_normalize_f32_device": (i32, [vp, u64, u32, i32, vp]),
     "granne_hip_quantize_f32_device": (i32, [vp, vp, u64, u32, i32, vp]),
+    "granne_hip_f32_to_f16_device": (i32, [vp, vp, u64, u32, i32, vp]),
+    "granne_hip_f16_to_f32_device": (i32, [vp, vp, u64, u32, i32, i32, vp]),
     "granne_hip_dist_pairs_device": (i32, [vp, vp, vp, vp, u64, vp, vp]),
     "granne_hip_dists_device": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
     "granne_hip_refine_device": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
@@ -103,6 +105,8 @@ SIGNATURES = {
     "granne_hip_normalize_f32": (i32, [vp, u64, u32, i32]),
     "granne_hip_quantize_f32": (i32, [vp, vp, u64, u32, i32]),
     "granne_hip_dist_pairs": (i32, [vp, vp, u32, vp, vp, u64, vp]),
+    "granne_hip_f32_to_f16": (i32, [vp, vp, u64, u32, i32]),
+    "granne_hip_f16_to_f32": (i32, [vp, vp, u64, u32, i32, i32]),
     "granne_hip_synth_rows_device": (i32, [vp, u64, u64, u64, u32, i32, vp]),
     "granne_hip_index_load": (i32, [C.POINTER(vp), vp, u64, vp, u64, i32, i32]),
     "granne_hip_index_load_files": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, i32, i32]),

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import BUILD_ALL, F32, BuildConfig, check, lib
-from .index import _ELEMENT_TYPES, EMBEDDINGS, Granne, _p, normalize, quantize
+from .index import _ELEMENT_TYPES, EMBEDDINGS, Granne, _p, _prepare_elements
 
 
 class GranneBuilder:
@@ -15,7 +15,8 @@ class GranneBuilder:
         """Keyword arguments follow the reference's GranneBuilder.__new__ (py/src/lib.rs:384-405);
         unset ones take BuildConfig::default() (src/index/mod.rs:220-231: multiplier 15,
         num_neighbors 30, max_search 200). batch_max / batch_div tune the GPU insertion schedule
-        (include/granne_hip.h)."""
+        (include/granne_hip.h). "angular_f16": the build runs over the f32 rows the halves stand for, which the builder
+        keeps beside the halves while it lives; get_index gives an index over the halves."""
         et = element_type.lower()
         self._se = None
         if et == EMBEDDINGS:  # elements: a granne_amd.SumEmbeddings; the build runs over its normalised rows
@@ -60,7 +61,7 @@ class GranneBuilder:
     def _prep(self, rows):
         if self._prepared:
             return np.ascontiguousarray(rows, dtype=self.np_dtype)
-        return normalize(rows, self.device) if self.element_type == "angular" else quantize(rows, self.device)
+        return _prepare_elements(self.element_type, rows, self.device)
 
     @classmethod
     def from_device(cls, element_type, d_elements_ptr, n_elements, dim, device=0, stream=0, **kwargs):

@@ -29,6 +29,10 @@ struct granne_hip_builder {
     uint64_t hbm_bytes = 0;
     ScratchCache scratch; // the build's searches (search_launch)
     std::shared_ptr<SeDev> se; // made by granne_hip_builder_create_sum_embeddings: the container d_elements was materialised from
+    // made with GRANNE_HIP_F16: the halves as an index keeps them (half_stride bytes apart). d_elements holds the rows they
+    // stand for -- normalize(widen(row)), f32 -- and the build is the f32 build over those; get_index hands out the halves.
+    uint8_t* d_half = nullptr;
+    uint32_t half_bytes = 0, half_stride = 0;
 };
 
 extern "C" void granne_hip_build_config_default(granne_hip_build_config* c) {
@@ -60,6 +64,7 @@ static void destroy_builder(granne_hip_builder* b) {
     if (!b) return;
     DeviceGuard g(b->device);
     if (b->d_elements) (void)hipFree(b->d_elements);
+    if (b->d_half) (void)hipFree(b->d_half);
     for (auto& L : b->layers)
         if (L.d_adj) (void)hipFree(L.d_adj);
     b->scratch.free_all();
@@ -71,7 +76,7 @@ static int builder_validate(granne_hip_builder** out, const granne_hip_build_con
     if (!out) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!cfg) return fail(GRANNE_HIP_ERR_INVALID, "config is null");
-    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!known_dtype(dtype)) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many elements (src/index/mod.rs:420)");
     if (cfg->num_neighbors < 1 || cfg->num_neighbors > BUILD_MAX_NEIGHBORS)
@@ -91,6 +96,39 @@ extern "C" int granne_hip_builder_create_device(granne_hip_builder** out, const 
     if (n_elements && !d_elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     DeviceGuard g(device_id);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    if (dtype == GRANNE_HIP_F16) {
+        // rows of halves: R = normalize(widen(rows)) is made once, the f32 builder runs over R, and the halves are kept
+        // in an index's layout for get_index. R lives as long as the builder.
+        hipStream_t s = (hipStream_t)stream;
+        float* d_R = nullptr;
+        const size_t r_bytes = (size_t)n_elements * dim * 4;
+        HIP_TRY(hipMalloc((void**)&d_R, r_bytes ? r_bytes : 16));
+        rc = f16_rows_to_f32((const uint8_t*)d_elements, (uint64_t)dim * 2u, d_R, n_elements, dim, 1, s);
+        if (rc == 0) rc = granne_hip_builder_create_device(out, cfg, d_R, n_elements, dim, GRANNE_HIP_F32, device_id, stream); // synchronises
+        else (void)hipStreamSynchronize(s);
+        (void)hipFree(d_R);
+        if (rc) return rc;
+        granne_hip_builder* b = *out;
+        granne_hip_index tmp;
+        tmp.device = device_id;
+        tmp.dim = dim;
+        tmp.dtype = GRANNE_HIP_F16;
+        tmp.n_elements = n_elements;
+        tmp.row_bytes = device_row_bytes(dim, GRANNE_HIP_F16);
+        tmp.row_stride = device_row_stride(dim, GRANNE_HIP_F16);
+        rc = upload_elements_from_device(&tmp, d_elements, s);
+        if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "sync failed");
+        b->d_half = tmp.d_elements;
+        b->half_bytes = tmp.row_bytes;
+        b->half_stride = tmp.row_stride;
+        b->hbm_bytes += tmp.hbm_bytes;
+        tmp.d_elements = nullptr;
+        if (rc) {
+            destroy_builder(b);
+            *out = nullptr;
+        }
+        return rc;
+    }
     granne_hip_builder* b = new granne_hip_builder();
     b->device = device_id;
     b->cfg = *cfg;
@@ -151,6 +189,7 @@ extern "C" int granne_hip_builder_append(granne_hip_builder* b, const void* elem
     if (n_new == 0) return GRANNE_HIP_OK;
     if (!elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     if (b->n_elements + n_new >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many elements (src/index/mod.rs:420)");
+    if (b->d_half) return fail(GRANNE_HIP_ERR_INVALID, "builder_append has no form for GRANNE_HIP_F16 (angular_f16) rows: make a new builder over all the rows");
     DeviceGuard g(b->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
     const size_t dense = (size_t)b->dim * elem_size(b->dtype);
@@ -531,15 +570,15 @@ extern "C" int granne_hip_builder_get_index(const granne_hip_builder* b, granne_
     granne_hip_index* ix = new granne_hip_index();
     ix->device = b->device;
     ix->dim = b->dim;
-    ix->dtype = b->dtype;
+    ix->dtype = b->d_half ? GRANNE_HIP_F16 : b->dtype;
     ix->n_elements = b->n_elements;
-    ix->row_bytes = b->row_bytes;
-    ix->row_stride = b->row_stride;
+    ix->row_bytes = b->d_half ? b->half_bytes : b->row_bytes;
+    ix->row_stride = b->d_half ? b->half_stride : b->row_stride;
     auto body = [&]() -> int {
-        size_t eb = (size_t)b->n_elements * b->row_stride;
+        size_t eb = (size_t)b->n_elements * ix->row_stride;
         HIP_TRY(hipMalloc((void**)&ix->d_elements, eb ? eb : 16));
         ix->hbm_bytes += eb;
-        if (eb) HIP_TRY(hipMemcpy(ix->d_elements, b->d_elements, eb, hipMemcpyDeviceToDevice));
+        if (eb) HIP_TRY(hipMemcpy(ix->d_elements, b->d_half ? b->d_half : b->d_elements, eb, hipMemcpyDeviceToDevice));
         for (const auto& BL : b->layers) {
             LayerHost L;
             L.len = BL.len;

@@ -341,7 +341,7 @@ extern "C" int granne_hip_index_load(granne_hip_index** out, const void* index_b
     if (!out) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!index_bytes || !elements_bytes) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!known_dtype(dtype)) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
     // elements: [u64 width][scalars] (src/slice_vector/mod.rs:213-221); width > 0, len % width == 0 (:116-118)
     if (elements_len < 8) return fail(GRANNE_HIP_ERR_IO, "elements file too small");
     const uint8_t* eb = (const uint8_t*)elements_bytes;
@@ -393,7 +393,7 @@ extern "C" int granne_hip_write_index_file(const char* path, uint32_t n_layers, 
 extern "C" int granne_hip_write_elements_file(const char* path, const void* elements, uint64_t n_elements, uint32_t dim,
                                               int dtype) {
     if (!path || (n_elements && !elements)) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
-    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!known_dtype(dtype)) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
     uint8_t hdr[8];
     granne_file::wr_u64(hdr, dim);
     if (!granne_file::write_file(path, hdr, 8, elements, (size_t)n_elements * dim * elem_size(dtype)))

@@ -226,7 +226,16 @@ struct granne_hip_index {
     uint64_t next_seq = 1;
 };
 
-static inline uint32_t elem_size(int dtype) { return dtype == GRANNE_HIP_F32 ? 4u : 1u; }
+static inline uint32_t elem_size(int dtype) { return dtype == GRANNE_HIP_F32 ? 4u : dtype == GRANNE_HIP_F16 ? 2u : 1u; }
+// bytes of a query component: rows of halves are searched with prepared f32 queries
+static inline uint32_t query_elem_size(int dtype) { return dtype == GRANNE_HIP_I8 ? 1u : 4u; }
+static inline bool known_dtype(int dtype) { return dtype == GRANNE_HIP_F32 || dtype == GRANNE_HIP_I8 || dtype == GRANNE_HIP_F16; }
+// what has no form for rows of halves says so
+#define GRANNE_HIP_F16_UNSUPPORTED(dt, what)                                                                            \
+    do {                                                                                                                \
+        if ((dt) == GRANNE_HIP_F16)                                                                                     \
+            return fail(GRANNE_HIP_ERR_INVALID, what " has no form for GRANNE_HIP_F16 (angular_f16) rows: use f32 or int8 rows"); \
+    } while (0)
 
 static uint32_t next_pow2(uint32_t v) {
     uint32_t p = 1;
@@ -239,6 +248,7 @@ static uint32_t next_pow2(uint32_t v) {
 // straddles more 128-byte lines than it has to (SURVEY 7 "unaligned rows").
 static uint32_t device_row_bytes(uint32_t dim, int dtype) {
     if (dtype == GRANNE_HIP_F32) return (dim * 4u + 15u) & ~15u;
+    if (dtype == GRANNE_HIP_F16) return f16_row_bytes(dim);
     if (dim <= 1024) return next_pow2(dim < 16 ? 16 : dim);
     return (dim + 1023u) & ~1023u;
 }
@@ -249,6 +259,8 @@ static uint32_t device_row_bytes(uint32_t dim, int dtype) {
 static uint32_t device_row_stride(uint32_t dim, int dtype) {
     const uint32_t rb = device_row_bytes(dim, dtype);
     if (dtype == GRANNE_HIP_F32 && rb >= 256u) return (rb + 127u) & ~127u;
+    // rows of halves of 128 bytes and more start on a line too: a row touches ceil(bytes / 128) of them (100-d: two)
+    if (dtype == GRANNE_HIP_F16 && rb >= 128u) return (rb + 127u) & ~127u;
     return rb;
 }
 // 16-byte units of a row's tail (the dim % 32 last floats) that LayerDev::adjx carries per neighbor; 0: the shape has no
@@ -274,7 +286,7 @@ static int validate_common(granne_hip_index** out, uint64_t n_elements, uint32_t
                            const uint64_t* layer_len) {
     if (!out) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!known_dtype(dtype)) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n_elements >= 0xFFFFFFFFull)
         return fail(GRANNE_HIP_ERR_INVALID, "too many elements (reference limit, src/index/mod.rs:420)");
@@ -898,7 +910,10 @@ struct SearchTarget {
     uint64_t n_elements;
     uint32_t dim;
     int dtype;
-    uint32_t row_bytes, row_stride;
+    // stage_row_bytes: bytes of a row AS THE WALKERS STAGE IT (the query in LDS, the stage slots; SearchParams::row_bytes):
+    // the device row's own for f32 and int8, the widened f32 row's for rows of halves. elem_row_bytes / row_stride: the
+    // device rows themselves -- what anything that READS rows goes by.
+    uint32_t stage_row_bytes, elem_row_bytes, row_stride;
     const LayerDev* d_layers;
     uint32_t n_layers;
     uint32_t max_dev_width;
@@ -917,8 +932,9 @@ struct SearchTarget {
     template <class G>
     SearchTarget(const G* g, const LayerDev* layers, uint32_t n_layers)
         : device(g->device), d_elements(g->d_elements), n_elements(g->n_elements), dim(g->dim), dtype(g->dtype),
-          row_bytes(g->row_bytes), row_stride(g->row_stride), d_layers(layers), n_layers(n_layers),
-          scratch(&const_cast<G*>(g)->scratch) {
+          stage_row_bytes(g->dtype == GRANNE_HIP_F16 ? (g->dim * 4u + 15u) & ~15u : g->row_bytes), elem_row_bytes(g->row_bytes),
+          row_stride(g->row_stride),
+          d_layers(layers), n_layers(n_layers), scratch(&const_cast<G*>(g)->scratch) {
         if constexpr (std::is_same<G, granne_hip_index>::value) {
             max_dev_width = g->max_dev_width;
             opt_visited_slots = g->opt_visited_slots;
@@ -974,9 +990,18 @@ static search_fn general_kernel_s(uint32_t S) {
 // the general walker of a compact SumEmbeddings index (sum_embeddings.h): f32, run-time dim, no trail walks
 static search_fn compact_kernel_s(uint32_t S) {
     switch (S) {
-    case 1: return search_kernel<DT_F32, 0, 1, false, true>;
-    case 2: return search_kernel<DT_F32, 0, 2, false, true>;
-    case 4: return search_kernel<DT_F32, 0, 4, false, true>;
+    case 1: return search_kernel<DT_F32, 0, 1, false, PV_SE>;
+    case 2: return search_kernel<DT_F32, 0, 2, false, PV_SE>;
+    case 4: return search_kernel<DT_F32, 0, 4, false, PV_SE>;
+    }
+    return nullptr;
+}
+// the general walker over rows of halves (f16.h): f32 queries, run-time dim, no trail walks
+static search_fn f16_kernel_s(uint32_t S) {
+    switch (S) {
+    case 1: return search_kernel<DT_F32, 0, 1, false, PV_F16>;
+    case 2: return search_kernel<DT_F32, 0, 2, false, PV_F16>;
+    case 4: return search_kernel<DT_F32, 0, 4, false, PV_F16>;
     }
     return nullptr;
 }
@@ -1040,13 +1065,13 @@ static search_fn fast_wide_kernel_s(uint32_t S) {
 static search_fn fast_kernel_of(const SearchTarget& T, uint32_t S, bool trail, int v16, bool wide, bool cr) {
     const bool i8 = T.dtype == GRANNE_HIP_I8;
     if (wide) { // (64-id layers: no visited set, no trail walks, int8 rows of 128 bytes)
-        if (trail || v16 != 3 || (i8 && T.row_bytes != 128)) return nullptr;
+        if (trail || v16 != 3 || (i8 && T.stage_row_bytes != 128)) return nullptr;
         if (i8) return fast_wide_kernel_s<DT_I8, 0>(S);
         return T.dim == 100 ? fast_wide_kernel_s<DT_F32, 100>(S) : T.dim == 200 ? fast_wide_kernel_s<DT_F32, 200>(S) : fast_wide_kernel_s<DT_F32, 0>(S);
     }
-    if (i8 && T.row_bytes == 256) return fast_kernel_s<DT_I8, 256>(S, trail, v16, cr);
-    if (i8 && T.row_bytes == 512) return fast_kernel_s<DT_I8, 512>(S, trail, v16, cr);
-    if (i8) return T.row_bytes == 128 ? fast_kernel_s<DT_I8, 0>(S, trail, v16, cr) : nullptr;
+    if (i8 && T.stage_row_bytes == 256) return fast_kernel_s<DT_I8, 256>(S, trail, v16, cr);
+    if (i8 && T.stage_row_bytes == 512) return fast_kernel_s<DT_I8, 512>(S, trail, v16, cr);
+    if (i8) return T.stage_row_bytes == 128 ? fast_kernel_s<DT_I8, 0>(S, trail, v16, cr) : nullptr;
     return T.dim == 100 ? fast_kernel_s<DT_F32, 100>(S, trail, v16, cr) : T.dim == 200 ? fast_kernel_s<DT_F32, 200>(S, trail, v16, cr) : fast_kernel_s<DT_F32, 0>(S, trail, v16, cr);
 }
 
@@ -1084,10 +1109,10 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
     // (ids: 31 bits. A 2^31-element index needs 275 GB for its bottom layer's 128-byte adjacency rows alone, so the
     //  reference's 2^32 - 2 capacity, src/index/mod.rs:27-28, is out of one device's reach whatever the key layout)
     const bool shape = T.max_dev_width <= 64 && T.n_elements <= WALK_MAX_ELEMENTS &&
-                       (!i8 || T.row_bytes == 128 || (!wide && (T.row_bytes == 256 || T.row_bytes == 512))); // (int8 dims <= 512)
+                       (!i8 || T.stage_row_bytes == 128 || (!wide && (T.stage_row_bytes == 256 || T.stage_row_bytes == 512))); // (int8 dims <= 512)
     // the longest max_search the register walker is instantiated for: lists of up to 17 x 64 keys for 64-id layers, int8
     // rows of 256 / 512 bytes and streamed f32 dims, else two-level lists of up to 129 x 64 keys
-    const uint32_t fast_max = (wide || (i8 ? T.row_bytes != 128 : streamed)) ? 1024u : FAST_MAX_SEARCH;
+    const uint32_t fast_max = (wide || (i8 ? T.stage_row_bytes != 128 : streamed)) ? 1024u : FAST_MAX_SEARCH;
     // a compact SumEmbeddings index has no rows, sketches or inline tails for the register walker to read: every walk of
     // it is the general walker's (max_search up to 256) or the exact walker's
     const bool compact = T.se != nullptr;
@@ -1095,7 +1120,14 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         fail(GRANNE_HIP_ERR_INVALID, "a compact SumEmbeddings index serves searches only: make the index with GRANNE_HIP_SE_MATERIALIZED");
         return P;
     }
-    const bool fast = !compact && shape && ef <= fast_max && !(wide && trail);
+    // rows of halves are normalised where they are read: the general walker (max_search up to 256) or the exact walker
+    // make them, never the register walker (walk_fast.h reads prepared f32 / int8 rows)
+    const bool f16 = T.dtype == GRANNE_HIP_F16;
+    if (f16 && trail) {
+        fail(GRANNE_HIP_ERR_INVALID, "reorder has no form for GRANNE_HIP_F16 (angular_f16) rows");
+        return P;
+    }
+    const bool fast = !compact && !f16 && shape && ef <= fast_max && !(wide && trail);
     const uint32_t ef_walk = fast ? ef : (ef > 256 ? 256 : ef); // what the register / general walker is sized for
     const bool all_slow = T.opt_force_slow || (!fast && ef > 256);
     P.walker = all_slow ? GRANNE_HIP_WALKER_EXACT
@@ -1116,7 +1148,7 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
     if (fast && !trail && ((none && !T.opt_visited_slots) || longest)) {
         // a launch of a few queries leaves the chip idle: its walkers touch the next node's rows ahead (walk_fast.h, TOUCH)
         const uint32_t touch_max = knobs().touch_max >= 0 ? (uint32_t)knobs().touch_max : 256u; // (round 5: +4 % at 256 queries, -10 % at 1024: profiles/r5_touch.txt)
-        const bool touch_shape = P.S == 1 && !wide && !streamed && !(i8 && T.row_bytes != 128);
+        const bool touch_shape = P.S == 1 && !wide && !streamed && !(i8 && T.stage_row_bytes != 128);
         P.v16 = (touch_shape && nq <= touch_max) ? 4 : 3;
         // launches of many walks are bound by bandwidth: their walkers skip revisits BEFORE the rows are fetched (walk_fast.h, SEEN)
         const uint64_t seen_min = knobs().seen_min >= 0 ? (uint64_t)knobs().seen_min : T.opt_seen_min; // (GRANNE_HIP_SEEN_MIN overrides the option: experiments)
@@ -1125,8 +1157,8 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         if (P.S <= 4 && !wide && !i8 && nq >= seen_min) P.v16 = 5; // (every f32 dim: unrolled and streamed)
         // ... and, where they reject neighbors by the index's row sketch, read the rows of the survivors only (walk_fast.h, CR)
         P.cr = P.v16 == 5 && !i8 && sketch_dim_ok(T.dim) && T.d_sketch != nullptr && knobs().compact_rows != 0;
-        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, 0u, P.v16 == 5, wide, P.cr ? GRANNE_HIP_CR_G : 0);
-        const uint32_t least = lds_query_bytes(T.row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
+        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.stage_row_bytes, P.S, 0u, P.v16 == 5, wide, P.cr ? GRANNE_HIP_CR_G : 0);
+        const uint32_t least = lds_query_bytes(T.stage_row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
         if (walk_lds < least) walk_lds = least;
     } else {
         // The front table must hold the walk's visited ids (~40 x max_search on 10M uniform points) below its 7/8
@@ -1149,16 +1181,16 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         P.visited_slots = want;
         P.upper_slots = want < 1024 ? want : 1024;
         if (fast) { // walk_fast.h: [query][S >= 8: 64*S keys][visited front table]
-            walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.row_bytes, P.S, P.visited_slots, false, wide);
+            walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.stage_row_bytes, P.S, P.visited_slots, false, wide);
         } else {
             // the general walker (search_kernel.h): int8 keeps its speculative adjacency rows in registers (Walker::REGSPEC),
             // run-time-dim f32 parks them in LDS. LDS plan: the visited table dominates; the f32 stage gets what keeps four
             // walkers per CU (160 KiB / 4) when that leaves it at least 16 rows, else up to 32 rows within 64 KiB, else
             // whatever fits in the CU's 160 KiB.
             P.adjspec_bytes = i8 ? 0u : LDS_ADJSPEC_BYTES;
-            const uint32_t fixed = lds_query_bytes(T.row_bytes) + LDS_FIXED_BYTES + P.adjspec_bytes;
+            const uint32_t fixed = lds_query_bytes(T.stage_row_bytes) + LDS_FIXED_BYTES + P.adjspec_bytes;
             if (!i8) {
-                P.lrow_bytes = ((T.row_bytes / 16) | 1u) * 16u; // odd number of 16-byte units: conflict-free ds_read_b128
+                P.lrow_bytes = ((T.stage_row_bytes / 16) | 1u) * 16u; // odd number of 16-byte units: conflict-free ds_read_b128
                 const uint32_t wmax = T.max_dev_width < 64 ? T.max_dev_width : 64;
                 const uint32_t used = fixed + P.visited_slots * 4u;
                 auto rows_in = [&](uint32_t budget) { return budget > used ? (budget - used) / P.lrow_bytes : 0u; };
@@ -1205,21 +1237,22 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
     // by SLOW_SCRATCH_BUDGET bytes (never below the option itself), so that a handful of streams searching beyond the
     // register lists hold a few GB, not tens.
     P.slow_blocks = (uint32_t)T.opt_slow_blocks;
-    const uint32_t slow_lds = lds_query_bytes(T.row_bytes) + 64 * 8;
+    const uint32_t slow_lds = lds_query_bytes(T.stage_row_bytes) + 64 * 8;
     if (all_slow) { // every query on the exact walker: its kernel alone
         uint32_t most = P.slow_blocks * 32u;
         const size_t per_block = (size_t)T.opt_slow_slots * 12 + (size_t)ef * 8;
         const size_t fit = SLOW_SCRATCH_BUDGET / per_block;
         if (most > fit) most = fit > P.slow_blocks ? (uint32_t)fit : P.slow_blocks;
         P.slow_blocks = nq < most ? (nq > P.slow_blocks ? nq : P.slow_blocks) : most;
-        P.fn = compact ? (search_fn)slow_kernel<DT_F32, true> : !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
+        P.fn = compact ? (search_fn)slow_kernel<DT_F32, PV_SE> : f16 ? (search_fn)slow_kernel<DT_F32, PV_F16>
+               : !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
         P.lds_bytes = slow_lds;
         P.grid = P.slow_blocks;
         return P;
     }
     if (!fast || wide) P.cr = false;
     if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
-    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
+    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : f16 ? f16_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
     if (!P.fn) {
         fail(GRANNE_HIP_ERR_INVALID, "no walker is instantiated for this launch (list slots %u, visited form %d, trail %d, 64-id layers %d)",
              P.S, P.v16, (int)trail, (int)wide);
@@ -1267,6 +1300,8 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
         return GRANNE_HIP_OK;
     }
     if (!c.queries || (!c.trail && (!c.ids || !c.dists || !c.counts))) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
+    if (T.row_stride < T.elem_row_bytes || (T.dtype == GRANNE_HIP_F16 && T.elem_row_bytes != f16_row_bytes(T.dim)))
+        return fail(GRANNE_HIP_ERR_INVALID, "search: inconsistent row layout (row bytes %u, stride %u)", T.elem_row_bytes, T.row_stride);
     const WalkPlan W = plan_walk(T, c.ef, nq, c.trail != nullptr);
     if (!W.fn) return GRANNE_HIP_ERR_INVALID;
 
@@ -1279,7 +1314,8 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     size_t off_pq = off_vis + (size_t)W.slow_blocks * slots * 4;
     size_t off_res = off_pq + (size_t)W.slow_blocks * slots * 8;
     size_t off_sex = (off_res + (size_t)W.slow_blocks * c.ef * 8 + 15) & ~(size_t)15; // compact indexes: a vector per lane of the exact walker
-    size_t total = off_sex + (T.se ? (size_t)W.slow_blocks * 64u * T.dim * 4u : 0u);
+    const bool lane_x = T.se || T.dtype == GRANNE_HIP_F16; // (rows of halves: the widened row, likewise)
+    size_t total = off_sex + (lane_x ? (size_t)W.slow_blocks * 64u * T.dim * 4u : 0u);
     // The cache's mutex covers finding (or growing) this stream's block and the enqueue -- host work of microseconds.
     // Whatever waits for the GPU (the synchronisation behind slow_count) happens after it is released: host threads
     // searching one index on streams of their own do not queue behind each other's kernels.
@@ -1311,12 +1347,12 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     p.elements = T.d_elements;
     p.n_elements = T.n_elements;
     p.dim = T.dim;
-    p.row_bytes = T.row_bytes;
+    p.row_bytes = T.stage_row_bytes;
     p.row_stride = T.row_stride;
     p.layers = T.d_layers;
     p.n_layers = T.n_layers;
     p.queries = (const uint8_t*)c.queries;
-    p.q_stride = c.q_stride ? c.q_stride : (int64_t)T.dim * elem_size(T.dtype);
+    p.q_stride = c.q_stride ? c.q_stride : (int64_t)T.dim * query_elem_size(T.dtype);
     p.nq = nq;
     p.ef = c.ef;
     p.k = c.k;
@@ -1358,7 +1394,7 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     p.se_table = T.se ? T.se->d_table : nullptr;
     p.se_offsets = T.se ? T.se->d_offsets : nullptr;
     p.se_terms = T.se ? T.se->d_terms : nullptr;
-    sp.se_x = T.se ? (float*)(scratch + off_sex) : nullptr;
+    sp.se_x = lane_x ? (float*)(scratch + off_sex) : nullptr;
 
     if (T.last_walker) T.last_walker->store(W.walker);
     if (T.last_compact) T.last_compact->store(W.cr ? 1 : 0);
@@ -1634,7 +1670,7 @@ static void host_call_release(granne_hip_index* ix, granne_hip_index::HostCall* 
 struct HostLayout {
     size_t qb, o_ids, o_d, o_c, o_s, total;
     HostLayout(const granne_hip_index* ix, size_t nq, size_t k) {
-        qb = nq * ix->dim * elem_size(ix->dtype);
+        qb = nq * ix->dim * query_elem_size(ix->dtype);
         o_ids = (qb + 255) & ~(size_t)255;
         o_d = o_ids + nq * k * 8;
         o_c = o_d + ((nq * k * 4 + 15) & ~(size_t)15);
@@ -1748,7 +1784,7 @@ static int search_batch_group(granne_hip_index* ix, unsigned slot, const Combine
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
     const size_t k = m[0]->num_neighbors;
-    const size_t row = (size_t)ix->dim * elem_size(ix->dtype);
+    const size_t row = (size_t)ix->dim * query_elem_size(ix->dtype);
     const HostLayout L(ix, nq, k);
     granne_hip_index::HostCall*& c = ix->group_call[slot]; // (the slot is this leader's alone until it returns)
     if (!c) {
@@ -1875,6 +1911,76 @@ extern "C" int granne_hip_quantize_f32_device(const float* d_rows, int8_t* d_out
     return GRANNE_HIP_OK;
 }
 
+// f32 rows -> halves (round to nearest even) and back (exact; optionally normalised as angular::Vector::from does):
+// the conversions of angular_f16 elements (f16.h). Dense rows on both sides.
+extern "C" int granne_hip_f32_to_f16_device(const float* d_rows, uint16_t* d_out, uint64_t n, uint32_t dim, int device_id,
+                                            void* stream) {
+    if ((!d_rows || !d_out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f32_to_f16: null buffer");
+    if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
+    if (n == 0) return GRANNE_HIP_OK;
+    DeviceGuard g(device_id);
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    hipLaunchKernelGGL(f32_to_f16_kernel, dim3(grid_for(n * dim, 256)), dim3(256), 0, (hipStream_t)stream, d_rows, d_out, n * dim);
+    HIP_TRY(hipGetLastError());
+    return GRANNE_HIP_OK;
+}
+
+// rows of halves `in_stride` bytes apart -> dense f32 rows (checked arguments, the device selected)
+static int f16_rows_to_f32(const uint8_t* d_rows16, uint64_t in_stride, float* d_out, uint64_t n, uint32_t dim, int normalised,
+                           hipStream_t s) {
+    if (n == 0) return GRANNE_HIP_OK;
+    const uint32_t lstride = dim | 1u;
+    uint32_t rpb = (60u * 1024u) / (lstride * 4u);
+    if (rpb > 256) rpb = 256;
+    if (rpb < 1) return fail(GRANNE_HIP_ERR_INVALID, "f16_to_f32: dim too large");
+    uint64_t blocks = (n + rpb - 1) / rpb;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3((uint32_t)blocks), dim3(256), rpb * lstride * 4, s, d_rows16, in_stride, d_out, n, dim,
+                       normalised, rpb, lstride);
+    HIP_TRY(hipGetLastError());
+    return GRANNE_HIP_OK;
+}
+
+extern "C" int granne_hip_f16_to_f32_device(const uint16_t* d_rows16, float* d_out, uint64_t n, uint32_t dim, int normalised,
+                                            int device_id, void* stream) {
+    if ((!d_rows16 || !d_out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f16_to_f32: null buffer");
+    if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
+    DeviceGuard g(device_id);
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    return f16_rows_to_f32((const uint8_t*)d_rows16, (uint64_t)dim * 2u, d_out, n, dim, normalised, (hipStream_t)stream);
+}
+
+// host conveniences: copy in, convert, copy out
+static int f16_convert_host(const void* in, size_t in_bytes, void* out, size_t out_bytes, uint64_t n, uint32_t dim, int to_half,
+                            int normalised, int device_id) {
+    if ((!in || !out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f16 conversion: null buffer");
+    if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
+    if (n == 0) return GRANNE_HIP_OK;
+    DeviceGuard g(device_id);
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    uint8_t *di = nullptr, *dout = nullptr;
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc((void**)&di, in_bytes));
+        HIP_TRY(hipMalloc((void**)&dout, out_bytes));
+        HIP_TRY(hipMemcpy(di, in, in_bytes, hipMemcpyHostToDevice));
+        int rc = to_half ? granne_hip_f32_to_f16_device((const float*)di, (uint16_t*)dout, n, dim, device_id, nullptr)
+                         : granne_hip_f16_to_f32_device((const uint16_t*)di, (float*)dout, n, dim, normalised, device_id, nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost));
+        return GRANNE_HIP_OK;
+    };
+    const int rc = body();
+    if (di) (void)hipFree(di);
+    if (dout) (void)hipFree(dout);
+    return rc;
+}
+extern "C" int granne_hip_f32_to_f16(const float* rows, uint16_t* out, uint64_t n, uint32_t dim, int device_id) {
+    return f16_convert_host(rows, (size_t)n * dim * 4, out, (size_t)n * dim * 2, n, dim, 1, 0, device_id);
+}
+extern "C" int granne_hip_f16_to_f32(const uint16_t* rows16, float* out, uint64_t n, uint32_t dim, int normalised, int device_id) {
+    return f16_convert_host(rows16, (size_t)n * dim * 2, out, (size_t)n * dim * 4, n, dim, 0, normalised, device_id);
+}
+
 static int dists_launch(const granne_hip_index* ix, const void* d_queries, const uint32_t* d_qidx, uint32_t m,
                         const uint32_t* d_ids, uint64_t n_pairs, float* d_out, uint32_t* d_status, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
@@ -1887,7 +1993,11 @@ static int dists_launch(const granne_hip_index* ix, const void* d_queries, const
     // eight lanes per pair, 32 pairs per 256-thread block; enough blocks to cover the chip many times
     uint64_t blocks = (n_pairs + 31) / 32;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
-    if (ix->dtype == GRANNE_HIP_F32)
+    if (ix->dtype == GRANNE_HIP_F16)
+        hipLaunchKernelGGL(dists_kernel<DT_F16>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements,
+                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
+                           d_out, st);
+    else if (ix->dtype == GRANNE_HIP_F32)
         hipLaunchKernelGGL(dists_kernel<0>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements,
                            ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
@@ -2003,6 +2113,7 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
                                              uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
     GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "brute_force");
+    GRANNE_HIP_F16_UNSUPPORTED(ix->dtype, "brute_force");
     if (nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
@@ -2120,12 +2231,13 @@ extern "C" int granne_hip_brute_force(const granne_hip_index* ix, const void* qu
                                       uint64_t* out_ids, float* out_dists, uint32_t* out_counts) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
     GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "brute_force");
+    GRANNE_HIP_F16_UNSUPPORTED(ix->dtype, "brute_force");
     if (nq == 0) return GRANNE_HIP_OK;
     if (!queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
-    const size_t qb = (size_t)nq * ix->dim * elem_size(ix->dtype);
+    const size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
     const size_t o_ids = (qb + 255) & ~(size_t)255, o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + (((size_t)nq * k * 4 + 15) & ~(size_t)15);
     const size_t total = o_c + (size_t)nq * 4;
     uint8_t* buf = nullptr;
@@ -2291,7 +2403,7 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
     }
     DeviceGuard g(ix->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
-    size_t qb = (size_t)nq * ix->dim * elem_size(ix->dtype);
+    size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
     uint8_t *dq = nullptr, *dqi = nullptr, *did = nullptr, *dout = nullptr;
     auto freeall = [&]() {
         if (dq) (void)hipFree(dq);

@@ -36,14 +36,14 @@ static int refine_launch(const granne_hip_index* rx, const void* d_queries, uint
     P.counts = d_cand_counts;
     P.m = m;
     P.k = k;
-    P.q_lds_bytes = rx->dtype == GRANNE_HIP_F32 ? ((rx->dim * 4u + 15u) & ~15u) : rx->row_bytes;
+    P.q_lds_bytes = rx->dtype != GRANNE_HIP_I8 ? ((rx->dim * 4u + 15u) & ~15u) : rx->row_bytes; // (rows of halves: f32 queries)
     P.out_ids = d_out_ids;
     P.out_dists = d_out_dists;
     P.out_counts = d_out_counts;
     P.status = d_refine_status;
     const uint64_t lds = (uint64_t)refine_lds_q_off(m) + P.q_lds_bytes;
     if (lds > 160u * 1024u - 64u) return fail(GRANNE_HIP_ERR_INVALID, "refine: dimension too large for the LDS stage");
-    void (*fn)(const RefineParams) = rx->dtype == GRANNE_HIP_F32 ? refine_kernel<0> : refine_kernel<1>;
+    void (*fn)(const RefineParams) = rx->dtype == GRANNE_HIP_F32 ? refine_kernel<0> : rx->dtype == GRANNE_HIP_F16 ? refine_kernel<DT_F16> : refine_kernel<1>;
     if (lds > 32u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, dim3(nq), dim3(REFINE_THREADS), (uint32_t)lds, s, P);
     HIP_TRY(hipGetLastError());
@@ -107,7 +107,7 @@ extern "C" int granne_hip_search_refined_batch(const granne_hip_index* wx, const
     DeviceGuard g(wx->device);
     if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", wx->device);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t wqb = (size_t)nq * wx->dim * elem_size(wx->dtype), rqb = (size_t)nq * rx->dim * elem_size(rx->dtype);
+    const size_t wqb = (size_t)nq * wx->dim * query_elem_size(wx->dtype), rqb = (size_t)nq * rx->dim * query_elem_size(rx->dtype);
     const size_t o_rq = up(wqb), o_ids = o_rq + up(rqb), o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + up((size_t)nq * k * 4);
     const size_t o_s = o_c + up((size_t)nq * 4), o_st = o_s + (size_t)nq * 24, total = o_st + 32; // status: the walk's four words, then the refine word
     granne_hip_index* mwx = const_cast<granne_hip_index*>(wx);

@@ -16,6 +16,9 @@
 //      before it, ids (u64) breaking equal distances, list positions breaking equal (distance, id) pairs -- a
 //      caller's list may name an id twice, and keeps both. m <= 1024, so a thread ranks at most four keys in one
 //      pass over the list. Nothing depends on m being a multiple of anything.
+// Rows of halves (DT_F16, f16.h) keep the eight-lanes-per-row shape: a lane's share of a 32-component block is 8 bytes of
+// a 64-byte block; the row is widened, normalised (its norm by the same ordered sum, the divides spread over the eight
+// lanes) and then met with the staged f32 query: f16_dist_group.
 // Compiled with -ffp-contract=off: every fused operation is an explicit fmaf.
 #pragma once
 
@@ -37,7 +40,7 @@ struct RefineParams {
     const uint64_t* cand;   // [nq][m]
     const uint32_t* counts; // [nq]: valid entries of a list (clamped to m), or null = all m
     uint32_t m, k;
-    uint32_t q_lds_bytes;   // the staged query: f32 dim x 4 padded to 16, int8 row_bytes
+    uint32_t q_lds_bytes;   // the staged query: f32 (also for rows of halves) dim x 4 padded to 16, int8 row_bytes
     uint64_t* out_ids;      // [nq][k]
     float* out_dists;       // [nq][k]
     uint32_t* out_counts;   // [nq]
@@ -94,14 +97,7 @@ __device__ __forceinline__ void refine_dist_f32(const uint8_t* (&row)[R], const 
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        float s = 0.0f; // ordered sum acc[0] .. acc[31]: lane `sub` is right after step `sub`
-#pragma unroll
-        for (int ps = 0; ps < 8; ++ps) {
-            float u = (ps == 0) ? 0.0f : lane_shr1(s);
-            u = u + a[r][0]; u = u + a[r][1]; u = u + a[r][2]; u = u + a[r][3];
-            s = u;
-        }
-        s = __shfl(s, (int)(lane | 7u), 64);
+        float s = ordered_sum8(a[r][0], a[r][1], a[r][2], a[r][3], lane); // acc[0] .. acc[31] in order
         for (uint32_t t = 0; t < tail; ++t) { // src/math.rs:47-49
             const uint32_t w = (t & 3u) == 0 ? vt[r].x : (t & 3u) == 1 ? vt[r].y : (t & 3u) == 2 ? vt[r].z : vt[r].w;
             const float xv = __uint_as_float((uint32_t)__shfl((int)w, (int)((lane & ~7u) + (t >> 2)), 64));
@@ -199,7 +195,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const RefinePara
 
     // 1. the query, once
     {
-        const uint32_t qbytes = P.dim * (DT == 0 ? 4u : 1u);
+        const uint32_t qbytes = P.dim * (DT == 1 ? 1u : 4u); // (rows of halves take f32 queries)
         const uint8_t* gq = P.queries + (size_t)qi * qbytes;
         if ((qbytes & 3u) == 0 && (reinterpret_cast<uintptr_t>(gq) & 3u) == 0) {
             for (uint32_t w = tid; w < (P.q_lds_bytes >> 2); w += REFINE_THREADS)
@@ -245,11 +241,13 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const RefinePara
         float d[2];
         if (base + REFINE_GROUPS < cnt) { // (uniform) the round has candidates for the groups' second rows
             if constexpr (DT == 0) refine_dist_f32<2>(row, reinterpret_cast<const float*>(lq), P.dim, P.row_bytes, lane, d);
+            else if constexpr (DT == DT_F16) f16_dist_group<2>(row, reinterpret_cast<const float*>(lq), P.dim, P.row_bytes, lane, d);
             else refine_dist_i8<2>(row, lq, P.row_bytes, lane, dy, d);
         } else {
             const uint8_t* one[1] = {row[0]};
             float d1[1];
             if constexpr (DT == 0) refine_dist_f32<1>(one, reinterpret_cast<const float*>(lq), P.dim, P.row_bytes, lane, d1);
+            else if constexpr (DT == DT_F16) f16_dist_group<1>(one, reinterpret_cast<const float*>(lq), P.dim, P.row_bytes, lane, d1);
             else refine_dist_i8<1>(one, lq, P.row_bytes, lane, dy, d1);
             d[0] = d1[0];
             d[1] = 0.0f;

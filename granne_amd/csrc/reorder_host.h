@@ -186,6 +186,7 @@ static int apply_order(granne_hip_index* ix, const uint32_t* d_order, ReorderScr
 static int reorder_precheck(granne_hip_index* ix) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
     GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "reorder");
+    GRANNE_HIP_F16_UNSUPPORTED(ix->dtype, "reorder");
     if (ix->layers.empty()) return fail(GRANNE_HIP_ERR_INVALID, "reorder of an index without layers (the reference panics)");
     if (ix->layers.back().len != ix->n_elements)
         return fail(GRANNE_HIP_ERR_INVALID,

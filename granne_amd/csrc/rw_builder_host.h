@@ -159,6 +159,7 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     if (!b) return fail(GRANNE_HIP_ERR_INVALID, "builder is null");
     if (max_elements == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_elements must be > 0");
     if (max_elements >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "max_elements must be < 2^32 - 1 (src/index/mod.rs:420)");
+    if (b->d_half) return fail(GRANNE_HIP_ERR_INVALID, "rw_builder_create has no form for GRANNE_HIP_F16 (angular_f16) rows: use f32 or int8 rows");
     if (b->se)
         return fail(GRANNE_HIP_ERR_INVALID, "an RwGranneBuilder over a SumEmbeddings container is not supported: make the "
                     "builder from dense rows (granne_hip_builder_create)");

@@ -25,6 +25,7 @@
 #include "dist.h"
 #include "wave_prims.h"
 #include "sum_embeddings.h"
+#include "f16.h"
 
 namespace granne_hip {
 
@@ -109,6 +110,8 @@ struct SearchParams {
     uint32_t n_batches;
     uint32_t batch_nq;
     BatchIO batch[MAX_LAUNCH_BATCHES];
+    // An index of halves (f16.h): `elements` are its rows, row_stride bytes apart; row_bytes is that of the WIDENED row
+    // (4 dim padded to 16: the staged query, the stage slots), the halves' own is f16_row_bytes(dim).
     // A compact SumEmbeddings index (sum_embeddings.h) keeps no dense rows: `elements` is null and an element's vector
     // is made from these where a walker needs it. The table's rows are row_bytes apart. Null for dense indexes.
     const float* se_table;      // [V][row_bytes / 4]
@@ -173,9 +176,15 @@ __device__ __forceinline__ void hand_over(const SearchParams& p, uint32_t qi) {
     }
 }
 
-// SE: the walker of a compact SumEmbeddings index (f32, run-time dim): step 3 sums term rows instead of staging dense ones
-template <int DT, int DIM, int S, bool SE = false>
+// Where step 3 finds a candidate's vector (f32, run-time dim for the last two):
+//   PV_DENSE  the index's dense rows, staged as they are
+//   PV_SE     a compact SumEmbeddings index: the sum of the candidate's term rows (sum_embeddings.h)
+//   PV_F16    rows of halves (f16.h): widened into the stage
+// and the last two normalise the staged vector before the dot (se_finish_dist).
+constexpr int PV_DENSE = 0, PV_SE = 1, PV_F16 = 2;
+template <int DT, int DIM, int S, int PV = PV_DENSE>
 struct Walker {
+    static constexpr bool SE = PV == PV_SE;
     // ---- immutable per-launch state
     const SearchParams& p;
     uint32_t lane;
@@ -254,6 +263,40 @@ struct Walker {
                         const uint64_t b = readlane64(o0, c), e = readlane64(o1, c);
                         se_sum_row(p.se_table, p.row_bytes >> 2, 0xFFFFFFFFu, p.se_terms + b, (uint32_t)(e - b), p.dim,
                                    reinterpret_cast<float*>(stage + (size_t)c * p.lrow_bytes), lane);
+                    }
+                    __syncthreads();
+                    if (lane >= g0 && lane < g0 + gm)
+                        d = se_finish_dist(reinterpret_cast<float*>(stage + (size_t)(lane - g0) * p.lrow_bytes),
+                                           reinterpret_cast<const float*>(lds_q), p.dim);
+                    __syncthreads();
+                    continue;
+                }
+                if constexpr (PV == PV_F16) {
+                    // the group's rows of halves, 16 bytes (8 components) per lane and step, four steps in flight; a row's
+                    // zero padding widens to zeros inside the slot's own padding (lrow_bytes >= row_bytes = 4 dim padded to 16)
+                    const uint32_t hrow16 = f16_row_bytes(p.dim) >> 4;
+                    const uint32_t htotal = gm * hrow16;
+                    for (uint32_t f0 = 0; f0 < htotal; f0 += 64u * 4u) {
+                        uint4 v[4];
+                        uint32_t dst[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const uint32_t f = f0 + (uint32_t)u * 64u + lane;
+                            const uint32_t fc = f < htotal ? f : htotal - 1u; // clamp: the load itself is unconditional
+                            const uint32_t row = fc / hrow16, part = fc - row * hrow16;
+                            v[u] = *reinterpret_cast<const uint4*>(p.elements + (size_t)cand[g0 + row] * p.row_stride + (size_t)part * 16u);
+                            dst[u] = f < htotal ? row * p.lrow_bytes + part * 32u : 0xFFFFFFFFu;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            if (dst[u] == 0xFFFFFFFFu) continue;
+                            float lo[4], hi[4];
+                            f16_widen4(make_uint2(v[u].x, v[u].y), lo);
+                            f16_widen4(make_uint2(v[u].z, v[u].w), hi);
+                            const uint32_t in_row = dst[u] % p.lrow_bytes;
+                            *reinterpret_cast<float4*>(stage + dst[u]) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+                            if (in_row + 32u <= p.row_bytes) *reinterpret_cast<float4*>(stage + dst[u] + 16u) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+                        }
                     }
                     __syncthreads();
                     if (lane >= g0 && lane < g0 + gm)
@@ -555,7 +598,7 @@ struct Walker {
     }
 };
 
-template <int DT, int DIM, int S, bool TRAIL, bool SE = false>
+template <int DT, int DIM, int S, bool TRAIL, int PV = PV_DENSE>
 __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t qi, uint8_t* smem) {
     const uint32_t lane = threadIdx.x;
     if (p.force_slow) {
@@ -563,7 +606,7 @@ __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t q
         return;
     }
 
-    Walker<DT, DIM, S, SE> w(p, smem);
+    Walker<DT, DIM, S, PV> w(p, smem);
     w.load_query(qi);
 
     if constexpr (TRAIL) { // find_entrypoint_trail: `ep` reads the still-zero eps[i], every walk starts at node 0

@@ -246,6 +246,7 @@ extern "C" int granne_hip_sharded_create_grouped(granne_hip_sharded** out, grann
     if (n_shards == 0 || n_shards > 64) return fail(GRANNE_HIP_ERR_INVALID, "n_shards must be in [1, 64]");
     for (uint32_t s = 0; s < n_shards; ++s) {
         if (!shards[s]) return fail(GRANNE_HIP_ERR_INVALID, "shard %u is null", s);
+        GRANNE_HIP_F16_UNSUPPORTED(shards[s]->dtype, "sharded_create");
         if (shards[s]->dim != shards[0]->dim || shards[s]->dtype != shards[0]->dtype)
             return fail(GRANNE_HIP_ERR_INVALID, "shard %u has another element type than shard 0", s);
         if (groups)
@@ -337,6 +338,7 @@ extern "C" int granne_hip_sharded_build(granne_hip_sharded** out, const granne_h
     if (!config || !device_ids) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
     if (n_shards == 0 || n_shards > 64) return fail(GRANNE_HIP_ERR_INVALID, "n_shards must be in [1, 64]");
     if (n_devices == 0 || n_devices > n_shards) return fail(GRANNE_HIP_ERR_INVALID, "n_devices must be in [1, n_shards]");
+    GRANNE_HIP_F16_UNSUPPORTED(dtype, "sharded_build");
     if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return fail(GRANNE_HIP_ERR_INVALID, "unknown dtype %d", dtype);
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n_elements && !elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");

@@ -44,7 +44,7 @@ struct SlowParams {
     uint32_t* status2; // caller's u32[2] (optional): [0] = 1 when a walk exhausts `slots`, [1] += queries that took this path
     uint32_t* host_status; // optional u32[2] in host-mapped memory, written with PLAIN stores (no PCIe atomics):
                            // [0] = 1 when a walk exhausts `slots`, [1] = queries that took this path
-    float* se_x;           // compact SumEmbeddings indexes: [blocks][64][dim] floats, a lane's vector in the making; else null
+    float* se_x;           // compact SumEmbeddings indexes and indexes of halves: [blocks][64][dim] floats, a lane's vector in the making; else null
 };
 
 // binary heaps over u64 keys, run by one lane
@@ -96,9 +96,12 @@ __device__ inline void gheap_replace_max(uint64_t* h, uint32_t n, uint64_t k) { 
     h[i] = k;
 }
 
-template <int DT, bool SE = false>
+template <int DT, int PV = PV_DENSE>
 __device__ inline float slow_dist(const SearchParams& p, const uint8_t* lds_q, uint32_t id, int dy, float* se_x = nullptr) {
-    if constexpr (SE) { // get(idx).dist(q) from the term lists (sum_embeddings.h); se_x: this lane's dim floats
+    if constexpr (PV == PV_F16) // get(idx).dist(q) of a row of halves (f16.h); se_x: this lane's dim floats
+        return f16_dist_lane(reinterpret_cast<const uint16_t*>(p.elements + (size_t)id * p.row_stride), se_x,
+                             reinterpret_cast<const float*>(lds_q), p.dim);
+    if constexpr (PV == PV_SE) { // get(idx).dist(q) from the term lists (sum_embeddings.h); se_x: this lane's dim floats
         const SeView se{p.se_table, p.se_offsets, p.se_terms, p.row_bytes >> 2, 0xFFFFFFFFu};
         return se_dist_scalar(se, id, reinterpret_cast<const float*>(lds_q), p.dim, se_x);
     }
@@ -120,7 +123,7 @@ __device__ inline float slow_dist(const SearchParams& p, const uint8_t* lds_q, u
 }
 
 // Block `me` of `n_blocks` walks entries me, me + n_blocks, ... of the hand-over list (or of 0..nq-1 when P.all).
-template <int DT, bool SE = false>
+template <int DT, int PV = PV_DENSE>
 __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, const uint32_t n_blocks,
                                       const uint32_t n_slow, uint8_t* smem) {
     const SearchParams& p = P.sp;
@@ -131,7 +134,7 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
     uint32_t* vis = P.vis + (size_t)me * P.slots;
     uint64_t* pq = P.pq + (size_t)me * P.slots;
     uint64_t* res = P.res + (size_t)me * p.ef;
-    float* se_x = SE ? P.se_x + ((size_t)me * 64u + lane) * p.dim : nullptr;
+    float* se_x = PV != PV_DENSE ? P.se_x + ((size_t)me * 64u + lane) * p.dim : nullptr;
     if (me == 0 && threadIdx.x == 0 && P.status2 && n_slow) atomicAdd(P.status2 + 1, n_slow);
     if (me == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = n_slow;
 
@@ -182,7 +185,7 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
             n_res = 0;
             if (lane == 0) {
                 vis[VisitedSet::hash(entrypoint) & mask] = entrypoint;
-                float d0 = slow_dist<DT, SE>(p, lds_q, entrypoint, dy, se_x);
+                float d0 = slow_dist<DT, PV>(p, lds_q, entrypoint, dy, se_x);
                 gheap_push_min(pq, n_pq, make_key(d0, entrypoint));
             }
             n_dist += 1;
@@ -238,7 +241,7 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
                     n_vis += m;
                     n_dist += m;
                     float d = 0.0f;
-                    if (fresh) d = slow_dist<DT, SE>(p, lds_q, nb, dy, se_x);
+                    if (fresh) d = slow_dist<DT, PV>(p, lds_q, nb, dy, se_x);
                     bool pass = fresh && (!full || d < worst);
                     uint64_t pm = wave_ballot(pass);
                     uint32_t np = (uint32_t)__popcll(pm);
@@ -351,7 +354,7 @@ __device__ __forceinline__ void walker_done(const SlowParams& P) {
 }
 
 // blocks nq.. of a walker launch
-template <int DT, bool SE = false>
+template <int DT, int PV = PV_DENSE>
 __device__ inline void tail_block(const SlowParams& P, uint8_t* smem) {
     const uint32_t nq = P.sp.nq;
     const uint32_t me = blockIdx.x - nq, n_blocks = gridDim.x - nq;
@@ -361,30 +364,30 @@ __device__ inline void tail_block(const SlowParams& P, uint8_t* smem) {
     }
     __syncthreads();
     const uint32_t n_slow = __hip_atomic_load(P.ctl + CTL_SLOW_COUNT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_slow) slow_walk_list<DT, SE>(P, me, n_blocks, n_slow, smem);
+    if (n_slow) slow_walk_list<DT, PV>(P, me, n_blocks, n_slow, smem);
     else if (me == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = 0u;
     slow_epilogue(P, n_blocks, n_slow);
 }
 
 // every query of the launch on the exact walker (max_search beyond the register walkers, GRANNE_HIP_OPT_FORCE_SLOW)
-template <int DT, bool SE = false>
+template <int DT, int PV = PV_DENSE>
 __global__ __launch_bounds__(64) void slow_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
-    slow_walk_list<DT, SE>(P, blockIdx.x, gridDim.x, P.sp.nq, smem);
+    slow_walk_list<DT, PV>(P, blockIdx.x, gridDim.x, P.sp.nq, smem);
     slow_epilogue(P, gridDim.x, P.sp.nq);
 }
 
 // The general walker's launch (search_kernel.h): block b < nq walks query b; the blocks after them are the tail.
 // TRAIL = true is the variant Granne::reorder launches (SearchParams::trail_out): a kernel of its own,
 // so that the search kernel carries one copy of the walker and nothing else.
-template <int DT, int DIM, int S, bool TRAIL = false, bool SE = false>
+template <int DT, int DIM, int S, bool TRAIL = false, int PV = PV_DENSE>
 __global__ __launch_bounds__(64) void search_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
     if (blockIdx.x < P.sp.nq) {
-        walk_one<DT, DIM, S, TRAIL, SE>(P.sp, blockIdx.x, smem);
+        walk_one<DT, DIM, S, TRAIL, PV>(P.sp, blockIdx.x, smem);
         walker_done(P);
     } else {
-        tail_block<DT, SE>(P, smem);
+        tail_block<DT, PV>(P, smem);
     }
 }
 

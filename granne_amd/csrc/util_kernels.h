@@ -3,6 +3,7 @@
 #pragma once
 
 #include "dist.h"
+#include "ordered_sum.h"
 #include "search_kernel.h"
 
 namespace granne_hip {
@@ -248,13 +249,7 @@ __global__ void quantize_rows_kernel(const float* __restrict__ rows, int8_t* __r
 // fetches eight rows with fully used 128-byte lines -- the same lane layout as the walk's
 // fast_rows. f32 keeps the reference's association: lane `sub` owns accumulators 4*sub..4*sub+3
 // of the 32, the ordered sum runs down the eight lanes, the tail is folded by sequential fmas.
-__device__ __forceinline__ float lane_shr1(float v) { // value of lane-1 (within a 16-lane row)
-#if GRANNE_HIP_USE_DPP
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111 /* row_shr:1 */, 0xf, 0xf, false));
-#else
-    return __shfl_up(v, 1, 64);
-#endif
-}
+// (lane_shr1 and the ordered sum down the eight lanes: ordered_sum.h)
 
 template <int DT>
 __global__ __launch_bounds__(256) void dists_kernel(const uint8_t* __restrict__ elements, uint64_t n_elements,
@@ -293,20 +288,18 @@ __global__ __launch_bounds__(256) void dists_kernel(const uint8_t* __restrict__ 
             uint4 vt = make_uint4(0, 0, 0, 0); // the (zero padded) tail block
             if (nfull * 128u + sub * 16u + 16u <= row_bytes)
                 vt = *reinterpret_cast<const uint4*>(row + (size_t)nfull * 128u + sub * 16u);
-            float r = 0.0f; // ordered sum acc[0] .. acc[31]: lane s is right after step s
-#pragma unroll
-            for (int ps = 0; ps < 8; ++ps) {
-                float u = (ps == 0) ? 0.0f : lane_shr1(r);
-                u = u + a0; u = u + a1; u = u + a2; u = u + a3;
-                r = u;
-            }
-            r = __shfl(r, (int)(lane | 7u), 64);
+            float r = ordered_sum8(a0, a1, a2, a3, lane); // acc[0] .. acc[31] in order
             for (uint32_t k = 0; k < tail; ++k) { // src/math.rs:47-49
                 const uint32_t w = (k & 3u) == 0 ? vt.x : (k & 3u) == 1 ? vt.y : (k & 3u) == 2 ? vt.z : vt.w;
                 const float xv = __uint_as_float((uint32_t)__shfl((int)w, (int)((lane & ~7u) + (k >> 2)), 64));
                 r = __builtin_fmaf(xv, q[nfull * 32u + k], r);
             }
             d = angular_from_dot(r);
+        } else if constexpr (DT == DT_F16) { // rows of halves, f32 queries (f16.h)
+            const uint8_t* one[1] = {row};
+            float d1[1];
+            f16_dist_group<1>(one, reinterpret_cast<const float*>(queries) + qi * dim, dim, row_bytes, lane, d1);
+            d = d1[0];
         } else {
             const int8_t* q = reinterpret_cast<const int8_t*>(queries) + qi * dim;
             int r = 0, dx = 0, dy = 0;

@@ -5,13 +5,21 @@ import os
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import ERR_INVALID, GranneHipError, check, lib
 
 SE_MATERIALIZED, SE_COMPACT = 0, 1
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _f32_table(embeddings):
+    """The table as float32 rows. A table of halves is refused: the container's sums are f32 chains over f32 rows
+    (create_embedding), and "angular_f16" is a dense element type, not a table format."""
+    if getattr(embeddings, "dtype", None) == np.float16:
+        raise GranneHipError(ERR_INVALID, "a SumEmbeddings table has no form for GRANNE_HIP_F16 (angular_f16) rows: pass float32 embeddings")
+    return np.ascontiguousarray(embeddings, dtype=np.float32)
 
 
 def csr_of(term_lists):
@@ -31,7 +39,7 @@ class SumEmbeddings:
 
     def __init__(self, embeddings, elements=(), device=0, offsets=None, terms=None):
         """elements: a sequence of term-id sequences -- or pass the CSR form (offsets [n + 1], terms) directly."""
-        tab = np.ascontiguousarray(embeddings, dtype=np.float32)
+        tab = _f32_table(embeddings)
         if tab.ndim != 2 or tab.shape[1] == 0:
             raise ValueError("embeddings must be [V, dim]")
         if offsets is None:
@@ -57,7 +65,7 @@ class SumEmbeddings:
     def from_bytes(cls, embeddings, elements_bytes, device=0):
         """SumEmbeddings::from_bytes: a table and the bytes of an elements file."""
         self = cls.__new__(cls)
-        tab = np.ascontiguousarray(embeddings, dtype=np.float32)
+        tab = _f32_table(embeddings)
         buf = np.frombuffer(elements_bytes, np.uint8)
         h = C.c_void_p()
         check(lib().granne_hip_sum_embeddings_load(C.byref(h), _p(tab), tab.shape[0], tab.shape[1], _p(buf), buf.size, device))

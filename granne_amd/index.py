@@ -12,12 +12,14 @@ import os
 
 import numpy as np
 
-from ._lib import F32, I8, check, lib
+from ._lib import F16, F32, I8, check, lib
 
 DEFAULT_MAX_SEARCH = 200   # py/src/lib.rs:14
 DEFAULT_NUM_ELEMENTS = 10  # py/src/lib.rs:15
 
-_ELEMENT_TYPES = {"angular": (F32, np.float32), "angular_int": (I8, np.int8)}
+# "angular_f16": rows of IEEE halves; the element a row stands for is Vector::from(widen(row)) -- normalised where it is
+# read -- and queries are prepared float32 rows, as for "angular"
+_ELEMENT_TYPES = {"angular": (F32, np.float32), "angular_int": (I8, np.int8), "angular_f16": (F16, np.float16)}
 EMBEDDINGS = "embeddings"  # embeddings::SumEmbeddings: `elements` is a granne_amd.SumEmbeddings, vectors are f32
 
 
@@ -44,6 +46,37 @@ def quantize(rows, device=0):
     return out.reshape(a.shape)
 
 
+def to_f16(rows, prepared=True, device=0):
+    """float32 rows -> the halves of an "angular_f16" container, rounded to nearest even on the device (the bits of
+    astype(float16)). prepared=False normalises in float32 first (Vector::from), then rounds."""
+    a = np.ascontiguousarray(rows, dtype=np.float32) if prepared else normalize(rows, device)
+    flat = a.reshape(1, -1) if a.ndim == 1 else a
+    out = np.empty(flat.shape, np.float16)
+    if flat.size:
+        check(lib().granne_hip_f32_to_f16(_p(flat), _p(out), flat.shape[0], flat.shape[1], device))
+    return out.reshape(a.shape)
+
+
+def from_f16(rows16, normalized=True, device=0):
+    """The float32 rows the halves stand for: widened exactly and (normalized=True) passed through Vector::from -- what
+    an "angular_f16" index computes its distances with."""
+    a = np.ascontiguousarray(rows16, dtype=np.float16)
+    flat = a.reshape(1, -1) if a.ndim == 1 else a
+    out = np.empty(flat.shape, np.float32)
+    if flat.size:
+        check(lib().granne_hip_f16_to_f32(_p(flat), _p(out), flat.shape[0], flat.shape[1], int(bool(normalized)), device))
+    return out.reshape(a.shape)
+
+
+def _prepare_elements(et, elements, device):
+    """Vector::from for raw float rows of a dense element type."""
+    if et == "angular":
+        return normalize(elements, device)
+    if et == "angular_f16":
+        return to_f16(elements, prepared=False, device=device)
+    return quantize(elements, device)
+
+
 def _is_term_lists(x):
     """A batch of queries for an "embeddings" index: sequences of term ids (True) or float rows (False)."""
     if isinstance(x, np.ndarray):
@@ -59,7 +92,7 @@ class Granne:
     """An HNSW index resident in the HBM of one MI355X."""
 
     def __init__(self, element_type, elements, layers, device=0, prepared=True, compact=False, coalesce=False):
-        """element_type: "angular" (f32), "angular_int" (int8) or "embeddings" (`elements` is a SumEmbeddings; with
+        """element_type: "angular" (f32), "angular_int" (int8), "angular_f16" (halves, searched with f32 queries) or "embeddings" (`elements` is a SumEmbeddings; with
         compact=True the index keeps the container instead of dense rows and makes vectors as it walks).
         coalesce=True: concurrent `search` calls of host threads share launches (the `coalesce` property).
         elements: [n, dim] array. With prepared=True (default) rows are taken as stored in a
@@ -79,7 +112,7 @@ class Granne:
         self.dtype_code, self.np_dtype = _ELEMENT_TYPES[et]
         self.device = device
         if not prepared:
-            elements = normalize(elements, device) if et == "angular" else quantize(elements, device)
+            elements = _prepare_elements(et, elements, device)
         el = np.ascontiguousarray(elements, dtype=self.np_dtype)
         if el.ndim != 2:
             raise ValueError("elements must be [n, dim]")
@@ -234,6 +267,11 @@ class Granne:
         except Exception:
             pass
 
+    @property
+    def query_dtype(self):
+        """numpy dtype of a prepared query: the elements', except that rows of halves take float32 queries."""
+        return np.float32 if self.dtype_code == F16 else self.np_dtype
+
     # ---- Index trait (src/index/mod.rs:54-71) --------------------------------------------------
     def __len__(self):
         return int(lib().granne_hip_index_len(self._h))
@@ -322,8 +360,8 @@ class Granne:
                 return self._se.create_embeddings(element, normalized=True)
             return np.ascontiguousarray(element, np.float32) if prepared else normalize(element, self.device)
         if prepared:
-            return np.ascontiguousarray(element, dtype=self.np_dtype)
-        return normalize(element, self.device) if self.element_type == "angular" else quantize(element, self.device)
+            return np.ascontiguousarray(element, dtype=self.query_dtype)
+        return quantize(element, self.device) if self.element_type == "angular_int" else normalize(element, self.device)
 
     def search(self, element, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS, prepared=True):
         """Granne.search (py/src/lib.rs:227-233): [(id, distance)] ascending by (distance, id).
@@ -468,7 +506,7 @@ class Granne:
         """ElementContainer::dists for a batch: queries [nq, dim] (prepared), ids [nq, m] -> [nq, m] f32
         (+inf where an id is out of range)."""
         import torch
-        q = np.ascontiguousarray(queries, dtype=self.np_dtype)
+        q = np.ascontiguousarray(queries, dtype=self.query_dtype)
         ii = np.ascontiguousarray(ids, dtype=np.uint32)
         if q.ndim != 2 or q.shape[1] != self.dim or ii.ndim != 2 or ii.shape[0] != q.shape[0]:
             raise ValueError("queries must be [nq, %d] and ids [nq, m]" % self.dim)
@@ -484,7 +522,7 @@ class Granne:
 
     def dists(self, queries, qidx, ids):
         """ElementContainer::dist_to_element for explicit (query, element) pairs."""
-        q = np.ascontiguousarray(queries, dtype=self.np_dtype)
+        q = np.ascontiguousarray(queries, dtype=self.query_dtype)
         qi = np.ascontiguousarray(qidx, dtype=np.uint32)
         ii = np.ascontiguousarray(ids, dtype=np.uint32)
         out = np.empty(qi.size, np.float32)
@@ -502,8 +540,8 @@ def compute_distance(element_type, a, b, device=0):
     et = element_type.lower()
     if et not in _ELEMENT_TYPES:
         raise ValueError("Unsupported element type")
-    prep = normalize if et == "angular" else quantize
-    pa = prep(np.asarray(a, np.float32), device).reshape(1, -1)
+    prep = quantize if et == "angular_int" else normalize
+    pa = _prepare_elements(et, np.asarray(a, np.float32), device).reshape(1, -1)
     pb = prep(np.asarray(b, np.float32), device).reshape(1, -1)
     ix = Granne(et, pa, [], device=device)
     try:

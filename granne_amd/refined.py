@@ -1,7 +1,8 @@
 """Refined search: walk one index, re-rank the walk's candidates by another index's rows.
 
 `RefinedGranne(walk, refine)` pairs two `Granne` handles over the SAME elements under the same ids -- typically int8 rows
-with their graph (a quarter of the bytes per walk) and the f32 rows, which need no graph (`layers=[]`). A search walks
+with their graph (a quarter of the bytes per walk) and the f32 rows -- or their "angular_f16" copy, half the bytes to keep
+and to read -- which need no graph (`layers=[]`). A search walks
 `walk` with num_neighbors = refine_from, gives every candidate its distance under `refine`'s own arithmetic and returns
 the k best by (distance, id): f32 distances and f32 order for about a tenth more traffic than the int8 walk
 (granne_hip_search_refined_batch*, include/granne_hip.h)."""
@@ -29,7 +30,7 @@ class RefinedGranne:
         normalised, and for an int8 index the normalised rows are then quantised, on the device."""
         if prepared:
             qw, qr = elements
-            return (np.ascontiguousarray(qw, dtype=self.walk.np_dtype), np.ascontiguousarray(qr, dtype=self.refine.np_dtype))
+            return (np.ascontiguousarray(qw, dtype=self.walk.query_dtype), np.ascontiguousarray(qr, dtype=self.refine.query_dtype))
         raw = elements if isinstance(elements, (tuple, list)) and len(elements) == 2 and np.ndim(elements[0]) == 2 else (elements, elements)
         out = []
         for ix, rows in zip((self.walk, self.refine), raw):
@@ -37,7 +38,7 @@ class RefinedGranne:
                 out.append(ix._prepare(rows, False))
                 continue
             rows = normalize(np.atleast_2d(np.asarray(rows, np.float32)), self.device)
-            out.append(rows if ix.np_dtype == np.float32 else quantize(rows, self.device))
+            out.append(rows if ix.query_dtype == np.float32 else quantize(rows, self.device))
         return tuple(out)
 
     def search_batch(self, elements, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS, refine_from=None,

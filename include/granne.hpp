@@ -23,6 +23,8 @@
 #include <utility>
 #include <vector>
 
+#include <type_traits>
+
 #include "granne_hip.h"
 
 namespace granne {
@@ -30,6 +32,12 @@ namespace granne {
 inline void check(int rc) {
     if (rc != GRANNE_HIP_OK) throw std::runtime_error(std::string("granne_hip: ") + granne_hip_last_error());
 }
+
+// One IEEE binary16 value of an "angular_f16" element set (GRANNE_HIP_F16): its bits. The element a row of them stands for
+// is angular::Vector::from(widen(row)), normalised where it is read.
+struct f16 {
+    uint16_t bits;
+};
 
 namespace detail {
 // a GranneBuilder's handle, until an RwGranneBuilder takes it over
@@ -40,6 +48,7 @@ struct BuilderDeleter {
 template <class Scalar> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = GRANNE_HIP_F32; };
 template <> struct dtype_of<int8_t> { static constexpr int value = GRANNE_HIP_I8; };
+template <> struct dtype_of<f16> { static constexpr int value = GRANNE_HIP_F16; };
 
 // dense_vector! (src/elements/dense_vector.rs): Vector = one row, Vectors = row-major collection
 template <class Scalar>
@@ -99,6 +108,26 @@ inline Vector from(const std::vector<float>& v, int device = 0) {
 }
 } // namespace angular_int
 
+// Rows of halves: the conversions. There is deliberately no angular_f16::Vectors: the class templates below take their
+// queries in the element type of their Elements, and the queries of an F16 index are prepared f32 rows (angular::Vector),
+// so Granne / GranneBuilder / RefinedGranne / ShardedGranne over f16 elements are rejected at compile time. An F16 index is
+// made and searched through the C entry points with detail::dtype_of<f16>::value (GRANNE_HIP_F16) and f32 queries.
+namespace angular_f16 {
+// f32 rows [n][dim] -> halves, rounded to nearest even, on the device
+inline std::vector<f16> to_f16(const std::vector<float>& rows, size_t dim, int device = 0) {
+    std::vector<f16> out(rows.size());
+    if (!rows.empty()) check(granne_hip_f32_to_f16(rows.data(), reinterpret_cast<uint16_t*>(out.data()), rows.size() / dim, (uint32_t)dim, device));
+    return out;
+}
+// halves -> the f32 rows they stand for: widened exactly, then (normalised) angular::Vector::from per row
+inline std::vector<float> from_f16(const std::vector<f16>& rows, size_t dim, bool normalised = true, int device = 0) {
+    std::vector<float> out(rows.size());
+    if (!rows.empty())
+        check(granne_hip_f16_to_f32(reinterpret_cast<const uint16_t*>(rows.data()), out.data(), rows.size() / dim, (uint32_t)dim, normalised ? 1 : 0, device));
+    return out;
+}
+} // namespace angular_f16
+
 // BuildConfig (src/index/mod.rs:198-291)
 class BuildConfig {
 public:
@@ -121,6 +150,8 @@ template <class Elements>
 class Granne {
 public:
     using Element = typename Elements::Element;
+    static_assert(!std::is_same<typename decltype(Element::data)::value_type, f16>::value,
+                  "an index over f16 rows takes f32 queries: use the C entry points with GRANNE_HIP_F16");
     explicit Granne(granne_hip_index* h) : h_(h, granne_hip_index_destroy) {}
 
     // Granne::from_file (mod.rs:122-135) over Vectors::from_file
@@ -362,6 +393,8 @@ private:
 template <class Elements>
 class GranneBuilder {
 public:
+    static_assert(!std::is_same<typename decltype(Elements::Element::data)::value_type, f16>::value,
+                  "a builder over f16 rows hands out an index that takes f32 queries: use the C entry points with GRANNE_HIP_F16");
     GranneBuilder(const BuildConfig& config, const Elements& elements, int device = 0) {
         granne_hip_builder* b = nullptr;
         using Scalar = typename decltype(Elements::Element::data)::value_type;

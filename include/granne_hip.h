@@ -36,7 +36,16 @@ extern "C" {
 /* element scalar types: granne::angular::Vectors (f32, rows normalised) and
  * granne::angular_int::Vectors (i8, rows quantised) -- src/elements/angular.rs:53,
  * src/elements/angular_int.rs:17 */
-enum { GRANNE_HIP_F32 = 0, GRANNE_HIP_I8 = 1 };
+enum { GRANNE_HIP_F32 = 0, GRANNE_HIP_I8 = 1, GRANNE_HIP_F16 = 2 };
+/* GRANNE_HIP_F16 ("angular_f16") has no counterpart among the reference's containers; it is defined the way the reference
+ * defines embeddings::SumEmbeddings (src/elements/embeddings/mod.rs:164-166): an element is dim IEEE binary16 values,
+ * get(i) = angular::Vector::from(widen(row_i)) -- the halves widened exactly to f32, then normalised as src/math.rs:123-150
+ * does it -- and dist_to_element(i, q) = get(i).dist(q). Queries are ordinary prepared f32 rows ([nq][dim] f32), so every
+ * result of an F16 index equals that of the f32 index over R = normalize(widen(rows)): ids, distance bits, order. Searches
+ * run on the general walker (max_search <= 256) and the exact walker; dists*, dist_pairs*, refine* (as the refine index,
+ * n_layers == 0 is enough), the builder, get_element (the stored halves) and the files (2-byte scalars) work.
+ * brute_force*, reorder*, rw_builder_create, sharded_create*, sharded_build and builder_append return GRANNE_HIP_ERR_INVALID. Device rows are
+ * padded to 16 bytes, and rows of 128 bytes and more start on a 128-byte line (100-d: 256 bytes, two lines). */
 
 enum {
     GRANNE_HIP_OK = 0,
@@ -262,6 +271,14 @@ int granne_hip_normalize_f32_device(float* d_rows, uint64_t n, uint32_t dim, int
 /* angular_int::Vector::quantize over n rows (src/elements/angular_int.rs:27-45). */
 int granne_hip_quantize_f32_device(const float* d_rows, int8_t* d_out, uint64_t n, uint32_t dim,
                                    int device_id, void* stream);
+/* The conversions of GRANNE_HIP_F16 elements, dense rows [n][dim] on both sides. f32 -> halves rounds to nearest, ties to
+ * even (the bits of numpy's astype(float16)); halves -> f32 is exact and, with normalised != 0, followed by
+ * angular::Vector::from (src/math.rs:123-150) per row: the rows an F16 index stands for. Device pointers. A row is staged
+ * whole in LDS (as granne_hip_normalize_f32_device stages it): dim <= 15,359, beyond that GRANNE_HIP_ERR_INVALID -- which
+ * is therefore also the largest dim of an F16 builder; index creation and search have no such limit. */
+int granne_hip_f32_to_f16_device(const float* d_rows, uint16_t* d_out, uint64_t n, uint32_t dim, int device_id, void* stream);
+int granne_hip_f16_to_f32_device(const uint16_t* d_rows16, float* d_out, uint64_t n, uint32_t dim, int normalised,
+                                 int device_id, void* stream);
 /* ElementContainer::dist_to_element for explicit (query, element id) pairs
  * (src/elements/dense_vector.rs:149-151): d_out[i] = dist(elements[d_ids[i]], queries[d_qidx[i]]). */
 int granne_hip_dist_pairs_device(const granne_hip_index* index, const void* d_queries,
@@ -280,6 +297,8 @@ int granne_hip_normalize_f32(float* rows, uint64_t n, uint32_t dim, int device_i
 int granne_hip_quantize_f32(const float* rows, int8_t* out, uint64_t n, uint32_t dim, int device_id);
 int granne_hip_dist_pairs(const granne_hip_index* index, const void* queries, uint32_t nq,
                           const uint32_t* qidx, const uint32_t* ids, uint64_t n_pairs, float* out);
+int granne_hip_f32_to_f16(const float* rows, uint16_t* out, uint64_t n, uint32_t dim, int device_id);
+int granne_hip_f16_to_f32(const uint16_t* rows16, float* out, uint64_t n, uint32_t dim, int normalised, int device_id);
 
 /* Synthetic element rows: component (row, col) = uniform [-0.5, 0.5) from a
  * splitmix64 counter, the distribution of src/test_helper.rs:3-6. Device pointer out [n][dim]. */

@@ -12,6 +12,8 @@ use std::os::raw::{c_char, c_int, c_void};
 
 pub const GRANNE_HIP_F32: c_int = 0;
 pub const GRANNE_HIP_I8: c_int = 1;
+/// rows of IEEE halves, normalised where they are read ("angular_f16"); queries are prepared f32 rows
+pub const GRANNE_HIP_F16: c_int = 2;
 pub const GRANNE_HIP_BUILD_ALL: u64 = u64::MAX;
 
 /// `granne_hip_build_config` (include/granne_hip.h) = `BuildConfig` (src/index/mod.rs:198-231)
@@ -206,6 +208,14 @@ extern "C" {
     // ---- Vector::from for whole arrays (src/elements/angular.rs:55-61, angular_int.rs:27-45), host buffers
     fn granne_hip_normalize_f32(rows: *mut f32, n: u64, dim: u32, device_id: c_int) -> c_int;
     fn granne_hip_quantize_f32(rows: *const f32, out: *mut i8, n: u64, dim: u32, device_id: c_int) -> c_int;
+    // ---- GRANNE_HIP_F16 rows: f32 -> halves (round to nearest even), halves -> f32 (exact, optionally Vector::from)
+    fn granne_hip_f32_to_f16(rows: *const f32, out: *mut u16, n: u64, dim: u32, device_id: c_int) -> c_int;
+    fn granne_hip_f16_to_f32(rows16: *const u16, out: *mut f32, n: u64, dim: u32, normalised: c_int,
+        device_id: c_int) -> c_int;
+    fn granne_hip_f32_to_f16_device(d_rows: *const f32, d_out: *mut u16, n: u64, dim: u32, device_id: c_int,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_f16_to_f32_device(d_rows16: *const u16, d_out: *mut f32, n: u64, dim: u32, normalised: c_int,
+        device_id: c_int, stream: *mut c_void) -> c_int;
     // ---- granne's files without an index handle (src/index/io.rs:11-113, src/slice_vector/mod.rs:460-466)
     fn granne_hip_write_index_file(path: *const c_char, n_layers: u32, layer_len: *const u64,
         layer_rows: *const *const u32, layer_width: *const u32) -> c_int;
@@ -327,6 +337,29 @@ macro_rules! gpu_elements {
 }
 gpu_elements!(angular, f32, GRANNE_HIP_F32);
 gpu_elements!(angular_int, i8, GRANNE_HIP_I8);
+
+/// Marker for "angular_f16" element sets: `dim` IEEE binary16 values per element (their bits as `u16`), the element
+/// they stand for being `angular::Vector::from(widen(row))`. The reference has no such container, so there is no
+/// `Vectors` type to implement `GpuElements` for: `rows_to_f16` / `rows_from_f16` convert on the device, and an F16
+/// index is made through the C entry points with `AngularF16::DTYPE`; its queries are `angular::Vector`s.
+pub struct AngularF16;
+impl AngularF16 {
+    pub const DTYPE: c_int = GRANNE_HIP_F16;
+    /// f32 rows ([n][dim], dense) -> halves, rounded to nearest even
+    pub fn rows_to_f16(rows: &[f32], dim: usize, device: i32) -> std::io::Result<Vec<u16>> {
+        let n = if dim == 0 { 0 } else { rows.len() / dim };
+        let mut out = vec![0u16; n * dim];
+        check(unsafe { granne_hip_f32_to_f16(rows.as_ptr(), out.as_mut_ptr(), n as u64, dim as u32, device as c_int) })?;
+        Ok(out)
+    }
+    /// halves -> the f32 rows they stand for (widened exactly; `normalised`: then `Vector::from`)
+    pub fn rows_from_f16(rows16: &[u16], dim: usize, normalised: bool, device: i32) -> std::io::Result<Vec<f32>> {
+        let n = if dim == 0 { 0 } else { rows16.len() / dim };
+        let mut out = vec![0f32; n * dim];
+        check(unsafe { granne_hip_f16_to_f32(rows16.as_ptr(), out.as_mut_ptr(), n as u64, dim as u32, normalised as c_int, device as c_int) })?;
+        Ok(out)
+    }
+}
 
 /// A `Granne` whose layers and elements live in the HBM of one MI355X.
 pub struct GpuGranne<E: GpuElements> { handle: *mut granne_hip_index, dim: usize, _e: PhantomData<E> }
