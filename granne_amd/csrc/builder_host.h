@@ -13,7 +13,7 @@
 struct BuilderLayer {
     uint64_t len = 0;      // rows in use
     uint64_t cap_rows = 0; // rows allocated
-    uint32_t* d_adj = nullptr;
+    DevBuf d_adj;          // uint32_t [cap_rows][W]
 };
 
 struct granne_hip_builder {
@@ -23,7 +23,7 @@ struct granne_hip_builder {
     int dtype = 0;
     uint64_t n_elements = 0;
     uint32_t row_bytes = 0, row_stride = 0; // data bytes of a device row; bytes from one row to the next
-    uint8_t* d_elements = nullptr;
+    DevBuf d_elements;
     uint32_t W = 32; // device row width
     std::vector<BuilderLayer> layers;
     uint64_t hbm_bytes = 0;
@@ -31,7 +31,7 @@ struct granne_hip_builder {
     std::shared_ptr<SeDev> se; // made by granne_hip_builder_create_sum_embeddings: the container d_elements was materialised from
     // made with GRANNE_HIP_F16: the halves as an index keeps them (half_stride bytes apart). d_elements holds the rows they
     // stand for -- normalize(widen(row)), f32 -- and the build is the f32 build over those; get_index hands out the halves.
-    uint8_t* d_half = nullptr;
+    DevBuf d_half;
     uint32_t half_bytes = 0, half_stride = 0;
 };
 
@@ -63,11 +63,6 @@ static uint64_t num_elements_in_layer(uint64_t total, float layer_multiplier, ui
 static void destroy_builder(granne_hip_builder* b) {
     if (!b) return;
     DeviceGuard g(b->device);
-    if (b->d_elements) (void)hipFree(b->d_elements);
-    if (b->d_half) (void)hipFree(b->d_half);
-    for (auto& L : b->layers)
-        if (L.d_adj) (void)hipFree(L.d_adj);
-    b->scratch.free_all();
     delete b;
 }
 
@@ -94,19 +89,17 @@ extern "C" int granne_hip_builder_create_device(granne_hip_builder** out, const 
     int rc = builder_validate(out, cfg, n_elements, dim, dtype);
     if (rc) return rc;
     if (n_elements && !d_elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     if (dtype == GRANNE_HIP_F16) {
         // rows of halves: R = normalize(widen(rows)) is made once, the f32 builder runs over R, and the halves are kept
         // in an index's layout for get_index. R lives as long as the builder.
         hipStream_t s = (hipStream_t)stream;
-        float* d_R = nullptr;
-        const size_t r_bytes = (size_t)n_elements * dim * 4;
-        HIP_TRY(hipMalloc((void**)&d_R, r_bytes ? r_bytes : 16));
-        rc = f16_rows_to_f32((const uint8_t*)d_elements, (uint64_t)dim * 2u, d_R, n_elements, dim, 1, s);
-        if (rc == 0) rc = granne_hip_builder_create_device(out, cfg, d_R, n_elements, dim, GRANNE_HIP_F32, device_id, stream); // synchronises
+        DevBuf d_R;
+        HIP_TRY(d_R.alloc((size_t)n_elements * dim * 4));
+        rc = f16_rows_to_f32((const uint8_t*)d_elements, (uint64_t)dim * 2u, d_R.as<float>(), n_elements, dim, 1, s);
+        if (rc == 0) rc = granne_hip_builder_create_device(out, cfg, d_R.get(), n_elements, dim, GRANNE_HIP_F32, device_id, stream); // synchronises
         else (void)hipStreamSynchronize(s);
-        (void)hipFree(d_R);
+        d_R.reset();
         if (rc) return rc;
         granne_hip_builder* b = *out;
         granne_hip_index tmp;
@@ -118,11 +111,10 @@ extern "C" int granne_hip_builder_create_device(granne_hip_builder** out, const 
         tmp.row_stride = device_row_stride(dim, GRANNE_HIP_F16);
         rc = upload_elements_from_device(&tmp, d_elements, s);
         if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "sync failed");
-        b->d_half = tmp.d_elements;
+        b->d_half = std::move(tmp.d_elements);
         b->half_bytes = tmp.row_bytes;
         b->half_stride = tmp.row_stride;
         b->hbm_bytes += tmp.hbm_bytes;
-        tmp.d_elements = nullptr;
         if (rc) {
             destroy_builder(b);
             *out = nullptr;
@@ -150,9 +142,8 @@ extern "C" int granne_hip_builder_create_device(granne_hip_builder** out, const 
     tmp.row_stride = b->row_stride;
     rc = upload_elements_from_device(&tmp, d_elements, (hipStream_t)stream);
     if (rc == 0 && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "sync failed");
-    b->d_elements = tmp.d_elements;
+    b->d_elements = std::move(tmp.d_elements);
     b->hbm_bytes = tmp.hbm_bytes;
-    tmp.d_elements = nullptr;
     if (rc) {
         destroy_builder(b);
         return rc;
@@ -167,19 +158,13 @@ extern "C" int granne_hip_builder_create(granne_hip_builder** out, const granne_
     int rc = builder_validate(out, cfg, n_elements, dim, dtype);
     if (rc) return rc;
     if (n_elements && !elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
-    void* d = nullptr;
+    GRANNE_HIP_ON_DEVICE(device_id);
+    DevBuf d;
     size_t bytes = (size_t)n_elements * dim * elem_size(dtype);
-    HIP_TRY(hipMalloc(&d, bytes ? bytes : 16));
-    hipError_t e = bytes ? hipMemcpy(d, elements, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(GRANNE_HIP_ERR_HIP, "element upload failed: %s", hipGetErrorString(e));
-    }
-    rc = granne_hip_builder_create_device(out, cfg, d, n_elements, dim, dtype, device_id, nullptr);
-    (void)hipFree(d);
-    return rc;
+    HIP_TRY(d.alloc(bytes));
+    hipError_t e = bytes ? hipMemcpy(d.get(), elements, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "element upload failed: %s", hipGetErrorString(e));
+    return granne_hip_builder_create_device(out, cfg, d.get(), n_elements, dim, dtype, device_id, nullptr);
 }
 
 // Builder::push for a batch of rows (src/index/mod.rs:303-315, dense_vector.rs push): the element
@@ -190,36 +175,24 @@ extern "C" int granne_hip_builder_append(granne_hip_builder* b, const void* elem
     if (!elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     if (b->n_elements + n_new >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many elements (src/index/mod.rs:420)");
     if (b->d_half) return fail(GRANNE_HIP_ERR_INVALID, "builder_append has no form for GRANNE_HIP_F16 (angular_f16) rows: make a new builder over all the rows");
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     const size_t dense = (size_t)b->dim * elem_size(b->dtype);
     const size_t old_bytes = (size_t)b->n_elements * b->row_stride, add_bytes = (size_t)n_new * b->row_stride;
-    uint8_t* grown = nullptr;
-    void* staged = nullptr;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&grown, old_bytes + add_bytes));
-        HIP_TRY(hipMalloc(&staged, n_new * dense));
-        HIP_TRY(hipMemcpy(staged, elements, n_new * dense, hipMemcpyHostToDevice));
-        if (old_bytes) HIP_TRY(hipMemcpyAsync(grown, b->d_elements, old_bytes, hipMemcpyDeviceToDevice, nullptr));
-        if (dense == b->row_stride) {
-            HIP_TRY(hipMemcpyAsync(grown + old_bytes, staged, add_bytes, hipMemcpyDeviceToDevice, nullptr));
-        } else {
-            const uint64_t units = n_new * (b->row_stride / 16);
-            hipLaunchKernelGGL(relayout_rows_kernel, dim3(grid_for(units, 256)), dim3(256), 0, nullptr,
-                               (const uint8_t*)staged, grown + old_bytes, n_new, (uint32_t)dense, b->row_stride);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        return GRANNE_HIP_OK;
-    };
-    int rc = body();
-    if (staged) (void)hipFree(staged);
-    if (rc) {
-        if (grown) (void)hipFree(grown);
-        return rc;
+    DevBuf grown, staged;
+    HIP_TRY(grown.alloc(old_bytes + add_bytes));
+    HIP_TRY(staged.alloc(n_new * dense));
+    HIP_TRY(hipMemcpy(staged.get(), elements, n_new * dense, hipMemcpyHostToDevice));
+    if (old_bytes) HIP_TRY(hipMemcpyAsync(grown.get(), b->d_elements.get(), old_bytes, hipMemcpyDeviceToDevice, nullptr));
+    if (dense == b->row_stride) {
+        HIP_TRY(hipMemcpyAsync(grown.as<uint8_t>() + old_bytes, staged.get(), add_bytes, hipMemcpyDeviceToDevice, nullptr));
+    } else {
+        const uint64_t units = n_new * (b->row_stride / 16);
+        hipLaunchKernelGGL(relayout_rows_kernel, dim3(grid_for(units, 256)), dim3(256), 0, nullptr,
+                           staged.as<uint8_t>(), grown.as<uint8_t>() + old_bytes, n_new, (uint32_t)dense, b->row_stride);
+        HIP_TRY(hipGetLastError());
     }
-    if (b->d_elements) (void)hipFree(b->d_elements);
-    b->d_elements = grown;
+    HIP_TRY(hipDeviceSynchronize());
+    b->d_elements = std::move(grown);
     b->n_elements += n_new;
     b->hbm_bytes += add_bytes;
     return GRANNE_HIP_OK;
@@ -256,19 +229,33 @@ static BuildKernels pick_build_kernels(int dtype, uint32_t dim) {
 }
 
 struct BuildScratch {
-    uint64_t *s_ids = nullptr, *op_keys = nullptr, *op_vals = nullptr, *sorted_keys = nullptr, *sorted_vals = nullptr;
-    float* s_dists = nullptr;
-    uint32_t *s_counts = nullptr, *seg_start = nullptr, *counters = nullptr; // counters: [0]=n_seg [1]=status [2]=slow count
-    void* sort_tmp = nullptr;
+    DevBuf s_ids, op_keys, op_vals, sorted_keys, sorted_vals; // uint64_t
+    DevBuf s_dists;                                           // float
+    DevBuf s_counts, seg_start, counters; // uint32_t; counters: [0]=n_seg [1]=status [2]=slow count
+    DevBuf sort_tmp;
     size_t sort_tmp_bytes = 0;
-    LayerDev* d_layers = nullptr;
-    uint8_t* selected = nullptr; // per row of the layer being built: BuildParams::selected
-    void free_all() {
-        void* ps[] = {s_ids, op_keys, op_vals, sorted_keys, sorted_vals, s_dists, s_counts, seg_start, counters, sort_tmp, d_layers, selected};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-    }
+    DevBuf d_layers; // LayerDev
+    DevBuf selected; // uint8_t per row of the layer being built: BuildParams::selected
 };
+
+// the blocks of a BuildScratch that are sized by a batch: `members` elements searched with `max_search`, `n_ops_max`
+// link updates sorted on `s`
+static int alloc_batch_scratch(BuildScratch& S, uint64_t members, uint32_t max_search, uint64_t n_ops_max, hipStream_t s) {
+    HIP_TRY(S.s_ids.alloc(members * max_search * 8));
+    HIP_TRY(S.s_dists.alloc(members * max_search * 4));
+    HIP_TRY(S.s_counts.alloc(members * 4));
+    HIP_TRY(S.op_keys.alloc(n_ops_max * 8));
+    HIP_TRY(S.op_vals.alloc(n_ops_max * 8));
+    HIP_TRY(S.sorted_keys.alloc(n_ops_max * 8));
+    HIP_TRY(S.sorted_vals.alloc(n_ops_max * 8));
+    HIP_TRY(S.seg_start.alloc(n_ops_max * 4));
+    HIP_TRY(S.counters.alloc(32));
+    HIP_TRY(hipMemsetAsync(S.counters.get(), 0, 32, s));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, S.sort_tmp_bytes, S.op_keys.as<uint64_t>(), S.sorted_keys.as<uint64_t>(),
+                                               S.op_vals.as<uint64_t>(), S.sorted_vals.as<uint64_t>(), (int)n_ops_max, 0, OP_KEY_BITS, s));
+    HIP_TRY(S.sort_tmp.alloc(S.sort_tmp_bytes));
+    return GRANNE_HIP_OK;
+}
 
 // What every launch of the three build kernels over one layer shares: the kernels of the row shape, the LDS carve-up
 // and its sizes, and the BuildParams that do not change from one batch to the next.
@@ -306,26 +293,26 @@ static int make_build_plan(const granne_hip_builder* b, const BuilderLayer& L, u
     out->lds = lds;
     out->lds_rows = lds_rows;
     BuildParams& P = out->P;
-    P.elements = b->d_elements;
+    P.elements = b->d_elements.as<uint8_t>();
     P.row_bytes = b->row_bytes;
     P.row_stride = b->row_stride;
     P.dim = b->dim;
     P.lrow = lrow;
-    P.adj = L.d_adj;
+    P.adj = L.d_adj.as<uint32_t>();
     P.W = b->W;
     P.cap = cap;
     P.m_layer = m_layer;
     P.layer_len = L.len;
     P.efc = max_search;
-    P.s_ids = S.s_ids;
-    P.s_dists = S.s_dists;
-    P.s_counts = S.s_counts;
-    P.op_keys = S.op_keys;
-    P.op_vals = S.op_vals;
-    P.sorted_keys = S.sorted_keys;
-    P.sorted_vals = S.sorted_vals;
-    P.seg_start = S.seg_start;
-    P.n_seg = S.counters;
+    P.s_ids = S.s_ids.as<uint64_t>();
+    P.s_dists = S.s_dists.as<float>();
+    P.s_counts = S.s_counts.as<uint32_t>();
+    P.op_keys = S.op_keys.as<uint64_t>();
+    P.op_vals = S.op_vals.as<uint64_t>();
+    P.sorted_keys = S.sorted_keys.as<uint64_t>();
+    P.sorted_vals = S.sorted_vals.as<uint64_t>();
+    P.seg_start = S.seg_start.as<uint32_t>();
+    P.n_seg = S.counters.as<uint32_t>();
     P.selected = selected;
     P.cand_cap = cand_cap;
     P.chunk = chunk;
@@ -343,23 +330,23 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
     const uint32_t bmax = b->cfg.batch_max;
     BuildPlan plan;
     {
-        int rc = make_build_plan(b, L, m_layer, max_search, S, S.selected, &plan);
+        int rc = make_build_plan(b, L, m_layer, max_search, S, S.selected.as<uint8_t>(), &plan);
         if (rc) return rc;
     }
     const BuildKernels K = plan.K;
     const uint32_t lds = plan.lds, lds_rows = plan.lds_rows;
     BuildParams& P = plan.P;
 
-    const SearchTarget T(b, S.d_layers, last + 1);
+    const SearchTarget T(b, S.d_layers.as<LayerDev>(), last + 1);
     SearchCall call; // phase A's searches: max_search neighbors of each batch's rows, from the rows themselves
     call.ef = call.k = max_search;
-    call.ids = S.s_ids;
-    call.dists = S.s_dists;
-    call.counts = S.s_counts;
-    call.status = S.counters + 1;
+    call.ids = S.s_ids.as<uint64_t>();
+    call.dists = S.s_dists.as<float>();
+    call.counts = S.s_counts.as<uint32_t>();
+    call.status = P.n_seg + 1;
     call.stream = s;
 
-    HIP_TRY(hipMemsetAsync(S.selected, 0, layer_len ? layer_len : 1, s)); // nothing is known about the rows of a pass
+    HIP_TRY(hipMemsetAsync(S.selected.get(), 0, layer_len ? layer_len : 1, s)); // nothing is known about the rows of a pass
 
     const bool debug = getenv("GRANNE_HIP_DEBUG") != nullptr;
     auto dbg = [&](const char* what, uint64_t pos_, uint64_t B_) {
@@ -380,7 +367,7 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
         const int64_t step = reinsert ? -1 : 1;
 
         // phase A: entry search through the previous layers + search_for_neighbors on this layer
-        call.queries = b->d_elements + (size_t)first * b->row_stride;
+        call.queries = P.elements + (size_t)first * b->row_stride;
         call.q_stride = step * (int64_t)b->row_stride;
         call.nq = (uint32_t)B;
         int rc = search_launch(T, call);
@@ -396,12 +383,12 @@ static int index_elements_pass(granne_hip_builder* b, uint32_t m_layer, uint32_t
 
         // phase B: sort the ops by (target row, order), one wave per target row replays them
         size_t tmp_bytes = S.sort_tmp_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp, tmp_bytes, S.op_keys, S.sorted_keys, S.op_vals,
-                                                   S.sorted_vals, (int)P.n_ops, 0, OP_KEY_BITS, s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp.get(), tmp_bytes, P.op_keys, S.sorted_keys.as<uint64_t>(), P.op_vals,
+                                                   S.sorted_vals.as<uint64_t>(), (int)P.n_ops, 0, OP_KEY_BITS, s));
         dbg("sort", pos, B);
-        HIP_TRY(hipMemsetAsync(S.counters, 0, 4, s));
-        hipLaunchKernelGGL(mark_heads_kernel, dim3(grid_for(P.n_ops, 256)), dim3(256), 0, s, S.sorted_keys, P.n_ops,
-                           S.seg_start, S.counters);
+        HIP_TRY(hipMemsetAsync(P.n_seg, 0, 4, s));
+        hipLaunchKernelGGL(mark_heads_kernel, dim3(grid_for(P.n_ops, 256)), dim3(256), 0, s, P.sorted_keys, P.n_ops,
+                           P.seg_start, P.n_seg);
         HIP_TRY(hipGetLastError());
         uint32_t grid = P.n_ops < 4096 ? P.n_ops : 4096;
         hipLaunchKernelGGL(K.apply, dim3(grid), dim3(64), lds_rows, s, P);
@@ -437,18 +424,15 @@ static int index_elements_in_last_layer(granne_hip_builder* b, uint64_t max_num_
     // layer.resize(num_elements, UNUSED), :730 (capacity: `ideal` rows, :670)
     const uint64_t already = L.len;
     if (num_in_layer > L.cap_rows) {
-        uint32_t* nrows = nullptr;
+        DevBuf nrows;
         size_t bytes = (size_t)ideal * b->W * 4;
-        HIP_TRY(hipMalloc((void**)&nrows, bytes));
-        b->hbm_bytes += bytes;
-        HIP_TRY(hipMemsetAsync(nrows, 0xFF, bytes, s));
-        if (L.len) HIP_TRY(hipMemcpyAsync(nrows, L.d_adj, (size_t)L.len * b->W * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(nrows.alloc(bytes));
+        HIP_TRY(hipMemsetAsync(nrows.get(), 0xFF, bytes, s));
+        if (L.len) HIP_TRY(hipMemcpyAsync(nrows.get(), L.d_adj.get(), (size_t)L.len * b->W * 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (L.d_adj) {
-            b->hbm_bytes -= (size_t)L.cap_rows * b->W * 4;
-            (void)hipFree(L.d_adj);
-        }
-        L.d_adj = nrows;
+        b->hbm_bytes += bytes;
+        if (L.d_adj) b->hbm_bytes -= (size_t)L.cap_rows * b->W * 4;
+        L.d_adj = std::move(nrows);
         L.cap_rows = ideal;
     }
     L.len = num_in_layer;
@@ -457,55 +441,38 @@ static int index_elements_in_last_layer(granne_hip_builder* b, uint64_t max_num_
     BuildScratch S;
     const uint64_t bmaxu = std::min<uint64_t>(b->cfg.batch_max, num_in_layer);
     const uint64_t n_ops_max = bmaxu * b->cfg.num_neighbors * 2;
-    int rc = GRANNE_HIP_OK;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&S.s_ids, bmaxu * max_search * 8));
-        HIP_TRY(hipMalloc((void**)&S.s_dists, bmaxu * max_search * 4));
-        HIP_TRY(hipMalloc((void**)&S.s_counts, bmaxu * 4));
-        HIP_TRY(hipMalloc((void**)&S.op_keys, n_ops_max * 8));
-        HIP_TRY(hipMalloc((void**)&S.op_vals, n_ops_max * 8));
-        HIP_TRY(hipMalloc((void**)&S.sorted_keys, n_ops_max * 8));
-        HIP_TRY(hipMalloc((void**)&S.sorted_vals, n_ops_max * 8));
-        HIP_TRY(hipMalloc((void**)&S.seg_start, n_ops_max * 4));
-        HIP_TRY(hipMalloc((void**)&S.counters, 32));
-        HIP_TRY(hipMalloc((void**)&S.selected, num_in_layer ? num_in_layer : 1));
-        HIP_TRY(hipMemsetAsync(S.counters, 0, 32, s));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, S.sort_tmp_bytes, S.op_keys, S.sorted_keys, S.op_vals,
-                                                   S.sorted_vals, (int)n_ops_max, 0, OP_KEY_BITS, s));
-        HIP_TRY(hipMalloc(&S.sort_tmp, S.sort_tmp_bytes ? S.sort_tmp_bytes : 16));
-        // layer table: finished layers + the one being built
-        std::vector<LayerDev> h(last + 1);
-        for (uint32_t l = 0; l <= last; ++l) {
-            h[l].adj = b->layers[l].d_adj;
-            h[l].len = b->layers[l].len;
-            h[l].width = b->W;
-            h[l].flags = 0; // connect_nodes never lists a neighbor twice (mod.rs:913-917)
-        }
-        HIP_TRY(hipMalloc((void**)&S.d_layers, sizeof(LayerDev) * h.size()));
-        HIP_TRY(hipMemcpyAsync(S.d_layers, h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
+    SettleStream settle{s}; // (declared after S: the stream is idle before an early return frees the scratch)
+    int rc = alloc_batch_scratch(S, bmaxu, max_search, n_ops_max, s);
+    if (rc) return rc;
+    HIP_TRY(S.selected.alloc(num_in_layer));
+    // layer table: finished layers + the one being built
+    std::vector<LayerDev> h(last + 1);
+    for (uint32_t l = 0; l <= last; ++l) {
+        h[l].adj = b->layers[l].d_adj.as<uint32_t>();
+        h[l].len = b->layers[l].len;
+        h[l].width = b->W;
+        h[l].flags = 0; // connect_nodes never lists a neighbor twice (mod.rs:913-917)
+    }
+    HIP_TRY(S.d_layers.alloc(sizeof(LayerDev) * h.size()));
+    HIP_TRY(hipMemcpyAsync(S.d_layers.get(), h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
 
-        int r = index_elements_pass(b, m_layer, max_search, false, already, S, s);
-        if (r) return r;
-        if (b->cfg.reinsert_elements) { // :692-710
-            if (b->cfg.show_progress) {
-                printf("Reinserting elements...\n");
-                fflush(stdout);
-            }
-            uint32_t ms2 = max_search / 2 > 1 ? max_search / 2 : 1;
-            r = index_elements_pass(b, m_layer, ms2, true, 0, S, s);
-            if (r) return r;
+    rc = index_elements_pass(b, m_layer, max_search, false, already, S, s);
+    if (rc) return rc;
+    if (b->cfg.reinsert_elements) { // :692-710
+        if (b->cfg.show_progress) {
+            printf("Reinserting elements...\n");
+            fflush(stdout);
         }
-        uint32_t hc[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(hc, S.counters, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (hc[1]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact-search scratch exhausted during build");
-        return GRANNE_HIP_OK;
-    };
-    rc = body();
-    (void)hipStreamSynchronize(s);
-    S.free_all();
-    return rc;
+        uint32_t ms2 = max_search / 2 > 1 ? max_search / 2 : 1;
+        rc = index_elements_pass(b, m_layer, ms2, true, 0, S, s);
+        if (rc) return rc;
+    }
+    uint32_t hc[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(hc, S.counters.get(), 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (hc[1]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact-search scratch exhausted during build");
+    return GRANNE_HIP_OK;
 }
 
 // build_partial, src/index/mod.rs:374-402
@@ -516,8 +483,7 @@ extern "C" int granne_hip_builder_build(granne_hip_builder* b, uint64_t num_elem
     if (num_elements > b->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "Cannot index more elements than exist.");
     if (!b->layers.empty() && num_elements < b->layers.back().len)
         return fail(GRANNE_HIP_ERR_INVALID, "Cannot index fewer elements than already in index.");
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     int rc = GRANNE_HIP_OK;
@@ -527,10 +493,10 @@ extern "C" int granne_hip_builder_build(granne_hip_builder* b, uint64_t num_elem
         if (!b->layers.empty()) {
             const BuilderLayer& pl = b->layers.back();
             size_t bytes = (size_t)pl.len * b->W * 4;
-            hipError_t e = hipMalloc((void**)&nl.d_adj, bytes ? bytes : 16);
+            hipError_t e = nl.d_adj.alloc(bytes);
             // on the builder's own stream: a device-to-device hipMemcpy on the null stream is
             // asynchronous and a non-blocking stream would not wait for it
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(nl.d_adj, pl.d_adj, bytes, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(nl.d_adj.get(), pl.d_adj.get(), bytes, hipMemcpyDeviceToDevice, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) {
                 rc = fail(GRANNE_HIP_ERR_HIP, "layer clone failed: %s", hipGetErrorString(e));
@@ -538,13 +504,13 @@ extern "C" int granne_hip_builder_build(granne_hip_builder* b, uint64_t num_elem
             }
             nl.len = pl.len;
             nl.cap_rows = pl.len;
-            b->hbm_bytes += bytes;
         }
         if (b->layers.size() >= 64) {
             rc = fail(GRANNE_HIP_ERR_INVALID, "too many layers");
             break;
         }
-        b->layers.push_back(nl);
+        b->hbm_bytes += (size_t)nl.cap_rows * b->W * 4; // (counted once the clone is the builder's)
+        b->layers.push_back(std::move(nl));
         rc = index_elements_in_last_layer(b, num_elements, s);
     }
     (void)hipStreamSynchronize(s);
@@ -558,45 +524,39 @@ extern "C" int granne_hip_builder_get_layer(const granne_hip_builder* b, uint32_
     DeviceGuard g(b->device);
     const BuilderLayer& L = b->layers[layer];
     const uint32_t nn = b->cfg.num_neighbors;
-    HIP_TRY(hipMemcpy2D(out_rows, (size_t)nn * 4, L.d_adj, (size_t)b->W * 4, (size_t)nn * 4, L.len, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(out_rows, (size_t)nn * 4, L.d_adj.get(), (size_t)b->W * 4, (size_t)nn * 4, L.len, hipMemcpyDeviceToHost));
     return GRANNE_HIP_OK;
 }
 
 extern "C" int granne_hip_builder_get_index(const granne_hip_builder* b, granne_hip_index** out) {
     if (!b || !out) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
     *out = nullptr;
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
-    granne_hip_index* ix = new granne_hip_index();
+    GRANNE_HIP_ON_DEVICE(b->device);
+    IndexPtr made(new granne_hip_index());
+    granne_hip_index* ix = made.get();
     ix->device = b->device;
     ix->dim = b->dim;
     ix->dtype = b->d_half ? GRANNE_HIP_F16 : b->dtype;
     ix->n_elements = b->n_elements;
     ix->row_bytes = b->d_half ? b->half_bytes : b->row_bytes;
     ix->row_stride = b->d_half ? b->half_stride : b->row_stride;
-    auto body = [&]() -> int {
-        size_t eb = (size_t)b->n_elements * ix->row_stride;
-        HIP_TRY(hipMalloc((void**)&ix->d_elements, eb ? eb : 16));
-        ix->hbm_bytes += eb;
-        if (eb) HIP_TRY(hipMemcpy(ix->d_elements, b->d_half ? b->d_half : b->d_elements, eb, hipMemcpyDeviceToDevice));
-        for (const auto& BL : b->layers) {
-            LayerHost L;
-            L.len = BL.len;
-            L.width = b->cfg.num_neighbors;
-            L.dev_width = b->W;
-            size_t bytes = (size_t)BL.len * b->W * 4;
-            HIP_TRY(hipMalloc((void**)&L.d_adj, bytes ? bytes : 16));
-            ix->hbm_bytes += bytes;
-            ix->layers.push_back(L);
-            if (bytes) HIP_TRY(hipMemcpy(L.d_adj, BL.d_adj, bytes, hipMemcpyDeviceToDevice));
-        }
-        return finish_layers(ix, nullptr);
-    };
-    int rc = body();
-    if (rc) {
-        destroy_index(ix);
-        return rc;
+    size_t eb = (size_t)b->n_elements * ix->row_stride;
+    HIP_TRY(ix->d_elements.alloc(eb));
+    ix->hbm_bytes += eb;
+    if (eb) HIP_TRY(hipMemcpy(ix->d_elements.get(), (b->d_half ? b->d_half : b->d_elements).get(), eb, hipMemcpyDeviceToDevice));
+    for (const auto& BL : b->layers) {
+        LayerHost L;
+        L.len = BL.len;
+        L.width = b->cfg.num_neighbors;
+        L.dev_width = b->W;
+        size_t bytes = (size_t)BL.len * b->W * 4;
+        HIP_TRY(L.d_adj.alloc(bytes));
+        ix->hbm_bytes += bytes;
+        ix->layers.push_back(std::move(L));
+        if (bytes) HIP_TRY(hipMemcpy(ix->layers.back().d_adj.get(), BL.d_adj.get(), bytes, hipMemcpyDeviceToDevice));
     }
-    *out = ix;
+    int rc = finish_layers(ix, nullptr);
+    if (rc) return rc;
+    *out = made.release();
     return GRANNE_HIP_OK;
 }

@@ -411,7 +411,7 @@ static int encode_device_index(const granne_hip_index* ix, std::vector<uint8_t>*
         const LayerHost& L = ix->layers[l];
         rows[l].resize((size_t)L.len * L.dev_width);
         if (!rows[l].empty())
-            HIP_TRY(hipMemcpy(rows[l].data(), L.d_adj, rows[l].size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(rows[l].data(), L.d_adj.get(), rows[l].size() * 4, hipMemcpyDeviceToHost));
         lens[l] = L.len;
         ptrs[l] = rows[l].data();
         widths[l] = L.dev_width;
@@ -425,8 +425,7 @@ extern "C" int granne_hip_index_encode(const granne_hip_index* ix, void** out_by
     if (!ix || !out_bytes || !out_len) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
     *out_bytes = nullptr;
     *out_len = 0;
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     std::vector<uint8_t> buf;
     int rc = encode_device_index(ix, &buf);
     if (rc) return rc;
@@ -442,8 +441,7 @@ extern "C" void granne_hip_bytes_free(void* bytes) { free(bytes); }
 // Index::write_index / write_elements for a device-resident index (downloads, then writes)
 extern "C" int granne_hip_index_save(const granne_hip_index* ix, const char* index_path, const char* elements_path) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     if (index_path) {
         std::vector<uint8_t> buf;
         int rc = encode_device_index(ix, &buf);
@@ -455,7 +453,7 @@ extern "C" int granne_hip_index_save(const granne_hip_index* ix, const char* ind
         size_t dense = (size_t)ix->dim * elem_size(ix->dtype);
         std::vector<uint8_t> el((size_t)ix->n_elements * dense);
         if (!el.empty())
-            HIP_TRY(hipMemcpy2D(el.data(), dense, ix->d_elements, ix->row_stride, dense, ix->n_elements, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy2D(el.data(), dense, ix->d_elements.get(), ix->row_stride, dense, ix->n_elements, hipMemcpyDeviceToHost));
         return granne_hip_write_elements_file(elements_path, el.data(), ix->n_elements, ix->dim, ix->dtype);
     }
     return GRANNE_HIP_OK;
@@ -510,14 +508,9 @@ extern "C" int granne_hip_builder_load_index(granne_hip_builder* b, const void* 
         prev = len;
     }
     if (layers.size() > 64) return fail(GRANNE_HIP_ERR_INVALID, "too many layers");
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     const uint32_t nn = b->cfg.num_neighbors, W = b->W;
     std::vector<BuilderLayer> fresh;
-    auto drop = [&]() {
-        for (auto& L : fresh)
-            if (L.d_adj) (void)hipFree(L.d_adj);
-    };
     for (size_t l = 0; l < layers.size(); ++l) {
         const granne_file::DecodedLayer& D = layers[l];
         const uint64_t len = D.offsets.size() - 1;
@@ -531,17 +524,13 @@ extern "C" int granne_hip_builder_load_index(granne_hip_builder* b, const void* 
         L.len = len;
         L.cap_rows = len;
         size_t bytes = rows.size() * 4;
-        hipError_t e = hipMalloc((void**)&L.d_adj, bytes ? bytes : 16);
-        if (e == hipSuccess && bytes) e = hipMemcpy(L.d_adj, rows.data(), bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (L.d_adj) (void)hipFree(L.d_adj);
-            drop();
-            return fail(GRANNE_HIP_ERR_HIP, "layer upload failed: %s", hipGetErrorString(e));
-        }
+        hipError_t e = L.d_adj.alloc(bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpy(L.d_adj.get(), rows.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "layer upload failed: %s", hipGetErrorString(e));
         b->hbm_bytes += bytes;
-        fresh.push_back(L);
+        fresh.push_back(std::move(L));
     }
-    b->layers = fresh;
+    b->layers = std::move(fresh);
     return GRANNE_HIP_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "util_kernels.h"
 #include "brute_force.h"
 #include "combiner.h"
+#include "dev_mem.h"
 
 using namespace granne_hip;
 
@@ -63,6 +64,16 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+// the stream is idle when the scope ends: declared AFTER the owners whose blocks the stream's work still uses, so that
+// an early return does not free them under a running kernel
+struct SettleStream {
+    hipStream_t s;
+    ~SettleStream() { (void)hipStreamSynchronize(s); }
+};
+// the guard of an entry point: `dev` is current until the scope ends, or the call fails here
+#define GRANNE_HIP_ON_DEVICE(dev)                                                                      \
+    DeviceGuard g(dev);                                                                               \
+    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", dev)
 
 extern "C" const char* granne_hip_last_error(void) { return g_last_error.c_str(); }
 extern "C" int granne_hip_abi_version(void) { return GRANNE_HIP_ABI_VERSION; }
@@ -108,8 +119,7 @@ static const EnvKnobs& knobs() {
 struct ScratchCache {
     struct Block {
         hipStream_t stream;
-        uint8_t* p;
-        size_t cap;
+        DevBuf p;
         uint64_t last_use;   // `uses` at the block's last launch
         uint32_t small_runs; // consecutive launches that needed less than a quarter of an oversized block
         std::chrono::steady_clock::time_point last_time; // wall clock of the block's last launch
@@ -119,14 +129,7 @@ struct ScratchCache {
     uint64_t uses = 0;
     // blocks of streams that gave their place up: freed by search_launch AFTER it has released `mu` (hipFree waits for
     // the device; every concurrent searcher of the index would wait with it under the lock)
-    std::vector<uint8_t*> graveyard;
-    void free_all() {
-        for (auto& b : blocks)
-            if (b.p) (void)hipFree(b.p);
-        blocks.clear();
-        for (auto* p : graveyard) (void)hipFree(p);
-        graveyard.clear();
-    }
+    std::vector<DevBuf> graveyard;
 };
 
 // A SumEmbeddings container's device copy (sum_embeddings_host.h): immutable once made, shared by the container and by
@@ -135,15 +138,11 @@ struct SeDev {
     int device = 0;
     uint32_t dim = 0, tstride = 0; // floats per table row; floats from one row to the next (rows padded to 16 bytes)
     uint64_t n_embeddings = 0, n = 0, n_terms = 0;
-    float* d_table = nullptr;
-    uint64_t* d_offsets = nullptr;
-    uint32_t* d_terms = nullptr;
+    DevBuf d_table, d_offsets, d_terms; // float [n_embeddings][tstride], uint64_t [n + 1], uint32_t [n_terms]
     uint64_t bytes() const { return n_embeddings * tstride * 4u + (n + 1) * 8u + n_terms * 4u; }
-    ~SeDev() {
+    ~SeDev() { // (the members go after this body: freed here, under the guard)
         DeviceGuard g(device);
-        if (d_table) (void)hipFree(d_table);
-        if (d_offsets) (void)hipFree(d_offsets);
-        if (d_terms) (void)hipFree(d_terms);
+        d_table.reset(), d_offsets.reset(), d_terms.reset();
     }
 };
 #define GRANNE_HIP_COMPACT_UNSUPPORTED(ix, what)                                                                        \
@@ -156,8 +155,8 @@ struct LayerHost {
     uint64_t len = 0;
     uint32_t width = 0;     // caller's row width
     uint32_t dev_width = 0; // multiple of 32
-    uint32_t* d_adj = nullptr;
-    uint8_t* d_adjx = nullptr; // the register walker's copy: ids + the neighbors' row tails (LayerDev::adjx), or null
+    DevBuf d_adj;  // uint32_t [len][dev_width]
+    DevBuf d_adjx; // the register walker's copy: ids + the neighbors' row tails (LayerDev::adjx), or empty
     uint32_t adjx_stride = 0;
 };
 
@@ -168,10 +167,10 @@ struct granne_hip_index {
     uint64_t n_elements = 0;
     uint32_t row_bytes = 0;  // data bytes of a device row (zero padded to 16)
     uint32_t row_stride = 0; // bytes from one device row to the next
-    uint8_t* d_elements = nullptr;
+    DevBuf d_elements;
     std::shared_ptr<SeDev> se; // a compact SumEmbeddings index: no d_elements, vectors are made from the term lists
     std::vector<LayerHost> layers;
-    LayerDev* d_layers = nullptr;
+    DevBuf d_layers; // LayerDev [layers.size()]
     uint64_t hbm_bytes = 0;
     uint32_t max_dev_width = 32;
     // options
@@ -190,18 +189,16 @@ struct granne_hip_index {
     std::atomic<uint64_t> last_compact{0}; // GRANNE_HIP_OPT_LAST_COMPACT_ROWS
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
-    float* d_inv_norm = nullptr;
+    DevBuf d_inv_norm;
     // f32 rows of the sketched shapes: one SKETCH_LINE per row (search_kernel.h), made with the index, or null
-    uint8_t* d_sketch = nullptr;
+    DevBuf d_sketch;
     // host-pointer searches (granne_hip_search / _search_batch): a stream, a device buffer and a pinned
     // staging buffer per concurrent caller, kept for the life of the index -- the reference's API is one
     // query per call (src/index/mod.rs:140-150), so a call must not pay stream creation and hipMalloc
     struct HostCall {
         hipStream_t stream = nullptr;
-        uint8_t* d_buf = nullptr;
-        size_t d_cap = 0;
-        uint8_t* h_pin = nullptr;
-        size_t h_cap = 0;
+        DevBuf d_buf;
+        PinBuf h_pin;
     };
     std::mutex call_mu;
     std::vector<HostCall*> call_free;
@@ -308,20 +305,10 @@ static int se_rows_to_host(const SeDev& se, uint64_t first, uint64_t count, int 
 static void destroy_index(granne_hip_index* ix) {
     if (!ix) return;
     DeviceGuard g(ix->device);
-    if (ix->d_elements) (void)hipFree(ix->d_elements);
-    for (auto& L : ix->layers) {
-        if (L.d_adj) (void)hipFree(L.d_adj);
-        if (L.d_adjx) (void)hipFree(L.d_adjx);
-    }
-    if (ix->d_layers) (void)hipFree(ix->d_layers);
-    if (ix->d_inv_norm) (void)hipFree(ix->d_inv_norm);
-    if (ix->d_sketch) (void)hipFree(ix->d_sketch);
     for (auto* c : ix->group_call)
         if (c) ix->call_free.push_back(c);
     for (auto* c : ix->call_free) {
         if (c->stream) (void)hipStreamDestroy(c->stream);
-        if (c->d_buf) (void)hipFree(c->d_buf);
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
         delete c;
     }
     for (auto& f : ix->flights) {
@@ -330,24 +317,28 @@ static void destroy_index(granne_hip_index* ix) {
         if (f.done) (void)hipEventDestroy(f.done);
         if (f.stream) (void)hipStreamDestroy(f.stream);
     }
-    ix->scratch.free_all();
-    delete ix;
+    delete ix; // (the memory goes here, under the guard, after the streams)
 }
+// an index in the making: destroyed by an early return, release()d to the caller once everything has been made
+struct IndexDeleter {
+    void operator()(granne_hip_index* ix) const { destroy_index(ix); }
+};
+using IndexPtr = std::unique_ptr<granne_hip_index, IndexDeleter>;
 
 // src is a device pointer to dense rows; fills ix->d_elements
 static int upload_elements_from_device(granne_hip_index* ix, const void* d_src, hipStream_t s) {
     uint64_t n = ix->n_elements;
     uint32_t dense = ix->dim * elem_size(ix->dtype);
     size_t bytes = (size_t)n * ix->row_stride;
-    HIP_TRY(hipMalloc((void**)&ix->d_elements, bytes ? bytes : 16));
+    HIP_TRY(ix->d_elements.alloc(bytes));
     ix->hbm_bytes += bytes;
     if (n == 0) return GRANNE_HIP_OK;
     if (dense == ix->row_stride) {
-        HIP_TRY(hipMemcpyAsync(ix->d_elements, d_src, bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix->d_elements.get(), d_src, bytes, hipMemcpyDeviceToDevice, s));
     } else {
         uint64_t units = n * (ix->row_stride / 16);
         hipLaunchKernelGGL(relayout_rows_kernel, dim3(grid_for(units, 256)), dim3(256), 0, s, (const uint8_t*)d_src,
-                           ix->d_elements, n, dense, ix->row_stride);
+                           ix->d_elements.as<uint8_t>(), n, dense, ix->row_stride);
         HIP_TRY(hipGetLastError());
     }
     return GRANNE_HIP_OK;
@@ -358,9 +349,8 @@ static int upload_elements_from_device(granne_hip_index* ix, const void* d_src, 
 static int make_inline_tails(granne_hip_index* ix, hipStream_t s) {
     for (auto& L : ix->layers) {
         if (L.d_adjx) {
-            (void)hipFree(L.d_adjx);
+            L.d_adjx.reset();
             ix->hbm_bytes -= (uint64_t)L.len * L.adjx_stride;
-            L.d_adjx = nullptr;
             L.adjx_stride = 0;
         }
     }
@@ -371,17 +361,15 @@ static int make_inline_tails(granne_hip_index* ix, hipStream_t s) {
     for (auto& L : ix->layers) {
         L.adjx_stride = 128u + 32u * tu * 16u;
         const size_t bytes = (size_t)L.len * L.adjx_stride;
-        if (hipMalloc((void**)&L.d_adjx, bytes ? bytes : 16) != hipSuccess) {
+        if (L.d_adjx.alloc(bytes) != hipSuccess) {
             // The copy is an accelerator, not part of the index: an index that fits without it (a 200M x 100-d shard: 128 GB
             // of copy) is made without it -- the walkers then read the tails from the rows' own last line.
             (void)hipGetLastError();
-            L.d_adjx = nullptr;
             for (auto& M : ix->layers) {
                 if (M.d_adjx) {
-                    (void)hipStreamSynchronize(s);
-                    (void)hipFree(M.d_adjx);
+                    (void)hipStreamSynchronize(s); // (inline_tails_kernel is still writing the copy)
+                    M.d_adjx.reset();
                     ix->hbm_bytes -= (uint64_t)M.len * M.adjx_stride;
-                    M.d_adjx = nullptr;
                 }
                 M.adjx_stride = 0;
             }
@@ -389,8 +377,9 @@ static int make_inline_tails(granne_hip_index* ix, hipStream_t s) {
         }
         ix->hbm_bytes += bytes;
         if (L.len)
-            hipLaunchKernelGGL(inline_tails_kernel, dim3(grid_for(L.len * 32u * (1u + tu), 256)), dim3(256), 0, s, L.d_adj,
-                               L.len, ix->d_elements, ix->row_stride, (ix->dim / 32u) * 128u, tu, L.d_adjx, L.adjx_stride);
+            hipLaunchKernelGGL(inline_tails_kernel, dim3(grid_for(L.len * 32u * (1u + tu), 256)), dim3(256), 0, s,
+                               L.d_adj.as<uint32_t>(), L.len, ix->d_elements.as<uint8_t>(), ix->row_stride, (ix->dim / 32u) * 128u, tu,
+                               L.d_adjx.as<uint8_t>(), L.adjx_stride);
         HIP_TRY(hipGetLastError());
     }
     return GRANNE_HIP_OK;
@@ -404,15 +393,13 @@ static int make_scan_norms(granne_hip_index* ix, hipStream_t s) {
     std::lock_guard<std::mutex> lk(ix->norm_mu);
     if (ix->d_inv_norm) return GRANNE_HIP_OK;
     const uint64_t n = ix->n_elements, n_pad = (n + 31u) & ~31ull;
-    float* dn = nullptr;
-    HIP_TRY(hipMalloc((void**)&dn, (size_t)inv_norm_bytes(n)));
-    hipLaunchKernelGGL(inv_norm_rows_kernel, dim3(grid_for(n * 8, 256)), dim3(256), 0, s, ix->d_elements, n, ix->row_stride, dn);
+    DevBuf norms;
+    HIP_TRY(norms.alloc((size_t)inv_norm_bytes(n)));
+    float* dn = norms.as<float>();
+    hipLaunchKernelGGL(inv_norm_rows_kernel, dim3(grid_for(n * 8, 256)), dim3(256), 0, s, ix->d_elements.as<uint8_t>(), n, ix->row_stride, dn);
     hipLaunchKernelGGL(inv_gmax_kernel, dim3(grid_for(n_pad / 16 + 1, 256)), dim3(256), 0, s, (const float*)dn, n, dn + n_pad);
-    if (hipGetLastError() != hipSuccess) {
-        (void)hipFree(dn);
-        return fail(GRANNE_HIP_ERR_HIP, "inv_norm_rows_kernel failed");
-    }
-    ix->d_inv_norm = dn; // (finish_layers synchronises s before the index is handed out)
+    if (hipGetLastError() != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "inv_norm_rows_kernel failed");
+    ix->d_inv_norm = std::move(norms); // (finish_layers synchronises s before the index is handed out)
     ix->hbm_bytes += inv_norm_bytes(n);
     return GRANNE_HIP_OK;
 }
@@ -432,15 +419,14 @@ static int make_row_sketch(granne_hip_index* ix, hipStream_t s) {
             return GRANNE_HIP_OK;
         }
         if ((uint64_t)free_b < (uint64_t)bytes + total_b / 32u) return GRANNE_HIP_OK;
-        if (hipMalloc((void**)&ix->d_sketch, bytes) != hipSuccess) {
+        if (ix->d_sketch.alloc(bytes) != hipSuccess) {
             (void)hipGetLastError();
-            ix->d_sketch = nullptr;
             return GRANNE_HIP_OK;
         }
         ix->hbm_bytes += bytes;
     }
-    hipLaunchKernelGGL(row_sketch_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ix->d_elements, n, ix->row_stride, ix->dim,
-                       ix->d_sketch);
+    hipLaunchKernelGGL(row_sketch_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ix->d_elements.as<uint8_t>(), n, ix->row_stride, ix->dim,
+                       ix->d_sketch.as<uint8_t>());
     HIP_TRY(hipGetLastError());
     return GRANNE_HIP_OK; // (finish_layers synchronises s before the index is handed out)
 }
@@ -455,21 +441,19 @@ static int finish_layers(granne_hip_index* ix, hipStream_t s) {
         if (r) return r;
     }
     // rows that name a neighbor twice (LAYER_TWIN_ROWS, walk_fast.h): looked for once, here, on the device rows
-    uint32_t* d_found = nullptr;
+    DevBuf found_buf;
     std::vector<uint32_t> found(h.size(), 0u);
     if (!h.empty()) {
-        HIP_TRY(hipMalloc((void**)&d_found, h.size() * 4));
-        if (hipMemsetAsync(d_found, 0, h.size() * 4, s) != hipSuccess) {
-            (void)hipFree(d_found);
-            return fail(GRANNE_HIP_ERR_HIP, "hipMemsetAsync failed");
-        }
+        HIP_TRY(found_buf.alloc(h.size() * 4));
+        if (hipMemsetAsync(found_buf.get(), 0, h.size() * 4, s) != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "hipMemsetAsync failed");
     }
+    uint32_t* const d_found = found_buf.as<uint32_t>();
     for (size_t l = 0; l < ix->layers.size(); ++l) {
-        h[l].adj = ix->layers[l].d_adj;
+        h[l].adj = ix->layers[l].d_adj.as<uint32_t>();
         h[l].len = ix->layers[l].len;
         h[l].width = ix->layers[l].dev_width;
         h[l].flags = 0;
-        h[l].adjx = ix->layers[l].d_adjx;
+        h[l].adjx = ix->layers[l].d_adjx.as<uint8_t>();
         h[l].adjx_stride = ix->layers[l].adjx_stride;
         h[l].reserved = 0;
         if (ix->layers[l].dev_width > ix->max_dev_width) ix->max_dev_width = ix->layers[l].dev_width;
@@ -480,16 +464,13 @@ static int finish_layers(granne_hip_index* ix, hipStream_t s) {
     if (!h.empty()) {
         hipError_t e = hipMemcpyAsync(found.data(), d_found, h.size() * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(d_found);
         if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "twin_rows_kernel: %s", hipGetErrorString(e));
         for (size_t l = 0; l < h.size(); ++l)
             if (found[l]) h[l].flags |= LAYER_TWIN_ROWS;
     }
     size_t bytes = sizeof(LayerDev) * (h.size() ? h.size() : 1);
-    if (ix->d_layers) (void)hipFree(ix->d_layers);
-    ix->d_layers = nullptr;
-    HIP_TRY(hipMalloc((void**)&ix->d_layers, bytes));
-    if (!h.empty()) HIP_TRY(hipMemcpyAsync(ix->d_layers, h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ix->d_layers.alloc(bytes));
+    if (!h.empty()) HIP_TRY(hipMemcpyAsync(ix->d_layers.get(), h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     return GRANNE_HIP_OK;
 }
@@ -502,14 +483,16 @@ static int add_layer_from_device_rows(granne_hip_index* ix, uint64_t len, uint32
     L.dev_width = (width + 31u) & ~31u;
     if (L.dev_width == 0) L.dev_width = 32;
     size_t bytes = (size_t)len * L.dev_width * 4;
-    HIP_TRY(hipMalloc((void**)&L.d_adj, bytes ? bytes : 16));
+    HIP_TRY(L.d_adj.alloc(bytes));
     ix->hbm_bytes += bytes;
-    ix->layers.push_back(L);
+    const uint32_t dev_width = L.dev_width;
+    ix->layers.push_back(std::move(L));
+    uint32_t* const d_adj = ix->layers.back().d_adj.as<uint32_t>();
     if (width == 0) {
-        HIP_TRY(hipMemsetAsync(L.d_adj, 0xFF, bytes, s));
+        HIP_TRY(hipMemsetAsync(d_adj, 0xFF, bytes, s));
     } else {
-        hipLaunchKernelGGL(relayout_adj_kernel, dim3(grid_for(len * L.dev_width, 256)), dim3(256), 0, s, d_rows,
-                           L.d_adj, len, width, L.dev_width);
+        hipLaunchKernelGGL(relayout_adj_kernel, dim3(grid_for(len * dev_width, 256)), dim3(256), 0, s, d_rows,
+                           d_adj, len, width, dev_width);
         HIP_TRY(hipGetLastError());
     }
     return GRANNE_HIP_OK;
@@ -523,8 +506,7 @@ extern "C" int granne_hip_index_create_device(granne_hip_index** out, const void
     if (rc) return rc;
     if (n_elements && !d_elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     if (n_layers && (!d_layer_rows || !layer_width)) return fail(GRANNE_HIP_ERR_INVALID, "layer arrays are null");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipStream_t s = (hipStream_t)stream;
     granne_hip_index* ix = new granne_hip_index();
     ix->device = device_id;
@@ -534,8 +516,9 @@ extern "C" int granne_hip_index_create_device(granne_hip_index** out, const void
     ix->row_bytes = device_row_bytes(dim, dtype);
     ix->row_stride = device_row_stride(dim, dtype);
     rc = upload_elements_from_device(ix, d_elements, s);
-    uint32_t* d_bad = nullptr; // neighbor ids outside their layer (the file loader checks the same on the host)
-    if (rc == 0 && hipMalloc((void**)&d_bad, 4) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMalloc failed");
+    DevBuf bad_buf; // neighbor ids outside their layer (the file loader checks the same on the host)
+    if (rc == 0 && bad_buf.alloc(4) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMalloc failed");
+    uint32_t* const d_bad = bad_buf.as<uint32_t>();
     if (rc == 0 && hipMemsetAsync(d_bad, 0, 4, s) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemsetAsync failed");
     for (uint32_t l = 0; rc == 0 && l < n_layers; ++l) {
         rc = add_layer_from_device_rows(ix, layer_len[l], layer_width[l], d_layer_rows[l], s);
@@ -547,7 +530,6 @@ extern "C" int granne_hip_index_create_device(granne_hip_index** out, const void
     if (rc == 0) rc = finish_layers(ix, s); // synchronises s
     uint32_t bad = 0;
     if (rc == 0 && hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemcpy failed");
-    if (d_bad) (void)hipFree(d_bad);
     if (rc == 0 && bad) rc = fail(GRANNE_HIP_ERR_INVALID, "%u neighbor ids lie outside their layer", bad);
     if (rc) {
         destroy_index(ix);
@@ -564,34 +546,26 @@ extern "C" int granne_hip_index_create(granne_hip_index** out, const void* eleme
     if (rc) return rc;
     if (n_elements && !elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     if (n_layers && (!layer_rows || !layer_width)) return fail(GRANNE_HIP_ERR_INVALID, "layer arrays are null");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
 
     // stage the host buffers on the device, then share the device path
-    void* d_el = nullptr;
+    DevBuf d_el;
     size_t el_bytes = (size_t)n_elements * dim * elem_size(dtype);
-    std::vector<uint32_t*> d_rows(n_layers, nullptr);
-    auto cleanup = [&]() {
-        if (d_el) (void)hipFree(d_el);
-        for (auto p : d_rows)
-            if (p) (void)hipFree(p);
-    };
-    hipError_t e = hipMalloc(&d_el, el_bytes ? el_bytes : 16);
-    if (e == hipSuccess && el_bytes) e = hipMemcpy(d_el, elements, el_bytes, hipMemcpyHostToDevice);
+    std::vector<DevBuf> staged(n_layers);
+    std::vector<const uint32_t*> d_rows(n_layers, nullptr);
+    hipError_t e = d_el.alloc(el_bytes);
+    if (e == hipSuccess && el_bytes) e = hipMemcpy(d_el.get(), elements, el_bytes, hipMemcpyHostToDevice);
     for (uint32_t l = 0; e == hipSuccess && l < n_layers; ++l) {
         size_t b = (size_t)layer_len[l] * layer_width[l] * 4;
-        e = hipMalloc((void**)&d_rows[l], b ? b : 16);
-        if (e == hipSuccess && b) e = hipMemcpy(d_rows[l], layer_rows[l], b, hipMemcpyHostToDevice);
+        e = staged[l].alloc(b);
+        d_rows[l] = staged[l].as<uint32_t>();
+        if (e == hipSuccess && b) e = hipMemcpy(staged[l].get(), layer_rows[l], b, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
-        cleanup();
+    if (e != hipSuccess)
         return fail(e == hipErrorNoDevice ? GRANNE_HIP_ERR_NO_DEVICE : GRANNE_HIP_ERR_HIP, "staging upload failed: %s",
                     hipGetErrorString(e));
-    }
-    rc = granne_hip_index_create_device(out, d_el, n_elements, dim, dtype, n_layers, layer_len,
-                                        (const uint32_t* const*)d_rows.data(), layer_width, device_id, nullptr);
-    cleanup();
-    return rc;
+    return granne_hip_index_create_device(out, d_el.get(), n_elements, dim, dtype, n_layers, layer_len, d_rows.data(), layer_width,
+                                          device_id, nullptr);
 }
 
 extern "C" int granne_hip_index_create_csr(granne_hip_index** out, const void* elements, uint64_t n_elements,
@@ -602,8 +576,7 @@ extern "C" int granne_hip_index_create_csr(granne_hip_index** out, const void* e
     if (rc) return rc;
     if (n_elements && !elements) return fail(GRANNE_HIP_ERR_INVALID, "elements is null");
     if (n_layers && (!layer_offsets || !layer_ids)) return fail(GRANNE_HIP_ERR_INVALID, "layer arrays are null");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
 
     granne_hip_index* ix = new granne_hip_index();
     ix->device = device_id;
@@ -612,58 +585,50 @@ extern "C" int granne_hip_index_create_csr(granne_hip_index** out, const void* e
     ix->n_elements = n_elements;
     ix->row_bytes = device_row_bytes(dim, dtype);
     ix->row_stride = device_row_stride(dim, dtype);
-    void* d_el = nullptr;
+    IndexPtr made(ix);
+    DevBuf d_el;
     size_t el_bytes = (size_t)n_elements * dim * elem_size(dtype);
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&d_el, el_bytes ? el_bytes : 16));
-        if (el_bytes) HIP_TRY(hipMemcpy(d_el, elements, el_bytes, hipMemcpyHostToDevice));
-        int r = upload_elements_from_device(ix, d_el, nullptr);
-        if (r) return r;
-        for (uint32_t l = 0; l < n_layers; ++l) {
-            uint64_t len = layer_len[l];
-            const uint64_t* off = layer_offsets[l];
-            uint32_t maxdeg = 0;
-            for (uint64_t i = 0; i < len; ++i) {
-                if (off[i + 1] < off[i]) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: offsets not monotone", l);
-                uint64_t d = off[i + 1] - off[i];
-                if (d > 0xFFFF) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: degree too large", l);
-                if (d > maxdeg) maxdeg = (uint32_t)d;
-            }
-            for (uint64_t t = 0; t < off[len]; ++t)
-                if (layer_ids[l][t] >= len) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: neighbor id outside the layer", l);
-            LayerHost L;
-            L.len = len;
-            L.width = maxdeg;
-            L.dev_width = ((maxdeg ? maxdeg : 1) + 31u) & ~31u;
-            size_t bytes = (size_t)len * L.dev_width * 4;
-            HIP_TRY(hipMalloc((void**)&L.d_adj, bytes ? bytes : 16));
-            ix->hbm_bytes += bytes;
-            ix->layers.push_back(L);
-            uint64_t* d_off = nullptr;
-            uint32_t* d_ids = nullptr;
-            size_t nids = (size_t)off[len];
-            HIP_TRY(hipMalloc((void**)&d_off, (len + 1) * 8));
-            HIP_TRY(hipMalloc((void**)&d_ids, nids ? nids * 4 : 16));
-            hipError_t e1 = hipMemcpy(d_off, off, (len + 1) * 8, hipMemcpyHostToDevice);
-            hipError_t e2 = nids ? hipMemcpy(d_ids, layer_ids[l], nids * 4, hipMemcpyHostToDevice) : hipSuccess;
-            if (e1 == hipSuccess && e2 == hipSuccess) {
-                hipLaunchKernelGGL(csr_to_adj_kernel, dim3(grid_for(len * L.dev_width, 256)), dim3(256), 0, nullptr,
-                                   d_off, d_ids, L.d_adj, len, L.dev_width);
-                e1 = hipDeviceSynchronize();
-            }
-            (void)hipFree(d_off);
-            (void)hipFree(d_ids);
-            if (e1 != hipSuccess || e2 != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "CSR upload failed");
+    HIP_TRY(d_el.alloc(el_bytes));
+    if (el_bytes) HIP_TRY(hipMemcpy(d_el.get(), elements, el_bytes, hipMemcpyHostToDevice));
+    rc = upload_elements_from_device(ix, d_el.get(), nullptr);
+    if (rc) return rc;
+    for (uint32_t l = 0; l < n_layers; ++l) {
+        uint64_t len = layer_len[l];
+        const uint64_t* off = layer_offsets[l];
+        uint32_t maxdeg = 0;
+        for (uint64_t i = 0; i < len; ++i) {
+            if (off[i + 1] < off[i]) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: offsets not monotone", l);
+            uint64_t d = off[i + 1] - off[i];
+            if (d > 0xFFFF) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: degree too large", l);
+            if (d > maxdeg) maxdeg = (uint32_t)d;
         }
-        return finish_layers(ix, nullptr);
-    };
-    rc = body();
-    if (d_el) (void)hipFree(d_el);
-    if (rc) {
-        destroy_index(ix);
-        return rc;
+        for (uint64_t t = 0; t < off[len]; ++t)
+            if (layer_ids[l][t] >= len) return fail(GRANNE_HIP_ERR_INVALID, "layer %u: neighbor id outside the layer", l);
+        LayerHost L;
+        L.len = len;
+        L.width = maxdeg;
+        L.dev_width = ((maxdeg ? maxdeg : 1) + 31u) & ~31u;
+        size_t bytes = (size_t)len * L.dev_width * 4;
+        HIP_TRY(L.d_adj.alloc(bytes));
+        ix->hbm_bytes += bytes;
+        const uint32_t dev_width = L.dev_width;
+        ix->layers.push_back(std::move(L));
+        DevBuf d_off, d_ids;
+        size_t nids = (size_t)off[len];
+        HIP_TRY(d_off.alloc((len + 1) * 8));
+        HIP_TRY(d_ids.alloc(nids * 4));
+        hipError_t e1 = hipMemcpy(d_off.get(), off, (len + 1) * 8, hipMemcpyHostToDevice);
+        hipError_t e2 = nids ? hipMemcpy(d_ids.get(), layer_ids[l], nids * 4, hipMemcpyHostToDevice) : hipSuccess;
+        if (e1 == hipSuccess && e2 == hipSuccess) {
+            hipLaunchKernelGGL(csr_to_adj_kernel, dim3(grid_for(len * dev_width, 256)), dim3(256), 0, nullptr,
+                               d_off.as<uint64_t>(), d_ids.as<uint32_t>(), ix->layers.back().d_adj.as<uint32_t>(), len, dev_width);
+            e1 = hipDeviceSynchronize();
+        }
+        if (e1 != hipSuccess || e2 != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "CSR upload failed");
     }
-    *out = ix;
+    rc = finish_layers(ix, nullptr);
+    if (rc) return rc;
+    *out = made.release();
     return GRANNE_HIP_OK;
 }
 
@@ -689,7 +654,7 @@ extern "C" int granne_hip_index_get_neighbors(const granne_hip_index* ix, uint64
     if (node >= L.len) return fail(GRANNE_HIP_ERR_INVALID, "node out of range");
     DeviceGuard g(ix->device);
     std::vector<uint32_t> row(L.dev_width);
-    HIP_TRY(hipMemcpy(row.data(), L.d_adj + node * L.dev_width, (size_t)L.dev_width * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(row.data(), L.d_adj.as<uint32_t>() + node * L.dev_width, (size_t)L.dev_width * 4, hipMemcpyDeviceToHost));
     uint32_t n = 0;
     while (n < L.dev_width && row[n] != GRANNE_HIP_UNUSED) ++n;
     *out_count = n;
@@ -702,7 +667,7 @@ extern "C" int granne_hip_index_get_element(const granne_hip_index* ix, uint64_t
     if (idx >= ix->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "element index out of range");
     if (ix->se) return se_rows_to_host(*ix->se, idx, 1, 1, (float*)out); // ElementContainer::get: the normalised vector
     DeviceGuard g(ix->device);
-    HIP_TRY(hipMemcpy(out, ix->d_elements + idx * ix->row_stride, (size_t)ix->dim * elem_size(ix->dtype),
+    HIP_TRY(hipMemcpy(out, ix->d_elements.as<uint8_t>() + idx * ix->row_stride, (size_t)ix->dim * elem_size(ix->dtype),
                       hipMemcpyDeviceToHost));
     return GRANNE_HIP_OK;
 }
@@ -714,7 +679,7 @@ extern "C" int granne_hip_index_get_sketch(const granne_hip_index* ix, uint64_t 
     if (first > ix->n_elements || count > ix->n_elements - first) return fail(GRANNE_HIP_ERR_INVALID, "rows out of range");
     if (count == 0) return GRANNE_HIP_OK;
     DeviceGuard g(ix->device);
-    HIP_TRY(hipMemcpy(out, ix->d_sketch + first * SKETCH_LINE, (size_t)count * SKETCH_LINE, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, ix->d_sketch.as<uint8_t>() + first * SKETCH_LINE, (size_t)count * SKETCH_LINE, hipMemcpyDeviceToHost));
     return GRANNE_HIP_OK;
 }
 
@@ -761,8 +726,7 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
     }
     case GRANNE_HIP_OPT_INLINE_TAILS: {
         if (value > 1) return fail(GRANNE_HIP_ERR_INVALID, "the inline-tails option is 0 or 1");
-        DeviceGuard g(ix->device);
-        if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+        GRANNE_HIP_ON_DEVICE(ix->device);
         HIP_TRY(hipDeviceSynchronize()); // (searches in flight read the copy and the layer table this replaces)
         ix->opt_inline_tails = value;
         return finish_layers(ix, nullptr);
@@ -864,8 +828,8 @@ static int scratch_for(ScratchCache* cache, hipStream_t s, size_t total, uint8_t
             // search keeps its block)
             const auto idle = std::chrono::steady_clock::now() - lru->last_time;
             if (idle > std::chrono::seconds(SCRATCH_IDLE_SECONDS)) {
-                if (lru->p) cache->graveyard.push_back(lru->p); // freed once the lock is released (search_launch)
-                *lru = {s, nullptr, 0, cache->uses, 0, std::chrono::steady_clock::now()};
+                if (lru->p) cache->graveyard.push_back(std::move(lru->p)); // freed once the lock is released (search_launch)
+                *lru = {s, DevBuf(), cache->uses, 0, std::chrono::steady_clock::now()};
                 b = lru;
             } else {
                 HIP_TRY(hipMallocAsync((void**)out, total, s));
@@ -874,7 +838,7 @@ static int scratch_for(ScratchCache* cache, hipStream_t s, size_t total, uint8_t
                 return GRANNE_HIP_OK;
             }
         } else {
-            cache->blocks.push_back({s, nullptr, 0, cache->uses, 0, std::chrono::steady_clock::now()});
+            cache->blocks.push_back({s, DevBuf(), cache->uses, 0, std::chrono::steady_clock::now()});
             b = &cache->blocks.back();
         }
     }
@@ -882,23 +846,19 @@ static int scratch_for(ScratchCache* cache, hipStream_t s, size_t total, uint8_t
     b->last_time = std::chrono::steady_clock::now();
     // a block left oversized by one exact-walker batch is let go once eight launches in a row needed less than a quarter
     // of it (not at the first: a stream that alternates the two kinds of batches keeps its block)
-    if (b->cap > SCRATCH_SHRINK_ABOVE && total < b->cap / 4) b->small_runs += 1;
+    if (b->p.capacity() > SCRATCH_SHRINK_ABOVE && total < b->p.capacity() / 4) b->small_runs += 1;
     else b->small_runs = 0;
     const bool oversized = b->small_runs >= 8;
-    if (b->cap < total || oversized) {
+    if (b->p.capacity() < total || oversized) {
         if (b->p) {
             HIP_TRY(hipStreamSynchronize(s)); // earlier launches on this stream still use the old block
-            (void)hipFree(b->p);
-            b->p = nullptr;
-            b->cap = 0;
+            b->p.reset();
         }
         b->small_runs = 0;
-        size_t want = total + (total >> 2); // some headroom: batch sizes vary
-        HIP_TRY(hipMalloc((void**)&b->p, want));
-        b->cap = want;
-        HIP_TRY(hipMemsetAsync(b->p, 0, SCRATCH_FIXED, s));
+        HIP_TRY(b->p.alloc(total + (total >> 2))); // some headroom: batch sizes vary
+        HIP_TRY(hipMemsetAsync(b->p.get(), 0, SCRATCH_FIXED, s));
     }
-    *out = b->p;
+    *out = b->p.as<uint8_t>();
     return GRANNE_HIP_OK;
 }
 
@@ -931,7 +891,7 @@ struct SearchTarget {
     // own), its own scratch cache, its row width W as the widest layer's; every other option keeps its default.
     template <class G>
     SearchTarget(const G* g, const LayerDev* layers, uint32_t n_layers)
-        : device(g->device), d_elements(g->d_elements), n_elements(g->n_elements), dim(g->dim), dtype(g->dtype),
+        : device(g->device), d_elements(g->d_elements.template as<uint8_t>()), n_elements(g->n_elements), dim(g->dim), dtype(g->dtype),
           stage_row_bytes(g->dtype == GRANNE_HIP_F16 ? (g->dim * 4u + 15u) & ~15u : g->row_bytes), elem_row_bytes(g->row_bytes),
           row_stride(g->row_stride),
           d_layers(layers), n_layers(n_layers), scratch(&const_cast<G*>(g)->scratch) {
@@ -944,7 +904,7 @@ struct SearchTarget {
             opt_overflow_slots = g->opt_overflow_slots;
             opt_visited16 = g->opt_visited16;
             opt_seen_min = g->opt_seen_min;
-            d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch : nullptr;
+            d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch.template as<uint8_t>() : nullptr;
             last_walker = &const_cast<G*>(g)->last_walker;
             last_compact = &const_cast<G*>(g)->last_compact;
             se = g->se.get();
@@ -1274,8 +1234,7 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     if (c.nq == 0) return GRANNE_HIP_OK;
     if (c.n_batches > MAX_LAUNCH_BATCHES) return fail(GRANNE_HIP_ERR_INVALID, "at most %u batches per launch", MAX_LAUNCH_BATCHES);
     if (c.n_batches && (uint64_t)c.n_batches * c.nq > 0x7FFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many queries in one launch");
-    DeviceGuard g(T.device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", T.device);
+    GRANNE_HIP_ON_DEVICE(T.device);
     hipStream_t s = c.stream;
     const uint32_t batch_nq = c.nq;
     uint32_t nq = c.nq; // walkers of the launch
@@ -1319,18 +1278,15 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     // The cache's mutex covers finding (or growing) this stream's block and the enqueue -- host work of microseconds.
     // Whatever waits for the GPU (the synchronisation behind slow_count) happens after it is released: host threads
     // searching one index on streams of their own do not queue behind each other's kernels.
-    struct Bury { // (declared before the lock: destroyed after it is released)
-        std::vector<uint8_t*> blocks;
-        ~Bury() {
-            for (auto* b : blocks) (void)hipFree(b); // waits for the device: whatever still used an evicted block is over
-        }
-    } bury;
+    // evicted blocks: declared before the lock, so freed after it is released (hipFree waits for the device: whatever
+    // still used an evicted block is over)
+    std::vector<DevBuf> bury;
     std::unique_lock<std::mutex> cache_lock(T.scratch->mu);
     uint8_t* scratch = nullptr;
     bool transient = false;
     {
         int r = scratch_for(T.scratch, s, total, &scratch, &transient);
-        bury.blocks.swap(T.scratch->graveyard);
+        bury.swap(T.scratch->graveyard);
         if (r) return r;
     }
     struct FreeTransient { // a block of the stream-ordered allocator goes back after the launch's last use of it
@@ -1391,9 +1347,9 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     sp.all = W.walker == GRANNE_HIP_WALKER_EXACT ? 1u : 0u;
     sp.status2 = c.status;
     sp.host_status = c.host_status;
-    p.se_table = T.se ? T.se->d_table : nullptr;
-    p.se_offsets = T.se ? T.se->d_offsets : nullptr;
-    p.se_terms = T.se ? T.se->d_terms : nullptr;
+    p.se_table = T.se ? T.se->d_table.as<float>() : nullptr;
+    p.se_offsets = T.se ? T.se->d_offsets.as<uint64_t>() : nullptr;
+    p.se_terms = T.se ? T.se->d_terms.as<uint32_t>() : nullptr;
     sp.se_x = lane_x ? (float*)(scratch + off_sex) : nullptr;
 
     if (T.last_walker) T.last_walker->store(W.walker);
@@ -1438,7 +1394,7 @@ extern "C" int granne_hip_search_batch_device(const granne_hip_index* ix, const 
                                               float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats,
                                               uint32_t* d_status, void* stream) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    return search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()),
+    return search_launch(SearchTarget(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size()),
                          index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, stream));
 }
 
@@ -1450,7 +1406,7 @@ extern "C" int granne_hip_search_batch_device_timed(const granne_hip_index* ix, 
     SearchCall c = index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, stream);
     c.ev_before = (hipEvent_t)ev_before;
     c.ev_after = (hipEvent_t)ev_after;
-    return search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()), c);
+    return search_launch(SearchTarget(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size()), c);
 }
 
 // A batch in flight beside the caller's stream. begin: the search is ordered after what `stream` holds (an event), runs on
@@ -1465,8 +1421,7 @@ extern "C" int granne_hip_search_begin_device(const granne_hip_index* cix, const
     if (!out_ticket) return fail(GRANNE_HIP_ERR_INVALID, "out_ticket is null");
     if (max_search == 0) return fail(GRANNE_HIP_ERR_INVALID, "max_search must be > 0 (the reference panics, src/index/mod.rs:1019)");
     granne_hip_index* ix = const_cast<granne_hip_index*>(cix);
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     std::lock_guard<std::mutex> lk(ix->flight_mu);
     // any flight that is free, looked for from the one after the last begun (tickets may be ended in any order)
     uint32_t fi = ix->depth;
@@ -1498,7 +1453,7 @@ extern "C" int granne_hip_search_begin_device(const granne_hip_index* cix, const
     }
     HIP_TRY(hipEventRecord(F.ready, (hipStream_t)stream));
     HIP_TRY(hipStreamWaitEvent(F.stream, F.ready, 0));
-    int rc = search_launch(SearchTarget(ix, ix->d_layers, (uint32_t)ix->layers.size()),
+    int rc = search_launch(SearchTarget(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size()),
                            index_call(d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_out_stats, d_status, F.stream));
     if (rc) {
         (void)hipStreamSynchronize(F.stream); // an error return leaves nothing running
@@ -1539,7 +1494,7 @@ extern "C" int granne_hip_search_batches_device(const granne_hip_index* ix, uint
     if (n_batches == 0 || nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_out_counts || (num_neighbors && (!d_out_ids || !d_out_dists)))
         return fail(GRANNE_HIP_ERR_INVALID, "null pointer array");
-    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+    const SearchTarget T(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size());
     // as many batches per launch as keep the launch's walker count within 31 bits (and the kernel argument table)
     uint32_t per = MAX_LAUNCH_BATCHES;
     while (per > 1 && (uint64_t)per * nq > 0x7FFFFFFFull) per >>= 1;
@@ -1575,39 +1530,36 @@ extern "C" int granne_hip_debug_phases(uint64_t* out, uint32_t nq) {
 extern "C" int granne_hip_device_malloc(void** out_ptr, uint64_t bytes, int device_id) {
     if (!out_ptr) return fail(GRANNE_HIP_ERR_INVALID, "out_ptr is null");
     *out_ptr = nullptr;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
-    HIP_TRY(hipMalloc(out_ptr, bytes ? bytes : 16));
+    GRANNE_HIP_ON_DEVICE(device_id);
+    DevBuf b;
+    HIP_TRY(b.alloc(bytes));
+    *out_ptr = b.release(); // the caller's, until granne_hip_device_free
     return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_device_free(void* ptr, int device_id) {
     if (!ptr) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     HIP_TRY(hipFree(ptr));
     return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_copy_to_device(void* d_dst, const void* src, uint64_t bytes, int device_id, void* stream) {
     if (bytes == 0) return GRANNE_HIP_OK;
     if (!d_dst || !src) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_copy_to_host(void* dst, const void* d_src, uint64_t bytes, int device_id, void* stream) {
     if (bytes == 0) return GRANNE_HIP_OK;
     if (!dst || !d_src) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
     return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_stream_create(void** out_stream, int device_id) {
     if (!out_stream) return fail(GRANNE_HIP_ERR_INVALID, "out_stream is null");
     *out_stream = nullptr;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     *out_stream = (void*)s;
@@ -1615,14 +1567,12 @@ extern "C" int granne_hip_stream_create(void** out_stream, int device_id) {
 }
 extern "C" int granne_hip_stream_destroy(void* stream, int device_id) {
     if (!stream) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     HIP_TRY(hipStreamDestroy((hipStream_t)stream));
     return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_stream_synchronize(void* stream, int device_id) {
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return GRANNE_HIP_OK;
 }
@@ -1684,8 +1634,7 @@ constexpr size_t HOST_PIN_BYTES = 256u << 10; // the pinned block of a call cont
 static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32_t nq, uint32_t max_search,
                                uint32_t num_neighbors, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
                                uint64_t* out_stats) {
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
 
     const size_t k = num_neighbors;
     const HostLayout L(ix, nq, k);
@@ -1702,15 +1651,10 @@ static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32
             host_call_release(ix, c);
         }
     } release{ix, c};
-    if (staged && c->h_cap < total) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr;
-        c->h_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->h_pin, HOST_PIN_BYTES + 64, hipHostMallocMapped));
-        c->h_cap = HOST_PIN_BYTES;
-    }
+    if (staged) HIP_TRY(c->h_pin.reserve(HOST_PIN_BYTES + 64, hipHostMallocMapped)); // (+64: the status words behind the block)
+    uint8_t* const h_pin = c->h_pin.as<uint8_t>();
     hipStream_t s = c->stream;
-    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+    const SearchTarget T(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size());
     SearchCall call = index_call(nullptr, nq, max_search, num_neighbors, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     uint32_t slow[2] = {0, 0};
     if (staged) {
@@ -1720,10 +1664,10 @@ static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32
         // scratch block is the caller context's own. What is left on the stream: one memset of the scratch
         // header, the walker, the (normally empty) exact walker, one synchronisation.
         void* dev_pin = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dev_pin, c->h_pin, 0));
+        HIP_TRY(hipHostGetDevicePointer(&dev_pin, h_pin, 0));
         uint8_t* dp = (uint8_t*)dev_pin;
-        uint32_t* hst = (uint32_t*)(c->h_pin + total);
-        memcpy(c->h_pin, queries, qb);
+        uint32_t* hst = (uint32_t*)(h_pin + total);
+        memcpy(h_pin, queries, qb);
         hst[0] = hst[1] = hst[2] = hst[3] = 0;
         call.queries = dp;
         call.ids = (uint64_t*)(dp + o_ids);
@@ -1739,20 +1683,14 @@ static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32
         slow[1] = hst[0]; // its scratch ran out
         ix->last_slow_count.store(slow[0]);
         if (slow[1]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact-search scratch exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
-        memcpy(out_ids, c->h_pin + o_ids, (size_t)nq * k * 8);
-        memcpy(out_dists, c->h_pin + o_d, (size_t)nq * k * 4);
-        memcpy(out_counts, c->h_pin + o_c, (size_t)nq * 4);
-        if (out_stats) memcpy(out_stats, c->h_pin + o_s, (size_t)nq * 24);
+        memcpy(out_ids, h_pin + o_ids, (size_t)nq * k * 8);
+        memcpy(out_dists, h_pin + o_d, (size_t)nq * k * 4);
+        memcpy(out_counts, h_pin + o_c, (size_t)nq * 4);
+        if (out_stats) memcpy(out_stats, h_pin + o_s, (size_t)nq * 24);
         return GRANNE_HIP_OK;
     }
-    if (c->d_cap < total) {
-        if (c->d_buf) (void)hipFree(c->d_buf);
-        c->d_buf = nullptr;
-        c->d_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_buf, total));
-        c->d_cap = total;
-    }
-    uint8_t* buf = c->d_buf;
+    HIP_TRY(c->d_buf.reserve(total));
+    uint8_t* buf = c->d_buf.as<uint8_t>();
     HIP_TRY(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));
     call.queries = buf;
     call.ids = (uint64_t*)(buf + o_ids);
@@ -1781,8 +1719,7 @@ static int search_batch_direct(granne_hip_index* ix, const void* queries, uint32
 // is search_launch's, sized there for the launch's nq (the group's) and kept for the slot's stream. Any non-zero return
 // sends every member to the direct path; the slot's stream is idle when this returns.
 static int search_batch_group(granne_hip_index* ix, unsigned slot, const CombineRequest* const* m, size_t n, uint32_t nq) {
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     const size_t k = m[0]->num_neighbors;
     const size_t row = (size_t)ix->dim * query_elem_size(ix->dtype);
     const HostLayout L(ix, nq, k);
@@ -1795,26 +1732,21 @@ static int search_batch_group(granne_hip_index* ix, unsigned slot, const Combine
             return fail(GRANNE_HIP_ERR_HIP, "cannot create a stream");
         }
     }
-    if (c->h_cap < L.total) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr;
-        c->h_cap = 0;
-        size_t want = HOST_PIN_BYTES;
-        while (want < L.total) want <<= 1;
-        HIP_TRY(hipHostMalloc((void**)&c->h_pin, want + 64, hipHostMallocMapped));
-        c->h_cap = want;
-    }
+    size_t want = HOST_PIN_BYTES;
+    while (want < L.total) want <<= 1;
+    HIP_TRY(c->h_pin.reserve(want + 64, hipHostMallocMapped)); // (+64: the status words behind the block)
+    uint8_t* const h_pin = c->h_pin.as<uint8_t>();
     void* dev_pin = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dev_pin, c->h_pin, 0));
+    HIP_TRY(hipHostGetDevicePointer(&dev_pin, h_pin, 0));
     uint8_t* dp = (uint8_t*)dev_pin;
-    uint32_t* hst = (uint32_t*)(c->h_pin + L.total);
+    uint32_t* hst = (uint32_t*)(h_pin + L.total);
     size_t q0 = 0;
     for (size_t i = 0; i < n; ++i) {
-        memcpy(c->h_pin + q0 * row, m[i]->queries, m[i]->nq * row);
+        memcpy(h_pin + q0 * row, m[i]->queries, m[i]->nq * row);
         q0 += m[i]->nq;
     }
     hst[0] = hst[1] = hst[2] = hst[3] = 0;
-    const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
+    const SearchTarget T(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size());
     SearchCall call = index_call(dp, nq, m[0]->max_search, (uint32_t)k, (uint64_t*)(dp + L.o_ids), (float*)(dp + L.o_d),
                                  (uint32_t*)(dp + L.o_c), (uint64_t*)(dp + L.o_s), nullptr, c->stream);
     call.host_status = (uint32_t*)(dp + L.total);
@@ -1827,10 +1759,10 @@ static int search_batch_group(granne_hip_index* ix, unsigned slot, const Combine
     q0 = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t mq = m[i]->nq;
-        memcpy(m[i]->ids, c->h_pin + L.o_ids + q0 * k * 8, mq * k * 8);
-        memcpy(m[i]->dists, c->h_pin + L.o_d + q0 * k * 4, mq * k * 4);
-        memcpy(m[i]->counts, c->h_pin + L.o_c + q0 * 4, mq * 4);
-        if (m[i]->stats) memcpy(m[i]->stats, c->h_pin + L.o_s + q0 * 24, mq * 24);
+        memcpy(m[i]->ids, h_pin + L.o_ids + q0 * k * 8, mq * k * 8);
+        memcpy(m[i]->dists, h_pin + L.o_d + q0 * k * 4, mq * k * 4);
+        memcpy(m[i]->counts, h_pin + L.o_c + q0 * 4, mq * 4);
+        if (m[i]->stats) memcpy(m[i]->stats, h_pin + L.o_s + q0 * 24, mq * 24);
         q0 += mq;
     }
     return GRANNE_HIP_OK;
@@ -1885,8 +1817,7 @@ extern "C" int granne_hip_normalize_f32_device(float* d_rows, uint64_t n, uint32
     if (!d_rows && n) return fail(GRANNE_HIP_ERR_INVALID, "rows is null");
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     uint32_t lstride = dim | 1u;
     uint32_t rpb = (60u * 1024u) / (lstride * 4u);
     if (rpb > 256) rpb = 256;
@@ -1903,8 +1834,7 @@ extern "C" int granne_hip_quantize_f32_device(const float* d_rows, int8_t* d_out
                                               int device_id, void* stream) {
     if ((!d_rows || !d_out) && n) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipLaunchKernelGGL(quantize_rows_kernel, dim3(grid_for(n * 64, 256)), dim3(256), 0, (hipStream_t)stream, d_rows,
                        d_out, n, dim);
     HIP_TRY(hipGetLastError());
@@ -1918,8 +1848,7 @@ extern "C" int granne_hip_f32_to_f16_device(const float* d_rows, uint16_t* d_out
     if ((!d_rows || !d_out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f32_to_f16: null buffer");
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipLaunchKernelGGL(f32_to_f16_kernel, dim3(grid_for(n * dim, 256)), dim3(256), 0, (hipStream_t)stream, d_rows, d_out, n * dim);
     HIP_TRY(hipGetLastError());
     return GRANNE_HIP_OK;
@@ -1945,8 +1874,7 @@ extern "C" int granne_hip_f16_to_f32_device(const uint16_t* d_rows16, float* d_o
                                             int device_id, void* stream) {
     if ((!d_rows16 || !d_out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f16_to_f32: null buffer");
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     return f16_rows_to_f32((const uint8_t*)d_rows16, (uint64_t)dim * 2u, d_out, n, dim, normalised, (hipStream_t)stream);
 }
 
@@ -1956,23 +1884,16 @@ static int f16_convert_host(const void* in, size_t in_bytes, void* out, size_t o
     if ((!in || !out) && n) return fail(GRANNE_HIP_ERR_INVALID, "f16 conversion: null buffer");
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
-    uint8_t *di = nullptr, *dout = nullptr;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&di, in_bytes));
-        HIP_TRY(hipMalloc((void**)&dout, out_bytes));
-        HIP_TRY(hipMemcpy(di, in, in_bytes, hipMemcpyHostToDevice));
-        int rc = to_half ? granne_hip_f32_to_f16_device((const float*)di, (uint16_t*)dout, n, dim, device_id, nullptr)
-                         : granne_hip_f16_to_f32_device((const uint16_t*)di, (float*)dout, n, dim, normalised, device_id, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost));
-        return GRANNE_HIP_OK;
-    };
-    const int rc = body();
-    if (di) (void)hipFree(di);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    GRANNE_HIP_ON_DEVICE(device_id);
+    DevBuf di, dout;
+    HIP_TRY(di.alloc(in_bytes));
+    HIP_TRY(dout.alloc(out_bytes));
+    HIP_TRY(hipMemcpy(di.get(), in, in_bytes, hipMemcpyHostToDevice));
+    const int rc = to_half ? granne_hip_f32_to_f16_device(di.as<float>(), dout.as<uint16_t>(), n, dim, device_id, nullptr)
+                           : granne_hip_f16_to_f32_device(di.as<uint16_t>(), dout.as<float>(), n, dim, normalised, device_id, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, dout.get(), out_bytes, hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
 }
 extern "C" int granne_hip_f32_to_f16(const float* rows, uint16_t* out, uint64_t n, uint32_t dim, int device_id) {
     return f16_convert_host(rows, (size_t)n * dim * 4, out, (size_t)n * dim * 2, n, dim, 1, 0, device_id);
@@ -1987,22 +1908,21 @@ static int dists_launch(const granne_hip_index* ix, const void* d_queries, const
     GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "dists");
     if (n_pairs == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_ids || !d_out) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t* st = d_status; // optional: count of out-of-range ids
     // eight lanes per pair, 32 pairs per 256-thread block; enough blocks to cover the chip many times
     uint64_t blocks = (n_pairs + 31) / 32;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
     if (ix->dtype == GRANNE_HIP_F16)
-        hipLaunchKernelGGL(dists_kernel<DT_F16>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements,
+        hipLaunchKernelGGL(dists_kernel<DT_F16>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
                            ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     else if (ix->dtype == GRANNE_HIP_F32)
-        hipLaunchKernelGGL(dists_kernel<0>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements,
+        hipLaunchKernelGGL(dists_kernel<0>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
                            ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     else
-        hipLaunchKernelGGL(dists_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements,
+        hipLaunchKernelGGL(dists_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
                            ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     HIP_TRY(hipGetLastError());
@@ -2117,8 +2037,7 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
     if (nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     hipStream_t s = (hipStream_t)stream;
     const uint64_t n = ix->n_elements;
     const uint32_t kk = k + BF_EXTRA < BF_KMAX ? k + BF_EXTRA : BF_KMAX;
@@ -2148,21 +2067,20 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
         granne_hip_index* mix = const_cast<granne_hip_index*>(ix);
         std::lock_guard<std::mutex> lk(mix->norm_mu);
         if (!mix->d_inv_norm) { // (made with the index, make_scan_norms: this is the path of an index that has no layers yet)
-            float* dn = nullptr;
-            HIP_TRY(hipMalloc((void**)&dn, (size_t)inv_norm_bytes(n)));
-            hipLaunchKernelGGL(inv_norm_rows_kernel, dim3(grid_for(n * 8, 256)), dim3(256), 0, s, ix->d_elements, n, ix->row_stride, dn);
+            DevBuf norms;
+            HIP_TRY(norms.alloc((size_t)inv_norm_bytes(n)));
+            float* dn = norms.as<float>();
+            hipLaunchKernelGGL(inv_norm_rows_kernel, dim3(grid_for(n * 8, 256)), dim3(256), 0, s, ix->d_elements.as<uint8_t>(), n, ix->row_stride, dn);
             hipLaunchKernelGGL(inv_gmax_kernel, dim3(grid_for(n_pad / 16 + 1, 256)), dim3(256), 0, s, (const float*)dn, n, dn + n_pad);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                (void)hipFree(dn);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
                 return fail(GRANNE_HIP_ERR_HIP, "inv_norm_rows_kernel failed");
-            }
-            mix->d_inv_norm = dn;
+            mix->d_inv_norm = std::move(norms);
             mix->hbm_bytes += inv_norm_bytes(n);
         }
-        P.inv_norm = mix->d_inv_norm;
-        P.inv_gmax = mix->d_inv_norm + n_pad;
+        P.inv_norm = mix->d_inv_norm.as<float>();
+        P.inv_gmax = P.inv_norm + n_pad;
     }
-    P.elements = ix->d_elements;
+    P.elements = ix->d_elements.as<uint8_t>();
     P.n = n;
     P.row_bytes = ix->row_bytes;
     P.row_stride = ix->row_stride;
@@ -2235,35 +2153,31 @@ extern "C" int granne_hip_brute_force(const granne_hip_index* ix, const void* qu
     if (nq == 0) return GRANNE_HIP_OK;
     if (!queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (k == 0 || k > BF_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", BF_KMAX);
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     const size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
     const size_t o_ids = (qb + 255) & ~(size_t)255, o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + (((size_t)nq * k * 4 + 15) & ~(size_t)15);
     const size_t total = o_c + (size_t)nq * 4;
-    uint8_t* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, total));
-    auto body = [&]() -> int {
-        HIP_TRY(hipMemcpy(buf, queries, qb, hipMemcpyHostToDevice));
-        int rc = granne_hip_brute_force_device(ix, buf, nq, k, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out_ids, buf + o_ids, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_dists, buf + o_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_counts, buf + o_c, (size_t)nq * 4, hipMemcpyDeviceToHost));
-        return GRANNE_HIP_OK;
-    };
-    const int rc = body();
-    (void)hipDeviceSynchronize();
-    (void)hipFree(buf);
-    return rc;
+    DevBuf block;
+    HIP_TRY(block.alloc(total));
+    struct Settle { // (declared after the block: whatever the scan left running is over before the block is freed)
+        ~Settle() { (void)hipDeviceSynchronize(); }
+    } settle;
+    uint8_t* const buf = block.as<uint8_t>();
+    HIP_TRY(hipMemcpy(buf, queries, qb, hipMemcpyHostToDevice));
+    const int rc = granne_hip_brute_force_device(ix, buf, nq, k, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_ids, buf + o_ids, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_dists, buf + o_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counts, buf + o_c, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
 }
 
 extern "C" int granne_hip_synth_rows_device(float* d_out, uint64_t seed, uint64_t row0, uint64_t n, uint32_t dim,
                                             int device_id, void* stream) {
     if (!d_out && n) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipLaunchKernelGGL(synth_rows_kernel, dim3(grid_for(n * dim, 256)), dim3(256), 0, (hipStream_t)stream, d_out, seed,
                        row0, n, dim);
     HIP_TRY(hipGetLastError());
@@ -2287,8 +2201,7 @@ static int merge_launch(const uint8_t* ids, const uint8_t* dists, const uint8_t*
         return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (n_shards == 0 || n_shards > 64) return fail(GRANNE_HIP_ERR_INVALID, "n_shards must be in [1, 64]");
     if (k == 0 || (uint64_t)n_shards * k > 4096) return fail(GRANNE_HIP_ERR_INVALID, "n_shards * k must be in [1, 4096]");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     MergeParams P;
     P.ids = ids;
     P.dists = dists;
@@ -2357,16 +2270,14 @@ extern "C" int granne_hip_search_batch_packed_device(const granne_hip_index* ix,
 extern "C" int granne_hip_normalize_f32(float* rows, uint64_t n, uint32_t dim, int device_id) {
     if (!rows && n) return fail(GRANNE_HIP_ERR_INVALID, "rows is null");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
-    float* d = nullptr;
+    GRANNE_HIP_ON_DEVICE(device_id);
+    DevBuf d;
     size_t bytes = (size_t)n * dim * 4;
-    HIP_TRY(hipMalloc((void**)&d, bytes));
+    HIP_TRY(d.alloc(bytes));
     int rc = GRANNE_HIP_OK;
-    hipError_t e = hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = granne_hip_normalize_f32_device(d, n, dim, device_id, nullptr);
-    if (e == hipSuccess && rc == 0) e = hipMemcpy(rows, d, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    hipError_t e = hipMemcpy(d.get(), rows, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = granne_hip_normalize_f32_device(d.as<float>(), n, dim, device_id, nullptr);
+    if (e == hipSuccess && rc == 0) e = hipMemcpy(rows, d.get(), bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "normalize: %s", hipGetErrorString(e));
     return rc;
 }
@@ -2374,19 +2285,15 @@ extern "C" int granne_hip_normalize_f32(float* rows, uint64_t n, uint32_t dim, i
 extern "C" int granne_hip_quantize_f32(const float* rows, int8_t* out, uint64_t n, uint32_t dim, int device_id) {
     if ((!rows || !out) && n) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (n == 0) return GRANNE_HIP_OK;
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
-    float* d = nullptr;
-    int8_t* o = nullptr;
+    GRANNE_HIP_ON_DEVICE(device_id);
+    DevBuf d, o;
     size_t bytes = (size_t)n * dim * 4;
-    HIP_TRY(hipMalloc((void**)&d, bytes));
-    hipError_t e = hipMalloc((void**)&o, (size_t)n * dim);
+    HIP_TRY(d.alloc(bytes));
+    hipError_t e = o.alloc((size_t)n * dim);
     int rc = GRANNE_HIP_OK;
-    if (e == hipSuccess) e = hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = granne_hip_quantize_f32_device(d, o, n, dim, device_id, nullptr);
-    if (e == hipSuccess && rc == 0) e = hipMemcpy(out, o, (size_t)n * dim, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (o) (void)hipFree(o);
+    if (e == hipSuccess) e = hipMemcpy(d.get(), rows, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = granne_hip_quantize_f32_device(d.as<float>(), o.as<int8_t>(), n, dim, device_id, nullptr);
+    if (e == hipSuccess && rc == 0) e = hipMemcpy(out, o.get(), (size_t)n * dim, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "quantize: %s", hipGetErrorString(e));
     return rc;
 }
@@ -2401,32 +2308,20 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
         if (qidx[i] >= nq) return fail(GRANNE_HIP_ERR_INVALID, "query index out of range");
         if (ids[i] >= ix->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "element id out of range");
     }
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
-    uint8_t *dq = nullptr, *dqi = nullptr, *did = nullptr, *dout = nullptr;
-    auto freeall = [&]() {
-        if (dq) (void)hipFree(dq);
-        if (dqi) (void)hipFree(dqi);
-        if (did) (void)hipFree(did);
-        if (dout) (void)hipFree(dout);
-    };
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&dq, qb));
-        HIP_TRY(hipMalloc((void**)&dqi, n_pairs * 4));
-        HIP_TRY(hipMalloc((void**)&did, n_pairs * 4));
-        HIP_TRY(hipMalloc((void**)&dout, n_pairs * 4));
-        HIP_TRY(hipMemcpy(dq, queries, qb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dqi, qidx, n_pairs * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(did, ids, n_pairs * 4, hipMemcpyHostToDevice));
-        int r = granne_hip_dist_pairs_device(ix, dq, (const uint32_t*)dqi, (const uint32_t*)did, n_pairs, (float*)dout, nullptr);
-        if (r) return r;
-        HIP_TRY(hipMemcpy(out, dout, n_pairs * 4, hipMemcpyDeviceToHost));
-        return GRANNE_HIP_OK;
-    };
-    int rc = body();
-    freeall();
-    return rc;
+    DevBuf dq, dqi, did, dout;
+    HIP_TRY(dq.alloc(qb));
+    HIP_TRY(dqi.alloc(n_pairs * 4));
+    HIP_TRY(did.alloc(n_pairs * 4));
+    HIP_TRY(dout.alloc(n_pairs * 4));
+    HIP_TRY(hipMemcpy(dq.get(), queries, qb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dqi.get(), qidx, n_pairs * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(did.get(), ids, n_pairs * 4, hipMemcpyHostToDevice));
+    int rc = granne_hip_dist_pairs_device(ix, dq.get(), dqi.as<uint32_t>(), did.as<uint32_t>(), n_pairs, dout.as<float>(), nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, dout.get(), n_pairs * 4, hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

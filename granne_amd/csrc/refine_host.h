@@ -26,7 +26,7 @@ static int refine_launch(const granne_hip_index* rx, const void* d_queries, uint
                          const uint32_t* d_cand_counts, uint32_t m, uint32_t k, uint64_t* d_out_ids, float* d_out_dists,
                          uint32_t* d_out_counts, uint32_t* d_refine_status, hipStream_t s) {
     RefineParams P;
-    P.elements = rx->d_elements;
+    P.elements = rx->d_elements.as<uint8_t>();
     P.n_elements = rx->n_elements;
     P.row_bytes = rx->row_bytes;
     P.row_stride = rx->row_stride;
@@ -57,8 +57,7 @@ extern "C" int granne_hip_refine_device(const granne_hip_index* rx, const void* 
     if (rc) return rc;
     if (nq == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_cand_ids || !d_out_ids || !d_out_dists || !d_out_counts) return fail(GRANNE_HIP_ERR_INVALID, "refine: null buffer");
-    DeviceGuard g(rx->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", rx->device);
+    GRANNE_HIP_ON_DEVICE(rx->device);
     return refine_launch(rx, d_queries, nq, d_cand_ids, d_cand_counts, m, k, d_out_ids, d_out_dists, d_out_counts, d_refine_status,
                          (hipStream_t)stream);
 }
@@ -73,8 +72,7 @@ extern "C" int granne_hip_search_refined_batch_device(const granne_hip_index* wx
     if (nq == 0) return GRANNE_HIP_OK;
     if (!d_walk_queries || !d_refine_queries || !d_out_ids || !d_out_dists || !d_out_counts)
         return fail(GRANNE_HIP_ERR_INVALID, "search_refined: null buffer");
-    DeviceGuard g(wx->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", wx->device);
+    GRANNE_HIP_ON_DEVICE(wx->device);
     hipStream_t s = (hipStream_t)stream;
     // the walk's lists: [nq][m] u64 ids, [nq][m] f32 distances (the walk's own, not used), [nq] u32 counts
     const uint32_t m = refine_from;
@@ -86,7 +84,7 @@ extern "C" int granne_hip_search_refined_batch_device(const granne_hip_index* wx
         hipStream_t s;
         ~Release() { (void)hipFreeAsync(p, s); }
     } release{scratch, s};
-    rc = search_launch(SearchTarget(wx, wx->d_layers, (uint32_t)wx->layers.size()),
+    rc = search_launch(SearchTarget(wx, wx->d_layers.as<LayerDev>(), (uint32_t)wx->layers.size()),
                        index_call(d_walk_queries, nq, max_search, m, (uint64_t*)scratch, (float*)(scratch + o_d), (uint32_t*)(scratch + o_c),
                                   d_out_stats, d_status, stream));
     if (rc) return rc;
@@ -104,8 +102,7 @@ extern "C" int granne_hip_search_refined_batch(const granne_hip_index* wx, const
     if (out_refine_status) *out_refine_status = 0;
     if (nq == 0) return GRANNE_HIP_OK;
     if (!walk_queries || !refine_queries || !out_ids || !out_dists || !out_counts) return fail(GRANNE_HIP_ERR_INVALID, "search_refined: null buffer");
-    DeviceGuard g(wx->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", wx->device);
+    GRANNE_HIP_ON_DEVICE(wx->device);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t wqb = (size_t)nq * wx->dim * query_elem_size(wx->dtype), rqb = (size_t)nq * rx->dim * query_elem_size(rx->dtype);
     const size_t o_rq = up(wqb), o_ids = o_rq + up(rqb), o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + up((size_t)nq * k * 4);
@@ -121,14 +118,8 @@ extern "C" int granne_hip_search_refined_batch(const granne_hip_index* wx, const
             host_call_release(ix, c);
         }
     } release{mwx, c};
-    if (c->d_cap < total) {
-        if (c->d_buf) (void)hipFree(c->d_buf);
-        c->d_buf = nullptr;
-        c->d_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_buf, total));
-        c->d_cap = total;
-    }
-    uint8_t* buf = c->d_buf;
+    HIP_TRY(c->d_buf.reserve(total));
+    uint8_t* buf = c->d_buf.as<uint8_t>();
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(buf, walk_queries, wqb, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(buf + o_rq, refine_queries, rqb, hipMemcpyHostToDevice, s));

@@ -94,90 +94,64 @@ __global__ __launch_bounds__(64) void remap_rows_kernel(const uint32_t* __restri
 
 namespace {
 
+// everything a reorder allocates besides the index's new buffers: owned by the entry point, which frees it once its
+// stream is idle
 struct ReorderScratch {
-    std::vector<void*> ptrs;
-    ~ReorderScratch() {
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T** out, size_t count) {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, count ? count * sizeof(T) : 16);
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = (T*)p;
-        return e;
-    }
+    DevBuf order, rev, order64;                            // the order (u32), its inverse (u32), the order as u64
+    DevBuf inv, trail, perm_b, keys_a, keys_b, overflow;   // Granne::reorder: compute_order's columns
+    DevBuf iota, keys, keys_out;                           // reorder_by_keys
+    DevBuf sort_tmp;
 };
 
 // stable sort of (keys, vals) by the full 64-bit key
-static int sort_pairs_u64(ReorderScratch& S, uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in,
-                          uint32_t* vals_out, uint64_t n, void*& tmp, size_t& tmp_bytes, hipStream_t s) {
+static int sort_pairs_u64(DevBuf& tmp, uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, uint64_t n,
+                          hipStream_t s) {
     size_t need = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 64, s));
-    if (need > tmp_bytes) {
-        HIP_TRY(S.alloc((uint8_t**)&tmp, need));
-        tmp_bytes = need;
+    if (need > tmp.capacity()) {
+        HIP_TRY(hipStreamSynchronize(s)); // (earlier sorts on this stream still use the smaller block)
+        HIP_TRY(tmp.alloc(need));
     }
-    size_t use = tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, use, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 64, s));
+    size_t use = tmp.capacity();
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), use, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 64, s));
     return GRANNE_HIP_OK;
 }
 
-// reorder_layers + elements.permute with a device order (u32, all of [0, n))
-static int apply_order(granne_hip_index* ix, const uint32_t* d_order, ReorderScratch& S, hipStream_t s) {
+// reorder_layers + elements.permute with the device order S.order (u32, all of [0, n))
+static int apply_order(granne_hip_index* ix, ReorderScratch& S, hipStream_t s) {
     using namespace granne_hip;
     const uint64_t n = ix->n_elements;
-    uint32_t* d_rev = nullptr;
-    HIP_TRY(S.alloc(&d_rev, n));
+    const uint32_t* d_order = S.order.as<uint32_t>();
+    HIP_TRY(S.rev.alloc(n * 4));
+    uint32_t* d_rev = S.rev.as<uint32_t>();
     hipLaunchKernelGGL(scatter_inverse_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_order, n, 0u, d_rev);
     HIP_TRY(hipGetLastError());
     // new buffers first, swap only once everything has been produced
-    std::vector<uint32_t*> new_adj(ix->layers.size(), nullptr);
-    uint8_t* new_el = nullptr;
-    auto drop = [&]() {
-        for (auto p : new_adj)
-            if (p) (void)hipFree(p);
-        if (new_el) (void)hipFree(new_el);
-    };
-    auto body = [&]() -> int {
-        for (size_t l = 0; l < ix->layers.size(); ++l) {
-            const LayerHost& L = ix->layers[l];
-            size_t bytes = (size_t)L.len * L.dev_width * 4;
-            HIP_TRY(hipMalloc((void**)&new_adj[l], bytes ? bytes : 16));
-            if (L.len == 0) continue;
-            uint32_t grid = L.len < 65536 ? (uint32_t)L.len : 65536u;
-            hipLaunchKernelGGL(remap_rows_kernel, dim3(grid), dim3(64), L.dev_width * 4, s, L.d_adj, new_adj[l], d_order,
-                               d_rev, L.len, L.dev_width);
-            HIP_TRY(hipGetLastError());
-        }
-        size_t el_bytes = (size_t)n * ix->row_stride;
-        HIP_TRY(hipMalloc((void**)&new_el, el_bytes ? el_bytes : 16));
-        if (n) {
-            hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_for(n * (ix->row_stride >> 4), 256)), dim3(256), 0, s,
-                               ix->d_elements, new_el, d_order, n, ix->row_stride);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        return GRANNE_HIP_OK;
-    };
-    int rc = body();
-    if (rc) {
-        drop();
-        return rc;
-    }
+    std::vector<DevBuf> new_adj(ix->layers.size());
+    DevBuf new_el;
     for (size_t l = 0; l < ix->layers.size(); ++l) {
-        (void)hipFree(ix->layers[l].d_adj);
-        ix->layers[l].d_adj = new_adj[l];
+        const LayerHost& L = ix->layers[l];
+        HIP_TRY(new_adj[l].alloc((size_t)L.len * L.dev_width * 4));
+        if (L.len == 0) continue;
+        uint32_t grid = L.len < 65536 ? (uint32_t)L.len : 65536u;
+        hipLaunchKernelGGL(remap_rows_kernel, dim3(grid), dim3(64), L.dev_width * 4, s, L.d_adj.as<uint32_t>(),
+                           new_adj[l].as<uint32_t>(), d_order, d_rev, L.len, L.dev_width);
+        HIP_TRY(hipGetLastError());
     }
-    (void)hipFree(ix->d_elements);
-    ix->d_elements = new_el;
+    HIP_TRY(new_el.alloc((size_t)n * ix->row_stride));
+    if (n) {
+        hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_for(n * (ix->row_stride >> 4), 256)), dim3(256), 0, s,
+                           ix->d_elements.as<uint8_t>(), new_el.as<uint8_t>(), d_order, n, ix->row_stride);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t l = 0; l < ix->layers.size(); ++l) ix->layers[l].d_adj = std::move(new_adj[l]);
+    ix->d_elements = std::move(new_el);
     {   // the rows have moved: the scan's per-row norms are taken again when it next runs
         std::lock_guard<std::mutex> lk(ix->norm_mu);
         if (ix->d_inv_norm) {
-            (void)hipFree(ix->d_inv_norm);
+            ix->d_inv_norm.reset();
             ix->hbm_bytes -= inv_norm_bytes(ix->n_elements);
-            ix->d_inv_norm = nullptr;
         }
     }
     return finish_layers(ix, s); // (the walkers' copies of the layers, LayerDev::adjx, are made again there)
@@ -194,135 +168,134 @@ static int reorder_precheck(granne_hip_index* ix) {
     return GRANNE_HIP_OK;
 }
 
-static int order_to_host(const uint32_t* d_order, uint64_t n, uint64_t* out_order, ReorderScratch& S, hipStream_t s) {
+static int order_to_host(uint64_t n, uint64_t* out_order, ReorderScratch& S, hipStream_t s) {
     if (!out_order || n == 0) return GRANNE_HIP_OK;
-    uint64_t* d64 = nullptr;
-    HIP_TRY(S.alloc(&d64, n));
-    hipLaunchKernelGGL(granne_hip::widen_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_order, n, d64);
+    HIP_TRY(S.order64.alloc(n * 8));
+    hipLaunchKernelGGL(granne_hip::widen_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, S.order.as<uint32_t>(), n,
+                       S.order64.as<uint64_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_order, d64, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_order, S.order64.get(), n * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return GRANNE_HIP_OK;
+}
+
+// Granne::reorder on stream s (the index checked, its device selected)
+static int reorder_on(granne_hip_index* ix, uint64_t* out_order, ReorderScratch& S, hipStream_t s) {
+    using namespace granne_hip;
+    const uint32_t n_layers = (uint32_t)ix->layers.size();
+    const uint64_t n = ix->n_elements;
+    const uint64_t inv_len = ix->layers[n_layers - 2].len;
+    uint64_t widest = 0;
+    for (uint32_t l = 1; l < n_layers; ++l) widest = std::max(widest, ix->layers[l].len - ix->layers[l - 1].len);
+    HIP_TRY(S.order.alloc(n * 4));
+    HIP_TRY(S.inv.alloc(inv_len * 4));
+    HIP_TRY(S.trail.alloc(widest * TRAIL_WIDTH * 4));
+    HIP_TRY(S.perm_b.alloc(widest * 4));
+    HIP_TRY(S.keys_a.alloc(widest * 8));
+    HIP_TRY(S.keys_b.alloc(widest * 8));
+    HIP_TRY(S.overflow.alloc(16));
+    uint32_t *d_order = S.order.as<uint32_t>(), *d_inv = S.inv.as<uint32_t>(), *d_trail = S.trail.as<uint32_t>();
+    uint32_t *d_perm_b = S.perm_b.as<uint32_t>(), *d_overflow = S.overflow.as<uint32_t>();
+    uint64_t *d_keys_a = S.keys_a.as<uint64_t>(), *d_keys_b = S.keys_b.as<uint64_t>();
+    HIP_TRY(hipMemsetAsync(d_inv, 0, inv_len * 4, s));     // vec![0; layer_len(num_layers - 2)], :137
+    HIP_TRY(hipMemsetAsync(d_overflow, 0, 16, s));
+    hipLaunchKernelGGL(iota_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_order, n, 0u); // :136
+    HIP_TRY(hipGetLastError());
+    const SearchTarget T(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size());
+    SearchCall call; // the trail walks: max_search 1
+    call.q_stride = ix->row_stride;
+    call.ef = call.k = 1;
+    call.status = d_overflow;
+    call.stream = s;
+    call.trail = d_trail;
+    for (uint32_t layer = 1; layer < n_layers; ++layer) { // :149
+        const uint64_t lo = ix->layers[layer - 1].len, hi = ix->layers[layer].len;
+        const uint64_t m = hi - lo;
+        if (m == 0) continue;
+        // find_entrypoint_trail for every idx in [lo, hi); the element rows are the queries
+        call.queries = ix->d_elements.as<uint8_t>() + (size_t)lo * ix->row_stride;
+        call.nq = (uint32_t)m;
+        call.trail_layers = layer;
+        int r = search_launch(T, call);
+        if (r) return r;
+        // (eps, idx) ascending: LSD over the column pairs, starting from idx order
+        uint32_t* perm = d_order + lo; // holds lo..hi-1 from the iota
+        uint32_t* other = d_perm_b;
+        const uint32_t cols = layer < TRAIL_WIDTH ? layer : TRAIL_WIDTH; // columns beyond map to order_inv[0] for all
+        for (int c = (int)((cols - 1) & ~1u); c >= 0; c -= 2) {
+            hipLaunchKernelGGL(trail_keys_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, d_trail, perm, d_inv, m,
+                               (uint32_t)lo, (uint32_t)c, d_keys_a);
+            HIP_TRY(hipGetLastError());
+            r = sort_pairs_u64(S.sort_tmp, d_keys_a, d_keys_b, perm, other, m, s);
+            if (r) return r;
+            std::swap(perm, other);
+        }
+        if (perm != d_order + lo) HIP_TRY(hipMemcpyAsync(d_order + lo, perm, m * 4, hipMemcpyDeviceToDevice, s));
+        if (layer < n_layers - 1) { // :167-171
+            hipLaunchKernelGGL(scatter_inverse_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, d_order + lo, m,
+                               (uint32_t)lo, d_inv);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    uint32_t h_over[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_over, d_overflow, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_over[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "a trail walk outgrew the slow-path containers (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
+    int r = order_to_host(n, out_order, S, s);
+    if (r) return r;
+    return apply_order(ix, S, s);
+}
+
+// reorder_by_keys on stream s (the index checked, its device selected)
+static int reorder_by_keys_on(granne_hip_index* ix, const uint64_t* keys, uint64_t* out_order, ReorderScratch& S, hipStream_t s) {
+    using namespace granne_hip;
+    const uint64_t n = ix->n_elements;
+    HIP_TRY(S.iota.alloc(n * 4));
+    HIP_TRY(S.order.alloc(n * 4));
+    HIP_TRY(S.keys.alloc(n * 8));
+    HIP_TRY(S.keys_out.alloc(n * 8));
+    uint32_t *d_iota = S.iota.as<uint32_t>(), *d_order = S.order.as<uint32_t>();
+    uint64_t *d_keys = S.keys.as<uint64_t>(), *d_keys_out = S.keys_out.as<uint64_t>();
+    HIP_TRY(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(iota_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_iota, n, 0u);
+    HIP_TRY(hipGetLastError());
+    for (size_t layer = 0; layer < ix->layers.size(); ++layer) { // reorder.rs:96-104: (key, idx) within each layer
+        const uint64_t lo = layer ? ix->layers[layer - 1].len : 0, hi = ix->layers[layer].len;
+        if (hi == lo) continue;
+        int r = sort_pairs_u64(S.sort_tmp, d_keys + lo, d_keys_out + lo, d_iota + lo, d_order + lo, hi - lo, s);
+        if (r) return r;
+    }
+    int r = order_to_host(n, out_order, S, s);
+    if (r) return r;
+    return apply_order(ix, S, s);
 }
 
 } // namespace
 
 extern "C" int granne_hip_index_reorder(granne_hip_index* ix, uint64_t* out_order) {
-    using namespace granne_hip;
     int rc = reorder_precheck(ix);
     if (rc) return rc;
-    const uint32_t n_layers = (uint32_t)ix->layers.size();
-    if (n_layers < 2)
+    if (ix->layers.size() < 2)
         return fail(GRANNE_HIP_ERR_INVALID, "reorder needs at least two layers (the reference panics, src/index/reorder.rs:137)");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     ReorderScratch S;
-    auto body = [&]() -> int {
-        const uint64_t n = ix->n_elements;
-        const uint64_t inv_len = ix->layers[n_layers - 2].len;
-        uint64_t widest = 0;
-        for (uint32_t l = 1; l < n_layers; ++l) widest = std::max(widest, ix->layers[l].len - ix->layers[l - 1].len);
-        uint32_t *d_order = nullptr, *d_inv = nullptr, *d_trail = nullptr, *d_perm_b = nullptr, *d_overflow = nullptr;
-        uint64_t *d_keys_a = nullptr, *d_keys_b = nullptr;
-        HIP_TRY(S.alloc(&d_order, n));
-        HIP_TRY(S.alloc(&d_inv, inv_len));
-        HIP_TRY(S.alloc(&d_trail, widest * TRAIL_WIDTH));
-        HIP_TRY(S.alloc(&d_perm_b, widest));
-        HIP_TRY(S.alloc(&d_keys_a, widest));
-        HIP_TRY(S.alloc(&d_keys_b, widest));
-        HIP_TRY(S.alloc(&d_overflow, 4));
-        HIP_TRY(hipMemsetAsync(d_inv, 0, inv_len * 4, s));     // vec![0; layer_len(num_layers - 2)], :137
-        HIP_TRY(hipMemsetAsync(d_overflow, 0, 16, s));
-        hipLaunchKernelGGL(iota_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_order, n, 0u); // :136
-        HIP_TRY(hipGetLastError());
-        void* tmp = nullptr;
-        size_t tmp_bytes = 0;
-        const SearchTarget T(ix, ix->d_layers, (uint32_t)ix->layers.size());
-        SearchCall call; // the trail walks: max_search 1
-        call.q_stride = ix->row_stride;
-        call.ef = call.k = 1;
-        call.status = d_overflow;
-        call.stream = s;
-        call.trail = d_trail;
-        for (uint32_t layer = 1; layer < n_layers; ++layer) { // :149
-            const uint64_t lo = ix->layers[layer - 1].len, hi = ix->layers[layer].len;
-            const uint64_t m = hi - lo;
-            if (m == 0) continue;
-            // find_entrypoint_trail for every idx in [lo, hi); the element rows are the queries
-            call.queries = ix->d_elements + (size_t)lo * ix->row_stride;
-            call.nq = (uint32_t)m;
-            call.trail_layers = layer;
-            int r = search_launch(T, call);
-            if (r) return r;
-            // (eps, idx) ascending: LSD over the column pairs, starting from idx order
-            uint32_t* perm = d_order + lo; // holds lo..hi-1 from the iota
-            uint32_t* other = d_perm_b;
-            const uint32_t cols = layer < TRAIL_WIDTH ? layer : TRAIL_WIDTH; // columns beyond map to order_inv[0] for all
-            for (int c = (int)((cols - 1) & ~1u); c >= 0; c -= 2) {
-                hipLaunchKernelGGL(trail_keys_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, d_trail, perm, d_inv, m,
-                                   (uint32_t)lo, (uint32_t)c, d_keys_a);
-                HIP_TRY(hipGetLastError());
-                r = sort_pairs_u64(S, d_keys_a, d_keys_b, perm, other, m, tmp, tmp_bytes, s);
-                if (r) return r;
-                std::swap(perm, other);
-            }
-            if (perm != d_order + lo) HIP_TRY(hipMemcpyAsync(d_order + lo, perm, m * 4, hipMemcpyDeviceToDevice, s));
-            if (layer < n_layers - 1) { // :167-171
-                hipLaunchKernelGGL(scatter_inverse_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, d_order + lo, m,
-                                   (uint32_t)lo, d_inv);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        uint32_t h_over[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(h_over, d_overflow, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h_over[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "a trail walk outgrew the slow-path containers (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
-        int r = order_to_host(d_order, n, out_order, S, s);
-        if (r) return r;
-        return apply_order(ix, d_order, S, s);
-    };
-    rc = body();
+    rc = reorder_on(ix, out_order, S, s);
     (void)hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
     return rc;
 }
 
 extern "C" int granne_hip_index_reorder_by_keys(granne_hip_index* ix, const uint64_t* keys, uint64_t* out_order) {
-    using namespace granne_hip;
     int rc = reorder_precheck(ix);
     if (rc) return rc;
     if (!keys && ix->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "keys is null");
-    DeviceGuard g(ix->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", ix->device);
+    GRANNE_HIP_ON_DEVICE(ix->device);
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     ReorderScratch S;
-    auto body = [&]() -> int {
-        const uint64_t n = ix->n_elements;
-        uint32_t *d_iota = nullptr, *d_order = nullptr;
-        uint64_t *d_keys = nullptr, *d_keys_out = nullptr;
-        HIP_TRY(S.alloc(&d_iota, n));
-        HIP_TRY(S.alloc(&d_order, n));
-        HIP_TRY(S.alloc(&d_keys, n));
-        HIP_TRY(S.alloc(&d_keys_out, n));
-        HIP_TRY(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(iota_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_iota, n, 0u);
-        HIP_TRY(hipGetLastError());
-        void* tmp = nullptr;
-        size_t tmp_bytes = 0;
-        for (size_t layer = 0; layer < ix->layers.size(); ++layer) { // reorder.rs:96-104: (key, idx) within each layer
-            const uint64_t lo = layer ? ix->layers[layer - 1].len : 0, hi = ix->layers[layer].len;
-            if (hi == lo) continue;
-            int r = sort_pairs_u64(S, d_keys + lo, d_keys_out + lo, d_iota + lo, d_order + lo, hi - lo, tmp, tmp_bytes, s);
-            if (r) return r;
-        }
-        int r = order_to_host(d_order, n, out_order, S, s);
-        if (r) return r;
-        return apply_order(ix, d_order, S, s);
-    };
-    rc = body();
+    rc = reorder_by_keys_on(ix, keys, out_order, S, s);
     (void)hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
     return rc;

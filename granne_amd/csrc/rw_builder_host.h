@@ -61,12 +61,11 @@ struct granne_hip_rw_builder {
     // insert / promotion hold it exclusively, everything that reads holds it shared, for the whole call
     RwGate mu;
     hipStream_t stream = nullptr; // inserts
-    BuildScratch S;               // sized for batch_cap members (d_layers and selected stay null in it: they are below)
+    BuildScratch S;               // sized for batch_cap members (d_layers and selected stay empty in it: they are below)
     uint64_t batch_cap = 0;
-    LayerDev* d_layers = nullptr; // [64]
-    uint8_t* selected = nullptr;  // [current layer's cap_rows]
-    void* d_stage = nullptr;      // dense rows of an insert call on their way into the element rows
-    size_t stage_cap = 0;
+    DevBuf d_layers; // LayerDev [64]
+    DevBuf selected; // uint8_t [current layer's cap_rows]
+    DevBuf d_stage;  // dense rows of an insert call on their way into the element rows
     uint64_t opt_small_ops = RW_SMALL_OPS;
     std::atomic<uint64_t> small_launches{0}, sorted_launches{0};
     // host-pointer searches: a stream and a device buffer per concurrent caller, kept for the life of the handle
@@ -83,18 +82,14 @@ static void rw_destroy(granne_hip_rw_builder* rw) {
             (void)hipStreamSynchronize(rw->stream);
             (void)hipStreamDestroy(rw->stream);
         }
-        rw->S.free_all();
-        if (rw->d_layers) (void)hipFree(rw->d_layers);
-        if (rw->selected) (void)hipFree(rw->selected);
-        if (rw->d_stage) (void)hipFree(rw->d_stage);
         for (auto* c : rw->call_free) {
             if (c->stream) (void)hipStreamDestroy(c->stream);
-            if (c->d_buf) (void)hipFree(c->d_buf);
             delete c;
         }
+        granne_hip_builder* b = rw->b;
+        delete rw; // (its memory goes here, under the guard, after the streams)
+        destroy_builder(b);
     }
-    destroy_builder(rw->b);
-    delete rw;
 }
 
 // the layer table the walkers read: previous layers, then the current one with all its (UNUSED-filled) capacity --
@@ -103,7 +98,7 @@ static int rw_upload_layers(granne_hip_rw_builder* rw) {
     const granne_hip_builder* b = rw->b;
     std::vector<LayerDev> h(b->layers.size());
     for (size_t l = 0; l < h.size(); ++l) {
-        h[l].adj = b->layers[l].d_adj;
+        h[l].adj = b->layers[l].d_adj.as<uint32_t>();
         h[l].len = l + 1 < h.size() ? b->layers[l].len : b->layers[l].cap_rows;
         h[l].width = b->W;
         h[l].flags = 0; // connect_nodes never lists a neighbor twice (mod.rs:913-917)
@@ -111,7 +106,7 @@ static int rw_upload_layers(granne_hip_rw_builder* rw) {
         h[l].adjx_stride = 0;
         h[l].reserved = 0;
     }
-    HIP_TRY(hipMemcpyAsync(rw->d_layers, h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, rw->stream));
+    HIP_TRY(hipMemcpyAsync(rw->d_layers.get(), h.data(), sizeof(LayerDev) * h.size(), hipMemcpyHostToDevice, rw->stream));
     HIP_TRY(hipStreamSynchronize(rw->stream));
     return GRANNE_HIP_OK;
 }
@@ -121,31 +116,20 @@ static int rw_make_current(granne_hip_rw_builder* rw, const BuilderLayer* from, 
                            BuilderLayer* out) {
     granne_hip_builder* b = rw->b;
     hipStream_t s = rw->stream;
-    uint32_t* adj = nullptr;
-    uint8_t* sel = nullptr;
+    DevBuf adj, sel;
     const size_t bytes = (size_t)rows * b->W * 4;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&adj, bytes ? bytes : 16));
-        HIP_TRY(hipMalloc((void**)&sel, rows ? rows : 1));
-        if (bytes) HIP_TRY(hipMemsetAsync(adj, 0xFF, bytes, s));
-        HIP_TRY(hipMemsetAsync(sel, 0, rows ? rows : 1, s));
-        if (keep) {
-            HIP_TRY(hipMemcpyAsync(adj, from->d_adj, (size_t)keep * b->W * 4, hipMemcpyDeviceToDevice, s));
-            if (rw->selected) HIP_TRY(hipMemcpyAsync(sel, rw->selected, keep, hipMemcpyDeviceToDevice, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        return GRANNE_HIP_OK;
-    };
-    int rc = body();
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        if (adj) (void)hipFree(adj);
-        if (sel) (void)hipFree(sel);
-        return rc;
+    SettleStream settle{s}; // (declared after the two: the stream is idle before an early return frees them)
+    HIP_TRY(adj.alloc(bytes));
+    HIP_TRY(sel.alloc(rows));
+    if (bytes) HIP_TRY(hipMemsetAsync(adj.get(), 0xFF, bytes, s));
+    HIP_TRY(hipMemsetAsync(sel.get(), 0, rows ? rows : 1, s));
+    if (keep) {
+        HIP_TRY(hipMemcpyAsync(adj.get(), from->d_adj.get(), (size_t)keep * b->W * 4, hipMemcpyDeviceToDevice, s));
+        if (rw->selected) HIP_TRY(hipMemcpyAsync(sel.get(), rw->selected.get(), keep, hipMemcpyDeviceToDevice, s));
     }
-    if (rw->selected) (void)hipFree(rw->selected);
-    rw->selected = sel;
-    out->d_adj = adj;
+    HIP_TRY(hipStreamSynchronize(s));
+    rw->selected = std::move(sel);
+    out->d_adj = std::move(adj);
     out->len = keep;
     out->cap_rows = rows;
     b->hbm_bytes += bytes;
@@ -163,8 +147,7 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     if (b->se)
         return fail(GRANNE_HIP_ERR_INVALID, "an RwGranneBuilder over a SumEmbeddings container is not supported: make the "
                     "builder from dense rows (granne_hip_builder_create)");
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
 
     // builder.config.expected_num_elements = Some(max_elements); builder.build(), :34-36
     const uint64_t expected_before = b->cfg.expected_num_elements;
@@ -177,16 +160,16 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     granne_hip_rw_builder* rw = new granne_hip_rw_builder();
     const uint64_t n = b->n_elements;
     BuilderLayer cur;
-    uint8_t* grown = nullptr;
-    auto body = [&]() -> int {
+    DevBuf grown;
+    auto body = [&]() -> int { // (a commit point: the builder becomes the handle's only once all of this has been made)
         HIP_TRY(hipStreamCreateWithFlags(&rw->stream, hipStreamNonBlocking));
-        HIP_TRY(hipMalloc((void**)&rw->d_layers, sizeof(LayerDev) * 64));
+        HIP_TRY(rw->d_layers.alloc(sizeof(LayerDev) * 64));
         // element storage for max(max_elements, n) rows, once: an insert writes its rows in place
         rw->elem_cap = max_elements > n ? max_elements : n;
         const size_t eb = (size_t)rw->elem_cap * b->row_stride;
-        HIP_TRY(hipMalloc((void**)&grown, eb));
-        HIP_TRY(hipMemsetAsync(grown, 0, eb, rw->stream));
-        if (n) HIP_TRY(hipMemcpyAsync(grown, b->d_elements, (size_t)n * b->row_stride, hipMemcpyDeviceToDevice, rw->stream));
+        HIP_TRY(grown.alloc(eb));
+        HIP_TRY(hipMemsetAsync(grown.get(), 0, eb, rw->stream));
+        if (n) HIP_TRY(hipMemcpyAsync(grown.get(), b->d_elements.get(), (size_t)n * b->row_stride, hipMemcpyDeviceToDevice, rw->stream));
         HIP_TRY(hipStreamSynchronize(rw->stream));
         // builder.layers.pop() or an empty layer, resized to max(len, compute_num_elements_in_layer(max_elements,
         // multiplier, layers.len())) rows of UNUSED, :38-48
@@ -202,7 +185,6 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     };
     rc = body();
     if (rc) {
-        if (grown) (void)hipFree(grown);
         b->cfg.expected_num_elements = expected_before;
         rw_destroy(rw); // (rw->b is null: the builder stays the caller's)
         return rc;
@@ -210,16 +192,13 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     // from here on the builder is the handle's
     rw->b = b;
     rw->max_elements = max_elements;
-    if (b->d_elements) (void)hipFree(b->d_elements);
     b->hbm_bytes += (size_t)(rw->elem_cap - n) * b->row_stride;
-    b->d_elements = grown;
+    b->d_elements = std::move(grown);
     if (!b->layers.empty()) {
-        BuilderLayer& old = b->layers.back();
-        b->hbm_bytes -= (size_t)old.cap_rows * b->W * 4;
-        if (old.d_adj) (void)hipFree(old.d_adj);
+        b->hbm_bytes -= (size_t)b->layers.back().cap_rows * b->W * 4;
         b->layers.pop_back();
     }
-    b->layers.push_back(cur);
+    b->layers.push_back(std::move(cur));
     rc = rw_upload_layers(rw);
     if (rc) { // (a failed copy of a few hundred bytes: the device is gone; the handle owns the builder by now)
         rw_destroy(rw);
@@ -240,25 +219,10 @@ static int rw_ensure_scratch(granne_hip_rw_builder* rw, uint64_t members) {
     if (cap > b->cfg.batch_max) cap = b->cfg.batch_max;
     if (cap < members) cap = members;
     HIP_TRY(hipStreamSynchronize(rw->stream));
-    rw->S.free_all();
-    rw->S = BuildScratch();
+    rw->S = BuildScratch(); // (the smaller blocks go first)
     rw->batch_cap = 0;
-    BuildScratch& S = rw->S;
-    const uint32_t ms = b->cfg.max_search;
-    const uint64_t n_ops_max = cap * b->cfg.num_neighbors * 2;
-    HIP_TRY(hipMalloc((void**)&S.s_ids, cap * ms * 8));
-    HIP_TRY(hipMalloc((void**)&S.s_dists, cap * ms * 4));
-    HIP_TRY(hipMalloc((void**)&S.s_counts, cap * 4));
-    HIP_TRY(hipMalloc((void**)&S.op_keys, n_ops_max * 8));
-    HIP_TRY(hipMalloc((void**)&S.op_vals, n_ops_max * 8));
-    HIP_TRY(hipMalloc((void**)&S.sorted_keys, n_ops_max * 8));
-    HIP_TRY(hipMalloc((void**)&S.sorted_vals, n_ops_max * 8));
-    HIP_TRY(hipMalloc((void**)&S.seg_start, n_ops_max * 4));
-    HIP_TRY(hipMalloc((void**)&S.counters, 32));
-    HIP_TRY(hipMemsetAsync(S.counters, 0, 32, rw->stream));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, S.sort_tmp_bytes, S.op_keys, S.sorted_keys, S.op_vals, S.sorted_vals,
-                                               (int)n_ops_max, 0, OP_KEY_BITS, rw->stream));
-    HIP_TRY(hipMalloc(&S.sort_tmp, S.sort_tmp_bytes ? S.sort_tmp_bytes : 16));
+    int rc = alloc_batch_scratch(rw->S, cap, b->cfg.max_search, cap * b->cfg.num_neighbors * 2, rw->stream);
+    if (rc) return rc;
     rw->batch_cap = cap;
     return GRANNE_HIP_OK;
 }
@@ -289,20 +253,20 @@ static int rw_index_elements(granne_hip_rw_builder* rw, uint64_t first, uint64_t
     BuildPlan plan;
     {
         // num_neighbors is the config's on every layer (rw/mod.rs:162 passes self.config): m_layer = cap
-        int rc = make_build_plan(b, L, cap, max_search, S, rw->selected, &plan);
+        int rc = make_build_plan(b, L, cap, max_search, S, rw->selected.as<uint8_t>(), &plan);
         if (rc) return rc;
     }
     BuildParams& P = plan.P;
     P.layer_len = L.cap_rows;
     P.idx_step = 1;
 
-    const SearchTarget T(b, rw->d_layers, (uint32_t)b->layers.size());
+    const SearchTarget T(b, rw->d_layers.as<LayerDev>(), (uint32_t)b->layers.size());
     SearchCall call; // entry through the previous layers at (1, 1), or id 0; search_for_neighbors on the current layer
     call.ef = call.k = max_search;
-    call.ids = S.s_ids;
-    call.dists = S.s_dists;
-    call.counts = S.s_counts;
-    call.status = S.counters + 1;
+    call.ids = S.s_ids.as<uint64_t>();
+    call.dists = S.s_dists.as<float>();
+    call.counts = S.s_counts.as<uint32_t>();
+    call.status = P.n_seg + 1;
     call.stream = s;
     call.q_stride = (int64_t)b->row_stride;
 
@@ -311,7 +275,7 @@ static int rw_index_elements(granne_hip_rw_builder* rw, uint64_t first, uint64_t
         uint64_t B = rw_sub_batch(b, first + pos);
         if (B > count - pos) B = count - pos;
         // phase A: every member searches the graph as it stands now, then select_neighbors
-        call.queries = b->d_elements + (size_t)(first + pos) * b->row_stride;
+        call.queries = P.elements + (size_t)(first + pos) * b->row_stride;
         call.nq = (uint32_t)B;
         int rc = search_launch(T, call);
         if (rc) return rc;
@@ -324,17 +288,17 @@ static int rw_index_elements(granne_hip_rw_builder* rw, uint64_t first, uint64_t
         if (rw->opt_small_ops && P.n_ops <= rw->opt_small_ops) {
             uint32_t threads = 64;
             while (threads < 1024 && threads * 2 < P.n_ops) threads <<= 1;
-            hipLaunchKernelGGL(sort_ops_small_kernel, dim3(1), dim3(threads), 0, s, S.op_keys, S.op_vals, P.n_ops, S.sorted_keys,
-                               S.sorted_vals, S.seg_start, S.counters);
+            hipLaunchKernelGGL(sort_ops_small_kernel, dim3(1), dim3(threads), 0, s, P.op_keys, P.op_vals, P.n_ops,
+                               S.sorted_keys.as<uint64_t>(), S.sorted_vals.as<uint64_t>(), P.seg_start, P.n_seg);
             HIP_TRY(hipGetLastError());
             rw->small_launches.fetch_add(1);
         } else {
             size_t tmp_bytes = S.sort_tmp_bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp, tmp_bytes, S.op_keys, S.sorted_keys, S.op_vals,
-                                                       S.sorted_vals, (int)P.n_ops, 0, OP_KEY_BITS, s));
-            HIP_TRY(hipMemsetAsync(S.counters, 0, 4, s));
-            hipLaunchKernelGGL(mark_heads_kernel, dim3(grid_for(P.n_ops, 256)), dim3(256), 0, s, S.sorted_keys, P.n_ops,
-                               S.seg_start, S.counters);
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp.get(), tmp_bytes, P.op_keys, S.sorted_keys.as<uint64_t>(), P.op_vals,
+                                                       S.sorted_vals.as<uint64_t>(), (int)P.n_ops, 0, OP_KEY_BITS, s));
+            HIP_TRY(hipMemsetAsync(P.n_seg, 0, 4, s));
+            hipLaunchKernelGGL(mark_heads_kernel, dim3(grid_for(P.n_ops, 256)), dim3(256), 0, s, P.sorted_keys, P.n_ops,
+                               P.seg_start, P.n_seg);
             HIP_TRY(hipGetLastError());
             rw->sorted_launches.fetch_add(1);
         }
@@ -345,7 +309,7 @@ static int rw_index_elements(granne_hip_rw_builder* rw, uint64_t first, uint64_t
     }
     // no final per-row limit pass (mod.rs:795-797 is index_elements', not reached from rw/mod.rs:159-169), no reinsertion
     uint32_t hc[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(hc, S.counters, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(hc, P.n_seg, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (hc[1]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact-search scratch exhausted during insert");
     return GRANNE_HIP_OK;
@@ -364,7 +328,7 @@ static int rw_promote(granne_hip_rw_builder* rw) {
     BuilderLayer cur;
     int rc = rw_make_current(rw, &full, full.len, rows, &cur);
     if (rc) return rc;
-    b->layers.push_back(cur);
+    b->layers.push_back(std::move(cur));
     return rw_upload_layers(rw);
 }
 
@@ -378,8 +342,7 @@ extern "C" int granne_hip_rw_builder_insert_batch(granne_hip_rw_builder* rw, con
     if (!out_ids) return fail(GRANNE_HIP_ERR_INVALID, "out_ids is null");
     std::unique_lock<RwGate> lk(rw->mu);
     granne_hip_builder* b = rw->b;
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     hipStream_t s = rw->stream;
     const size_t dense = (size_t)b->dim * elem_size(b->dtype);
     const uint8_t* src = (const uint8_t*)rows;
@@ -395,21 +358,16 @@ extern "C" int granne_hip_rw_builder_insert_batch(granne_hip_rw_builder* rw, con
         const uint64_t take = std::min<uint64_t>(remaining, L.cap_rows - len); // :141
         // elements.push, :146-148: the rows go where they stay
         if (dense == b->row_stride) {
-            HIP_TRY(hipMemcpyAsync(b->d_elements + (size_t)len * b->row_stride, src, take * dense, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(b->d_elements.as<uint8_t>() + (size_t)len * b->row_stride, src, take * dense, hipMemcpyHostToDevice, s));
         } else {
-            if (rw->stage_cap < take * dense) {
-                HIP_TRY(hipStreamSynchronize(s));
-                if (rw->d_stage) (void)hipFree(rw->d_stage);
-                rw->d_stage = nullptr;
-                rw->stage_cap = 0;
-                size_t want = take * dense < 4096 ? 4096 : take * dense;
-                HIP_TRY(hipMalloc(&rw->d_stage, want));
-                rw->stage_cap = want;
+            if (rw->d_stage.capacity() < take * dense) {
+                HIP_TRY(hipStreamSynchronize(s)); // (the previous round's relayout still reads the smaller block)
+                HIP_TRY(rw->d_stage.reserve(take * dense < 4096 ? 4096 : take * dense));
             }
-            HIP_TRY(hipMemcpyAsync(rw->d_stage, src, take * dense, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(rw->d_stage.get(), src, take * dense, hipMemcpyHostToDevice, s));
             const uint64_t units = take * (b->row_stride / 16);
-            hipLaunchKernelGGL(relayout_rows_kernel, dim3(grid_for(units, 256)), dim3(256), 0, s, (const uint8_t*)rw->d_stage,
-                               b->d_elements + (size_t)len * b->row_stride, take, (uint32_t)dense, b->row_stride);
+            hipLaunchKernelGGL(relayout_rows_kernel, dim3(grid_for(units, 256)), dim3(256), 0, s, rw->d_stage.as<uint8_t>(),
+                               b->d_elements.as<uint8_t>() + (size_t)len * b->row_stride, take, (uint32_t)dense, b->row_stride);
             HIP_TRY(hipGetLastError());
         }
         b->n_elements = len + take;
@@ -472,8 +430,7 @@ extern "C" int granne_hip_rw_builder_search_batch(granne_hip_rw_builder* rw, con
         if (out_stats) memset(out_stats, 0, (size_t)nq * 24);
         return GRANNE_HIP_OK;
     }
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     const size_t qb = (size_t)nq * b->dim * elem_size(b->dtype);
     const size_t o_ids = (qb + 255) & ~(size_t)255;
     const size_t o_d = o_ids + (size_t)nq * k * 8;
@@ -492,20 +449,14 @@ extern "C" int granne_hip_rw_builder_search_batch(granne_hip_rw_builder* rw, con
             rw->call_free.push_back(c);
         }
     } release{rw, c};
-    if (c->d_cap < total) {
-        if (c->d_buf) (void)hipFree(c->d_buf);
-        c->d_buf = nullptr;
-        c->d_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_buf, total));
-        c->d_cap = total;
-    }
+    HIP_TRY(c->d_buf.reserve(total));
     hipStream_t s = c->stream;
-    uint8_t* buf = c->d_buf;
+    uint8_t* buf = c->d_buf.as<uint8_t>();
     HIP_TRY(hipMemcpyAsync(buf, queries, qb, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(buf + o_st, 0, 16, s));
     // index.search(q, 1, 1) over the previous layers, then search_for_neighbors on the current layer from its result
     // (:198-199) is Granne::search over previous + current: the ordinary walk, over the rows where they are
-    const SearchTarget T(b, rw->d_layers, (uint32_t)b->layers.size());
+    const SearchTarget T(b, rw->d_layers.as<LayerDev>(), (uint32_t)b->layers.size());
     SearchCall call;
     call.queries = buf;
     call.nq = nq;
@@ -565,7 +516,7 @@ extern "C" int granne_hip_rw_builder_get_element(granne_hip_rw_builder* rw, uint
     const granne_hip_builder* b = rw->b;
     if (idx >= b->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "element index out of range");
     DeviceGuard g(b->device);
-    HIP_TRY(hipMemcpy(out, b->d_elements + idx * b->row_stride, (size_t)b->dim * elem_size(b->dtype), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, b->d_elements.as<uint8_t>() + idx * b->row_stride, (size_t)b->dim * elem_size(b->dtype), hipMemcpyDeviceToHost));
     return GRANNE_HIP_OK;
 }
 
@@ -575,12 +526,11 @@ extern "C" int granne_hip_rw_builder_save(granne_hip_rw_builder* rw, const char*
     if (!rw || !index_path || !elements_path) return fail(GRANNE_HIP_ERR_INVALID, "null argument");
     std::shared_lock<RwGate> lk(rw->mu); // inserts wait (the reference's write_lock), searches go on
     const granne_hip_builder* b = rw->b;
-    DeviceGuard g(b->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", b->device);
+    GRANNE_HIP_ON_DEVICE(b->device);
     const uint64_t n = b->n_elements;
     const size_t dense = (size_t)b->dim * elem_size(b->dtype);
     std::vector<uint8_t> el((size_t)n * dense);
-    if (n) HIP_TRY(hipMemcpy2D(el.data(), dense, b->d_elements, b->row_stride, dense, n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy2D(el.data(), dense, b->d_elements.get(), b->row_stride, dense, n, hipMemcpyDeviceToHost));
     int rc = granne_hip_write_elements_file(elements_path, el.data(), n, b->dim, b->dtype);
     if (rc) return rc;
     const uint32_t nn = b->cfg.num_neighbors;

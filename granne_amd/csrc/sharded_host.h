@@ -119,9 +119,9 @@ struct granne_hip_sharded {
     // host-pointer calls: [queries | ids | dists | counts | status] of one batch in pinned memory and on the merge device
     // (the calls' own buffers, `depth` of them in rotation: independent of which slot a batch's begin happens to take)
     struct HostIO {
-        uint8_t* h_pin = nullptr;
+        PinBuf h_pin;
         uint8_t* d_io = nullptr;
-        size_t h_cap = 0, io_cap = 0;
+        size_t io_cap = 0;
         hipEvent_t h_done = nullptr;
     };
     HostIO host_io[SHARDED_MAX_DEPTH];
@@ -199,7 +199,7 @@ static void sharded_free(granne_hip_sharded* sh) {
         DeviceGuard g(sh->merge_device);
         for (auto& H : sh->host_io) {
             if (H.h_done) (void)hipEventDestroy(H.h_done);
-            if (H.h_pin) (void)hipHostFree(H.h_pin);
+            H.h_pin.reset();
             if (H.d_io) (void)hipFree(H.d_io);
         }
         if (sh->merge_stream) (void)hipStreamDestroy(sh->merge_stream);
@@ -218,8 +218,7 @@ static int sharded_init_slot(granne_hip_sharded* sh, granne_hip_sharded::Slot& L
     L.xdone.assign(nd, nullptr);
     L.searched.assign(G, nullptr);
     for (size_t d = 0; d < nd; ++d) {
-        DeviceGuard g(sh->devices[d].id);
-        if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", sh->devices[d].id);
+        GRANNE_HIP_ON_DEVICE(sh->devices[d].id);
         HIP_TRY(hipEventCreateWithFlags(&L.q_there[d], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&L.xdone[d], hipEventDisableTiming));
     }
@@ -230,6 +229,59 @@ static int sharded_init_slot(granne_hip_sharded* sh, granne_hip_sharded::Slot& L
     DeviceGuard g(sh->merge_device);
     HIP_TRY(hipEventCreateWithFlags(&L.ready, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&L.merged, hipEventDisableTiming));
+    return GRANNE_HIP_OK;
+}
+
+// the shards, devices, streams and slots of a new handle (granne_hip_sharded_create_grouped frees it on failure)
+static int sharded_setup(granne_hip_sharded* sh, granne_hip_index* const* shards, const uint64_t* id_offsets, uint32_t n_shards,
+                         const uint32_t* groups) {
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        auto& S = sh->shards[s];
+        S.ix = shards[s];
+        S.offset = id_offsets[s];
+        uint32_t d = 0;
+        if (groups) { // the group of an earlier shard with the same label, else a new one
+            uint32_t t = 0;
+            while (t < s && groups[t] != groups[s]) ++t;
+            d = t < s ? sh->shards[t].dev : (uint32_t)sh->devices.size();
+        } else {
+            while (d < sh->devices.size() && sh->devices[d].id != S.ix->device) ++d;
+        }
+        if (d == sh->devices.size()) {
+            sh->devices.emplace_back();
+            sh->devices.back().id = S.ix->device;
+        }
+        S.dev = d;
+        S.local = sh->devices[d].n_local++;
+        GRANNE_HIP_ON_DEVICE(S.ix->device);
+        HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+        if (S.ix->device != sh->merge_device) { // peer copies in both directions (queries out, results back)
+            int can = 0;
+            if (hipDeviceCanAccessPeer(&can, S.ix->device, sh->merge_device) == hipSuccess && can)
+                (void)hipDeviceEnablePeerAccess(sh->merge_device, 0); // already enabled is fine
+            DeviceGuard gm(sh->merge_device);
+            can = 0;
+            if (gm.ok && hipDeviceCanAccessPeer(&can, sh->merge_device, S.ix->device) == hipSuccess && can)
+                (void)hipDeviceEnablePeerAccess(S.ix->device, 0);
+        }
+    }
+    // one all-gather needs equal contributions in rank order: shard s on device s / n_local
+    sh->uniform = true;
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        const auto& S = sh->shards[s];
+        const uint32_t per = sh->devices[0].n_local;
+        if (sh->devices[S.dev].n_local != per || S.dev != s / per || S.local != s % per) sh->uniform = false;
+    }
+    (void)hipGetLastError(); // (a "peer access already enabled" above is not an error of ours)
+    DeviceGuard g(sh->merge_device);
+    HIP_TRY(hipStreamCreateWithFlags(&sh->merge_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&sh->io_stream, hipStreamNonBlocking));
+    sh->devices[0].xstream = sh->merge_stream; // (device 0 of the list is shard 0's = the merge device)
+    sh->slots.resize(sh->depth);
+    for (auto& L : sh->slots) {
+        int rc = sharded_init_slot(sh, L);
+        if (rc) return rc;
+    }
     return GRANNE_HIP_OK;
 }
 
@@ -260,58 +312,7 @@ extern "C" int granne_hip_sharded_create_grouped(granne_hip_sharded** out, grann
     sh->dtype = shards[0]->dtype;
     sh->merge_device = shards[0]->device;
     sh->shards.resize(n_shards);
-    auto body = [&]() -> int {
-        for (uint32_t s = 0; s < n_shards; ++s) {
-            auto& S = sh->shards[s];
-            S.ix = shards[s];
-            S.offset = id_offsets[s];
-            uint32_t d = 0;
-            if (groups) { // the group of an earlier shard with the same label, else a new one
-                uint32_t t = 0;
-                while (t < s && groups[t] != groups[s]) ++t;
-                d = t < s ? sh->shards[t].dev : (uint32_t)sh->devices.size();
-            } else {
-                while (d < sh->devices.size() && sh->devices[d].id != S.ix->device) ++d;
-            }
-            if (d == sh->devices.size()) {
-                sh->devices.emplace_back();
-                sh->devices.back().id = S.ix->device;
-            }
-            S.dev = d;
-            S.local = sh->devices[d].n_local++;
-            DeviceGuard g(S.ix->device);
-            if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", S.ix->device);
-            HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-            if (S.ix->device != sh->merge_device) { // peer copies in both directions (queries out, results back)
-                int can = 0;
-                if (hipDeviceCanAccessPeer(&can, S.ix->device, sh->merge_device) == hipSuccess && can)
-                    (void)hipDeviceEnablePeerAccess(sh->merge_device, 0); // already enabled is fine
-                DeviceGuard gm(sh->merge_device);
-                can = 0;
-                if (gm.ok && hipDeviceCanAccessPeer(&can, sh->merge_device, S.ix->device) == hipSuccess && can)
-                    (void)hipDeviceEnablePeerAccess(S.ix->device, 0);
-            }
-        }
-        // one all-gather needs equal contributions in rank order: shard s on device s / n_local
-        sh->uniform = true;
-        for (uint32_t s = 0; s < n_shards; ++s) {
-            const auto& S = sh->shards[s];
-            const uint32_t per = sh->devices[0].n_local;
-            if (sh->devices[S.dev].n_local != per || S.dev != s / per || S.local != s % per) sh->uniform = false;
-        }
-        (void)hipGetLastError(); // (a "peer access already enabled" above is not an error of ours)
-        DeviceGuard g(sh->merge_device);
-        HIP_TRY(hipStreamCreateWithFlags(&sh->merge_stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&sh->io_stream, hipStreamNonBlocking));
-        sh->devices[0].xstream = sh->merge_stream; // (device 0 of the list is shard 0's = the merge device)
-        sh->slots.resize(sh->depth);
-        for (auto& L : sh->slots) {
-            int rc = sharded_init_slot(sh, L);
-            if (rc) return rc;
-        }
-        return GRANNE_HIP_OK;
-    };
-    int rc = body();
+    int rc = sharded_setup(sh, shards, id_offsets, n_shards, groups);
     if (rc) {
         sharded_free(sh);
         return rc;
@@ -527,8 +528,7 @@ static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, u
 
     // buffers (sized once per (nq, k); a change waits for the slot's previous batch: hipFree synchronises)
     for (uint32_t d = 0; d < nd; ++d) {
-        DeviceGuard g(sh->devices[d].id);
-        if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", sh->devices[d].id);
+        GRANNE_HIP_ON_DEVICE(sh->devices[d].id);
         // the merge device holds every shard's block; another device its own shards' (peer) or everybody's (all-gather)
         const size_t blocks = (d == 0 || rccl) ? G : sh->devices[d].n_local;
         int rc = slot_grow(&L.d_recv[d], &L.recv_cap[d], stride * blocks);
@@ -551,8 +551,7 @@ static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, u
     std::vector<char> q_sent(nd, 0);
     for (uint32_t s = 0; s < G; ++s) {
         auto& S = sh->shards[s];
-        DeviceGuard g(S.ix->device);
-        if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", S.ix->device);
+        GRANNE_HIP_ON_DEVICE(S.ix->device);
         HIP_TRY(hipStreamWaitEvent(S.stream, L.ready, 0));
         if (L.used) { // the slot's previous batch has left these buffers
             HIP_TRY(hipStreamWaitEvent(S.stream, L.merged, 0));
@@ -728,20 +727,20 @@ extern "C" int granne_hip_sharded_search_batches(granne_hip_sharded* sh, const v
             }
         }
     } quiesce{sh, &pending};
-    DeviceGuard g(sh->merge_device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", sh->merge_device);
+    GRANNE_HIP_ON_DEVICE(sh->merge_device);
     auto finish = [&](const Pending& P) -> int {
         auto& H = sh->host_io[P.io];
         rc = granne_hip_sharded_end_device(sh, P.ticket, sh->io_stream);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(H.h_pin + o_ids, H.d_io + o_ids, total - o_ids, hipMemcpyDeviceToHost, sh->io_stream));
+        uint8_t* const h_pin = H.h_pin.as<uint8_t>();
+        HIP_TRY(hipMemcpyAsync(h_pin + o_ids, H.d_io + o_ids, total - o_ids, hipMemcpyDeviceToHost, sh->io_stream));
         HIP_TRY(hipEventRecord(H.h_done, sh->io_stream));
         HIP_TRY(hipEventSynchronize(H.h_done));
-        const uint32_t* st = (const uint32_t*)(H.h_pin + o_st);
+        const uint32_t* st = (const uint32_t*)(h_pin + o_st);
         if (st[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "a shard's exact-search scratch is exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
-        memcpy(out_ids + (size_t)P.batch * nq * k, H.h_pin + o_ids, (size_t)nq * k * 8);
-        memcpy(out_dists + (size_t)P.batch * nq * k, H.h_pin + o_d, (size_t)nq * k * 4);
-        memcpy(out_counts + (size_t)P.batch * nq, H.h_pin + o_c, (size_t)nq * 4);
+        memcpy(out_ids + (size_t)P.batch * nq * k, h_pin + o_ids, (size_t)nq * k * 8);
+        memcpy(out_dists + (size_t)P.batch * nq * k, h_pin + o_d, (size_t)nq * k * 4);
+        memcpy(out_counts + (size_t)P.batch * nq, h_pin + o_c, (size_t)nq * 4);
         return GRANNE_HIP_OK;
     };
     const uint32_t depth = sh->depth;
@@ -754,17 +753,11 @@ extern "C" int granne_hip_sharded_search_batches(granne_hip_sharded* sh, const v
         const uint32_t io = b % depth;
         auto& H = sh->host_io[io];
         if (!H.h_done) HIP_TRY(hipEventCreateWithFlags(&H.h_done, hipEventDisableTiming));
-        if (H.h_cap < total) {
-            if (H.h_pin) (void)hipHostFree(H.h_pin);
-            H.h_pin = nullptr;
-            H.h_cap = 0;
-            HIP_TRY(hipHostMalloc((void**)&H.h_pin, total + (total >> 2), hipHostMallocDefault));
-            H.h_cap = total + (total >> 2);
-        }
+        if (H.h_pin.capacity() < total) HIP_TRY(H.h_pin.reserve(total + (total >> 2), hipHostMallocDefault));
         rc = slot_grow(&H.d_io, &H.io_cap, total);
         if (rc) return rc;
-        memcpy(H.h_pin, (const uint8_t*)queries + (size_t)b * qb, qb);
-        HIP_TRY(hipMemcpyAsync(H.d_io, H.h_pin, qb, hipMemcpyHostToDevice, sh->io_stream));
+        memcpy(H.h_pin.get(), (const uint8_t*)queries + (size_t)b * qb, qb);
+        HIP_TRY(hipMemcpyAsync(H.d_io, H.h_pin.get(), qb, hipMemcpyHostToDevice, sh->io_stream));
         HIP_TRY(hipMemsetAsync(H.d_io + o_st, 0, 16, sh->io_stream));
         Pending P{b, io, 0};
         for (;;) {

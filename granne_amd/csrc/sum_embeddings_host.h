@@ -108,8 +108,7 @@ extern "C" int granne_hip_sum_embeddings_create_device(granne_hip_sum_embeddings
     if (dim == 0) return fail(GRANNE_HIP_ERR_INVALID, "dim must be > 0");
     if ((n_embeddings && !d_table) || !d_offsets) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (n_embeddings > 0xFFFFFFFFull || n_elements >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "too many embeddings or elements");
-    DeviceGuard g(device_id);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", device_id);
+    GRANNE_HIP_ON_DEVICE(device_id);
     hipStream_t s = (hipStream_t)stream;
     // the term lists are checked on the host before any kernel indexes the table with them
     std::vector<float> table((size_t)n_embeddings * dim);
@@ -213,8 +212,7 @@ static int se_device(const granne_hip_sum_embeddings* cse, std::shared_ptr<SeDev
     auto* se = const_cast<granne_hip_sum_embeddings*>(cse);
     std::lock_guard<std::mutex> lk(se->mu);
     if (se->dev) return *out = se->dev, GRANNE_HIP_OK;
-    DeviceGuard g(se->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", se->device);
+    GRANNE_HIP_ON_DEVICE(se->device);
     auto d = std::make_shared<SeDev>();
     d->device = se->device;
     d->dim = se->dim;
@@ -223,16 +221,16 @@ static int se_device(const granne_hip_sum_embeddings* cse, std::shared_ptr<SeDev
     d->n = se->offsets.size() - 1;
     d->n_terms = se->terms.size();
     const size_t tb = (size_t)d->n_embeddings * d->tstride * 4u;
-    HIP_TRY(hipMalloc((void**)&d->d_table, tb ? tb : 16));
-    HIP_TRY(hipMalloc((void**)&d->d_offsets, se->offsets.size() * 8));
-    HIP_TRY(hipMalloc((void**)&d->d_terms, d->n_terms ? d->n_terms * 4 : 16));
+    HIP_TRY(d->d_table.alloc(tb));
+    HIP_TRY(d->d_offsets.alloc(se->offsets.size() * 8));
+    HIP_TRY(d->d_terms.alloc(d->n_terms * 4));
     if (tb) {
-        HIP_TRY(hipMemset(d->d_table, 0, tb));
-        HIP_TRY(hipMemcpy2D(d->d_table, (size_t)d->tstride * 4u, se->table.data(), (size_t)se->dim * 4u, (size_t)se->dim * 4u,
+        HIP_TRY(hipMemset(d->d_table.get(), 0, tb));
+        HIP_TRY(hipMemcpy2D(d->d_table.get(), (size_t)d->tstride * 4u, se->table.data(), (size_t)se->dim * 4u, (size_t)se->dim * 4u,
                             d->n_embeddings, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMemcpy(d->d_offsets, se->offsets.data(), se->offsets.size() * 8, hipMemcpyHostToDevice));
-    if (d->n_terms) HIP_TRY(hipMemcpy(d->d_terms, se->terms.data(), d->n_terms * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->d_offsets.get(), se->offsets.data(), se->offsets.size() * 8, hipMemcpyHostToDevice));
+    if (d->n_terms) HIP_TRY(hipMemcpy(d->d_terms.get(), se->terms.data(), d->n_terms * 4, hipMemcpyHostToDevice));
     se->dev = d;
     *out = d;
     return GRANNE_HIP_OK;
@@ -250,7 +248,7 @@ static int se_rows_launch(const SeDev& d, const uint64_t* d_offsets, const uint3
     if (rpp < 1) return fail(GRANNE_HIP_ERR_INVALID, "dim too large");
     uint64_t blocks = (count + rpp - 1) / rpp;
     if (blocks > 256u * 32u) blocks = 256u * 32u;
-    const SeView v{d.d_table, d_offsets, d_terms, d.tstride, (uint32_t)d.n_embeddings};
+    const SeView v{d.d_table.as<float>(), d_offsets, d_terms, d.tstride, (uint32_t)d.n_embeddings};
     hipLaunchKernelGGL(sum_embeddings_rows_kernel, dim3((uint32_t)blocks), dim3(64), rpp * lstride * 4u, s, v, first, count, d.dim,
                        normalised, d_out, stride, rpp, lstride);
     HIP_TRY(hipGetLastError());
@@ -260,14 +258,12 @@ static int se_rows_launch(const SeDev& d, const uint64_t* d_offsets, const uint3
 static int se_rows_to_host(const SeDev& d, uint64_t first, uint64_t count, int normalised, float* out) {
     if (count == 0) return GRANNE_HIP_OK;
     if (!out) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
-    DeviceGuard g(d.device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", d.device);
-    float* d_out = nullptr;
+    GRANNE_HIP_ON_DEVICE(d.device);
+    DevBuf d_out;
     const size_t bytes = (size_t)count * d.dim * 4u;
-    HIP_TRY(hipMalloc((void**)&d_out, bytes));
-    int rc = se_rows_launch(d, d.d_offsets, d.d_terms, first, count, normalised, d_out, d.dim, nullptr);
-    if (rc == 0 && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemcpy failed");
-    (void)hipFree(d_out);
+    HIP_TRY(d_out.alloc(bytes));
+    int rc = se_rows_launch(d, d.d_offsets.as<uint64_t>(), d.d_terms.as<uint32_t>(), first, count, normalised, d_out.as<float>(), d.dim, nullptr);
+    if (rc == 0 && hipMemcpy(out, d_out.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemcpy failed");
     return rc;
 }
 
@@ -283,7 +279,7 @@ extern "C" int granne_hip_sum_embeddings_materialize_device(const granne_hip_sum
     int rc = se_device(se, &d);
     if (rc) return rc;
     DeviceGuard g(d->device);
-    return se_rows_launch(*d, d->d_offsets, d->d_terms, first, count, normalised, d_out, stride, (hipStream_t)stream);
+    return se_rows_launch(*d, d->d_offsets.as<uint64_t>(), d->d_terms.as<uint32_t>(), first, count, normalised, d_out, stride, (hipStream_t)stream);
 }
 
 extern "C" int granne_hip_sum_embeddings_materialize(const granne_hip_sum_embeddings* se, uint64_t first, uint64_t count,
@@ -325,26 +321,17 @@ extern "C" int granne_hip_sum_embeddings_embed(const granne_hip_sum_embeddings* 
     rc = se_device(se, &d);
     if (rc) return rc;
     DeviceGuard g(d->device);
-    uint64_t* d_off = nullptr;
-    uint32_t* d_terms = nullptr;
-    float* d_out = nullptr;
+    DevBuf d_off, d_terms, d_out;
     const size_t nt = (size_t)offsets[nq], bytes = (size_t)nq * d->dim * 4u;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void**)&d_off, (nq + 1) * 8));
-        HIP_TRY(hipMalloc((void**)&d_terms, nt ? nt * 4 : 16));
-        HIP_TRY(hipMalloc((void**)&d_out, bytes));
-        HIP_TRY(hipMemcpy(d_off, offsets, (nq + 1) * 8, hipMemcpyHostToDevice));
-        if (nt) HIP_TRY(hipMemcpy(d_terms, terms, nt * 4, hipMemcpyHostToDevice));
-        int r = se_rows_launch(*d, d_off, d_terms, 0, nq, normalised, d_out, d->dim, nullptr);
-        if (r) return r;
-        HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
-        return GRANNE_HIP_OK;
-    };
-    rc = body();
-    if (d_off) (void)hipFree(d_off);
-    if (d_terms) (void)hipFree(d_terms);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    HIP_TRY(d_off.alloc((nq + 1) * 8));
+    HIP_TRY(d_terms.alloc(nt * 4));
+    HIP_TRY(d_out.alloc(bytes));
+    HIP_TRY(hipMemcpy(d_off.get(), offsets, (nq + 1) * 8, hipMemcpyHostToDevice));
+    if (nt) HIP_TRY(hipMemcpy(d_terms.get(), terms, nt * 4, hipMemcpyHostToDevice));
+    rc = se_rows_launch(*d, d_off.as<uint64_t>(), d_terms.as<uint32_t>(), 0, nq, normalised, d_out.as<float>(), d->dim, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, d_out.get(), bytes, hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
 }
 
 // An index over a container from layers in DEVICE memory ([len][width] u32 rows, UNUSED padded). Materialised: the
@@ -357,19 +344,16 @@ static int se_index_from_device_layers(granne_hip_index** out, const std::shared
     if (rc) return rc;
     if (n_layers && (!d_layer_rows || !layer_width)) return fail(GRANNE_HIP_ERR_INVALID, "layer arrays are null");
     if (mode != GRANNE_HIP_SE_MATERIALIZED && mode != GRANNE_HIP_SE_COMPACT) return fail(GRANNE_HIP_ERR_INVALID, "unknown mode %d", mode);
-    DeviceGuard g(d->device);
-    if (!g.ok) return fail(GRANNE_HIP_ERR_NO_DEVICE, "cannot select HIP device %d", d->device);
+    GRANNE_HIP_ON_DEVICE(d->device);
     if (mode == GRANNE_HIP_SE_MATERIALIZED) {
-        float* d_rows = nullptr;
-        const size_t bytes = (size_t)d->n * d->dim * 4u;
-        HIP_TRY(hipMalloc((void**)&d_rows, bytes ? bytes : 16));
-        rc = se_rows_launch(*d, d->d_offsets, d->d_terms, 0, d->n, 1, d_rows, d->dim, s);
+        DevBuf d_rows;
+        HIP_TRY(d_rows.alloc((size_t)d->n * d->dim * 4u));
+        rc = se_rows_launch(*d, d->d_offsets.as<uint64_t>(), d->d_terms.as<uint32_t>(), 0, d->n, 1, d_rows.as<float>(), d->dim, s);
         if (rc == 0)
-            rc = granne_hip_index_create_device(out, d_rows, d->n, d->dim, GRANNE_HIP_F32, n_layers, layer_len, d_layer_rows,
+            rc = granne_hip_index_create_device(out, d_rows.get(), d->n, d->dim, GRANNE_HIP_F32, n_layers, layer_len, d_layer_rows,
                                                 layer_width, d->device, s); // synchronises s
         else
             (void)hipStreamSynchronize(s);
-        (void)hipFree(d_rows);
         return rc;
     }
     granne_hip_index* ix = new granne_hip_index();
@@ -381,8 +365,9 @@ static int se_index_from_device_layers(granne_hip_index** out, const std::shared
     ix->row_stride = ix->row_bytes;
     ix->se = d;
     ix->hbm_bytes += d->bytes();
-    uint32_t* d_bad = nullptr; // neighbor ids outside their layer, as granne_hip_index_create_device looks for them
-    if (hipMalloc((void**)&d_bad, 4) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMalloc failed");
+    DevBuf bad_buf; // neighbor ids outside their layer, as granne_hip_index_create_device looks for them
+    if (bad_buf.alloc(4) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMalloc failed");
+    uint32_t* const d_bad = bad_buf.as<uint32_t>();
     if (rc == 0 && hipMemsetAsync(d_bad, 0, 4, s) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemsetAsync failed");
     for (uint32_t l = 0; rc == 0 && l < n_layers; ++l) {
         rc = add_layer_from_device_rows(ix, layer_len[l], layer_width[l], d_layer_rows[l], s);
@@ -393,7 +378,6 @@ static int se_index_from_device_layers(granne_hip_index** out, const std::shared
     if (rc == 0) rc = finish_layers(ix, s); // synchronises s
     uint32_t bad = 0;
     if (rc == 0 && hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "hipMemcpy failed");
-    if (d_bad) (void)hipFree(d_bad);
     if (rc == 0 && bad) rc = fail(GRANNE_HIP_ERR_INVALID, "%u neighbor ids lie outside their layer", bad);
     if (rc) {
         destroy_index(ix);
@@ -417,18 +401,17 @@ extern "C" int granne_hip_index_create_sum_embeddings(granne_hip_index** out, co
     rc = se_device(se, &d);
     if (rc) return rc;
     DeviceGuard g(d->device);
-    std::vector<uint32_t*> d_rows(n_layers, nullptr);
+    std::vector<DevBuf> staged(n_layers);
+    std::vector<const uint32_t*> d_rows(n_layers, nullptr);
     hipError_t e = hipSuccess;
     for (uint32_t l = 0; e == hipSuccess && l < n_layers; ++l) {
         const size_t b = (size_t)layer_len[l] * layer_width[l] * 4;
-        e = hipMalloc((void**)&d_rows[l], b ? b : 16);
-        if (e == hipSuccess && b) e = hipMemcpy(d_rows[l], layer_rows[l], b, hipMemcpyHostToDevice);
+        e = staged[l].alloc(b);
+        d_rows[l] = staged[l].as<uint32_t>();
+        if (e == hipSuccess && b) e = hipMemcpy(staged[l].get(), layer_rows[l], b, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) rc = fail(GRANNE_HIP_ERR_HIP, "staging upload failed: %s", hipGetErrorString(e));
-    else rc = se_index_from_device_layers(out, d, n_layers, layer_len, (const uint32_t* const*)d_rows.data(), layer_width, mode, nullptr);
-    for (auto p : d_rows)
-        if (p) (void)hipFree(p);
-    return rc;
+    if (e != hipSuccess) return fail(GRANNE_HIP_ERR_HIP, "staging upload failed: %s", hipGetErrorString(e));
+    return se_index_from_device_layers(out, d, n_layers, layer_len, d_rows.data(), layer_width, mode, nullptr);
 }
 
 // Granne::from_file over a SumEmbeddings container: index file + embeddings file + elements file
@@ -481,13 +464,11 @@ extern "C" int granne_hip_builder_create_sum_embeddings(granne_hip_builder** out
     rc = se_device(se, &d);
     if (rc) return rc;
     DeviceGuard g(d->device);
-    float* d_rows = nullptr;
-    const size_t bytes = (size_t)d->n * d->dim * 4u;
-    HIP_TRY(hipMalloc((void**)&d_rows, bytes ? bytes : 16));
-    rc = se_rows_launch(*d, d->d_offsets, d->d_terms, 0, d->n, 1, d_rows, d->dim, nullptr);
-    if (rc == 0) rc = granne_hip_builder_create_device(out, config, d_rows, d->n, d->dim, GRANNE_HIP_F32, d->device, nullptr); // synchronises
+    DevBuf d_rows;
+    HIP_TRY(d_rows.alloc((size_t)d->n * d->dim * 4u));
+    rc = se_rows_launch(*d, d->d_offsets.as<uint64_t>(), d->d_terms.as<uint32_t>(), 0, d->n, 1, d_rows.as<float>(), d->dim, nullptr);
+    if (rc == 0) rc = granne_hip_builder_create_device(out, config, d_rows.get(), d->n, d->dim, GRANNE_HIP_F32, d->device, nullptr); // synchronises
     else (void)hipDeviceSynchronize();
-    (void)hipFree(d_rows);
     if (rc == 0) (*out)->se = d;
     return rc;
 }
@@ -505,7 +486,7 @@ extern "C" int granne_hip_builder_get_index_compact(const granne_hip_builder* b,
     for (const auto& L : b->layers) {
         lens.push_back(L.len);
         widths.push_back(b->W); // (the builder's rows are W ids wide, UNUSED beyond num_neighbors)
-        ptrs.push_back(L.d_adj);
+        ptrs.push_back(L.d_adj.as<uint32_t>());
     }
     return se_index_from_device_layers(out, b->se, (uint32_t)lens.size(), lens.data(), ptrs.data(), widths.data(), GRANNE_HIP_SE_COMPACT, nullptr);
 }
