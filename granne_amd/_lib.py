@@ -19,6 +19,7 @@ OPT_SKETCH = 12
 # concurrent host-pointer calls share launches (granne_amd/csrc/combiner.h); the last two are read-only counters
 OPT_COALESCE, OPT_COALESCE_MAX, OPT_COALESCE_WAIT_US, OPT_COALESCED_LAUNCHES, OPT_COALESCED_QUERIES = 13, 14, 15, 16, 17
 OPT_LAST_COMPACT_ROWS = 18  # read-only: the last launch ran the compacted row stage of the sketched walkers
+OPT_LAST_SPLIT_TAIL = 19  # read-only: the last launch ran its tail blocks as a kernel of their own, behind the walkers'
 COALESCE_CALL_MAX = 64  # GRANNE_HIP_COALESCE_CALL_MAX
 COALESCE_MAX = 1024  # GRANNE_HIP_COALESCE_MAX
 WALKER_NONE, WALKER_REGISTER, WALKER_REGISTER_WIDE, WALKER_GENERAL, WALKER_EXACT = 0, 1, 2, 3, 4

@@ -187,6 +187,7 @@ struct granne_hip_index {
     std::atomic<uint64_t> last_slow_count{0};
     std::atomic<uint64_t> last_walker{0}; // GRANNE_HIP_OPT_LAST_WALKER
     std::atomic<uint64_t> last_compact{0}; // GRANNE_HIP_OPT_LAST_COMPACT_ROWS
+    std::atomic<uint64_t> last_split{0};   // GRANNE_HIP_OPT_LAST_SPLIT_TAIL
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
     DevBuf d_inv_norm;
@@ -756,6 +757,7 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
     case GRANNE_HIP_OPT_COALESCED_LAUNCHES:
     case GRANNE_HIP_OPT_COALESCED_QUERIES:
     case GRANNE_HIP_OPT_LAST_COMPACT_ROWS:
+    case GRANNE_HIP_OPT_LAST_SPLIT_TAIL:
         return fail(GRANNE_HIP_ERR_INVALID, "option %d is read-only", option);
     default:
         return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
@@ -783,6 +785,7 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     case GRANNE_HIP_OPT_COALESCED_LAUNCHES: *value = ix->combiner.launches(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_COALESCED_QUERIES: *value = ix->combiner.queries(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_LAST_COMPACT_ROWS: *value = ix->last_compact.load(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_LAST_SPLIT_TAIL: *value = ix->last_split.load(); return GRANNE_HIP_OK;
     default: return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -885,6 +888,7 @@ struct SearchTarget {
     ScratchCache* scratch;             // search_launch's per-stream scratch blocks
     std::atomic<uint64_t>* last_walker = nullptr; // which walker the last launch took (an index's read-only option)
     std::atomic<uint64_t>* last_compact = nullptr; // ... and whether it ran the compacted row stage
+    std::atomic<uint64_t>* last_split = nullptr;   // ... and whether its tail blocks were a kernel of their own
 
     // G: granne_hip_index, or granne_hip_builder (builder_host.h) searching its `layers`. A builder's searches differ in
     // these ways only: no row sketches, seen_min never reached (its layers change between launches, its batches are its
@@ -907,6 +911,7 @@ struct SearchTarget {
             d_sketch = (g->opt_sketch && knobs().sketch) ? g->d_sketch.template as<uint8_t>() : nullptr;
             last_walker = &const_cast<G*>(g)->last_walker;
             last_compact = &const_cast<G*>(g)->last_compact;
+            last_split = &const_cast<G*>(g)->last_split;
             se = g->se.get();
         } else {
             max_dev_width = g->W;
@@ -979,7 +984,7 @@ template <int DT, int DIM, int S>
 static search_fn fast_kernel_v(int v16, bool cr) {
     constexpr bool streamed = (DT == DT_F32 && DIM == 0) || (DT == DT_I8 && DIM >= 256);
     if constexpr (DT == DT_F32 && sketch_dim_ok((uint32_t)DIM) && S <= 4) { // the sketched launches: survivors' rows only (walk_fast.h, CR)
-        if (v16 == 5 && cr) return fast_kernel<DT, DIM, S, false, 5, false, GRANNE_HIP_CR_G>;
+        if (v16 == 5 && cr) return fast_kernel<DT, DIM, S, false, 5, false, GRANNE_HIP_CR_G>; // (the walkers alone: tail_kernel follows, plan_walk's `split`)
     }
     if constexpr (S == 1 && !streamed) {
         if (v16 == 4) return fast_kernel<DT, DIM, S, false, 4>;
@@ -1049,6 +1054,12 @@ struct WalkPlan {
     uint32_t maxc = 0, lrow_bytes = 16, stage_bytes = 0, adjspec_bytes = 0;
     uint32_t ovf_slots = 0, ovf_regions = 0; // visited-set overflow tables
     uint32_t slow_blocks = 0, tail_blocks = 0; // the exact walker's containers; its blocks behind the walkers
+    // The split form (the compacted launches: walk_fast.h, fast_kernel's CR): `fn` is the walkers alone on a grid of nq, and
+    // tail_fn (slow_kernel.h, tail_kernel) follows it on the stream with tail_blocks blocks of tail_lds bytes. hand_all:
+    // every walker hands its query over (GRANNE_HIP_OPT_FORCE_SLOW on a launch that splits).
+    bool split = false, hand_all = false;
+    search_fn tail_fn = nullptr;
+    uint32_t tail_lds = 0;
 };
 
 // The register walker (walk_fast.h) serves the common shapes: every layer up to 64 ids wide on the device, ids within 31
@@ -1117,7 +1128,12 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         if (P.S <= 4 && !wide && !i8 && nq >= seen_min) P.v16 = 5; // (every f32 dim: unrolled and streamed)
         // ... and, where they reject neighbors by the index's row sketch, read the rows of the survivors only (walk_fast.h, CR)
         P.cr = P.v16 == 5 && !i8 && sketch_dim_ok(T.dim) && T.d_sketch != nullptr && knobs().compact_rows != 0;
-        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.stage_row_bytes, P.S, 0u, P.v16 == 5, wide, P.cr ? GRANNE_HIP_CR_G : 0);
+        // ... in a kernel that holds the walker and nothing else, built for five or six waves per SIMD: the tail blocks of these
+        // launches are a kernel of their own behind it (slow_kernel.h, tail_kernel). Measured on launches of 2,048 and of 4,096
+        // walks, which the chip holds whole at four waves per SIMD, as on the larger ones: the second kernel costs 5 us and
+        // the walkers gain more, so every compacted launch takes this form.
+        P.split = P.cr && !wide;
+        walk_lds = fast_lds_bytes(i8, streamed, T.dim, T.stage_row_bytes, P.S, 0u, P.v16 == 5, wide);
         const uint32_t least = lds_query_bytes(T.stage_row_bytes) + 64u * 8u; // int8 query staging; a tail block (slow_kernel.h)
         if (walk_lds < least) walk_lds = least;
     } else {
@@ -1204,13 +1220,30 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         const size_t fit = SLOW_SCRATCH_BUDGET / per_block;
         if (most > fit) most = fit > P.slow_blocks ? (uint32_t)fit : P.slow_blocks;
         P.slow_blocks = nq < most ? (nq > P.slow_blocks ? nq : P.slow_blocks) : most;
+        if (T.opt_force_slow && fast && P.split) {
+            // the option on a launch that splits: the same two kernels, every walker hands its query over and as many tail
+            // blocks as the exact walker's own launch has walk the list
+            P.hand_all = true;
+            P.fn = fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr);
+            P.tail_fn = (search_fn)tail_kernel<DT_F32>;
+            if (!P.fn) {
+                fail(GRANNE_HIP_ERR_INVALID, "no split walker is instantiated for this launch (list slots %u)", P.S);
+                return P;
+            }
+            P.lds_bytes = walk_lds;
+            P.tail_lds = slow_lds;
+            P.tail_blocks = P.slow_blocks;
+            P.grid = nq;
+            return P;
+        }
+        P.split = false;
         P.fn = compact ? (search_fn)slow_kernel<DT_F32, PV_SE> : f16 ? (search_fn)slow_kernel<DT_F32, PV_F16>
                : !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
         P.lds_bytes = slow_lds;
         P.grid = P.slow_blocks;
         return P;
     }
-    if (!fast || wide) P.cr = false;
+    if (!fast || wide) P.cr = P.split = false;
     if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
     P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : f16 ? f16_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
     if (!P.fn) {
@@ -1225,6 +1258,13 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         return P;
     }
     P.tail_blocks = P.slow_blocks < nq ? P.slow_blocks : nq;
+    if (P.split) { // the walkers alone (the compacted f32 walkers: their LDS, not a tail block's); the tail blocks behind them
+        P.tail_fn = (search_fn)tail_kernel<DT_F32>;
+        P.lds_bytes = walk_lds;
+        P.tail_lds = slow_lds;
+        P.grid = nq;
+        return P;
+    }
     P.grid = nq + P.tail_blocks;
     return P;
 }
@@ -1325,7 +1365,7 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     p.adjspec_bytes = W.adjspec_bytes;
     p.slow_count = ctl + CTL_SLOW_COUNT;
     p.slow_list = (uint32_t*)(scratch + off_list);
-    p.force_slow = 0;
+    p.force_slow = W.hand_all ? 1u : 0u;
     p.spec = 1;
     p.sketch = T.d_sketch;
     p.ovf.tables = (uint32_t*)(scratch + off_ovf);
@@ -1344,7 +1384,7 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     sp.pq = (uint64_t*)(scratch + off_pq);
     sp.res = (uint64_t*)(scratch + off_res);
     sp.slots = slots;
-    sp.all = W.walker == GRANNE_HIP_WALKER_EXACT ? 1u : 0u;
+    sp.all = (W.walker == GRANNE_HIP_WALKER_EXACT && !W.split) ? 1u : 0u; // (a split launch walks the hand-over list, whoever filled it)
     sp.status2 = c.status;
     sp.host_status = c.host_status;
     p.se_table = T.se ? T.se->d_table.as<float>() : nullptr;
@@ -1354,11 +1394,16 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
 
     if (T.last_walker) T.last_walker->store(W.walker);
     if (T.last_compact) T.last_compact->store(W.cr ? 1 : 0);
-    if (W.walker != GRANNE_HIP_WALKER_EXACT && W.lds_bytes > 32u * 1024u)
+    if (T.last_split) T.last_split->store(W.split ? 1 : 0);
+    if ((W.walker != GRANNE_HIP_WALKER_EXACT || W.split) && W.lds_bytes > 32u * 1024u)
         HIP_TRY(hipFuncSetAttribute((const void*)W.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W.lds_bytes));
     if (c.ev_before) HIP_TRY(hipEventRecord(c.ev_before, s));
     hipLaunchKernelGGL(W.fn, dim3(W.grid), dim3(64), W.lds_bytes, s, sp);
     HIP_TRY(hipGetLastError());
+    if (W.split) { // the tail blocks: stream order is what they wait for
+        hipLaunchKernelGGL(W.tail_fn, dim3(W.tail_blocks), dim3(64), W.tail_lds, s, sp);
+        HIP_TRY(hipGetLastError());
+    }
     if (c.ev_after) HIP_TRY(hipEventRecord(c.ev_after, s));
 
     if (c.slow_count) {

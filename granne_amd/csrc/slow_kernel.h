@@ -9,7 +9,7 @@
 // It is slow on purpose of simplicity: lane 0 runs the heaps; the 64 lanes split the neighbor
 // row (visited insert + one exact distance each, rows read straight from HBM).
 //
-// One launch per search. The hand-over list is served INSIDE the walker's launch: the grid is nq walker
+// One launch per search, with one exception. The hand-over list is served INSIDE the walker's launch: the grid is nq walker
 // blocks plus a few tail blocks; a tail block sleeps until the launch's `done` counter says every walker
 // block has finished, reads the list (device-scope atomics on both sides: the list crosses XCDs) and walks
 // its share; the last tail block out re-arms the control words, so the scratch block needs no memset
@@ -17,6 +17,12 @@
 // stream-ordered malloc/free per call, 20-37 us per step). Tail blocks never hold a walker up: walkers do
 // not wait for anything, so the order in which the dispatcher places blocks does not matter. Searches that
 // are known to go to the exact walker wholesale launch `slow_kernel` alone.
+// The exception: the sketched compacted f32 launches (walk_fast.h, FastWalker's CR; plan_walk's `split`) are TWO kernels --
+// fast_kernel<.., CR> with a grid of nq walkers, then tail_kernel with the tail blocks. The exact walker's code set the one
+// kernel's register allocation (127 VGPRs, 18 scalar spills, for code that 16 of 20,496 blocks ran); without it the walker
+// fits six waves per SIMD. Stream order replaces the spin on CTL_DONE (which stays zero), the last tail block re-arms the
+// control words as before: still no memset, nothing allocated, nothing waited for on the host. Those launches are of
+// 2,048 walks and more (GRANNE_HIP_OPT_SEEN_MIN); every other one -- the latency shapes among them -- keeps the one kernel.
 #pragma once
 
 #include "search_kernel.h"
@@ -367,6 +373,17 @@ __device__ inline void tail_block(const SlowParams& P, uint8_t* smem) {
     if (n_slow) slow_walk_list<DT, PV>(P, me, n_blocks, n_slow, smem);
     else if (me == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = 0u;
     slow_epilogue(P, n_blocks, n_slow);
+}
+
+// The tail blocks of a split launch (walk_fast.h, fast_kernel's CR): enqueued right behind the walkers' kernel, whose
+// end the stream's order stands for -- nothing spins on CTL_DONE. P.sp.force_slow: every walker handed its query over.
+template <int DT, int PV = PV_DENSE>
+__global__ __launch_bounds__(64) void tail_kernel(const SlowParams P) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const uint32_t n_slow = __hip_atomic_load(P.ctl + CTL_SLOW_COUNT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (n_slow) slow_walk_list<DT, PV>(P, blockIdx.x, gridDim.x, n_slow, smem);
+    else if (blockIdx.x == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = 0u;
+    slow_epilogue(P, gridDim.x, n_slow);
 }
 
 // every query of the launch on the exact walker (max_search beyond the register walkers, GRANNE_HIP_OPT_FORCE_SLOW)

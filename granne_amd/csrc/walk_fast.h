@@ -91,18 +91,31 @@ constexpr uint32_t WPOS_NONE = 0xFFFFFFFFu;
 constexpr uint32_t VCACHE_SLOTS = 512; // FastWalker::vcache (power of two, 2 KB of LDS per walker)
 constexpr uint32_t VCACHE_SLOTS_SEEN = 2048; // ... of the walkers that skip revisits before their rows are fetched (SEEN: 8 KB; f32 rows -- 12 walkers per CU)
 constexpr uint64_t WALK_MAX_ELEMENTS = 1ull << 31; // ids must fit 31 bits
-// CR (FastWalker's compacted row stage): lanes per surviving row (8 or 4), and the waves per SIMD its launches are built
-// for -- five of them leave a walker 8 KB of LDS, so its cache of evaluated ids halves (a miss means nothing).
+// CR (FastWalker's compacted row stage): lanes per surviving row (8 or 4). Its kernel is the walker and nothing else --
+// the tail blocks of its launches are tail_kernel's (slow_kernel.h), enqueued behind it -- with one row register set in
+// compact_rows, and it is built for as many waves per SIMD as each list length compiles to without scratch
+// (cr_waves; tests/test_walker_registers.py holds the table to the compile report). GRANNE_HIP_CR_WAVES = 4, 5 or 6
+// overrides the table for all three (A/B builds). From five waves on a walker's cache of evaluated ids is 1024 slots (a
+// miss means nothing): 24 walks of 5,392 bytes are 129 KB of the CU's 160.
 #ifndef GRANNE_HIP_CR_G
 #define GRANNE_HIP_CR_G 8
 #endif
 #ifndef GRANNE_HIP_CR_WAVES
-#define GRANNE_HIP_CR_WAVES 4
+#define GRANNE_HIP_CR_WAVES 0
 #endif
 static_assert(GRANNE_HIP_CR_G == 8 || GRANNE_HIP_CR_G == 4, "a surviving row is held by 8 or by 4 lanes");
-static_assert(GRANNE_HIP_CR_WAVES == 4 || GRANNE_HIP_CR_WAVES == 5, "four or five waves per SIMD");
-__host__ __device__ constexpr uint32_t fast_vcache_slots(bool seen, int cr) {
-    return seen ? ((cr && GRANNE_HIP_CR_WAVES == 5) ? 1024u : VCACHE_SLOTS_SEEN) : VCACHE_SLOTS;
+static_assert(GRANNE_HIP_CR_WAVES == 0 || (GRANNE_HIP_CR_WAVES >= 4 && GRANNE_HIP_CR_WAVES <= 6), "the table's value, or four to six waves per SIMD");
+__host__ __device__ constexpr int cr_waves(int S) {
+    // (compiled alone for gfx950: one slot 86 / 88 / 80 VGPRs at 4 / 5 / 6 waves, no scratch; two slots 92 at 5, 12 bytes of
+    //  scratch at 6; four slots 97 / 90 at 4 / 5, 32 bytes of scratch at 6)
+    return GRANNE_HIP_CR_WAVES ? GRANNE_HIP_CR_WAVES : S == 1 ? 6 : 5;
+}
+// sketched: the shape whose launches use an index's row sketch (FastWalker::SK), S: its list slots (what a CR kernel's
+// waves per SIMD go by). The walker of the same shape on an index WITHOUT sketches (CR = 0) takes the same cache: n_dist
+// counts a neighbor evaluated again after its id was pushed out of its slot, and the three counters of a search do not
+// depend on whether the index has a sketch (tests/test_gpu_compact_rows.py, tests/test_gpu_sketch.py).
+__host__ __device__ constexpr uint32_t fast_vcache_slots(bool seen, bool sketched, int S) {
+    return seen ? ((sketched && cr_waves(S) >= 5) ? 1024u : VCACHE_SLOTS_SEEN) : VCACHE_SLOTS;
 }
 
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t m) { // set bits of m below this lane
@@ -646,9 +659,10 @@ struct FastWalker {
     // first lane takes +0.0 instead, whatever its lower neighbor holds) which adds its accumulators in order -- every lane
     // runs every step, lane t is right from step t on, the last lane after step G - 1. That lane applies the tail
     // (math.rs:32-39; from the expanded node's record via R when the layer carries tails, else from the row) and the
-    // distance goes back to the survivor's own lane by one ds_bpermute. Two passes (2 x 64 / G survivors) have their loads
-    // in flight together, in a register set each; more survivors (the first expansions of a layer, while theta is
-    // +inf) loop. The distances are the bits finish_rows gives: tests/test_compact_rows_model.py replays the schedule.
+    // distance goes back to the survivor's own lane by one ds_bpermute. A pass serves 64 / G survivors from ONE register set
+    // (a second set, with two passes' loads in flight together, cost 20 VGPRs: the difference between four waves per SIMD
+    // and six); more survivors (the two first bottom expansions and a layer's entry, while theta is +inf) loop.
+    // The distances are the bits finish_rows gives: tests/test_compact_rows_model.py replays the schedule.
     static constexpr int CG = CR ? CR : 8;         // lanes per row
     static constexpr int CU = 8 / CG;              // 16-byte units of a chunk per lane
     static constexpr uint32_t CNG = 64u / CG;      // rows per pass
@@ -720,25 +734,20 @@ struct FastWalker {
         const uint64_t* cs = cr_slots();
         float d = 0.0f;
         uint32_t base = 0;
-        CRows ra, rb;
+        CRows ra; // ONE register set: a pass of CNG survivors issues its loads, then finishes; further passes loop
+#pragma unroll 1
         do {
-            const uint32_t sa = base + g, sb = base + CNG + g; // (below 32: stale places are read, never used)
-            const uint64_t ea = cs[sa], eb = cs[sb];
+            const uint32_t sa = base + g; // (at most 31: base < ns <= 32 is a multiple of CNG)
+            const uint64_t ea = cs[sa];
             cr_issue(ra, ea, sa < ns, ct, xtails);
-            cr_issue(rb, eb, sb < ns, ct, xtails);
-            asm volatile("" ::: "memory"); // both sets' loads are in flight here
-            const uint32_t rel = srank - base; // (a rank below base: beyond every pass of this trip)
+            asm volatile("" ::: "memory"); // the pass's loads are in flight here
+            const uint32_t rel = srank - base; // (a rank below base: served by an earlier pass)
             const int from = (int)(((rel & (CNG - 1u)) * (uint32_t)CG + (uint32_t)(CG - 1)) * 4u);
             const float da = cr_finish(ra, ct);
             const float ba = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(da)));
             d = (surv && rel < CNG) ? ba : d;
-            if (base + CNG < ns) {
-                const float db = cr_finish(rb, ct);
-                const float bb = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(db)));
-                d = (surv && rel >= CNG && rel < 2u * CNG) ? bb : d;
-            }
-            base += 2u * CNG;
-        } while (2u * CNG < 32u && base < ns);
+            base += CNG;
+        } while (base < ns);
         return d;
     }
 
@@ -993,7 +1002,7 @@ struct FastWalker {
     // loop: a hit means "this node entered the list earlier in this walk of the layer", i.e. the reference's visited set
     // holds it and skips it (mod.rs:1026); a miss (never entered, or evicted by a colliding id) means nothing -- the
     // candidate goes the exact way. Results do not depend on the cache.
-    static constexpr uint32_t VSLOTS = fast_vcache_slots(V16 == 5, CR);
+    static constexpr uint32_t VSLOTS = fast_vcache_slots(V16 == 5, SK, S);
     __device__ __forceinline__ static uint32_t vcache_slot(uint32_t id) {
         if constexpr (V16 == 5) return (id ^ (id >> 11) ^ (id >> 22)) & (VSLOTS - 1u);
         else return (id ^ (id >> 9)) & (VSLOTS - 1u);
@@ -1699,7 +1708,7 @@ constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, boo
 #if GRANNE_HIP_PHASE_TIMERS
     return 1; // the phase clocks live in registers too: no cap, the diagnostics run is one wave per SIMD anyway
 #endif
-    if (CR && S == 1) return GRANNE_HIP_CR_WAVES; // (the compacted row stage: two sets of 128 / G bytes per chunk instead of one of 64)
+    if (CR) return cr_waves(S); // (the compacted row stage: no tail blocks in the kernel, one row register set -- 6 waves = 80 VGPRs, 5 = 96)
     // lists of 2112 / 4160 keys: 2 registers per 64 keys + the merge's bookkeeping; 17 / 33 KB of LDS mirror each. Two
     // walkers per SIMD for the 33-slot lists (256 registers: measured 137 k against 97 k queries/s at max_search 1600 when the
     // allocation crept to 259), one for the 65-slot ones
@@ -1714,10 +1723,14 @@ constexpr int fast_waves_per_simd(int DT, int DIM, int S, bool WIDE = false, boo
 }
 
 // Blocks nq.. are the tail (slow_kernel.h): they serve the hand-over list inside the same launch.
+// CR: a grid of nq walkers and nothing else -- tail_kernel follows on the stream. A kernel's register allocation holds
+// for every wave of it, and the exact walker's code cost the 100-d sketched walker 21 VGPRs and 18 scalar spills.
 template <int DT, int DIM, int S, bool TRAIL = false, int V16 = 0, bool WIDE = false, int CR = 0>
 __global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE, V16 == 5, CR)) void fast_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
-    if (blockIdx.x < P.sp.nq) {
+    if constexpr (CR != 0) {
+        fast_walk_one<DT, DIM, S, TRAIL, V16, WIDE, CR>(P.sp, blockIdx.x, smem);
+    } else if (blockIdx.x < P.sp.nq) {
         fast_walk_one<DT, DIM, S, TRAIL, V16, WIDE, CR>(P.sp, blockIdx.x, smem);
         walker_done(P);
     } else {
@@ -1725,13 +1738,13 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(DT, DIM, S, WIDE, V16 == 5,
     }
 }
 
-__host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S, uint32_t visited_slots, bool seen = false, bool wide = false, int cr = 0) {
+__host__ __device__ inline uint32_t fast_lds_bytes(bool i8, bool gen, uint32_t dim, uint32_t row_bytes, uint32_t S, uint32_t visited_slots, bool seen = false, bool wide = false) {
     const bool lng = walk_list_is_long((int)S, wide);
     // [query][the list's image][lists of up to 17 slots: the cache of entered ids][visited]
     // (lists beyond 1024 keys: M's image, then F's of 128 keys)
     // (+ the launches that skip revisits on the sketched shapes: the query's sketch codes where the visited table would be)
     const uint32_t sk = (seen && !i8 && !gen && !wide && sketch_dim_ok(dim)) ? SKETCH_LINE : 0u;
-    return fast_query_bytes(i8, gen, dim, row_bytes, S, seen) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + fast_vcache_slots(seen, cr) * 4u + visited_slots * 4u + sk;
+    return fast_query_bytes(i8, gen, dim, row_bytes, S, seen) + (64u * S + (lng ? 0u : 32u)) * 8u + (lng ? 128u * 8u : 0u) + fast_vcache_slots(seen, sk != 0u, (int)S) * 4u + visited_slots * 4u + sk;
 }
 
 } // namespace granne_hip

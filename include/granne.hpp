@@ -272,6 +272,8 @@ public:
     uint64_t coalesced_queries() const { return get_option(GRANNE_HIP_OPT_COALESCED_QUERIES); }
     // whether the last search launch ran the compacted row stage of the sketched walkers (GRANNE_HIP_OPT_LAST_COMPACT_ROWS)
     bool last_compact_rows() const { return get_option(GRANNE_HIP_OPT_LAST_COMPACT_ROWS) != 0; }
+    // whether the last search launch ran its tail blocks as a kernel of their own (GRANNE_HIP_OPT_LAST_SPLIT_TAIL)
+    bool last_split_tail() const { return get_option(GRANNE_HIP_OPT_LAST_SPLIT_TAIL) != 0; }
     uint64_t get_option(int option) const {
         uint64_t v = 0;
         check(granne_hip_index_get_option(h_.get(), option, &v));

@@ -761,9 +761,13 @@ enum {
                                          first -- a throughput knob (and what makes tests of grouping deterministic) */
     GRANNE_HIP_OPT_COALESCED_LAUNCHES = 16, /* read-only: launches made for groups (that served them) since the index was created */
     GRANNE_HIP_OPT_COALESCED_QUERIES = 17,  /* read-only: queries those launches served */
-    GRANNE_HIP_OPT_LAST_COMPACT_ROWS = 18   /* read-only: 1 when the index's last search launch ran the register walker's compacted
+    GRANNE_HIP_OPT_LAST_COMPACT_ROWS = 18,  /* read-only: 1 when the index's last search launch ran the register walker's compacted
                                                row stage -- the launches that use the row sketch (GRANNE_HIP_OPT_SKETCH) read
                                                and evaluate only the neighbors that survive it, several lanes to a row; same bits */
+    GRANNE_HIP_OPT_LAST_SPLIT_TAIL = 19     /* read-only: 1 when the index's last search launch was two kernels on the stream --
+                                               the walkers, then the exact walker's tail blocks in a kernel of their own: the
+                                               compacted launches of more walks than the chip holds at once. Same bits, same
+                                               status words, nothing allocated or waited for; every other launch is one kernel */
 };
 #define GRANNE_HIP_COALESCE_CALL_MAX 64 /* calls of more queries than this never take part in GRANNE_HIP_OPT_COALESCE */
 #define GRANNE_HIP_COALESCE_MAX 1024    /* the largest (and default) GRANNE_HIP_OPT_COALESCE_MAX */
