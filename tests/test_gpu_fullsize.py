@@ -9,6 +9,18 @@ size-independent properties:
   * elements of the set, used as queries, find themselves (the reference's verify_search,
     src/index/tests.rs:50-62);
   * a larger max_search never returns a worse k-th distance on the same query.
+The same fixtures serve the operators that read rows by id * row_stride at ids past byte offset 2^32 of the device rows
+(the f32 indexes are 5.12 GB and 11.2 GB): element preparation at the high end, get_element / get_sketch, dists, refine,
+the exact scan, and angular_f16 rows made from the 200-d set (tests/high_ids.py holds the checks). Audited before their
+first run -- every kernel and host function they reach widens to 64 bits before it multiplies a row id, a row count
+or an element count; nothing had to be fixed: row_sketch_kernel, relayout_rows_kernel, inline_tails_kernel,
+synth_rows_kernel, normalize_rows_kernel, quantize_rows_kernel, dists_kernel, refine_kernel, f16_dist_group,
+f32_to_f16_kernel, f16_to_f32_kernel, the bf_* scan kernels with inv_norm_rows_kernel / inv_gmax_kernel /
+bf_narrow_ids_kernel / bf_final_kernel, merge_topk_kernel; on the host grid_for, upload_elements_from_device,
+make_inline_tails, make_scan_norms, make_row_sketch, get_element / get_sketch, the *_device preparation and conversion
+entries, dists_launch, refine_launch, plan_scan, ScanScratch, granne_hip_brute_force_device (tests/README.md has the
+notes). With GRANNE_FULLSIZE_N shrunk below the mark these tests run on the top of the id range and print that the
+past-the-mark assertions did not run.
 Set GRANNE_FULLSIZE_N / GRANNE_FULLSIZE_N200 to run on fewer points (defaults 10,000,000 / 12,500,000)."""
 import ctypes as C
 import os
@@ -16,6 +28,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import high_ids  # noqa: E402
 from tests.conftest import assert_counters  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -175,6 +188,145 @@ def test_larger_max_search_is_never_worse(built):
     d200 = ix.search_batch(q[:256], 200, 10)[1]
     assert (d200[:, 0] <= d50[:, 0]).mean() > 0.99
     assert (d200[:, 9] <= d50[:, 9]).mean() > 0.99
+
+
+# ---- the row-reading operators at ids past byte offset 2^32 of the device rows (tests/high_ids.py) ----------------
+# At the default sizes the f32 index is 10M rows of 512 bytes (ids >= 8,388,608 lie past 4 GiB) and the 200-d one 12.5M
+# rows of 896 bytes (ids >= 4,793,491); the int8 one is 1.28 GB, a full-size operator check (tests/test_gpu_past_4gib.py
+# holds the int8 rows past the mark). Audit of the address computations: tests/README.md.
+def _range(built, what):
+    return high_ids.Range(built.n, high_ids.device_row_stride(built[0], built.dim), "%s[%s x %d]" % (what, built[0], built.dim))
+
+
+def test_prepared_rows_at_the_high_end_are_the_oracles(built, oracle):
+    """normalize_f32_device / quantize_f32_device wrote the fixture's rows; nothing read the high ones back. The last
+    4,096 rows, regenerated (synth_rows' row0 form) and prepared by the oracle, are the fixture's bytes. The mark here is
+    that of the DENSE buffer the two kernels write (dim x 4 or dim bytes a row): the 200-d window lies 5.7 GB past it
+    (dense rows n - 4096 .. and their aliases 5,368,709 rows below hold different pseudo-random bytes), the 100-d ones
+    end below it (4.0 GB and 1.0 GB) and are checks of the range's top.
+    Device memory on top of the fixture: 3 MB; host: 7 MB."""
+    from granne_amd import _lib
+    kind, el = built[0], built[1]
+    n, dim, w = built.n, built.dim, min(4096, built.n)
+    R = high_ids.Range(n, dim * (4 if kind == "f32" else 1), "dense rows[%s x %d]" % (kind, dim))
+    if R.past:
+        assert n - w >= R.top0
+        print("  past-the-mark assertion ran: the window starts %d rows past the mark" % (n - w - R.top0))
+    raw = high_ids.synth(_lib, SEED, n - w, w, dim, None).cpu().numpy()
+    assert raw.tobytes() == oracle.synth_rows(SEED, n - w, w, dim).tobytes()
+    want = oracle.normalize_f32(raw) if kind == "f32" else oracle.quantize(raw)
+    assert el[n - w:].cpu().numpy().tobytes() == want.tobytes()
+
+
+def test_get_element_and_sketch_at_high_ids(built):
+    """get_element (a copy from elements + idx * row_stride, on the host) at 1,200 ids, 1,100 of them past the mark with
+    n - 1, first_high and first_high - 1; for the 100-d f32 index the sketch table's last 4,096 lines against the host
+    model of tests/test_sketch_bound.py. Truncated to 32 bits, id reads row id - 8,388,608 (512-byte rows) or the bytes
+    at (id * 896) mod 2^32 (200-d): other pseudo-random rows (high_ids.aliases_differ asserts it).
+    Device memory on top of the fixture: < 1 MB; host: < 2 MB."""
+    from tests.test_sketch_bound import row_sketch
+    kind, el, _, ix = built[:4]
+    n = built.n
+    R = _range(built, "get_element")
+    high_ids.check_get_element(ix, el, R, np.random.default_rng(11))
+    if kind == "f32" and built.dim == 100:
+        w = min(4096, n)
+        tab = ix.get_sketch(n - w, w)
+        assert tab is not None and tab.tobytes() == row_sketch(el[n - w:].cpu().numpy()).tobytes()
+
+
+def test_dists_at_high_ids(built, oracle):
+    """dists_kernel through dists_many (64 x 128 ids, status word) and the pair form (8,192 pairs): half the ids past the
+    mark, with n - 1, first_high, first_high - 1 and one id >= n (+inf, status 1); bit-equal to oracle.dist over rows
+    fetched by torch indexing. A row offset truncated to 32 bits reads row id - 2^32 / 512 (or the bytes at
+    (id * 896) mod 2^32): other rows, other distances.
+    Device memory on top of the fixture: < 1 MB; host: 10 MB."""
+    kind, el, q, ix = built[:4]
+    high_ids.check_dists(oracle, ix, el, lambda r: r, q, _range(built, "dists"), np.random.default_rng(12))
+
+
+def test_refine_at_high_ids(built, oracle):
+    """refine_kernel: 64 ragged lists of up to 257 candidates from the same id mix, k = 10, one candidate >= n (dropped
+    and counted), against tests/refine_model.py: ids, distance bytes, counts, the dropped word. Truncation aliases as in
+    test_dists_at_high_ids.
+    Device memory on top of the fixture: < 1 MB; host: 15 MB."""
+    kind, el, q, ix = built[:4]
+    high_ids.check_refine(oracle, ix, el, lambda r: r, q, _range(built, "refine"), np.random.default_rng(13))
+
+
+def test_exact_scan_over_the_whole_index(built, oracle):
+    """brute_force (k = 10 and 16) over every row: 16 of the fixture's queries and 16 member rows with ids past the mark
+    (n - 1 and first_high among them), against a reference made in two stages (high_ids.scan_reference: float64 scores
+    of all rows on the device by torch, the oracle's distances on the shortlist), guarded on the reference alone, with
+    the assertions and tolerances of tests/test_gpu_bruteforce.py. A member query's rank 0 is the member itself at the
+    oracle's self-distance: a scan whose tile addresses were truncated to 32 bits would never score the rows past the
+    mark -- it would score their aliases (id - 2^32 / 512, other bytes) twice -- and the members past the mark, whose
+    nearest other row is ~0.5 away, would be missing from their own lists.
+    Device memory on top of the fixture: 2.7 GB (a 1M-row chunk in float64, its [32, 1M] scores and ids); host: 20 MB."""
+    kind, el, q, ix = built[:4]
+    n = built.n
+    R = _range(built, "exact scan")
+    rng = np.random.default_rng(14)
+    mem = np.concatenate([[n - 1, R.top0], rng.integers(R.top0, n, 14)]).astype(np.int64)
+    queries = np.concatenate([q[:16], high_ids.fetch(el, mem)])
+    ref_i, _ = high_ids.check_exact_scan(oracle, ix, el, lambda r: r, queries, kind, {16 + j: int(i) for j, i in enumerate(mem)})
+    if R.past:  # the fixture's queries find neighbours on both sides of the mark
+        assert (ref_i[:16, :16] >= R.top0).any() and (ref_i[:16, :16] < R.top0).any()
+        print("  past-the-mark assertions ran: 16 member queries with ids >= %d, %d of the other queries' 256 results past it"
+              % (R.top0, int((ref_i[:16, :16] >= R.top0).sum())))
+
+
+def test_f16_rows_past_the_mark(built, oracle):
+    """angular_f16 rows past 4 GiB: the fixture's 12.5M x 200 f32 rows (10 GB dense) converted by
+    granne_hip_f32_to_f16_device (5 GB dense), a rows-only handle over them (512-byte rows: 6.4 GB, ids >= 8,388,608 past
+    the mark), get_element / dists / refine on it against the f32 oracle over normalize_f32(widen(row)), and
+    granne_hip_f16_to_f32_device back over the whole buffer. Windows of 4,096 rows at the end and around the 4 GiB marks
+    of the f32 buffer (row 5,368,709.1: 800-byte rows) and of the halves' (row 10,737,418.2: 400-byte rows). A flat index
+    truncated to 32 bits reads element t - 2^32 of the buffer, 5.4M (f32) or 10.7M (halves) rows lower: other
+    pseudo-random rows; a truncated row offset on the handle reads row id - 8,388,608.
+    Device memory on top of the fixture: 5 + 6.4 GB while the handle lives, 5 + 10 GB for the way back; host: 30 MB."""
+    import torch
+    import granne_amd
+    from granne_amd import _lib
+    kind, el, q, _ = built[:4]
+    if built.dim != 200:
+        pytest.skip("rows of halves past 4 GiB are made from the 200-d case's rows only (5 GB of halves)")
+    n, dim = built.n, built.dim
+    lib = _lib.lib()
+    sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    marks = sorted({high_ids.first_high(dim * 4), high_ids.first_high(dim * 2)})
+    windows = [(max(0, m - 2048), min(n, m + 2048)) for m in marks if m + 2048 <= n] + [(max(0, n - 4096), n)]
+    if len(windows) == 3:
+        print("f16 conversions: windows around rows %d and %d (the 4 GiB marks of the f32 and f16 buffers) and at the end; "
+              "past-the-mark assertions ran" % tuple(marks))
+    else:
+        print("f16 conversions: %d rows end below a 4 GiB mark; windows %s" % (n, windows))
+    el16 = torch.empty((n, dim), dtype=torch.float16, device="cuda")
+    _lib.check(lib.granne_hip_f32_to_f16_device(C.c_void_p(el.data_ptr()), C.c_void_p(el16.data_ptr()), n, dim, 0, sp))
+    torch.cuda.synchronize()
+    for a, b in windows:
+        assert el16[a:b].cpu().numpy().tobytes() == el[a:b].cpu().numpy().astype(np.float16).tobytes(), (a, b)
+    ix = granne_amd.Granne.from_device("angular_f16", el16.data_ptr(), n, dim, [], [], [])
+    try:
+        stride = high_ids.device_row_stride("f16", dim)
+        assert ix.hbm_bytes() == n * stride and stride == 512
+        R = high_ids.Range(n, stride, "f16 handle")
+
+        def prep(rows16):
+            return oracle.normalize_f32(rows16.astype(np.float32))
+        high_ids.check_get_element(ix, el16, R, np.random.default_rng(21))
+        high_ids.check_dists(oracle, ix, el16, prep, q, R, np.random.default_rng(22))
+        high_ids.check_refine(oracle, ix, el16, prep, q, R, np.random.default_rng(23))
+    finally:
+        ix.close()
+    back = torch.empty((n, dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.granne_hip_f16_to_f32_device(C.c_void_p(el16.data_ptr()), C.c_void_p(back.data_ptr()), n, dim, 1, 0, sp))
+    torch.cuda.synchronize()
+    for a, b in windows:
+        want = oracle.normalize_f32(el16[a:b].cpu().numpy().astype(np.float32))
+        assert back[a:b].cpu().numpy().tobytes() == want.tobytes(), (a, b)
+    del back, el16
+    torch.cuda.empty_cache()
 
 
 def test_reorder_at_full_size(built):

@@ -353,3 +353,61 @@ def test_merge_topk_accepts_lists_in_any_order(shards, k):
     for q in range(nq):
         c = int(want[2][q])
         assert got_d[q, :c].tobytes() == want[1][q, :c].tobytes() and (got_ids[q, :c] == want[0][q, :c]).all(), q
+
+
+def _merge_on_the_device(ids, ds, cnt, offsets, k, packed):
+    """granne_hip_merge_topk_device over three [shards][...] arrays, or granne_hip_merge_topk_packed_device over the shards'
+    records as oracle.merge.pack_topk lays them out, one after the other"""
+    import torch
+    from granne_amd import _lib
+    from oracle.merge import pack_topk, packed_bytes
+    shards, nq = cnt.shape
+    o_ids = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+    o_ds = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+    o_cnt = torch.empty(nq, dtype=torch.int32, device="cuda")
+    off = (C.c_uint64 * shards)(*[int(x) for x in offsets])
+    outs = (C.c_void_p(o_ids.data_ptr()), C.c_void_p(o_ds.data_ptr()), C.c_void_p(o_cnt.data_ptr()), 0,
+            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if packed:
+        rec = np.concatenate([pack_topk(ids[s], ds[s], cnt[s]) for s in range(shards)])
+        assert rec.size == shards * packed_bytes(nq, k) == shards * int(_lib.lib().granne_hip_packed_topk_bytes(nq, k))
+        d_rec = torch.from_numpy(rec).cuda()
+        _lib.check(_lib.lib().granne_hip_merge_topk_packed_device(C.c_void_p(d_rec.data_ptr()), off, shards, nq, k, *outs))
+    else:
+        d_ids, d_ds, d_cnt = (torch.from_numpy(ids.view(np.int64)).cuda(), torch.from_numpy(ds).cuda(), torch.from_numpy(cnt.view(np.int32)).cuda())
+        _lib.check(_lib.lib().granne_hip_merge_topk_device(C.c_void_p(d_ids.data_ptr()), C.c_void_p(d_ds.data_ptr()),
+                                                           C.c_void_p(d_cnt.data_ptr()), off, shards, nq, k, *outs))
+    torch.cuda.synchronize()
+    return o_ids.cpu().numpy().view(np.uint64), o_ds.cpu().numpy(), o_cnt.cpu().numpy().astype(np.uint32)
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("offsets", ["straddle_2_32", "shard_shl_33", "shard_shl_41"])
+@pytest.mark.parametrize("shards,k", [(3, 10), (7, 16), (64, 16)])
+def test_merge_topk_orders_by_the_full_64_bit_global_id(shards, k, offsets, packed):
+    """merge_topk_kernel carries a global id's high word through its own pair of readlanes and breaks distance ties on the
+    full 64 bits; test_merge_topk_accepts_lists_in_any_order keeps every id below 2^19. Here: offsets 2^32 - 2500 + 5000 s
+    (shards whose ids straddle the word boundary: a sum that dropped the carry, or a compare of low words alone, orders
+    them wrongly), and offsets s << 33 / s << 41 with local ids drawn from 8 values and distances from 12, so that many
+    candidates tie on the distance AND on the low word of the id and differ in the high word only (a tie-break on the low
+    word, or a high word taken from the wrong lane, shows). Reference: oracle.merge.merge_topk_numpy, itself held to
+    sorted() of (dist, id) tuples on such input in tests/test_sharded_gloo.py. Both entries: three arrays and packed records."""
+    rng = np.random.default_rng(shards * 100 + k + len(offsets))
+    nq = 37
+    if offsets == "straddle_2_32":
+        off = np.uint64((1 << 32) - 2500) + np.arange(shards, dtype=np.uint64) * np.uint64(5000)
+        ids = rng.integers(0, 5000, (shards, nq, k)).astype(np.uint64)
+    else:
+        off = np.arange(shards, dtype=np.uint64) << np.uint64(33 if offsets == "shard_shl_33" else 41)
+        ids = rng.choice(np.array([0, 1, 2, 3, 5, 8, 13, 21], np.uint64), (shards, nq, k))
+    ds = (rng.integers(0, 12, (shards, nq, k)) / 16.0).astype(np.float32)
+    cnt = rng.integers(0, k + 1, (shards, nq)).astype(np.uint32)
+    cnt[0, :] = k
+    want = merge_topk_numpy(ids, ds, cnt, off, k)
+    assert (want[2] == k).all() and int(want[0][want[0] != np.iinfo(np.uint64).max].max()) >= 1 << 32
+    if offsets != "straddle_2_32":  # the input does hold ties that only the high word decides
+        flat = [(float(ds[s, 0, j]), int(ids[s, 0, j])) for s in range(shards) for j in range(int(cnt[s, 0]))]
+        assert len(set(flat)) < len(flat)
+    got_ids, got_d, got_c = _merge_on_the_device(ids, ds, cnt, off, k, packed)
+    assert (got_c == want[2]).all()
+    assert got_d.tobytes() == want[1].tobytes() and (got_ids == want[0]).all(), np.nonzero((got_ids != want[0]).any(axis=1))[0][:5]

@@ -168,6 +168,21 @@ def test_partitioned_search_two_ranks_gloo(tmp_path, oracle):
     assert (want[1][:, 0] <= ds[:, :, 0].min(axis=0)).all()
 
 
+def test_merge_topk_numpy_orders_by_the_full_64_bit_id():
+    """The GPU merge's reference on global ids beyond 32 bits: shards that straddle 2^32, and offsets s << 33 / s << 41
+    with few local ids and few distances, so that candidates tie on the distance and on the id's low word."""
+    rng = np.random.default_rng(64)
+    G, nq, k = 7, 5, 6
+    for off in ([(1 << 32) - 2500 + 5000 * s for s in range(G)], [s << 33 for s in range(G)], [s << 41 for s in range(G)]):
+        ids = rng.choice(np.array([0, 1, 2, 3, 5, 8, 13, 4999], np.uint64), (G, nq, k))
+        ds = (rng.integers(0, 4, (G, nq, k)) / 16.0).astype(np.float32)
+        cnt = rng.integers(1, k + 1, (G, nq)).astype(np.uint32)
+        got = merge_topk_numpy(ids, ds, cnt, np.array(off, np.uint64), k)
+        for q in range(nq):
+            want = sorted((float(ds[g, q, j]), int(ids[g, q, j]) + off[g]) for g in range(G) for j in range(int(cnt[g, q])))[:k]
+            assert list(zip(got[1][q].tolist(), got[0][q].tolist())) == want and int(got[2][q]) == k
+
+
 def test_shard_bounds():
     from granne_amd import sharded
     assert sharded.shard_bounds(10, 4) == [(0, 3), (3, 6), (6, 9), (9, 10)]
