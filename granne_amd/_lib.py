@@ -20,6 +20,10 @@ OPT_SKETCH = 12
 OPT_COALESCE, OPT_COALESCE_MAX, OPT_COALESCE_WAIT_US, OPT_COALESCED_LAUNCHES, OPT_COALESCED_QUERIES = 13, 14, 15, 16, 17
 OPT_LAST_COMPACT_ROWS = 18  # read-only: the last launch ran the compacted row stage of the sketched walkers
 OPT_LAST_SPLIT_TAIL = 19  # read-only: the last launch ran its tail blocks as a kernel of their own, behind the walkers'
+OPT_LAST_SCAN = 20  # read-only: what the last exact scan ran, one packed word (last_scan() takes it apart)
+# GRANNE_HIP_SCAN_*: the exact scan's kernel forms, one per rule of its dispatch
+(SCAN_NONE, SCAN_RING, SCAN_I8, SCAN_I8_CHUNKED, SCAN_B16_7_4, SCAN_B16_13_2, SCAN_B16_16_1, SCAN_B16_CHUNKED, SCAN_F32_52_4,
+ SCAN_F32_100_2, SCAN_F32_128_1) = range(11)
 COALESCE_CALL_MAX = 64  # GRANNE_HIP_COALESCE_CALL_MAX
 COALESCE_MAX = 1024  # GRANNE_HIP_COALESCE_MAX
 WALKER_NONE, WALKER_REGISTER, WALKER_REGISTER_WIDE, WALKER_GENERAL, WALKER_EXACT = 0, 1, 2, 3, 4
@@ -30,6 +34,14 @@ SHARDED_EXCHANGE_PEER, SHARDED_EXCHANGE_RCCL = 0, 1
 RW_OPT_SMALL_OPS, RW_OPT_SMALL_LAUNCHES, RW_OPT_SORTED_LAUNCHES = 1, 2, 3  # GRANNE_HIP_RW_OPT_*
 RW_SMALL_OPS = 2048  # GRANNE_HIP_RW_SMALL_OPS
 SE_MATERIALIZED, SE_COMPACT = 0, 1  # GRANNE_HIP_SE_*: the two forms of an index over a SumEmbeddings container
+
+
+def last_scan(word):
+    """GRANNE_HIP_OPT_LAST_SCAN's word (include/granne_hip.h) as a dict: form (SCAN_*), ranges (G), primed (bool),
+    prime_ranges (Gs, 0 with fewer than 32 ranges), kk."""
+    word = int(word)
+    return {"form": word & 0xFF, "ranges": word >> 8 & 0xFFFF, "primed": bool(word >> 24 & 1),
+            "prime_ranges": word >> 32 & 0xFF, "kk": word >> 40 & 0xFF}
 
 
 class GranneHipError(RuntimeError):

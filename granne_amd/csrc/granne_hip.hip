@@ -188,6 +188,7 @@ struct granne_hip_index {
     std::atomic<uint64_t> last_walker{0}; // GRANNE_HIP_OPT_LAST_WALKER
     std::atomic<uint64_t> last_compact{0}; // GRANNE_HIP_OPT_LAST_COMPACT_ROWS
     std::atomic<uint64_t> last_split{0};   // GRANNE_HIP_OPT_LAST_SPLIT_TAIL
+    std::atomic<uint64_t> last_scan{0};    // GRANNE_HIP_OPT_LAST_SCAN
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
     DevBuf d_inv_norm;
@@ -758,6 +759,7 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
     case GRANNE_HIP_OPT_COALESCED_QUERIES:
     case GRANNE_HIP_OPT_LAST_COMPACT_ROWS:
     case GRANNE_HIP_OPT_LAST_SPLIT_TAIL:
+    case GRANNE_HIP_OPT_LAST_SCAN:
         return fail(GRANNE_HIP_ERR_INVALID, "option %d is read-only", option);
     default:
         return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
@@ -786,6 +788,7 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     case GRANNE_HIP_OPT_COALESCED_QUERIES: *value = ix->combiner.queries(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_LAST_COMPACT_ROWS: *value = ix->last_compact.load(); return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_LAST_SPLIT_TAIL: *value = ix->last_split.load(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_LAST_SCAN: *value = ix->last_scan.load(); return GRANNE_HIP_OK;
     default: return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -1994,6 +1997,7 @@ static int merge_launch(const uint8_t* ids, const uint8_t* dists, const uint8_t*
 
 // which scan kernel serves an index's rows (brute_force.h), and how it is launched
 struct ScanPlan {
+    uint64_t form; // GRANNE_HIP_SCAN_*: what GRANNE_HIP_OPT_LAST_SCAN reports
     void (*fn)(const BruteParams);
     void (*prime)(const BruteParams); // the same scan keeping only the best score per (range, query)
     BfGeometry geo, prime_geo;
@@ -2002,26 +2006,26 @@ struct ScanPlan {
 static ScanPlan plan_scan(const granne_hip_index* ix, uint32_t nq) {
     if (ix->dtype == GRANNE_HIP_I8) {
         if (ix->row_bytes > 128u) // rows of any length: in chunks of 128 bytes (brute_force.h, bf_i8_chunked_kernel)
-            return {bf_i8_chunked_kernel<4>, bf_i8_chunked_kernel<4, true>, bf_i8_chunked_geometry<4>(), bf_i8_chunked_geometry<4>()};
+            return {GRANNE_HIP_SCAN_I8_CHUNKED, bf_i8_chunked_kernel<4>, bf_i8_chunked_kernel<4, true>, bf_i8_chunked_geometry<4>(), bf_i8_chunked_geometry<4>()};
         if (knobs().bf_ring && ix->row_bytes == 128u && ix->row_stride == 128u && ix->n_elements < (1ull << 29)) {
             // tiles by LDS-DMA into a ring, 64 queries per wave (brute_force.h, bf_i8_ring_kernel); the priming pass stays
-            ScanPlan P{bf_i8_ring_kernel, bf_i8_kernel<4, true>, bf_ring_geometry(), bf_i8_geometry<4>()};
+            ScanPlan P{GRANNE_HIP_SCAN_RING, bf_i8_ring_kernel, bf_i8_kernel<4, true>, bf_ring_geometry(), bf_i8_geometry<4>()};
             // 512 queries per block: half as many blocks per range, so twice the ranges fill the chip (merged in two steps)
             if ((uint64_t)((nq + P.geo.qt - 1) / P.geo.qt) * 64u < 256u) P.max_ranges = 128;
             return P;
         }
-        return {bf_i8_kernel<4>, bf_i8_kernel<4, true>, bf_i8_geometry<4>(), bf_i8_geometry<4>()};
+        return {GRANNE_HIP_SCAN_I8, bf_i8_kernel<4>, bf_i8_kernel<4, true>, bf_i8_geometry<4>(), bf_i8_geometry<4>()};
     }
     // f32 rows on the bf16 matrix path, three instructions per product (brute_force.h)
-    if (knobs().bf_b16 && ix->dim <= 112) return {bf_b16_kernel<7, 4>, bf_b16_kernel<7, 4, true>, bf_b16_geometry<7, 4>(), bf_b16_geometry<7, 4>()};
-    if (knobs().bf_b16 && ix->dim <= 208) return {bf_b16_kernel<13, 2>, bf_b16_kernel<13, 2, true>, bf_b16_geometry<13, 2>(), bf_b16_geometry<13, 2>()};
+    if (knobs().bf_b16 && ix->dim <= 112) return {GRANNE_HIP_SCAN_B16_7_4, bf_b16_kernel<7, 4>, bf_b16_kernel<7, 4, true>, bf_b16_geometry<7, 4>(), bf_b16_geometry<7, 4>()};
+    if (knobs().bf_b16 && ix->dim <= 208) return {GRANNE_HIP_SCAN_B16_13_2, bf_b16_kernel<13, 2>, bf_b16_kernel<13, 2, true>, bf_b16_geometry<13, 2>(), bf_b16_geometry<13, 2>()};
     // rows of any length: the vector in chunks of 128 components (brute_force.h, bf_b16_chunked_kernel; tiles of 64 rows:
     // 128 take 256 registers and spill)
-    if (ix->dim > 256) return {bf_b16_chunked_kernel<2>, bf_b16_chunked_kernel<2, true>, bf_b16_chunked_geometry<2>(), bf_b16_chunked_geometry<2>()};
-    if (knobs().bf_b16) return {bf_b16_kernel<16, 1>, bf_b16_kernel<16, 1, true>, bf_b16_geometry<16, 1>(), bf_b16_geometry<16, 1>()};
-    if (ix->dim <= 104) return {bf_f32_kernel<52, 4>, bf_f32_kernel<52, 4, true>, bf_f32_geometry<52, 4>(), bf_f32_geometry<52, 4>()};
-    if (ix->dim <= 200) return {bf_f32_kernel<100, 2>, bf_f32_kernel<100, 2, true>, bf_f32_geometry<100, 2>(), bf_f32_geometry<100, 2>()};
-    return {bf_f32_kernel<128, 1>, bf_f32_kernel<128, 1, true>, bf_f32_geometry<128, 1>(), bf_f32_geometry<128, 1>()};
+    if (ix->dim > 256) return {GRANNE_HIP_SCAN_B16_CHUNKED, bf_b16_chunked_kernel<2>, bf_b16_chunked_kernel<2, true>, bf_b16_chunked_geometry<2>(), bf_b16_chunked_geometry<2>()};
+    if (knobs().bf_b16) return {GRANNE_HIP_SCAN_B16_16_1, bf_b16_kernel<16, 1>, bf_b16_kernel<16, 1, true>, bf_b16_geometry<16, 1>(), bf_b16_geometry<16, 1>()};
+    if (ix->dim <= 104) return {GRANNE_HIP_SCAN_F32_52_4, bf_f32_kernel<52, 4>, bf_f32_kernel<52, 4, true>, bf_f32_geometry<52, 4>(), bf_f32_geometry<52, 4>()};
+    if (ix->dim <= 200) return {GRANNE_HIP_SCAN_F32_100_2, bf_f32_kernel<100, 2>, bf_f32_kernel<100, 2, true>, bf_f32_geometry<100, 2>(), bf_f32_geometry<100, 2>()};
+    return {GRANNE_HIP_SCAN_F32_128_1, bf_f32_kernel<128, 1>, bf_f32_kernel<128, 1, true>, bf_f32_geometry<128, 1>(), bf_f32_geometry<128, 1>()};
 }
 
 // the scan's scratch: the ranges' lists, the merged lists, the candidates and their exact distances, the thresholds, what
@@ -2094,6 +2098,19 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
     uint64_t per_range = (n + G - 1) / G;
     per_range = (per_range + tile - 1) / tile * tile;
     if (per_range < tile) per_range = tile;
+    // The priming pass (brute_force.h, bf_tau_kernel) scans the first range alone, cut into up to 64 sub-ranges so that the
+    // whole chip scans it (1/64 of the scan proper, without its lists: the best score per sub-range and query). It runs
+    // when there are at least 32 ranges and its sub-ranges hold kk maxima; GRANNE_HIP_OPT_LAST_SCAN says what this call runs
+    const uint64_t prime_n = per_range < n ? per_range : n;
+    uint64_t prime_per = 0, Gs = 0; // (Gs stays 0 with fewer than 32 ranges)
+    if (G >= 32) {
+        Gs = (prime_n + tile - 1) / tile;
+        if (Gs > 64) Gs = 64;
+        prime_per = ((prime_n + Gs - 1) / Gs + tile - 1) / tile * tile;
+        Gs = (prime_n + prime_per - 1) / prime_per;
+    }
+    const bool primed = G >= 32 && Gs >= kk;
+    const_cast<granne_hip_index*>(ix)->last_scan.store(S.form | G << 8 | (uint64_t)(primed ? 1 : 0) << 24 | Gs << 32 | (uint64_t)kk << 40);
     const size_t share_bytes = (size_t)nq * BF_SHARE_BUCKETS * 4;
     const size_t qpad_bytes = (ix->dtype == GRANNE_HIP_I8 && ix->row_bytes > 128u) ? (size_t)nq * ix->row_bytes : 0;
     const ScanScratch o(G, nq, kk, share_bytes, qpad_bytes);
@@ -2147,28 +2164,20 @@ extern "C" int granne_hip_brute_force_device(const granne_hip_index* ix, const v
         HIP_TRY(hipGetLastError());
         P.qpad = scratch + o.qpad;
     }
-    if (G >= 32) {
-        // the priming pass (brute_force.h, bf_tau_kernel): the first range alone, cut into up to 64 sub-ranges so that the
-        // whole chip scans it (1/64 of the scan proper, without its lists: the best score per sub-range and query)
+    if (primed) {
         BruteParams Q = P;
-        Q.n = per_range < n ? per_range : n;
-        uint64_t Gs = (Q.n + tile - 1) / tile;
-        if (Gs > 64) Gs = 64;
-        Q.per_range = ((Q.n + Gs - 1) / Gs + tile - 1) / tile * tile;
-        Gs = (Q.n + Q.per_range - 1) / Q.per_range;
-        if (Gs >= kk) {
-            const BfGeometry& pg = S.prime_geo;
-            if (pg.lds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)S.prime, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg.lds));
-            hipLaunchKernelGGL(S.prime, dim3((nq + pg.qt - 1) / pg.qt, (uint32_t)Gs), dim3(pg.threads), pg.lds, s, Q);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(bf_tau_kernel, dim3(nq), dim3(64), 0, s, (const float*)P.part_d, (uint32_t)Gs, nq, kk,
-                               (float*)(scratch + o.tau));
-            HIP_TRY(hipGetLastError());
-            P.tau_in = (const float*)(scratch + o.tau);
-            // the ranges of a query tell each other what they have seen (brute_force.h, BfShare)
-            HIP_TRY(hipMemsetAsync(scratch + o.share, 0, share_bytes, s));
-            P.share_hist = (uint32_t*)(scratch + o.share);
-        }
+        Q.n = prime_n;
+        Q.per_range = prime_per;
+        const BfGeometry& pg = S.prime_geo;
+        if (pg.lds > 64u * 1024u) HIP_TRY(hipFuncSetAttribute((const void*)S.prime, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg.lds));
+        hipLaunchKernelGGL(S.prime, dim3((nq + pg.qt - 1) / pg.qt, (uint32_t)Gs), dim3(pg.threads), pg.lds, s, Q);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(bf_tau_kernel, dim3(nq), dim3(64), 0, s, (const float*)P.part_d, (uint32_t)Gs, nq, kk, (float*)(scratch + o.tau));
+        HIP_TRY(hipGetLastError());
+        P.tau_in = (const float*)(scratch + o.tau);
+        // the ranges of a query tell each other what they have seen (brute_force.h, BfShare)
+        HIP_TRY(hipMemsetAsync(scratch + o.share, 0, share_bytes, s));
+        P.share_hist = (uint32_t*)(scratch + o.share);
     }
     hipLaunchKernelGGL(S.fn, dim3((nq + S.geo.qt - 1) / S.geo.qt, (uint32_t)G), dim3(S.geo.threads), S.geo.lds, s, P);
     HIP_TRY(hipGetLastError());

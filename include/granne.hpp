@@ -274,6 +274,16 @@ public:
     bool last_compact_rows() const { return get_option(GRANNE_HIP_OPT_LAST_COMPACT_ROWS) != 0; }
     // whether the last search launch ran its tail blocks as a kernel of their own (GRANNE_HIP_OPT_LAST_SPLIT_TAIL)
     bool last_split_tail() const { return get_option(GRANNE_HIP_OPT_LAST_SPLIT_TAIL) != 0; }
+    // what the last exact scan ran (GRANNE_HIP_OPT_LAST_SCAN): the kernel form, the ranges, whether the priming pass ran
+    struct LastScan {
+        unsigned form, ranges, prime_ranges, kk; // GRANNE_HIP_SCAN_*, G, Gs, min(k + 6, 16)
+        bool primed;
+    };
+    LastScan last_scan() const {
+        const uint64_t w = get_option(GRANNE_HIP_OPT_LAST_SCAN);
+        return {GRANNE_HIP_LAST_SCAN_FORM(w), GRANNE_HIP_LAST_SCAN_RANGES(w), GRANNE_HIP_LAST_SCAN_PRIME_RANGES(w),
+                GRANNE_HIP_LAST_SCAN_KK(w), GRANNE_HIP_LAST_SCAN_PRIMED(w) != 0};
+    }
     uint64_t get_option(int option) const {
         uint64_t v = 0;
         check(granne_hip_index_get_option(h_.get(), option, &v));

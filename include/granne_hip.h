@@ -764,10 +764,37 @@ enum {
     GRANNE_HIP_OPT_LAST_COMPACT_ROWS = 18,  /* read-only: 1 when the index's last search launch ran the register walker's compacted
                                                row stage -- the launches that use the row sketch (GRANNE_HIP_OPT_SKETCH) read
                                                and evaluate only the neighbors that survive it, several lanes to a row; same bits */
-    GRANNE_HIP_OPT_LAST_SPLIT_TAIL = 19     /* read-only: 1 when the index's last search launch was two kernels on the stream --
+    GRANNE_HIP_OPT_LAST_SPLIT_TAIL = 19,    /* read-only: 1 when the index's last search launch was two kernels on the stream --
                                                the walkers, then the exact walker's tail blocks in a kernel of their own: the
                                                compacted launches of more walks than the chip holds at once. Same bits, same
                                                status words, nothing allocated or waited for; every other launch is one kernel */
+    GRANNE_HIP_OPT_LAST_SCAN = 20           /* read-only: what the index's last exact scan (granne_hip_brute_force*) ran, one packed
+                                               word set on every call before anything is launched; 0 before the first scan.
+                                                 bits  0..7   the kernel form, GRANNE_HIP_SCAN_* below
+                                                 bits  8..23  G: the element ranges the scan was cut into (1..128)
+                                                 bit   24     1 when the priming pass and the threshold shared by the ranges ran
+                                                 bits 32..39  Gs: the priming pass's sub-ranges of the first range (0 when G < 32;
+                                                              the pass runs when G >= 32 and Gs >= kk)
+                                                 bits 40..47  kk = min(k + 6, 16): the candidates kept per query
+                                               GRANNE_HIP_LAST_SCAN_*() take the word apart */
+};
+#define GRANNE_HIP_LAST_SCAN_FORM(w) ((unsigned)((w) & 0xFFu))
+#define GRANNE_HIP_LAST_SCAN_RANGES(w) ((unsigned)((w) >> 8 & 0xFFFFu))
+#define GRANNE_HIP_LAST_SCAN_PRIMED(w) ((unsigned)((w) >> 24 & 1u))
+#define GRANNE_HIP_LAST_SCAN_PRIME_RANGES(w) ((unsigned)((w) >> 32 & 0xFFu))
+#define GRANNE_HIP_LAST_SCAN_KK(w) ((unsigned)((w) >> 40 & 0xFFu))
+enum { /* the exact scan's kernel forms (brute_force.h), one per rule of the dispatch */
+    GRANNE_HIP_SCAN_NONE = 0,        /* no scan yet */
+    GRANNE_HIP_SCAN_RING = 1,        /* int8 rows of 128 bytes: bf_i8_ring_kernel (tiles by LDS-DMA; up to 128 ranges) */
+    GRANNE_HIP_SCAN_I8 = 2,          /* int8 rows of up to 128 bytes otherwise: bf_i8_kernel<4> */
+    GRANNE_HIP_SCAN_I8_CHUNKED = 3,  /* int8 rows of more than 128 bytes: bf_i8_chunked_kernel<4> */
+    GRANNE_HIP_SCAN_B16_7_4 = 4,     /* f32 rows of up to 112 dims as bf16 pieces: bf_b16_kernel<7, 4> */
+    GRANNE_HIP_SCAN_B16_13_2 = 5,    /* 113..208 dims: bf_b16_kernel<13, 2> */
+    GRANNE_HIP_SCAN_B16_16_1 = 6,    /* 209..256 dims: bf_b16_kernel<16, 1> */
+    GRANNE_HIP_SCAN_B16_CHUNKED = 7, /* more than 256 dims: bf_b16_chunked_kernel<2> */
+    GRANNE_HIP_SCAN_F32_52_4 = 8,    /* the f32 matrix path (GRANNE_HIP_BF_B16=0), up to 104 dims: bf_f32_kernel<52, 4> */
+    GRANNE_HIP_SCAN_F32_100_2 = 9,   /* ... 105..200 dims: bf_f32_kernel<100, 2> */
+    GRANNE_HIP_SCAN_F32_128_1 = 10   /* ... 201..256 dims: bf_f32_kernel<128, 1> */
 };
 #define GRANNE_HIP_COALESCE_CALL_MAX 64 /* calls of more queries than this never take part in GRANNE_HIP_OPT_COALESCE */
 #define GRANNE_HIP_COALESCE_MAX 1024    /* the largest (and default) GRANNE_HIP_OPT_COALESCE_MAX */

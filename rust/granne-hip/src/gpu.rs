@@ -181,6 +181,7 @@ pub const GRANNE_HIP_OPT_COALESCED_LAUNCHES: c_int = 16;
 pub const GRANNE_HIP_OPT_COALESCED_QUERIES: c_int = 17;
 pub const GRANNE_HIP_OPT_LAST_COMPACT_ROWS: c_int = 18;
 pub const GRANNE_HIP_OPT_LAST_SPLIT_TAIL: c_int = 19;
+pub const GRANNE_HIP_OPT_LAST_SCAN: c_int = 20;
 pub const GRANNE_HIP_RW_OPT_SMALL_OPS: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;

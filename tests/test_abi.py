@@ -85,6 +85,33 @@ def test_abi_version(lib):
     assert lib.granne_hip_abi_version() == 3
 
 
+def test_last_scan_option_agrees_in_every_binding():
+    """GRANNE_HIP_OPT_LAST_SCAN continues the option enum at 20 in include/granne_hip.h, granne_amd/_lib.py and
+    rust/granne-hip/src/gpu.rs; the ten kernel forms carry the same values in the header and in _lib; _lib.last_scan takes
+    the word apart as the header's macros do; include/granne.hpp reaches it; the option is read-only."""
+    header = open(os.path.join(ROOT, "include", "granne_hip.h")).read()
+    rust = open(RUST_GPU_RS).read()
+    assert int(re.search(r"\bGRANNE_HIP_OPT_LAST_SPLIT_TAIL\s*=\s*(\d+)", header).group(1)) == 19
+    assert int(re.search(r"\bGRANNE_HIP_OPT_LAST_SCAN\s*=\s*(\d+)", header).group(1)) == 20 == _lib.OPT_LAST_SCAN
+    assert "pub const GRANNE_HIP_OPT_LAST_SCAN: c_int = 20;" in rust
+    forms = dict((n, int(v)) for n, v in re.findall(r"\bGRANNE_HIP_SCAN_([A-Z0-9_]+)\s*=\s*(\d+)", header))
+    assert sorted(forms.values()) == list(range(11)) and forms["NONE"] == 0
+    for name, value in forms.items():
+        assert getattr(_lib, "SCAN_" + name) == value, name
+    macros = dict(re.findall(r"#define GRANNE_HIP_LAST_SCAN_([A-Z_]+)\(w\) \(\(unsigned\)\((.*)\)\)", header))
+    assert sorted(macros) == ["FORM", "KK", "PRIMED", "PRIME_RANGES", "RANGES"]
+    word = 7 | 128 << 8 | 1 << 24 | 16 << 32 | 15 << 40  # b16_chunked, 128 ranges, primed, 16 sub-ranges, kk 15
+    got = _lib.last_scan(word)
+    assert got == {"form": _lib.SCAN_B16_CHUNKED, "ranges": 128, "primed": True, "prime_ranges": 16, "kk": 15}
+    key = {"FORM": "form", "RANGES": "ranges", "PRIMED": "primed", "PRIME_RANGES": "prime_ranges", "KK": "kk"}
+    for name, expr in macros.items():  # the macro bodies are C that reads as Python once the suffixes are gone
+        assert eval(expr.replace("(w)", "(%d)" % word).replace("u", "")) == int(got[key[name]]), name
+    assert "LastScan last_scan() const" in open(os.path.join(ROOT, "include", "granne.hpp")).read()
+    hip = open(os.path.join(ROOT, "granne_amd", "csrc", "granne_hip.hip")).read()
+    setter = hip[hip.index('extern "C" int granne_hip_index_set_option'):hip.index('extern "C" int granne_hip_index_get_option')]
+    assert re.search(r"case GRANNE_HIP_OPT_LAST_SCAN:\s*return fail\(GRANNE_HIP_ERR_INVALID, \"option %d is read-only\"", setter)
+
+
 def test_library_contains_gfx950_code_object():
     blob = open(build.LIB_PATH, "rb").read()
     assert b"gfx950" in blob

@@ -12,6 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests.conftest import random_floats  # noqa: E402
+from tests.scan_forms import structured_rows as _data  # noqa: E402
 from tests.test_sketch_bound import row_sketch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,23 +29,6 @@ def oracle():
     from oracle import oracle as orc
     orc.build()
     return orc
-
-
-def _data(kind, rng, n, dim=100):
-    if kind == "uniform":
-        return random_floats(rng, n, dim)
-    if kind == "latent":
-        base = rng.standard_normal((8, dim)).astype(np.float32)
-        return (rng.standard_normal((n, 8)).astype(np.float32) @ base + 0.05 * random_floats(rng, n, dim)).astype(np.float32)
-    if kind == "mixture":
-        centers = random_floats(rng, 64, dim)
-        return (centers[rng.integers(0, 64, n)] + 0.05 * random_floats(rng, n, dim)).astype(np.float32)
-    if kind == "duplicates":
-        base = random_floats(rng, n // 4, dim)
-        return base[rng.integers(0, n // 4, n)].copy()
-    if kind == "grid":  # few distinct values per component: many equal distances
-        return (rng.integers(-1, 2, (n, dim)).astype(np.float32) * np.float32(0.25)).astype(np.float32)
-    raise ValueError(kind)
 
 
 def _index(ga, oracle, kind, seed, n=6000):

@@ -302,7 +302,9 @@ def test_exact_scan_on_value_edges(ga, oracle, name):
     2 % by the oracle alone: the returned distances are the oracle's bits for the returned ids, ascending by (distance,
     id); every distance within the tolerance of the true one at its rank; ids equal in more than 98 % of the positions
     and within the tolerance elsewhere. Blocks whose lane halves see norms 40 x apart, queries whose best scores are all
-    negative, and (primed sizes) a nearest neighbour of 1 / 40 of its block's norms."""
+    negative, and (primed sizes) a nearest neighbour of 1 / 40 of its block's norms. Every scan asserts the kernel form, the
+    ranges and whether the priming pass ran (value_edges.SCAN_RAN)."""
+    from granne_amd import _lib
     el, q, tol = ve.scan_input(name)
     n, nq = len(el), len(q)
     primed = name.endswith("primed")
@@ -311,6 +313,10 @@ def test_exact_scan_on_value_edges(ga, oracle, name):
     checked = range(nq) if not primed else list(range(ve.PLANTED + 8)) + [nq - 1]
     for k in ve.SCAN_KS:
         ids, ds, cnt = ix.brute_force(q, k)
+        form, ranges, primed_ks = ve.SCAN_RAN[name]
+        ran = _lib.last_scan(ix.get_option(_lib.OPT_LAST_SCAN))
+        assert (ran["form"], ran["ranges"], ran["primed"]) == (getattr(_lib, "SCAN_" + form), ranges, k in primed_ks), (k, ran)
+        assert not primed or ran["primed"]
         want_i, want_d = truth_i[:, :k], truth_d[:, :k]
         assert (cnt == k).all()
         for qi in checked:

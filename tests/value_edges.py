@@ -133,11 +133,23 @@ SCAN_INPUTS = {
     "short_f32_100": ("short_f32", 100, 5000, 70, 8),
     "short_f32_300": ("short_f32", 300, 1300, 70, 9),
     "unit_f32_100": ("unit_f32", 100, 5000, 70, 10),
-    # the two smallest sizes at which the priming pass, the shared threshold and (128-byte rows) the ring run
-    "odd_i8_128_primed": ("odd_i8_planted", 128, 70_049, 520, 11),
-    "odd_i8_100_primed": ("odd_i8_planted", 100, 150_000, 200, 12),
+    # the smallest sizes (and 32 rows: a last tile of 33) at which the priming pass and the shared threshold run at every k of
+    # SCAN_KS on the ring: 122,881 rows with four query tiles (64 ranges), 245,761 with fewer (128 ranges)
+    "odd_i8_128_primed": ("odd_i8_planted", 128, 122_913, 1540, 11),
+    "odd_i8_100_primed": ("odd_i8_planted", 100, 245_793, 200, 12),
     # rows shorter than 128 bytes keep the first int8 kernel: primed, its thresholds are sharp enough for its block bound to cut
     "odd_i8_17_primed": ("odd_i8_planted", 17, 150_000, 100, 13),
+}
+# name -> what the scan runs (GRANNE_HIP_OPT_LAST_SCAN): the kernel form, the ranges, and the k of SCAN_KS at which the priming
+# pass runs. far_side_i8_17's first range holds 9 tiles: enough for kk = 7 alone.
+SCAN_RAN = {
+    "odd_i8_17": ("I8", 24, ()), "odd_i8_100": ("RING", 40, ()), "odd_i8_128": ("RING", 24, ()),
+    "odd_i8_200": ("I8_CHUNKED", 16, ()), "odd_i8_300": ("I8_CHUNKED", 12, ()),
+    "one_sided_i8_100": ("RING", 24, ()), "one_sided_i8_128": ("RING", 24, ()),
+    "far_side_i8_17": ("I8", 64, (1,)), "far_side_i8_100": ("RING", 128, ()),
+    "short_f32_100": ("B16_7_4", 40, ()), "short_f32_300": ("B16_CHUNKED", 21, ()), "unit_f32_100": ("B16_7_4", 40, ()),
+    "odd_i8_128_primed": ("RING", 64, (1, 10, 16)), "odd_i8_100_primed": ("RING", 128, (1, 10, 16)),
+    "odd_i8_17_primed": ("I8", 64, (1, 10, 16)),
 }
 PLANTED = 32
 
