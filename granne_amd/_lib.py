@@ -24,6 +24,8 @@ OPT_LAST_SCAN = 20  # read-only: what the last exact scan ran, one packed word (
 # GRANNE_HIP_SCAN_*: the exact scan's kernel forms, one per rule of its dispatch
 (SCAN_NONE, SCAN_RING, SCAN_I8, SCAN_I8_CHUNKED, SCAN_B16_7_4, SCAN_B16_13_2, SCAN_B16_16_1, SCAN_B16_CHUNKED, SCAN_F32_52_4,
  SCAN_F32_100_2, SCAN_F32_128_1) = range(11)
+EXACT_TOPK_KMAX = 1024  # GRANNE_HIP_EXACT_TOPK_KMAX
+EXACT_TOPK_CAP = 4096  # GRANNE_HIP_EXACT_TOPK_CAP: candidates ranked per query
 COALESCE_CALL_MAX = 64  # GRANNE_HIP_COALESCE_CALL_MAX
 COALESCE_MAX = 1024  # GRANNE_HIP_COALESCE_MAX
 WALKER_NONE, WALKER_REGISTER, WALKER_REGISTER_WIDE, WALKER_GENERAL, WALKER_EXACT = 0, 1, 2, 3, 4
@@ -132,6 +134,8 @@ SIGNATURES = {
     "granne_hip_index_file_decode_layer": (i32, [vp, u64, u32, vp, vp]),
     "granne_hip_brute_force_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
     "granne_hip_brute_force": (i32, [vp, vp, u32, u32, vp, vp, vp]),
+    "granne_hip_exact_topk_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_topk": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
     "granne_hip_merge_topk_device": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp]),
     "granne_hip_packed_topk_bytes": (u64, [u32, u32]),
     "granne_hip_search_batch_packed_device": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ._lib import F16, F32, I8, check, lib
+from ._lib import ERR_OVERFLOW, EXACT_TOPK_CAP, F16, F32, I8, GranneHipError, check, lib
 
 DEFAULT_MAX_SEARCH = 200   # py/src/lib.rs:14
 DEFAULT_NUM_ELEMENTS = 10  # py/src/lib.rs:15
@@ -453,6 +453,46 @@ class Granne:
                                 torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.synchronize(dev)
         return ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+
+    def exact_topk_device(self, d_queries, nq, k, d_ids, d_dists, d_counts, d_status=0, stream=0):
+        """Exact k (up to EXACT_TOPK_KMAX) nearest elements of every query in the reference's own arithmetic, selected by
+        (distance bits, id) (granne_hip_exact_topk_device). Raw device pointers (int; d_status: u32[4] zeroed by the
+        caller, or 0), asynchronous on `stream`."""
+        check(lib().granne_hip_exact_topk_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_ids),
+                                                 C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_status),
+                                                 C.c_void_p(stream)))
+
+    def exact_topk(self, queries, k, prepared=True, stats=False):
+        """Host convenience over exact_topk_device (torch moves the buffers): ids [nq, k] u64, dists [nq, k] f32, counts
+        [nq] u32, ascending by (distance, id) -- what a scalar scan sorted by that key gives, ties included, k up to
+        EXACT_TOPK_KMAX. A query that overflows the selection (status[0]: more than EXACT_TOPK_CAP rows inside one
+        second-level bin at its k-th distance) gets count 0 and a filled row: with stats=False that raises
+        GranneHipError(ERR_OVERFLOW); with stats=True the four status words are returned as a fourth value instead.
+        prepared=False applies Vector::from to the queries first, as `search` does."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        k = int(k)
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(q.shape[0], -1)).to(dev)
+        ids = torch.empty((q.shape[0], max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((q.shape[0], max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(q.shape[0], dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.exact_topk_device(tq.data_ptr(), q.shape[0], k, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(), st.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        status = st.cpu().numpy().astype(np.uint32)
+        out = ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk: %d queries have more than %d rows inside one second-level bin "
+                                 "at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
+        return out
 
     def dists_device(self, d_queries, nq, d_ids, m, d_out, d_status=0, stream=0):
         """ElementContainer::dists (src/elements/mod.rs:35-39) batched on device: out[q, j] =

@@ -210,6 +210,26 @@ public:
         return out;
     }
 
+    // The k (up to 1024) nearest elements of every query by a scan of all rows in the reference's own arithmetic,
+    // selected by (distance bits, id): exact by construction, ties included (granne_hip_exact_topk). Throws when a query
+    // overflowed the selection (thousands of copies of one row at its k-th distance).
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk(const Element* elements, size_t nq, size_t k) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        std::vector<uint64_t> ids(nq * k);
+        std::vector<float> ds(nq * k);
+        std::vector<uint32_t> counts(nq);
+        check(granne_hip_exact_topk(h_.get(), q.data(), (uint32_t)nq, (uint32_t)k, ids.data(), ds.data(), counts.data(), nullptr));
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // A handle over the rows alone (no layers): what RefinedGranne re-ranks by; get_element and the distance operators work
     static Granne from_elements(const Elements& elements, int device = 0) {
         granne_hip_index* h = nullptr;

@@ -44,7 +44,7 @@ enum { GRANNE_HIP_F32 = 0, GRANNE_HIP_I8 = 1, GRANNE_HIP_F16 = 2 };
  * result of an F16 index equals that of the f32 index over R = normalize(widen(rows)): ids, distance bits, order. Searches
  * run on the general walker (max_search <= 256) and the exact walker; dists*, dist_pairs*, refine* (as the refine index,
  * n_layers == 0 is enough), the builder, get_element (the stored halves) and the files (2-byte scalars) work.
- * brute_force*, reorder*, rw_builder_create, sharded_create*, sharded_build and builder_append return GRANNE_HIP_ERR_INVALID. Device rows are
+ * brute_force*, exact_topk*, reorder*, rw_builder_create, sharded_create*, sharded_build and builder_append return GRANNE_HIP_ERR_INVALID. Device rows are
  * padded to 16 bytes, and rows of 128 bytes and more start on a 128-byte line (100-d: 256 bytes, two lines). */
 
 enum {
@@ -365,13 +365,46 @@ int granne_hip_merge_topk_device(const uint64_t* d_ids, const float* d_dists, co
  * query are within the score's rounding of each other at the boundary of the selection: min(k + 6, 16)
  * candidates per query are selected and re-ranked, so k <= 10 has six spare candidates, k = 16 none. k <= 16; f32 rows
  * and int8 rows of any dimension (f32 beyond 256 dims and int8 beyond 128 are walked in chunks of 128 components /
- * bytes, at about half the rate per operation). queries: dense [nq][dim], prepared like the elements (the Python and
+ * bytes, at about half the rate per operation). For k > 10, k > 16 or near-tied data use granne_hip_exact_topk* below.
+ * queries: dense [nq][dim], prepared like the elements (the Python and
  * C++ wrappers check the width). Asynchronous on `stream`. */
 int granne_hip_brute_force_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
                                   uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, void* stream);
 /* the same with host buffers in and out (synchronous) */
 int granne_hip_brute_force(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
                            uint64_t* out_ids, float* out_dists, uint32_t* out_counts);
+
+/* Exact k nearest elements of every query, exact BY CONSTRUCTION, k up to 1024: every (query, row) distance is computed
+ * in the reference's own arithmetic (angular::Dist / angular_int::Dist, the bits granne_hip_dists* returns) and the k
+ * smallest are selected by the total key (distance bits, id) -- no score, no spare candidates, no clause about ids at a
+ * boundary. For finite inputs on or off the unit sphere, ties included, row q of the result is what a scalar scan sorted
+ * by (distance, id) gives: count[q] = min(k, n_elements) entries ascending by (distance, id); places past the count hold
+ * id UINT64_MAX and distance +inf. It is the yardstick and slower than granne_hip_brute_force*, which stays the fast
+ * form (several passes over the rows on the vector units; granne_amd/csrc/exact_topk.h).
+ *   queries    dense [nq][dim], prepared like the elements (the wrappers check the width). All n_elements rows of the handle
+ *              are scanned; a handle without layers is fine. f32 and int8 rows of any dimension and materialised
+ *              SumEmbeddings handles; GRANNE_HIP_F16 and compact SumEmbeddings handles are GRANNE_HIP_ERR_INVALID, as
+ *              are k == 0 and k > GRANNE_HIP_EXACT_TOPK_KMAX. nq == 0 does nothing and returns GRANNE_HIP_OK.
+ *   selection  distances are binned by a monotone function of their value over [0, +inf] (3072 bins, then 2048 inside the
+ *              bin of the k-th distance for the queries that need them); at most GRANNE_HIP_EXACT_TOPK_CAP candidates per
+ *              query are ranked. A query with more than that many rows inside one second-level bin at its k-th distance
+ *              (below distance 2 such a bin is 2^-21 wide: thousands of copies of one row, or a zero query over more than
+ *              4096 rows, whose every distance is exactly 1) OVERFLOWS: count 0 and a filled row, never a partial or
+ *              wrong list.
+ *   d_status   u32[4], optional, zeroed by the caller; every word accumulates: [0] queries that overflowed, [1] queries
+ *              that needed the second binning level, [2] the largest number of candidates ranked for one query, [3] 0.
+ * The device entry is stream-ordered: no host synchronisation, no host-side decision between its kernels; its scratch
+ * (hipMallocAsync on `stream`, about 34 MB whatever nq is: queries are taken 1024 at a time) is the call's own, so
+ * concurrent calls on a shared handle are safe. Neither entry writes GRANNE_HIP_OPT_LAST_SCAN. */
+#define GRANNE_HIP_EXACT_TOPK_KMAX 1024
+#define GRANNE_HIP_EXACT_TOPK_CAP  4096   /* candidates kept per query before the final ranking */
+int granne_hip_exact_topk_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                 uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                 uint32_t* d_status /* u32[4], optional, zeroed by the caller */, void* stream);
+/* the same with host buffers in and out (synchronous). GRANNE_HIP_ERR_OVERFLOW when status[0] != 0: the outputs (and
+ * out_status, optional) are still written. */
+int granne_hip_exact_topk(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                          uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
 
 /* The per-shard top-k of one batch as ONE buffer -- what a rank contributes to the single exchange
  * step of the partitioned mode (one all-gather, or one peer copy):
@@ -606,7 +639,7 @@ int granne_hip_sum_embeddings_embed(const granne_hip_sum_embeddings* se, const u
  *                               walker's (max_search <= 256) or the exact walker's, which make a candidate's vector from
  *                               its terms where they need it; results are the materialised index's, bit for bit.
  *                               search*, search_begin/end, packed results, use as a shard, get_neighbors, get_element (the
- *                               normalised vector), encode and save of the index file work. brute_force*, dists*,
+ *                               normalised vector), encode and save of the index file work. brute_force*, exact_topk*, dists*,
  *                               dist_pairs*, reorder*, get_sketch and save of an elements file return
  *                               GRANNE_HIP_ERR_INVALID: they need the dense rows of the materialised form.
  * The index shares the container's device copy; the container may be destroyed before it. */

@@ -272,6 +272,10 @@ extern "C" {
         d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, stream: *mut c_void) -> c_int;
     fn granne_hip_brute_force(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32) -> c_int;
+    fn granne_hip_exact_topk_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32, k: u32,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_topk(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_merge_topk_device(d_ids: *const u64, d_dists: *const f32, d_counts: *const u32,
         shard_offsets: *const u64, n_shards: u32, nq: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
         d_out_counts: *mut u32, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -440,6 +444,19 @@ impl<E: GpuElements> GpuGranne<E> {
             counts.as_mut_ptr(), std::ptr::null_mut()) }).expect("granne_hip_search_batch");
         (0..nq).map(|i| (0..counts[i] as usize)
             .map(|j| (ids[i * num_neighbors + j] as usize, ds[i * num_neighbors + j])).collect()).collect()
+    }
+    /// `granne_hip_exact_topk`: the `k` (up to 1024) nearest elements of every query by a scan of all rows in the
+    /// reference's own arithmetic, selected by (distance bits, id): the exact answer `search` approximates, ties
+    /// included. An `Err` when a query overflowed the selection (thousands of copies of one row at its k-th distance).
+    pub fn exact_topk(&self, elements: &[E::Vector], k: usize) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        let mut q = Vec::new();
+        for e in elements { assert_eq!(E::query_len(e), self.dim); E::append_query(&mut q, e); }
+        let (mut ids, mut ds) = (vec![0u64; nq * k], vec![0f32; nq * k]);
+        let mut counts = vec![0u32; nq];
+        check(unsafe { granne_hip_exact_topk(self.handle, q.as_ptr() as *const c_void, nq as u32, k as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
     }
     /// `granne_hip_search_refined_batch`: walk `self` (say, int8 rows and their graph), give the walk's `refine_from` best
     /// candidates their distances under `refine`'s rows (say, the f32 rows of the same elements; a handle made with no
