@@ -195,6 +195,11 @@ SIGNATURES = {
     "granne_hip_index_load_files_sum_embeddings": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, i32, i32]),
     "granne_hip_builder_create_sum_embeddings": (i32, [C.POINTER(vp), vp, vp]),
     "granne_hip_builder_get_index_compact": (i32, [vp, C.POINTER(vp)]),
+    "granne_hip_refine_sum_embeddings_device": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_search_refined_sum_embeddings_batch_device": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_search_refined_sum_embeddings_batch": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_sum_embeddings_rows_device": (i32, [vp, u64, u64, i32, vp, u64, vp]),
+    "granne_hip_sum_embeddings_rows": (i32, [vp, u64, u64, i32, vp]),
     "granne_hip_rw_builder_create": (i32, [C.POINTER(vp), vp, u64]),
     "granne_hip_rw_builder_destroy": (None, [vp]),
     "granne_hip_rw_builder_insert_batch": (i32, [vp, vp, u64, vp, C.POINTER(u64)]),

@@ -2549,3 +2549,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // refined search: walk one index, re-rank by another's rows
 // ------------------------------------------------------------------------------------------------
 #include "refine_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// refined search over a SumEmbeddings container: re-rank by term sums; the container as prepared rows
+// ------------------------------------------------------------------------------------------------
+#include "refine_se_host.h"

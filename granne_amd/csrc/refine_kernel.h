@@ -168,6 +168,63 @@ __device__ __forceinline__ bool refine_before(uint32_t da, uint64_t ia, uint32_t
     return da < db || (da == db && (ia < ib || (ia == ib && pa < pb)));
 }
 
+// Phase 1 of the re-rank kernels (refine_kernel below, refine_se_kernel.h): the query's qbytes bytes staged in LDS, zero
+// padded to lds_bytes
+__device__ __forceinline__ void refine_stage_query(const uint8_t* gq, uint32_t qbytes, uint8_t* lq, uint32_t lds_bytes, uint32_t tid) {
+    if ((qbytes & 3u) == 0 && (reinterpret_cast<uintptr_t>(gq) & 3u) == 0) {
+        for (uint32_t w = tid; w < (lds_bytes >> 2); w += REFINE_THREADS)
+            reinterpret_cast<uint32_t*>(lq)[w] = (w * 4u < qbytes) ? reinterpret_cast<const uint32_t*>(gq)[w] : 0u;
+    } else {
+        for (uint32_t b = tid; b < lds_bytes; b += REFINE_THREADS) lq[b] = b < qbytes ? gq[b] : (uint8_t)0;
+    }
+}
+
+// Phase 3 of the re-rank kernels: the cnt keys (kd, ki) of LDS ranked by counting, the k best of query qi written, the
+// rest of its k slots padded, its count and the dropped-candidates word. A dropped candidate's key (0xFFFFFFFF,
+// UINT64_MAX) lies behind every kept one: distances are >= 0 and never NaN (angular.rs:70-72, angular_int.rs:55), so
+// their bits order as unsigned numbers and stay below it.
+__device__ __forceinline__ void refine_rank_write(const uint64_t* ki, const uint32_t* kd, uint32_t cnt, uint32_t n_dropped,
+                                                  uint32_t k, uint32_t qi, uint32_t tid, uint64_t* out_ids, float* out_dists,
+                                                  uint32_t* out_counts, uint32_t* status) {
+    const uint32_t kept = cnt - n_dropped;
+    uint32_t md[REFINE_KEYS_PER_THREAD], rank[REFINE_KEYS_PER_THREAD];
+    uint64_t mi[REFINE_KEYS_PER_THREAD];
+#pragma unroll
+    for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t) {
+        const uint32_t p = tid + t * REFINE_THREADS;
+        md[t] = p < cnt ? kd[p] : 0xFFFFFFFFu;
+        mi[t] = p < cnt ? ki[p] : ~0ull;
+        rank[t] = 0;
+    }
+    if (cnt <= REFINE_THREADS) { // one key per thread: the common shape (m = max_search of a walk)
+        for (uint32_t p = 0; p < cnt; ++p) rank[0] += refine_before(kd[p], ki[p], p, md[0], mi[0], tid) ? 1u : 0u;
+    } else {
+        for (uint32_t p = 0; p < cnt; ++p) {
+            const uint32_t dp = kd[p];
+            const uint64_t ip = ki[p];
+#pragma unroll
+            for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t)
+                rank[t] += refine_before(dp, ip, p, md[t], mi[t], tid + t * REFINE_THREADS) ? 1u : 0u;
+        }
+    }
+    const uint32_t out_n = kept < k ? kept : k;
+#pragma unroll
+    for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t) {
+        if (tid + t * REFINE_THREADS < cnt && rank[t] < out_n) { // (ranks below `kept` belong to kept candidates)
+            out_ids[(size_t)qi * k + rank[t]] = mi[t];
+            out_dists[(size_t)qi * k + rank[t]] = __uint_as_float(md[t]);
+        }
+    }
+    for (uint32_t e = out_n + tid; e < k; e += REFINE_THREADS) {
+        out_ids[(size_t)qi * k + e] = ~0ull;
+        out_dists[(size_t)qi * k + e] = __builtin_inff();
+    }
+    if (tid == 0) {
+        out_counts[qi] = out_n;
+        if (n_dropped && status) atomicAdd(status, n_dropped);
+    }
+}
+
 template <int DT>
 __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const RefineParams P) {
     extern __shared__ __align__(16) uint8_t smem_r[];
@@ -194,17 +251,8 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const RefinePara
     }
 
     // 1. the query, once
-    {
-        const uint32_t qbytes = P.dim * (DT == 1 ? 1u : 4u); // (rows of halves take f32 queries)
-        const uint8_t* gq = P.queries + (size_t)qi * qbytes;
-        if ((qbytes & 3u) == 0 && (reinterpret_cast<uintptr_t>(gq) & 3u) == 0) {
-            for (uint32_t w = tid; w < (P.q_lds_bytes >> 2); w += REFINE_THREADS)
-                reinterpret_cast<uint32_t*>(lq)[w] = (w * 4u < qbytes) ? reinterpret_cast<const uint32_t*>(gq)[w] : 0u;
-        } else {
-            for (uint32_t b = tid; b < P.q_lds_bytes; b += REFINE_THREADS) lq[b] = b < qbytes ? gq[b] : (uint8_t)0;
-        }
-        if (tid == 0) n_dropped = 0;
-    }
+    refine_stage_query(P.queries + (size_t)qi * (P.dim * (DT == 1 ? 1u : 4u)), P.dim * (DT == 1 ? 1u : 4u), lq, P.q_lds_bytes, tid); // (rows of halves take f32 queries)
+    if (tid == 0) n_dropped = 0;
     __syncthreads();
 
     // 2. the candidates' distances
@@ -266,45 +314,8 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const RefinePara
     if (dropped) atomicAdd(&n_dropped, dropped);
     __syncthreads();
 
-    // 3. rank. A dropped candidate's key (0xFFFFFFFF, UINT64_MAX) lies behind every kept one: distances are >= 0 and
-    // never NaN (angular.rs:70-72, angular_int.rs:55), so their bits order as unsigned numbers and stay below it.
-    const uint32_t kept = cnt - n_dropped;
-    uint32_t md[REFINE_KEYS_PER_THREAD], rank[REFINE_KEYS_PER_THREAD];
-    uint64_t mi[REFINE_KEYS_PER_THREAD];
-#pragma unroll
-    for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t) {
-        const uint32_t p = tid + t * REFINE_THREADS;
-        md[t] = p < cnt ? kd[p] : 0xFFFFFFFFu;
-        mi[t] = p < cnt ? ki[p] : ~0ull;
-        rank[t] = 0;
-    }
-    if (cnt <= REFINE_THREADS) { // one key per thread: the common shape (m = max_search of a walk)
-        for (uint32_t p = 0; p < cnt; ++p) rank[0] += refine_before(kd[p], ki[p], p, md[0], mi[0], tid) ? 1u : 0u;
-    } else {
-        for (uint32_t p = 0; p < cnt; ++p) {
-            const uint32_t dp = kd[p];
-            const uint64_t ip = ki[p];
-#pragma unroll
-            for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t)
-                rank[t] += refine_before(dp, ip, p, md[t], mi[t], tid + t * REFINE_THREADS) ? 1u : 0u;
-        }
-    }
-    const uint32_t out_n = kept < k ? kept : k;
-#pragma unroll
-    for (uint32_t t = 0; t < REFINE_KEYS_PER_THREAD; ++t) {
-        if (tid + t * REFINE_THREADS < cnt && rank[t] < out_n) { // (ranks below `kept` belong to kept candidates)
-            P.out_ids[(size_t)qi * k + rank[t]] = mi[t];
-            P.out_dists[(size_t)qi * k + rank[t]] = __uint_as_float(md[t]);
-        }
-    }
-    for (uint32_t e = out_n + tid; e < k; e += REFINE_THREADS) {
-        P.out_ids[(size_t)qi * k + e] = ~0ull;
-        P.out_dists[(size_t)qi * k + e] = __builtin_inff();
-    }
-    if (tid == 0) {
-        P.out_counts[qi] = out_n;
-        if (n_dropped && P.status) atomicAdd(P.status, n_dropped);
-    }
+    // 3. rank
+    refine_rank_write(ki, kd, cnt, n_dropped, k, qi, tid, P.out_ids, P.out_dists, P.out_counts, P.status);
 }
 
 } // namespace granne_hip

@@ -22,6 +22,20 @@ def _f32_table(embeddings):
     return np.ascontiguousarray(embeddings, dtype=np.float32)
 
 
+def _dense_type(element_type):
+    """(GRANNE_HIP_* code, numpy dtype) of a dense element type: its name ("angular", "angular_int", "angular_f16") or its
+    code (F32, I8, F16). Anything else is ERR_INVALID here, before a buffer is sized by it."""
+    from .index import _ELEMENT_TYPES
+    if isinstance(element_type, str):
+        if element_type.lower() in _ELEMENT_TYPES:
+            return _ELEMENT_TYPES[element_type.lower()]
+    else:
+        for code, np_dtype in _ELEMENT_TYPES.values():
+            if element_type == code and not isinstance(element_type, bool):
+                return code, np_dtype
+    raise GranneHipError(ERR_INVALID, "to_rows: unknown %s %r" % ("element type" if isinstance(element_type, str) else "dtype", element_type))
+
+
 def csr_of(term_lists):
     """(offsets u64 [n + 1], terms u32) of a sequence of term-id sequences."""
     lists = [np.asarray(t, dtype=np.int64).reshape(-1) for t in term_lists]
@@ -70,6 +84,19 @@ class SumEmbeddings:
         h = C.c_void_p()
         check(lib().granne_hip_sum_embeddings_load(C.byref(h), _p(tab), tab.shape[0], tab.shape[1], _p(buf), buf.size, device))
         self._h, self.dim, self.device = h, tab.shape[1], device
+        return self
+
+    @classmethod
+    def from_device(cls, d_table, n_embeddings, dim, d_offsets, d_terms, n_elements, device=0, stream=0):
+        """granne_hip_sum_embeddings_create_device: the table (float32 [n_embeddings, dim], dense) and the CSR (u64 offsets
+        [n_elements + 1], u32 term ids) at raw device pointers (int) on `device`. They are copied (the term lists are
+        checked on the host): the caller's buffers are free again when the call returns."""
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        check(lib().granne_hip_sum_embeddings_create_device(C.byref(h), C.c_void_p(d_table), int(n_embeddings), int(dim),
+                                                            C.c_void_p(d_offsets), C.c_void_p(d_terms), int(n_elements), device,
+                                                            C.c_void_p(stream)))
+        self._h, self.dim, self.device = h, int(dim), device
         return self
 
     def close(self):
@@ -132,6 +159,85 @@ class SumEmbeddings:
     def create_embedding(self, terms, normalized=False):
         """SumEmbeddings::create_embedding: the raw sum of the terms' rows."""
         return self.create_embeddings([terms], normalized)[0]
+
+    # ---- the container as the re-ranking side of refined search, and as the rows of the index that is walked ----
+    query_dtype = np.float32  # queries are prepared float32 rows, as for "angular"
+
+    def _queries(self, queries, prepared):
+        """Prepared float32 queries [nq, dim] from prepared rows, raw rows (prepared=False) or term lists."""
+        from .index import _is_term_lists, normalize
+        if not prepared and _is_term_lists(queries):
+            return self.create_embeddings(queries, normalized=True)
+        q = np.ascontiguousarray(queries, np.float32) if prepared else normalize(queries, self.device)
+        return q[None] if q.ndim == 1 else q
+
+    def refine_device(self, d_queries, nq, d_cand_ids, d_cand_counts, m, k, d_ids, d_dists, d_counts, d_refine_status=0,
+                      stream=0):
+        """granne_hip_refine_sum_embeddings_device: re-rank u64 candidate lists [nq, m] by the vectors this container
+        stands for. Raw device pointers (int; d_cand_counts and d_refine_status may be 0), asynchronous on `stream`."""
+        check(lib().granne_hip_refine_sum_embeddings_device(self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_cand_ids),
+                                                            C.c_void_p(d_cand_counts), int(m), int(k), C.c_void_p(d_ids),
+                                                            C.c_void_p(d_dists), C.c_void_p(d_counts),
+                                                            C.c_void_p(d_refine_status), C.c_void_p(stream)))
+
+    def refine(self, queries, ids, counts=None, k=10, prepared=True, dropped=False):
+        """Granne.refine with the container as the rows side: the candidates ids [nq, m] (query q's list: its first
+        counts[q] entries; None = all m) by get(id).dist(query), the k best ascending by (distance, id): ids [nq, k] u64,
+        dists [nq, k] f32, counts [nq] u32 -- and, with dropped=True, how many candidates were out of range. Queries are
+        prepared float32 rows; prepared=False takes raw rows or term lists. Bad shapes, m outside [1, 1024] and k < 1 are
+        GranneHipError(ERR_INVALID) before anything touches the device."""
+        q = self._queries(queries, prepared)
+        ii = np.ascontiguousarray(ids, dtype=np.uint64)
+        if q.ndim != 2 or q.shape[1] != self.dim or ii.ndim != 2 or ii.shape[0] != q.shape[0]:
+            raise GranneHipError(ERR_INVALID, "refine: queries must be [nq, %d] and ids [nq, m]" % self.dim)
+        nq, m, k = q.shape[0], ii.shape[1], int(k)
+        cc = None
+        if counts is not None:
+            cc = np.ascontiguousarray(counts, dtype=np.uint32)
+            if cc.shape != (nq,):
+                raise GranneHipError(ERR_INVALID, "refine: counts must be [nq]")
+        if not 1 <= m <= 1024:  # (the library checks the same; here nothing has been moved to the device yet)
+            raise GranneHipError(ERR_INVALID, "refine: candidates per query must be in [1, 1024]")
+        if k < 1:
+            raise GranneHipError(ERR_INVALID, "refine: k must be > 0")
+        if nq == 0:  # nothing to do
+            res = (np.empty((0, k), np.uint64), np.empty((0, k), np.float32), np.zeros(0, np.uint32))
+            return res + (0,) if dropped else res
+        import torch
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q).to(dev)
+        ti = torch.from_numpy(ii.view(np.int64)).to(dev)
+        tc = torch.from_numpy(cc.view(np.int32)).to(dev) if cc is not None else None
+        out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        out_d = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_c = torch.zeros(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            self.refine_device(tq.data_ptr(), nq, ti.data_ptr(), tc.data_ptr() if tc is not None else 0, m, k,
+                               out_ids.data_ptr(), out_d.data_ptr(), out_c.data_ptr(), st.data_ptr(),
+                               torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        res = (out_ids.cpu().numpy().view(np.uint64), out_d.cpu().numpy(), out_c.cpu().numpy().view(np.uint32))
+        return res + (int(st.cpu().numpy().view(np.uint32)[0]),) if dropped else res
+
+    def to_rows_device(self, element_type, d_out, first=0, count=None, stride_bytes=None, stream=0):
+        """granne_hip_sum_embeddings_rows_device: elements first .. first + count - 1 as prepared rows of a dense
+        element type ("angular", "angular_int", "angular_f16") at the raw device pointer d_out (int), stride_bytes from
+        one row to the next (None: dense). Asynchronous on `stream`; at most 64 MB of scratch whatever count is."""
+        code, np_dtype = _dense_type(element_type)
+        count = len(self) - first if count is None else count
+        stride = self.dim * np.dtype(np_dtype).itemsize if stride_bytes is None else stride_bytes
+        check(lib().granne_hip_sum_embeddings_rows_device(self._h, int(first), int(count), code, C.c_void_p(d_out), int(stride),
+                                                          C.c_void_p(stream)))
+
+    def to_rows(self, element_type, first=0, count=None):
+        """The same as a numpy array [count, dim] of the element type's scalar: what Granne(element_type, rows, layers)
+        and GranneBuilder(element_type, rows) take as prepared elements."""
+        code, np_dtype = _dense_type(element_type)
+        count = len(self) - first if count is None else count
+        out = np.empty((max(int(count), 0), self.dim), np_dtype)
+        check(lib().granne_hip_sum_embeddings_rows(self._h, int(first), int(count), code, _p(out)))
+        return out
 
     def save_elements(self, path):
         check(lib().granne_hip_sum_embeddings_save_elements(self._h, os.fsencode(path)))

@@ -595,12 +595,64 @@ public:
         check(granne_hip_builder_create_sum_embeddings(&b, &config, h_.get()));
         return b;
     }
+    // elements first .. first + count - 1 as prepared int8 rows (normalised, then quantised): the rows of the index that
+    // RefinedSumEmbeddingsGranne walks (granne_hip_sum_embeddings_rows, GRANNE_HIP_I8)
+    std::vector<int8_t> rows_i8(size_t first, size_t count) const {
+        std::vector<int8_t> rows(count * dim());
+        check(granne_hip_sum_embeddings_rows(h_.get(), first, count, GRANNE_HIP_I8, rows.data()));
+        return rows;
+    }
     granne_hip_sum_embeddings* handle() const { return h_.get(); }
+    std::shared_ptr<granne_hip_sum_embeddings> shared() const { return h_; }
 
 private:
     explicit SumEmbeddings(granne_hip_sum_embeddings* h) : h_(h, granne_hip_sum_embeddings_destroy) {}
     std::shared_ptr<granne_hip_sum_embeddings> h_;
 };
 } // namespace embeddings
+
+// RefinedGranne's sibling over a container (granne_hip_search_refined_sum_embeddings_batch): walk one index -- typically
+// the int8 rows of SumEmbeddings::rows_i8 with their graph -- and re-rank the walk's refine_from best candidates by the
+// container's own vectors, made from their terms inside the kernel: f32 SumEmbeddings distances without dense f32 rows.
+// A refine query is dim() prepared (normalised) floats. Both handles are shared with the objects they came from.
+template <class WalkElements>
+class RefinedSumEmbeddingsGranne {
+public:
+    using WalkElement = typename WalkElements::Element;
+    RefinedSumEmbeddingsGranne(const Granne<WalkElements>& walk, const embeddings::SumEmbeddings& refine) : walk_(walk), se_(refine.shared()) {}
+
+    // refine_from = 0 means max_search; 1 <= refine_from <= min(max_search, 1024)
+    std::vector<std::vector<std::pair<size_t, float>>> search_batch(const WalkElement* walk_elements,
+                                                                    const std::vector<float>* refine_queries, size_t nq,
+                                                                    size_t max_search, size_t num_neighbors,
+                                                                    size_t refine_from = 0) const {
+        const size_t wdim = granne_hip_index_dim(walk_.raw()), rdim = granne_hip_sum_embeddings_dim(se_.get());
+        std::vector<typename decltype(WalkElement::data)::value_type> qw(nq * wdim);
+        std::vector<float> qr(nq * rdim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (walk_elements[i].len() != wdim || refine_queries[i].size() != rdim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(qw.data() + i * wdim, walk_elements[i].as_slice(), wdim * sizeof(qw[0]));
+            std::memcpy(qr.data() + i * rdim, refine_queries[i].data(), rdim * sizeof(float));
+        }
+        std::vector<uint64_t> ids(nq * num_neighbors);
+        std::vector<float> ds(nq * num_neighbors);
+        std::vector<uint32_t> counts(nq);
+        check(granne_hip_search_refined_sum_embeddings_batch(walk_.raw(), se_.get(), qw.data(), qr.data(), (uint32_t)nq,
+                                                             (uint32_t)max_search, (uint32_t)(refine_from ? refine_from : max_search),
+                                                             (uint32_t)num_neighbors, ids.data(), ds.data(), counts.data(), nullptr, nullptr));
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * num_neighbors + j], ds[i * num_neighbors + j]);
+        return out;
+    }
+    std::vector<std::pair<size_t, float>> search(const WalkElement& walk_element, const std::vector<float>& refine_query, size_t max_search,
+                                                 size_t num_neighbors, size_t refine_from = 0) const {
+        return std::move(search_batch(&walk_element, &refine_query, 1, max_search, num_neighbors, refine_from)[0]);
+    }
+
+private:
+    Granne<WalkElements> walk_;
+    std::shared_ptr<granne_hip_sum_embeddings> se_;
+};
 
 } // namespace granne

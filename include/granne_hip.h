@@ -657,6 +657,52 @@ int granne_hip_builder_create_sum_embeddings(granne_hip_builder** out, const gra
                                              const granne_hip_sum_embeddings* se);
 int granne_hip_builder_get_index_compact(const granne_hip_builder* builder, granne_hip_index** out);
 
+/* ---- refined search over a container: walk dense rows, re-rank by term sums -------------------------
+ * The CONTAINER as the re-ranking side of refined search. (A compact INDEX is still refused there, and by dists*,
+ * brute_force* and exact_topk*; these entries take the container itself, which is a rows provider and has no layers.)
+ * A candidate's distance is get(id).dist(q): its terms' table rows are gathered and added in list order, the sum is
+ * normalised and met with the prepared f32 query inside the re-rank kernel -- the bits of the materialised index's row and
+ * of granne_hip_refine_device over it. What stays in HBM is the index that is walked (int8 rows with their graph: 128
+ * bytes per element at 100 dimensions) and the container (granne_hip_sum_embeddings_hbm_bytes); no dense f32 rows.
+ * A candidate costs 16 bytes of offsets, 4 per term id and terms x (dim x 4, padded to 16) bytes of table rows.
+ *
+ * granne_hip_refine_sum_embeddings_device is granne_hip_refine_device with the container in place of refine_index:
+ * d_queries f32 [nq][dim] prepared, d_cand_ids u64 [nq][m], 1 <= m <= 1024, d_cand_counts u32 [nq] or NULL, k >= 1; an id
+ * >= granne_hip_sum_embeddings_len -- UINT64_MAX included -- is dropped and counted in *d_refine_status; outputs, padding
+ * and counts as there. nq == 0 does nothing. The query and m x 12 bytes of keys must fit 160 KB of LDS.
+ * Every argument of these entries is checked before any device call. The container's device copy is taken when a call
+ * begins: elements appended between two calls are seen by the second. */
+int granne_hip_refine_sum_embeddings_device(const granne_hip_sum_embeddings* se, const float* d_queries, uint32_t nq,
+                                            const uint64_t* d_cand_ids, const uint32_t* d_cand_counts, uint32_t m, uint32_t k,
+                                            uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                            uint32_t* d_refine_status, void* stream);
+/* granne_hip_search_refined_batch_device / _batch, argument for argument, with the container in place of refine_index:
+ * walk_index is any handle on the container's device over the same elements under the same ids (typically int8 rows
+ * with their graph; a compact index works too), d_refine_queries f32 [nq][container dim] prepared.
+ * 1 <= refine_from <= min(max_search, 1024); devices that differ are GRANNE_HIP_ERR_INVALID. */
+int granne_hip_search_refined_sum_embeddings_batch_device(const granne_hip_index* walk_index, const granne_hip_sum_embeddings* se,
+                                                          const void* d_walk_queries, const void* d_refine_queries, uint32_t nq,
+                                                          uint32_t max_search, uint32_t refine_from, uint32_t k,
+                                                          uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                                          uint64_t* d_out_stats, uint32_t* d_status, uint32_t* d_refine_status,
+                                                          void* stream);
+int granne_hip_search_refined_sum_embeddings_batch(const granne_hip_index* walk_index, const granne_hip_sum_embeddings* se,
+                                                   const void* walk_queries, const void* refine_queries, uint32_t nq,
+                                                   uint32_t max_search, uint32_t refine_from, uint32_t k, uint64_t* out_ids,
+                                                   float* out_dists, uint32_t* out_counts, uint64_t* out_stats,
+                                                   uint32_t* out_refine_status);
+/* Elements first .. first + count - 1 as PREPARED ROWS of a dense element type, stride_bytes (>= dim x the scalar's size,
+ * a multiple of it) from one row to the next: GRANNE_HIP_F32 the normalised vectors (materialize with normalised = 1),
+ * GRANNE_HIP_I8 granne_hip_quantize_f32_device of those, GRANNE_HIP_F16 granne_hip_f32_to_f16_device of those -- the same
+ * bytes. The work runs chunk by chunk in stream-ordered scratch of at most 64 MB whatever count is (the device form needs
+ * none for f32 rows; the host form stages every dtype through one device buffer of a chunk's rows, within the same bound),
+ * so the rows of an int8 index over 10^9 elements are made without a dense f32 copy; GRANNE_HIP_SE_ROWS_CHUNK in the
+ * environment lowers the rows per chunk. _device: d_out on the container's device, asynchronous on `stream`. The host
+ * form writes dense rows [count][dim] and is synchronous. Any other dtype is GRANNE_HIP_ERR_INVALID. */
+int granne_hip_sum_embeddings_rows_device(const granne_hip_sum_embeddings* se, uint64_t first, uint64_t count, int dtype,
+                                          void* d_out, uint64_t stride_bytes, void* stream);
+int granne_hip_sum_embeddings_rows(const granne_hip_sum_embeddings* se, uint64_t first, uint64_t count, int dtype, void* out);
+
 /* ---- RwGranneBuilder on the GPU (src/index/rw/mod.rs:15-224) ---------------------------------------
  * The builder that takes inserts while it answers searches. The handle keeps what the reference's keeps: the previous
  * layers, a CURRENT layer allocated for the size its level will have at max_elements, and element storage for

@@ -147,6 +147,23 @@ extern "C" {
     fn granne_hip_builder_create_sum_embeddings(out: *mut *mut granne_hip_builder,
         config: *const granne_hip_build_config, se: *const granne_hip_sum_embeddings) -> c_int;
     fn granne_hip_builder_get_index_compact(builder: *const granne_hip_builder, out: *mut *mut granne_hip_index) -> c_int;
+    // ---- refined search over a container: walk dense rows, re-rank by term sums; the container as prepared rows
+    fn granne_hip_refine_sum_embeddings_device(se: *const granne_hip_sum_embeddings, d_queries: *const f32,
+        nq: u32, d_cand_ids: *const u64, d_cand_counts: *const u32, m: u32, k: u32, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_refine_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_search_refined_sum_embeddings_batch_device(walk_index: *const granne_hip_index,
+        se: *const granne_hip_sum_embeddings, d_walk_queries: *const c_void, d_refine_queries: *const c_void,
+        nq: u32, max_search: u32, refine_from: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_out_stats: *mut u64, d_status: *mut u32, d_refine_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_search_refined_sum_embeddings_batch(walk_index: *const granne_hip_index,
+        se: *const granne_hip_sum_embeddings, walk_queries: *const c_void, refine_queries: *const c_void, nq: u32,
+        max_search: u32, refine_from: u32, k: u32, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_stats: *mut u64, out_refine_status: *mut u32) -> c_int;
+    fn granne_hip_sum_embeddings_rows_device(se: *const granne_hip_sum_embeddings, first: u64, count: u64,
+        dtype: c_int, d_out: *mut c_void, stride_bytes: u64, stream: *mut c_void) -> c_int;
+    fn granne_hip_sum_embeddings_rows(se: *const granne_hip_sum_embeddings, first: u64, count: u64, dtype: c_int,
+        out: *mut c_void) -> c_int;
     // ---- RwGranneBuilder (src/index/rw/mod.rs:15-224)
     fn granne_hip_rw_builder_create(out: *mut *mut granne_hip_rw_builder, builder: *mut granne_hip_builder,
         max_elements: u64) -> c_int;
@@ -478,6 +495,24 @@ impl<E: GpuElements> GpuGranne<E> {
         Ok((0..nq).map(|i| (0..counts[i] as usize)
             .map(|j| (ids[i * num_neighbors + j] as usize, ds[i * num_neighbors + j])).collect()).collect())
     }
+    /// `granne_hip_search_refined_sum_embeddings_batch`: `refined` with a SumEmbeddings container as the re-ranking side.
+    /// Every candidate's f32 vector is made from its terms inside the re-rank kernel, so no dense f32 rows are held;
+    /// the distances are the container's own. `refine_queries`: `nq x se.dim()` prepared (normalised) floats.
+    pub fn refined_sum_embeddings(&self, se: &GpuSumEmbeddings, walk_elements: &[E::Vector], refine_queries: &[f32],
+                                  max_search: usize, refine_from: usize, num_neighbors: usize)
+                                  -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = walk_elements.len();
+        assert_eq!(nq * se.dim(), refine_queries.len());
+        let mut qw = Vec::new();
+        for e in walk_elements { assert_eq!(E::query_len(e), self.dim); E::append_query(&mut qw, e); }
+        let (mut ids, mut ds) = (vec![0u64; nq * num_neighbors], vec![0f32; nq * num_neighbors]);
+        let mut counts = vec![0u32; nq];
+        check(unsafe { granne_hip_search_refined_sum_embeddings_batch(self.handle, se.handle, qw.as_ptr() as *const c_void,
+            refine_queries.as_ptr() as *const c_void, nq as u32, max_search as u32, refine_from as u32, num_neighbors as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        Ok((0..nq).map(|i| (0..counts[i] as usize)
+            .map(|j| (ids[i * num_neighbors + j] as usize, ds[i * num_neighbors + j])).collect()).collect())
+    }
     // ---- the device-resident entries, safe: buffers and streams are owned types (below), a batch in flight BORROWS its
     // buffers until it is ended, so the compiler keeps them alive and unaliased for exactly as long as the GPU uses them
     /// Queries of one batch in HBM (`Vector::from` applied on the host: `E::append_query`).
@@ -598,6 +633,33 @@ impl<E: GpuElements> GpuGranne<E> {
     }
 }
 impl<E: GpuElements> Drop for GpuGranne<E> { fn drop(&mut self) { unsafe { granne_hip_index_destroy(self.handle) } } }
+
+/// `embeddings::SumEmbeddings` (src/elements/embeddings/mod.rs:41-216) as the library holds it: the table and the elements'
+/// term lists (CSR). The re-ranking side of `GpuGranne::refined_sum_embeddings`; `rows` gives its elements as prepared
+/// rows of a dense element type, which is what the index to walk is built from.
+pub struct GpuSumEmbeddings { handle: *mut granne_hip_sum_embeddings }
+unsafe impl Send for GpuSumEmbeddings {}
+impl GpuSumEmbeddings {
+    /// `table`: `n_embeddings x dim` floats, not normalised; `offsets`: `n + 1` positions in `terms`, the first 0.
+    pub fn new(table: &[f32], dim: usize, offsets: &[u64], terms: &[u32], device: i32) -> std::io::Result<Self> {
+        assert!(dim > 0 && table.len() % dim == 0 && !offsets.is_empty());
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { granne_hip_sum_embeddings_create(&mut handle, table.as_ptr(), (table.len() / dim) as u64, dim as u32,
+            offsets.as_ptr(), terms.as_ptr(), (offsets.len() - 1) as u64, device) })?;
+        Ok(Self { handle })
+    }
+    pub fn len(&self) -> usize { unsafe { granne_hip_sum_embeddings_len(self.handle) as usize } }
+    pub fn dim(&self) -> usize { unsafe { granne_hip_sum_embeddings_dim(self.handle) as usize } }
+    /// `granne_hip_sum_embeddings_rows` for `GRANNE_HIP_I8`: elements `first .. first + count` normalised and quantised,
+    /// `count x dim` bytes -- the rows of the int8 index that `refined_sum_embeddings` walks.
+    pub fn rows_i8(&self, first: usize, count: usize) -> std::io::Result<Vec<i8>> {
+        let mut out = vec![0i8; count * self.dim()];
+        check(unsafe { granne_hip_sum_embeddings_rows(self.handle, first as u64, count as u64, GRANNE_HIP_I8,
+            out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+}
+impl Drop for GpuSumEmbeddings { fn drop(&mut self) { unsafe { granne_hip_sum_embeddings_destroy(self.handle) } } }
 
 /// The reference's `Index` trait (src/index/mod.rs:54-71): code that is generic over `Index` takes a `GpuGranne`.
 impl<E: GpuElements> Index for GpuGranne<E> {
