@@ -35,6 +35,8 @@ SHARDED_OPT_DEPTH, SHARDED_OPT_EXCHANGE = 1, 2
 SHARDED_EXCHANGE_PEER, SHARDED_EXCHANGE_RCCL = 0, 1
 RW_OPT_SMALL_OPS, RW_OPT_SMALL_LAUNCHES, RW_OPT_SORTED_LAUNCHES = 1, 2, 3  # GRANNE_HIP_RW_OPT_*
 RW_SMALL_OPS = 2048  # GRANNE_HIP_RW_SMALL_OPS
+CODEC_STAGING_DEFAULT = 64 << 20  # GRANNE_HIP_CODEC_STAGING_DEFAULT: the device codec's pinned ring (staging_bytes=0)
+CODEC_STAGING_MIN = 64 << 10  # GRANNE_HIP_CODEC_STAGING_MIN: smaller values are raised to it
 SE_MATERIALIZED, SE_COMPACT = 0, 1  # GRANNE_HIP_SE_*: the two forms of an index over a SumEmbeddings container
 
 
@@ -130,6 +132,10 @@ SIGNATURES = {
     "granne_hip_index_save": (i32, [vp, C.c_char_p, C.c_char_p]),
     "granne_hip_index_encode": (i32, [vp, C.POINTER(vp), C.POINTER(u64)]),
     "granne_hip_bytes_free": (None, [vp]),
+    "granne_hip_index_encode_on_device": (i32, [vp, u64, C.POINTER(vp), C.POINTER(u64), vp]),
+    "granne_hip_index_save_on_device": (i32, [vp, C.c_char_p, C.c_char_p, u64, vp]),
+    "granne_hip_index_load_on_device": (i32, [C.POINTER(vp), vp, u64, vp, u64, i32, i32, u64, vp]),
+    "granne_hip_index_load_files_on_device": (i32, [C.POINTER(vp), C.c_char_p, C.c_char_p, i32, i32, u64, vp]),
     "granne_hip_index_file_info": (i32, [vp, u64, C.POINTER(u32), vp, vp, u32]),
     "granne_hip_index_file_decode_layer": (i32, [vp, u64, u32, vp, vp]),
     "granne_hip_brute_force_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),

@@ -169,9 +169,18 @@ class GranneBuilder:
         ix.dim = self.dim
         return ix
 
-    def save_index(self, path):
-        """GranneBuilder.save_index (py/src/lib.rs:509-521): the compressed on-disk form."""
+    def save_index(self, path, on_device=False, staging_bytes=None):
+        """GranneBuilder.save_index (py/src/lib.rs:509-521): the compressed on-disk form. on_device=True: through
+        get_index() and the device codec (Granne.save_index); the info words are kept in `last_codec_info`."""
         import os
+        if on_device:
+            ix = self.get_index()
+            try:
+                ix.save_index(path, on_device=True, staging_bytes=staging_bytes)
+                self.last_codec_info = ix.last_codec_info
+            finally:
+                ix.close()
+            return
         layers = self.layers()
         n = len(layers)
         lens = (C.c_uint64 * max(n, 1))(*[l.shape[0] for l in layers])

@@ -2531,6 +2531,11 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 #include "fileformat_host.h"
 
 // ------------------------------------------------------------------------------------------------
+// the same files through the device codec, streamed in bounded memory
+// ------------------------------------------------------------------------------------------------
+#include "codec_host.h"
+
+// ------------------------------------------------------------------------------------------------
 // partitioned indexes driven by one host process
 // ------------------------------------------------------------------------------------------------
 #include "sharded_host.h"

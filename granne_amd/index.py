@@ -168,16 +168,21 @@ class Granne:
         return self
 
     @classmethod
-    def from_files(cls, index_path, element_type, elements_path, device=0, embeddings_path=None, compact=False):
+    def from_files(cls, index_path, element_type, elements_path, device=0, embeddings_path=None, compact=False,
+                   on_device=False, staging_bytes=None):
         """Granne(index_path, element_type, elements_path) of the reference's binding
         (py/src/lib.rs:177-214): an index file written by write_index + a Vectors file -- or, for "embeddings", an
-        elements file of term lists + embeddings_path (the table), materialised or compact."""
+        elements file of term lists + embeddings_path (the table), materialised or compact.
+        on_device=True (dense element types): the files are read in pieces into a pinned ring of `staging_bytes` (None: the
+        library's default) and decoded on the GPU; the index is the same, `last_codec_info` holds the call's info words."""
         self = cls.__new__(cls)
         et = element_type.lower()
         if et == EMBEDDINGS:
             from .embeddings import SumEmbeddings
             if embeddings_path is None:
                 raise ValueError("embeddings_path is required")  # the reference panics (py/src/lib.rs:199-202)
+            if on_device:
+                raise ValueError("on_device reads dense element files; an \"embeddings\" index loads through the host codec")
             self.element_type = EMBEDDINGS
             self.dtype_code, self.np_dtype = F32, np.float32
             self.device, self.compact = device, bool(compact)
@@ -194,15 +199,22 @@ class Granne:
         self.dtype_code, self.np_dtype = _ELEMENT_TYPES[et]
         self.device = device
         h = C.c_void_p()
-        check(lib().granne_hip_index_load_files(C.byref(h), os.fsencode(index_path), os.fsencode(elements_path),
-                                                self.dtype_code, device))
+        if on_device:
+            info = (C.c_uint64 * 4)()
+            check(lib().granne_hip_index_load_files_on_device(C.byref(h), os.fsencode(index_path), os.fsencode(elements_path),
+                                                              self.dtype_code, device, int(staging_bytes or 0), info))
+            self.last_codec_info = tuple(int(v) for v in info)
+        else:
+            check(lib().granne_hip_index_load_files(C.byref(h), os.fsencode(index_path), os.fsencode(elements_path),
+                                                    self.dtype_code, device))
         self._h = h
         self.dim = int(lib().granne_hip_index_dim(h))
         return self
 
     @classmethod
-    def from_bytes(cls, index_bytes, element_type, elements_bytes, device=0):
-        """Granne::from_bytes (src/index/mod.rs:106-113) over Vectors::from_bytes."""
+    def from_bytes(cls, index_bytes, element_type, elements_bytes, device=0, on_device=False, staging_bytes=None):
+        """Granne::from_bytes (src/index/mod.rs:106-113) over Vectors::from_bytes. on_device=True: decoded by the device
+        codec (see from_files)."""
         self = cls.__new__(cls)
         et = element_type.lower()
         if et not in _ELEMENT_TYPES:
@@ -213,27 +225,59 @@ class Granne:
         ib = np.frombuffer(index_bytes, np.uint8)
         eb = np.frombuffer(elements_bytes, np.uint8)
         h = C.c_void_p()
-        check(lib().granne_hip_index_load(C.byref(h), _p(ib), ib.size, _p(eb), eb.size, self.dtype_code, device))
+        if on_device:
+            info = (C.c_uint64 * 4)()
+            check(lib().granne_hip_index_load_on_device(C.byref(h), _p(ib), ib.size, _p(eb), eb.size, self.dtype_code, device,
+                                                        int(staging_bytes or 0), info))
+            self.last_codec_info = tuple(int(v) for v in info)
+        else:
+            check(lib().granne_hip_index_load(C.byref(h), _p(ib), ib.size, _p(eb), eb.size, self.dtype_code, device))
         self._h = h
         self.dim = int(lib().granne_hip_index_dim(h))
         return self
 
-    def save_index(self, path):
-        """py/src/lib.rs:318-330."""
-        check(lib().granne_hip_index_save(self._h, os.fsencode(path), None))
+    # the four info words of the last on-device codec call of this object (include/granne_hip.h: layers through the device
+    # codec, layers through the host codec, peak device scratch bytes, peak host staging bytes), or None
+    last_codec_info = None
 
-    def index_bytes(self):
+    def _save(self, index_path, elements_path, on_device, staging_bytes):
+        ip = os.fsencode(index_path) if index_path is not None else None
+        ep = os.fsencode(elements_path) if elements_path is not None else None
+        if not on_device:
+            check(lib().granne_hip_index_save(self._h, ip, ep))
+            return
+        info = (C.c_uint64 * 4)()
+        try:
+            check(lib().granne_hip_index_save_on_device(self._h, ip, ep, int(staging_bytes or 0), info))
+        finally:
+            self.last_codec_info = tuple(int(v) for v in info)
+
+    def save_index(self, path, on_device=False, staging_bytes=None):
+        """py/src/lib.rs:318-330. on_device=True: encoded by the device codec and streamed through a pinned ring of
+        `staging_bytes` (None: the library's default); the file's bytes are the same."""
+        self._save(path, None, on_device, staging_bytes)
+
+    def index_bytes(self, on_device=False, staging_bytes=None):
         """Index::write_index into a buffer (src/index/mod.rs:67-70): the bytes of the index file."""
         out, n = C.c_void_p(), C.c_uint64(0)
-        check(lib().granne_hip_index_encode(self._h, C.byref(out), C.byref(n)))
+        if on_device:
+            info = (C.c_uint64 * 4)()
+            check(lib().granne_hip_index_encode_on_device(self._h, int(staging_bytes or 0), C.byref(out), C.byref(n), info))
+            self.last_codec_info = tuple(int(v) for v in info)
+        else:
+            check(lib().granne_hip_index_encode(self._h, C.byref(out), C.byref(n)))
         try:
             return C.string_at(out, n.value)
         finally:
             lib().granne_hip_bytes_free(out)
 
-    def save_elements(self, path):
+    def save_elements(self, path, on_device=False, staging_bytes=None):
         """py/src/lib.rs:332-343."""
-        check(lib().granne_hip_index_save(self._h, None, os.fsencode(path)))
+        self._save(None, path, on_device, staging_bytes)
+
+    def save(self, index_path, elements_path, on_device=False, staging_bytes=None):
+        """save_index and save_elements in one call."""
+        self._save(index_path, elements_path, on_device, staging_bytes)
 
     @classmethod
     def from_device(cls, element_type, d_elements_ptr, n_elements, dim, layer_lens, d_layer_ptrs, layer_widths,

@@ -160,6 +160,14 @@ public:
         check(granne_hip_index_load_files(&h, index_path.c_str(), elements_path.c_str(), dtype(), device));
         return Granne(h);
     }
+    // from_file through the device codec: read in pieces into a pinned ring of staging_bytes (0: the library's default),
+    // decoded on the GPU; info (optional, u64[4]): layers on the device / host codec, peak device scratch, peak host staging
+    static Granne load_files_on_device(const std::string& index_path, const std::string& elements_path, int device = 0,
+                                       uint64_t staging_bytes = 0, uint64_t* info = nullptr) {
+        granne_hip_index* h = nullptr;
+        check(granne_hip_index_load_files_on_device(&h, index_path.c_str(), elements_path.c_str(), dtype(), device, staging_bytes, info));
+        return Granne(h);
+    }
     // Granne::from_bytes (mod.rs:106-113)
     static Granne from_bytes(const void* index, size_t index_len, const void* elements, size_t elements_len, int device = 0) {
         granne_hip_index* h = nullptr;
@@ -267,6 +275,12 @@ public:
     }
     void write_index(const std::string& path) const { check(granne_hip_index_save(h_.get(), path.c_str(), nullptr)); }
     void write_elements(const std::string& path) const { check(granne_hip_index_save(h_.get(), nullptr, path.c_str())); }
+    // write_index + write_elements through the device codec (either path may be empty: not written); the same bytes
+    void save_on_device(const std::string& index_path, const std::string& elements_path, uint64_t staging_bytes = 0,
+                        uint64_t* info = nullptr) const {
+        check(granne_hip_index_save_on_device(h_.get(), index_path.empty() ? nullptr : index_path.c_str(),
+                                              elements_path.empty() ? nullptr : elements_path.c_str(), staging_bytes, info));
+    }
     // Index::write_index into a writer (src/index/mod.rs:67-70): the bytes of the index file
     std::vector<uint8_t> index_bytes() const {
         void* p = nullptr;

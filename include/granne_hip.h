@@ -332,6 +332,34 @@ int granne_hip_index_save(const granne_hip_index* index, const char* index_path,
  * its writer. */
 int granne_hip_index_encode(const granne_hip_index* index, void** out_bytes, uint64_t* out_len);
 void granne_hip_bytes_free(void* bytes);
+/* The same files through the DEVICE codec (granne_amd/csrc/codec_kernels.h): the layers' rows are sorted, delta- and
+ * stream-vbyte-encoded where they live, and decoded straight into their final rows; the files' bytes and the loaded index
+ * equal those of the four host entries above, which stay as they are. Data crosses the bus through a pinned ring of
+ * `staging_bytes` (two slots of half that, each with a device segment of the same size), so host memory is proportional to
+ * `staging_bytes`, never to the file -- except _encode_on_device's returned buffer, which is the file -- and device scratch
+ * stays within 2 * staging_bytes + 16 bytes per 60 nodes + the offset scan's temporary storage.
+ *   staging_bytes  0 selects GRANNE_HIP_CODEC_STAGING_DEFAULT; values below GRANNE_HIP_CODEC_STAGING_MIN are raised to
+ *                  it, values above 4 GiB lowered to that
+ *   out_info       NULL, or u64[4] set by the call: [0] layers that went through the device codec, [1] layers that fell
+ *                  back to the host codec inside the call (rows wider than 64 ids), [2] peak device scratch bytes beyond
+ *                  the index itself, [3] peak host staging bytes (the ring, plus a fallback layer's buffers)
+ * Errors as the host entries': GRANNE_HIP_ERR_INVALID for null arguments or an unknown dtype before any device work,
+ * GRANNE_HIP_ERR_IO for anything wrong with a file; a compact SumEmbeddings handle saves its index file but refuses
+ * `elements_path`. A malformed file is refused by bounds checks on the host and in the kernels, never by a fault. */
+/* The default was chosen by measurement (profiles/index_codec.json: 10M nodes, 2 GB of files): a call allocates its ring,
+ * and 64 MiB saved in 0.44 s and loaded in 0.14 s where 256 MiB took 0.55 / 0.18 s and 1 GiB 0.65 / 0.30 s (16 MiB: 0.49 /
+ * 0.10 s). */
+#define GRANNE_HIP_CODEC_STAGING_DEFAULT (64ull << 20) /* 64 MiB */
+#define GRANNE_HIP_CODEC_STAGING_MIN (64ull << 10)      /* 64 KiB: a slot holds any chunk of 60 64-id records */
+int granne_hip_index_encode_on_device(const granne_hip_index* index, uint64_t staging_bytes, void** out_bytes,
+                                      uint64_t* out_len, uint64_t* out_info);
+int granne_hip_index_save_on_device(const granne_hip_index* index, const char* index_path, const char* elements_path,
+                                    uint64_t staging_bytes, uint64_t* out_info);
+int granne_hip_index_load_on_device(granne_hip_index** out, const void* index_bytes, uint64_t index_len,
+                                    const void* elements_bytes, uint64_t elements_len, int dtype, int device_id,
+                                    uint64_t staging_bytes, uint64_t* out_info);
+int granne_hip_index_load_files_on_device(granne_hip_index** out, const char* index_path, const char* elements_path,
+                                          int dtype, int device_id, uint64_t staging_bytes, uint64_t* out_info);
 /* Host-only inspection of an index file (no device involved): layer count, nodes and ids per
  * layer (arrays of `cap` entries), and the decoded CSR form of one layer
  * (out_offsets[layer_len + 1], out_ids[ids of that layer], ascending within a node). */

@@ -48,6 +48,16 @@ extern "C" {
     fn granne_hip_index_save(index: *const granne_hip_index, index_path: *const c_char, elements_path: *const c_char) -> c_int;
     fn granne_hip_index_encode(index: *const granne_hip_index, out_bytes: *mut *mut c_void, out_len: *mut u64) -> c_int;
     fn granne_hip_bytes_free(bytes: *mut c_void);
+    // the same files through the device codec (granne_amd/csrc/codec_kernels.h), streamed through a pinned ring
+    fn granne_hip_index_encode_on_device(index: *const granne_hip_index, staging_bytes: u64,
+        out_bytes: *mut *mut c_void, out_len: *mut u64, out_info: *mut u64) -> c_int;
+    fn granne_hip_index_save_on_device(index: *const granne_hip_index, index_path: *const c_char,
+        elements_path: *const c_char, staging_bytes: u64, out_info: *mut u64) -> c_int;
+    fn granne_hip_index_load_on_device(out: *mut *mut granne_hip_index, index_bytes: *const c_void, index_len: u64,
+        elements_bytes: *const c_void, elements_len: u64, dtype: c_int, device_id: c_int, staging_bytes: u64,
+        out_info: *mut u64) -> c_int;
+    fn granne_hip_index_load_files_on_device(out: *mut *mut granne_hip_index, index_path: *const c_char,
+        elements_path: *const c_char, dtype: c_int, device_id: c_int, staging_bytes: u64, out_info: *mut u64) -> c_int;
     fn granne_hip_index_destroy(index: *mut granne_hip_index);
     fn granne_hip_index_len(index: *const granne_hip_index) -> u64;
     fn granne_hip_index_num_layers(index: *const granne_hip_index) -> u32;
@@ -430,6 +440,28 @@ impl<E: GpuElements> GpuGranne<E> {
         let mut h = std::ptr::null_mut();
         check(unsafe { granne_hip_index_load_files(&mut h, ip.as_ptr(), ep.as_ptr(), E::DTYPE, device) })?;
         Ok(Self::wrap(h))
+    }
+    /// `from_files` through the device codec: the files are read in pieces into a pinned ring of `staging_bytes` (0: the
+    /// library's default) and decoded on the GPU; the index equals `from_files`'. Returns the call's four info words
+    /// (layers on the device codec, layers on the host codec, peak device scratch bytes, peak host staging bytes).
+    pub fn from_files_on_device(index_path: &std::path::Path, elements_path: &std::path::Path, device: i32,
+                                staging_bytes: u64) -> std::io::Result<(Self, [u64; 4])> {
+        use std::os::unix::ffi::OsStrExt;
+        let ip = std::ffi::CString::new(index_path.as_os_str().as_bytes())?;
+        let ep = std::ffi::CString::new(elements_path.as_os_str().as_bytes())?;
+        let mut h = std::ptr::null_mut();
+        let mut info = [0u64; 4];
+        check(unsafe { granne_hip_index_load_files_on_device(&mut h, ip.as_ptr(), ep.as_ptr(), E::DTYPE, device, staging_bytes, info.as_mut_ptr()) })?;
+        Ok((Self::wrap(h), info))
+    }
+    /// `save` through the device codec: the same two files, encoded on the GPU and streamed through the pinned ring.
+    pub fn save_on_device(&self, index_path: &std::path::Path, elements_path: &std::path::Path, staging_bytes: u64) -> std::io::Result<[u64; 4]> {
+        use std::os::unix::ffi::OsStrExt;
+        let ip = std::ffi::CString::new(index_path.as_os_str().as_bytes())?;
+        let ep = std::ffi::CString::new(elements_path.as_os_str().as_bytes())?;
+        let mut info = [0u64; 4];
+        check(unsafe { granne_hip_index_save_on_device(self.handle, ip.as_ptr(), ep.as_ptr(), staging_bytes, info.as_mut_ptr()) })?;
+        Ok(info)
     }
     /// `write_index` + `write_elements` (src/index/io.rs:11-70, slice_vector/mod.rs:460-466) to two files.
     pub fn save(&self, index_path: &std::path::Path, elements_path: &std::path::Path) -> std::io::Result<()> {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """BASELINE.json configs[4] through FILES: shards of 125M x 100-d int8 built by the GPU builder, written with
 granne_hip_index_save (granne's own index / elements formats), dropped, loaded back with granne_hip_index_load_files (mmap)
-and searched as one partitioned index (ef_search 200, batches of 4096).
+-- or, with --on-device, with the device codec's granne_hip_index_save_on_device / _load_files_on_device -- and searched as one partitioned index (ef_search 200, batches of 4096).
 
   python tools/c5_files.py --shards 1            # the round trip of one shard: seconds, bytes, 4096 queries bit for bit
   python tools/c5_files.py --shards 8            # the whole 1B job on one GPU (265 GB of 288)
@@ -25,6 +25,9 @@ ap.add_argument("--dir", default="/dev/shm/granne_c5")
 ap.add_argument("--nq", type=int, default=4096)
 ap.add_argument("--ef", type=int, default=200)
 ap.add_argument("--steps", type=int, default=6)
+ap.add_argument("--on-device", action="store_true", help="save and load through the device codec (granne_hip_index_save_on_device / "
+                "_load_files_on_device) instead of the host codec; the records carry the calls' info words")
+ap.add_argument("--staging-bytes", type=int, default=0, help="the device codec's pinned ring (0: the library's default)")
 a = ap.parse_args()
 sys.argv = [sys.argv[0]]
 import bench  # noqa: E402
@@ -81,10 +84,11 @@ for s in range(a.shards):
     torch.cuda.empty_cache()
     pi, pe = os.path.join(a.dir, "shard%d.granne" % s), os.path.join(a.dir, "shard%d.elements" % s)
     t0 = time.time()
-    ix.save_index(pi)
+    ix.save_index(pi, on_device=a.on_device, staging_bytes=a.staging_bytes)
     t_si = time.time() - t0
+    info_si = ix.last_codec_info
     t0 = time.time()
-    ix.save_elements(pe)
+    ix.save_elements(pe, on_device=a.on_device, staging_bytes=a.staging_bytes)
     t_se = time.time() - t0
     del ix
     torch.cuda.empty_cache()
@@ -92,7 +96,7 @@ for s in range(a.shards):
     emit({"stage": "built+saved", "shard": s, "gen_s": round(t_gen, 1), "build_s": round(t_build, 1), "layers": layers,
           "index_hbm_gb": round(hbm / 1e9, 2), "save_index_s": round(t_si, 1), "save_elements_s": round(t_se, 1),
           "index_file_gb": round(os.path.getsize(pi) / 1e9, 2), "elements_file_gb": round(os.path.getsize(pe) / 1e9, 2),
-          "cgroup_memory_gb": round(cgroup_gb(), 1)})
+          "cgroup_memory_gb": round(cgroup_gb(), 1), "on_device": a.on_device, "codec_info": info_si})
     if cgroup_gb() > 285:
         emit({"stage": "stop", "why": "host memory (tmpfs files + process) close to the cgroup limit"})
         sys.exit(3)
@@ -101,7 +105,7 @@ for s in range(a.shards):
 loaded = []
 for s, (pi, pe) in enumerate(paths):
     t0 = time.time()
-    ix = granne_amd.Granne.from_files(pi, "angular_int", pe, device=B.dev)
+    ix = granne_amd.Granne.from_files(pi, "angular_int", pe, device=B.dev, on_device=a.on_device, staging_bytes=a.staging_bytes)
     torch.cuda.synchronize()
     t_load = time.time() - t0
     ids = torch.empty((nq, k), dtype=torch.int64, device="cuda")
@@ -115,7 +119,7 @@ for s, (pi, pe) in enumerate(paths):
     emit({"stage": "loaded", "shard": s, "load_files_s": round(t_load, 1), "index_hbm_gb": round(ix.hbm_bytes() / 1e9, 2),
           "hbm_in_indexes_gb": round(sum(i.hbm_bytes() for i in loaded) / 1e9, 1), "queries_checked": nq,
           "equal_to_the_in_memory_index_bit_for_bit": same, "slow_path_queries": int(ix.last_slow_count()),
-          "cgroup_memory_gb": round(cgroup_gb(), 1)})
+          "cgroup_memory_gb": round(cgroup_gb(), 1), "on_device": a.on_device, "codec_info": ix.last_codec_info})
     if not same:
         sys.exit(4)
 
