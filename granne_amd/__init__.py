@@ -9,5 +9,6 @@ from .builder import GranneBuilder  # noqa: F401
 from .embeddings import SumEmbeddings  # noqa: F401
 from .rw_builder import RwGranneBuilder  # noqa: F401
 from .refined import RefinedGranne  # noqa: F401
+from .filters import Filter  # noqa: F401
 
-__all__ = ["Granne", "GranneBuilder", "RwGranneBuilder", "RefinedGranne", "SumEmbeddings", "compute_distance", "normalize", "quantize", "to_f16", "from_f16", "GranneHipError", "F32", "I8", "F16", "UNUSED"]
+__all__ = ["Granne", "GranneBuilder", "RwGranneBuilder", "RefinedGranne", "Filter", "SumEmbeddings", "compute_distance", "normalize", "quantize", "to_f16", "from_f16", "GranneHipError", "F32", "I8", "F16", "UNUSED"]

@@ -21,6 +21,7 @@ OPT_COALESCE, OPT_COALESCE_MAX, OPT_COALESCE_WAIT_US, OPT_COALESCED_LAUNCHES, OP
 OPT_LAST_COMPACT_ROWS = 18  # read-only: the last launch ran the compacted row stage of the sketched walkers
 OPT_LAST_SPLIT_TAIL = 19  # read-only: the last launch ran its tail blocks as a kernel of their own, behind the walkers'
 OPT_LAST_SCAN = 20  # read-only: what the last exact scan ran, one packed word (last_scan() takes it apart)
+OPT_FORCE_GENERAL = 21  # 1: no register walker (tests and measurement: the unfiltered baseline of filtered search)
 # GRANNE_HIP_SCAN_*: the exact scan's kernel forms, one per rule of its dispatch
 (SCAN_NONE, SCAN_RING, SCAN_I8, SCAN_I8_CHUNKED, SCAN_B16_7_4, SCAN_B16_13_2, SCAN_B16_16_1, SCAN_B16_CHUNKED, SCAN_F32_52_4,
  SCAN_F32_100_2, SCAN_F32_128_1) = range(11)
@@ -221,6 +222,12 @@ SIGNATURES = {
     "granne_hip_rw_builder_get_index": (i32, [vp, C.POINTER(vp)]),
     "granne_hip_rw_builder_set_option": (i32, [vp, i32, u64]),
     "granne_hip_rw_builder_get_option": (i32, [vp, i32, C.POINTER(u64)]),
+    "granne_hip_search_filtered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_search_filtered_batch": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_filter_words": (i32, [u64, C.POINTER(u64)]),
+    "granne_hip_filter_from_ids_device": (i32, [vp, u64, u64, vp, vp, i32, vp]),
+    "granne_hip_filter_from_mask_device": (i32, [vp, u64, vp, i32, vp]),
+    "granne_hip_filter_count_device": (i32, [vp, u64, vp, i32, vp]),
 }
 
 

@@ -177,6 +177,7 @@ struct granne_hip_index {
     // options
     uint64_t opt_visited_slots = 0;
     uint64_t opt_force_slow = 0;
+    uint64_t opt_force_general = 0; // GRANNE_HIP_OPT_FORCE_GENERAL: no register walker
     uint64_t opt_slow_slots = 1u << 18;
     uint64_t opt_slow_blocks = 16;
     uint64_t opt_overflow_slots = 0; // 0 auto, 1 off, else slots per overflow table
@@ -700,6 +701,9 @@ extern "C" int granne_hip_index_set_option(granne_hip_index* ix, int option, uin
     case GRANNE_HIP_OPT_FORCE_SLOW:
         ix->opt_force_slow = value ? 1 : 0;
         return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_FORCE_GENERAL:
+        ix->opt_force_general = value ? 1 : 0;
+        return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SLOW_SLOTS:
         if (value < 256 || value > (1ull << 30) || (value & (value - 1)))
             return fail(GRANNE_HIP_ERR_INVALID, "slow slots must be a power of two in [256, 2^30]");
@@ -772,6 +776,7 @@ extern "C" int granne_hip_index_get_option(const granne_hip_index* ix, int optio
     switch (option) {
     case GRANNE_HIP_OPT_VISITED_SLOTS: *value = ix->opt_visited_slots; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_FORCE_SLOW: *value = ix->opt_force_slow; return GRANNE_HIP_OK;
+    case GRANNE_HIP_OPT_FORCE_GENERAL: *value = ix->opt_force_general; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SLOW_SLOTS: *value = ix->opt_slow_slots; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_SLOW_BLOCKS: *value = ix->opt_slow_blocks; return GRANNE_HIP_OK;
     case GRANNE_HIP_OPT_OVERFLOW_SLOTS: *value = ix->opt_overflow_slots; return GRANNE_HIP_OK;
@@ -884,6 +889,7 @@ struct SearchTarget {
     const LayerDev* d_layers;
     uint32_t n_layers;
     uint32_t max_dev_width;
+    uint64_t opt_force_general = 0;
     uint64_t opt_visited_slots = 0, opt_force_slow = 0, opt_slow_slots = 1u << 18, opt_slow_blocks = 16, opt_overflow_slots = 0;
     uint64_t opt_visited16 = 0;
     uint64_t opt_seen_min = 0xFFFFFFFFull;
@@ -907,6 +913,7 @@ struct SearchTarget {
             max_dev_width = g->max_dev_width;
             opt_visited_slots = g->opt_visited_slots;
             opt_force_slow = g->opt_force_slow;
+            opt_force_general = g->opt_force_general;
             opt_slow_slots = g->opt_slow_slots;
             opt_slow_blocks = g->opt_slow_blocks;
             opt_overflow_slots = g->opt_overflow_slots;
@@ -942,6 +949,11 @@ struct SearchCall {
     uint32_t* host_status = nullptr; // u32[2], host-mapped: hand-over count and exhaustion flag, plain stores
     const BatchIO* batches = nullptr;
     uint32_t n_batches = 0;          // > 0: `nq` queries in EACH of these, one launch
+    // filtered search (filter.h, filter_host.h): the bitmaps, words from one query's to the next (0: one for all), the
+    // cap on bottom-layer pops (0: none). Never planned on a register walker.
+    const uint32_t* filter = nullptr;
+    uint64_t filter_stride = 0;
+    uint32_t max_expand = 0;
 };
 
 typedef void (*search_fn)(const SlowParams);
@@ -971,6 +983,16 @@ static search_fn f16_kernel_s(uint32_t S) {
     case 1: return search_kernel<DT_F32, 0, 1, false, PV_F16>;
     case 2: return search_kernel<DT_F32, 0, 2, false, PV_F16>;
     case 4: return search_kernel<DT_F32, 0, 4, false, PV_F16>;
+    }
+    return nullptr;
+}
+// the general walker under an id bitmap (filter.h): dense f32 / int8 rows, run-time dims, no trail walks
+template <int DT>
+static search_fn filtered_kernel_s(uint32_t S) {
+    switch (S) {
+    case 1: return search_kernel<DT, 0, 1, false, PV_DENSE, true>;
+    case 2: return search_kernel<DT, 0, 2, false, PV_DENSE, true>;
+    case 4: return search_kernel<DT, 0, 4, false, PV_DENSE, true>;
     }
     return nullptr;
 }
@@ -1073,7 +1095,8 @@ struct WalkPlan {
 // a run of ties.
 constexpr uint32_t FAST_MAX_SEARCH = 8192; // f32 rows of 100 / 200 dims and int8 rows of 128 bytes: two-level lists of up to 129 x 64 keys
 
-static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool trail) {
+// `filtered`: a filtered search -- the general walker when max_search allows it, else the exact one, never a register walker.
+static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool trail, bool filtered = false) {
     WalkPlan P;
     const bool i8 = T.dtype == GRANNE_HIP_I8;
     const bool streamed = !i8 && T.dim != 100 && T.dim != 200; // f32: 100 and 200 fully unrolled, any other dim streamed (dims below 32: the tail alone)
@@ -1102,7 +1125,11 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         fail(GRANNE_HIP_ERR_INVALID, "reorder has no form for GRANNE_HIP_F16 (angular_f16) rows");
         return P;
     }
-    const bool fast = !compact && !f16 && shape && ef <= fast_max && !(wide && trail);
+    if (filtered && (compact || f16 || trail)) {
+        fail(GRANNE_HIP_ERR_INVALID, "filtered search has no form for this index");
+        return P;
+    }
+    const bool fast = !compact && !f16 && !filtered && !(T.opt_force_general && !trail) && shape && ef <= fast_max && !(wide && trail);
     const uint32_t ef_walk = fast ? ef : (ef > 256 ? 256 : ef); // what the register / general walker is sized for
     const bool all_slow = T.opt_force_slow || (!fast && ef > 256);
     P.walker = all_slow ? GRANNE_HIP_WALKER_EXACT
@@ -1242,6 +1269,7 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
         }
         P.split = false;
         P.fn = compact ? (search_fn)slow_kernel<DT_F32, PV_SE> : f16 ? (search_fn)slow_kernel<DT_F32, PV_F16>
+               : filtered ? (!i8 ? (search_fn)slow_kernel<DT_F32, PV_DENSE, true> : (search_fn)slow_kernel<DT_I8, PV_DENSE, true>)
                : !i8 ? (search_fn)slow_kernel<DT_F32> : (search_fn)slow_kernel<DT_I8>;
         P.lds_bytes = slow_lds;
         P.grid = P.slow_blocks;
@@ -1249,7 +1277,8 @@ static WalkPlan plan_walk(const SearchTarget& T, uint32_t ef, uint32_t nq, bool 
     }
     if (!fast || wide) P.cr = P.split = false;
     if (fast && wide) P.v16 = 3; // (the two-pass walker exists without a visited set only; the same LDS as the touching one)
-    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : f16 ? f16_kernel_s(P.S) : general_kernel_of(T.dtype, P.S, trail);
+    P.fn = fast ? fast_kernel_of(T, P.S, trail, P.v16, wide, P.cr) : compact ? compact_kernel_s(P.S) : f16 ? f16_kernel_s(P.S)
+           : filtered ? (i8 ? filtered_kernel_s<DT_I8>(P.S) : filtered_kernel_s<DT_F32>(P.S)) : general_kernel_of(T.dtype, P.S, trail);
     if (!P.fn) {
         fail(GRANNE_HIP_ERR_INVALID, "no walker is instantiated for this launch (list slots %u, visited form %d, trail %d, 64-id layers %d)",
              P.S, P.v16, (int)trail, (int)wide);
@@ -1305,7 +1334,8 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     if (!c.queries || (!c.trail && (!c.ids || !c.dists || !c.counts))) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     if (T.row_stride < T.elem_row_bytes || (T.dtype == GRANNE_HIP_F16 && T.elem_row_bytes != f16_row_bytes(T.dim)))
         return fail(GRANNE_HIP_ERR_INVALID, "search: inconsistent row layout (row bytes %u, stride %u)", T.elem_row_bytes, T.row_stride);
-    const WalkPlan W = plan_walk(T, c.ef, nq, c.trail != nullptr);
+    if (c.filter && (c.n_batches || c.trail)) return fail(GRANNE_HIP_ERR_INVALID, "a filtered search is one batch");
+    const WalkPlan W = plan_walk(T, c.ef, nq, c.trail != nullptr, c.filter != nullptr);
     if (!W.fn) return GRANNE_HIP_ERR_INVALID;
 
     // scratch: [control words][region states] (zero between launches) [hand-over list][overflow tables][exact walker]
@@ -1395,6 +1425,10 @@ static int search_launch(const SearchTarget& T, SearchCall c) {
     p.se_offsets = T.se ? T.se->d_offsets.as<uint64_t>() : nullptr;
     p.se_terms = T.se ? T.se->d_terms.as<uint32_t>() : nullptr;
     sp.se_x = lane_x ? (float*)(scratch + off_sex) : nullptr;
+    p.filter = c.filter;
+    p.filter_stride = c.filter_stride;
+    p.max_expand = c.max_expand;
+    p.cut_count = c.status ? c.status + 3 : nullptr;
 
     if (T.last_walker) T.last_walker->store(W.walker);
     if (T.last_compact) T.last_compact->store(W.cr ? 1 : 0);
@@ -2559,3 +2593,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // refined search over a SumEmbeddings container: re-rank by term sums; the container as prepared rows
 // ------------------------------------------------------------------------------------------------
 #include "refine_se_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// filtered search: the walk under an id bitmap; the bitmap makers
+// ------------------------------------------------------------------------------------------------
+#include "filter_host.h"

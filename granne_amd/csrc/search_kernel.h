@@ -26,6 +26,7 @@
 #include "wave_prims.h"
 #include "sum_embeddings.h"
 #include "f16.h"
+#include "filter.h"
 
 namespace granne_hip {
 
@@ -117,6 +118,12 @@ struct SearchParams {
     const float* se_table;      // [V][row_bytes / 4]
     const uint64_t* se_offsets; // [n_elements + 1]
     const uint32_t* se_terms;
+    // Filtered search (filter.h; the FILT instantiations read these, nothing else does): walker i's bitmap starts at
+    // filter + i * filter_stride words (stride 0: one bitmap for all).
+    const uint32_t* filter;
+    uint64_t filter_stride;
+    uint32_t max_expand;        // bottom-layer pops a walk may make; 0: no cap
+    uint32_t* cut_count;        // += walks that max_expand cut, or null
 };
 constexpr uint32_t TRAIL_WIDTH = 8; // NUM_LAYERS, reorder.rs:177
 
@@ -181,8 +188,10 @@ __device__ __forceinline__ void hand_over(const SearchParams& p, uint32_t qi) {
 //   PV_SE     a compact SumEmbeddings index: the sum of the candidate's term rows (sum_embeddings.h)
 //   PV_F16    rows of halves (f16.h): widened into the stage
 // and the last two normalise the staged vector before the dot (se_finish_dist).
+// FILT: the walk of the bottom layer runs under an id bitmap (filter.h states the semantic). `res` then holds allowed
+// ids only; `pq` holds the ALLOWED queued keys and fs.qd the disallowed ones, pop takes the smaller head.
 constexpr int PV_DENSE = 0, PV_SE = 1, PV_F16 = 2;
-template <int DT, int DIM, int S, int PV = PV_DENSE>
+template <int DT, int DIM, int S, int PV = PV_DENSE, bool FILT = false>
 struct Walker {
     static constexpr bool SE = PV == PV_SE;
     // ---- immutable per-launch state
@@ -204,6 +213,7 @@ struct Walker {
     SortedList<S> pq;  // `pq`, bounded at 64*S entries
     WalkStats st;
     bool bail; // visited table full or unsafe queue drop: hand over to the slow path
+    FilterState<FILT> fs; // (empty unless FILT)
 
     __device__ __forceinline__ Walker(const SearchParams& p_, uint8_t* smem) : p(p_) {
         lane = threadIdx.x;
@@ -403,6 +413,32 @@ struct Walker {
         }
     }
 
+    // FILT: push a DISALLOWED key. Under a filter only allowed keys fill `res`, so the argument above does not cover a
+    // disallowed key X that falls off its queue: X may be dropped only when at least ef ALLOWED keys of strictly smaller
+    // distance exist in pq + res. Those in pq sort before X and are popped before X could be (a break or max_expand
+    // before that ends the walk before X too), each enters `res` unless `res` already holds ef smaller ones, so at X's
+    // turn `res` is full with res.max.dist < X.dist: the loop breaks there, and breaks the same way at whatever follows
+    // X when X is gone. The count is by DISTANCE (keys below (X.dist, id 0)), so a tie never counts; keys that pq itself
+    // dropped are not counted, which only errs towards handing over. Anything short of ef: `bail`.
+    // pq keeps the unfiltered rule: an allowed key falling off it has 64*S >= ef allowed keys before it.
+    __device__ __forceinline__ void qd_push(uint64_t ck, uint32_t ef) {
+        if constexpr (FILT) {
+            constexpr uint32_t CAP = 64u * FILTER_QD_S;
+            uint32_t r = fs.qd.rank(ck);
+            uint64_t dropped;
+            if (r >= CAP) {
+                dropped = ck;
+            } else {
+                dropped = fs.qd.get(CAP - 1);
+                fs.qd.insert_at(r, ck, lane);
+            }
+            if (dropped != KEY_INF) {
+                const uint64_t below = dropped & 0xFFFFFFFF00000000ull; // (dist, id 0): every key of a smaller distance sorts before it
+                if (pq.rank(below) + res.rank(below) < ef) bail = true;
+            }
+        }
+    }
+
     // ---- narrow layers (device row width 32) on the paths without a fast expansion -----------------
     // (f32 with a runtime dim, i8 rows other than 128 bytes): candidates are compacted through LDS
     // and `distances` gathers their rows; the candidates' adjacency rows are still fetched
@@ -447,11 +483,18 @@ struct Walker {
     }
 
     // mod.rs:1029-1031 + pq.push for the candidates of one expansion (lane c < m holds d, cid)
+    // FILT: `ok` = the candidate's bit. The allowed candidates take the unfiltered path into pq (first: they count
+    // towards what lets a disallowed key go), the disallowed ones go to fs.qd one by one.
     __device__ __forceinline__ void offer_candidates(uint32_t m, float d, uint32_t cid, bool full, float worst,
-                                                     uint32_t ef) {
+                                                     uint32_t ef, bool ok = true) {
         uint64_t ck = make_key(d, cid);
         // `res` is frozen during an expansion, so the filter is too
         bool pass = (lane < m) && (!full || d < worst);
+        bool pass_d = false;
+        if constexpr (FILT) {
+            pass_d = pass && !ok;
+            pass = pass && ok;
+        }
         // entries that cannot enter a full queue are dropped right here
         uint64_t last = pq.get(64u * S - 1);
         if (last != KEY_INF) {
@@ -465,6 +508,14 @@ struct Walker {
             pm &= pm - 1;
             pq_push(readlane64(ck, src), ef);
         }
+        if constexpr (FILT) {
+            uint64_t dm = wave_ballot(pass_d);
+            while (dm) {
+                uint32_t src = (uint32_t)__builtin_ctzll(dm);
+                dm &= dm - 1;
+                qd_push(readlane64(ck, src), ef);
+            }
+        }
     }
 
     // search_for_neighbors (mod.rs:999-1037) on one layer. Result: `res` (ascending).
@@ -474,7 +525,9 @@ struct Walker {
         res.init();
         pq.init();
         __syncthreads();
-        uint32_t n_popped = 0;
+        uint32_t n_popped = 0; // entries pushed to `res` (FILT: the allowed pops)
+        [[maybe_unused]] uint32_t n_expanded = 0; // FILT: pops of this layer, what max_expand caps
+        if constexpr (FILT) fs.qd.init();
 
         const bool narrow = p.spec && L.width == 32 && (DT == DT_I8 || DIM > 0 || p.maxc >= 32);
         const gptr_u32 adjg = (gptr_u32)L.adj;
@@ -491,25 +544,46 @@ struct Walker {
             float d0 = distances(1);
             st.n_dist += 1;
             uint64_t k0 = readlane64(make_key(d0, entrypoint), 0);
-            pq.insert_at(0, k0, lane);
+            bool ok0 = true;
+            if constexpr (FILT) ok0 = !fs.on || fs.view.allowed(entrypoint);
+            if (ok0) pq.insert_at(0, k0, lane);
+            if constexpr (FILT)
+                if (!ok0) fs.qd.insert_at(0, k0, lane);
         }
 
         for (;;) {
             uint64_t x = pq.get(0); // pq.pop(), mod.rs:1018
+            bool x_ok = true;         // FILT: the popped id is allowed (it came from pq, not from fs.qd)
+            if constexpr (FILT) {
+                const uint64_t xd = fs.qd.get(0);
+                if (xd < x) {
+                    x = xd;
+                    x_ok = false;
+                }
+            }
             if (x == KEY_INF) break;
             bool full = n_popped >= ef;
             if (full && key_dist(x) > key_dist(res.get(ef - 1))) break; // mod.rs:1019-1021
-            pq.pop_front(lane);
+            if constexpr (FILT) {
+                if (fs.on && p.max_expand && n_expanded == p.max_expand) { // the work cap (filter.h)
+                    fs.cut = true;
+                    break;
+                }
+                n_expanded += 1;
+            }
+            if (x_ok) pq.pop_front(lane);
+            if constexpr (FILT)
+                if (!x_ok) fs.qd.pop_front(lane);
 
-            // res.push((d, idx)), max_size_heap.rs:18-32
-            {
+            // res.push((d, idx)), max_size_heap.rs:18-32 (FILT: allowed ids only)
+            if (x_ok) {
                 uint32_t r = res.rank(x);
                 if (r < ef) {
                     res.insert_at(r, x, lane);
                     if (ef < 64u * S) res.clear_at(ef, lane);
                 }
+                n_popped += 1;
             }
-            n_popped += 1;
             full = n_popped >= ef;
             const float worst = full ? key_dist(res.get(ef - 1)) : 0.0f;
 
@@ -543,7 +617,11 @@ struct Walker {
                     nb = (lane < 32) ? row[lane] : ID_EMPTY;
                 }
                 // prefetch the adjacency of the queue's new head for the next iteration
-                const uint64_t head = pq.get(0);
+                uint64_t head = pq.get(0);
+                if constexpr (FILT) {
+                    const uint64_t hd = fs.qd.get(0);
+                    if (hd < head) head = hd;
+                }
                 specA_id = (head != KEY_INF) ? key_id(head) : ID_EMPTY;
                 if (specA_id != ID_EMPTY) specA_nb = (lane < 32) ? adjg[(size_t)specA_id * 32u + lane] : ID_EMPTY;
 
@@ -560,12 +638,16 @@ struct Walker {
                         __syncthreads(); // adjspec / cand of the previous expansion are dead from here on
                         if (fresh) cand[pos] = nb;
                         __syncthreads();
+                        [[maybe_unused]] uint32_t fw = 0xFFFFFFFFu; // FILT: the candidate's filter word, in flight with its row
+                        if constexpr (FILT)
+                            if (fs.on && lane < m) fw = fs.view.word_of(cand[lane]);
                         float d = distances_narrow(m, adjg); // mod.rs:1027
                         st.n_dist += m;
                         uint32_t cid = (lane < m) ? cand[lane] : ID_EMPTY;
                         specB_m = m;
                         specB_cid = cid;
-                        offer_candidates(m, d, cid, full, worst, ef);
+                        if constexpr (FILT) offer_candidates(m, d, cid, full, worst, ef, FilterView::bit_of(fw, cid));
+                        else offer_candidates(m, d, cid, full, worst, ef);
                     }
                 }
                 if (!vis.make_room(p.ovf, lane)) bail = true;
@@ -583,10 +665,14 @@ struct Walker {
                         uint32_t pos = (uint32_t)__popcll(fm & ((1ull << lane) - 1ull));
                         if (fresh) cand[pos] = nb;
                         __syncthreads();
+                        [[maybe_unused]] uint32_t fw = 0xFFFFFFFFu; // FILT: as above
+                        if constexpr (FILT)
+                            if (fs.on && lane < m) fw = fs.view.word_of(cand[lane]);
                         float d = distances(m); // mod.rs:1027
                         st.n_dist += m;
                         uint32_t cid = (lane < m) ? cand[lane] : 0u;
-                        offer_candidates(m, d, cid, full, worst, ef);
+                        if constexpr (FILT) offer_candidates(m, d, cid, full, worst, ef, FilterView::bit_of(fw, cid));
+                        else offer_candidates(m, d, cid, full, worst, ef);
                         __syncthreads();
                     }
                     if (!vis.make_room(p.ovf, lane)) bail = true;
@@ -598,7 +684,7 @@ struct Walker {
     }
 };
 
-template <int DT, int DIM, int S, bool TRAIL, int PV = PV_DENSE>
+template <int DT, int DIM, int S, bool TRAIL, int PV = PV_DENSE, bool FILT = false>
 __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t qi, uint8_t* smem) {
     const uint32_t lane = threadIdx.x;
     if (p.force_slow) {
@@ -606,8 +692,13 @@ __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t q
         return;
     }
 
-    Walker<DT, DIM, S, PV> w(p, smem);
+    static_assert(!(TRAIL && FILT), "trail walks are not filtered");
+    Walker<DT, DIM, S, PV, FILT> w(p, smem);
     w.load_query(qi);
+    if constexpr (FILT) {
+        w.fs.view.words = p.filter + (size_t)qi * p.filter_stride;
+        w.fs.on = w.fs.cut = false;
+    }
 
     if constexpr (TRAIL) { // find_entrypoint_trail: `ep` reads the still-zero eps[i], every walk starts at node 0
         const uint32_t take = min(min(p.trail_layers, TRAIL_WIDTH), p.n_layers);
@@ -631,6 +722,7 @@ __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t q
     for (uint32_t l = 0; l < p.n_layers; ++l) {
         const LayerDev L = p.layers[l];
         const bool bottom = (l + 1 == p.n_layers);
+        if constexpr (FILT) w.fs.on = bottom; // find_entrypoint is unfiltered: every key goes through pq
         w.search_layer(L, entrypoint, bottom ? p.ef : 1u, bottom ? p.visited_slots : p.upper_slots);
         if (w.bail) break;
         if (!bottom) entrypoint = key_id(w.res.get(0)); // res[0].0, mod.rs:993
@@ -665,6 +757,8 @@ __device__ __forceinline__ void walk_one(const SearchParams& p, const uint32_t q
     }
     if (lane == 0) {
         *io.count = count;
+        if constexpr (FILT)
+            if (w.fs.cut && p.cut_count) atomicAdd(p.cut_count, 1u);
         if (io.stats) {
             io.stats[0] = w.st.n_dist;
             io.stats[1] = w.st.n_expand;

@@ -129,7 +129,10 @@ __device__ inline float slow_dist(const SearchParams& p, const uint8_t* lds_q, u
 }
 
 // Block `me` of `n_blocks` walks entries me, me + n_blocks, ... of the hand-over list (or of 0..nq-1 when P.all).
-template <int DT, int PV = PV_DENSE>
+// FILT: the bottom layer's walk runs under the query's id bitmap (filter.h states the semantic): only allowed ids enter
+// `res`, and max_expand caps the layer's pops. The heaps are unbounded, so nothing else changes; a very selective filter
+// visits about max_search / selectivity nodes, which GRANNE_HIP_OPT_SLOW_SLOTS bounds as it bounds every walk here.
+template <int DT, int PV = PV_DENSE, bool FILT = false>
 __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, const uint32_t n_blocks,
                                       const uint32_t n_slow, uint8_t* smem) {
     const SearchParams& p = P.sp;
@@ -171,6 +174,9 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
         uint32_t entrypoint = 0;
         uint32_t n_res = 0;
         bool overflow = false;
+        [[maybe_unused]] FilterView fv{nullptr};
+        [[maybe_unused]] uint32_t cut = 0;
+        if constexpr (FILT) fv.words = p.filter + (size_t)qi * p.filter_stride;
 
         const bool trail = p.trail_out != nullptr; // reorder.rs:180-208, see search_kernel.h
         const uint32_t walk_layers = trail ? min(min(p.trail_layers, TRAIL_WIDTH), p.n_layers) : p.n_layers;
@@ -189,6 +195,7 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
 
             uint32_t n_pq = 0, n_vis = 1;
             n_res = 0;
+            [[maybe_unused]] uint32_t n_expanded = 0; // FILT: pops of this layer (lane 0 counts)
             if (lane == 0) {
                 vis[VisitedSet::hash(entrypoint) & mask] = entrypoint;
                 float d0 = slow_dist<DT, PV>(p, lds_q, entrypoint, dy, se_x);
@@ -206,11 +213,23 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
                     if (n_pq > 0) {
                         uint64_t top = pq[0];
                         bool was_full = n_res >= ef;
-                        if (!(was_full && key_dist(top) > key_dist(res[0]))) {
+                        bool go = !(was_full && key_dist(top) > key_dist(res[0]));
+                        if constexpr (FILT) {
+                            if (go && bottom && p.max_expand && n_expanded == p.max_expand) { // the work cap
+                                go = false;
+                                cut = 1;
+                            }
+                        }
+                        if (go) {
                             x = gheap_pop_min(pq, n_pq);
-                            if (!was_full) {
+                            bool ok = true; // FILT: only allowed ids enter res (a disallowed node is expanded all the same)
+                            if constexpr (FILT) {
+                                n_expanded += 1;
+                                ok = !bottom || fv.allowed(key_id(x));
+                            }
+                            if (ok && !was_full) {
                                 gheap_push_max(res, n_res, x);
-                            } else if (x < res[0]) {
+                            } else if (ok && x < res[0]) {
                                 gheap_replace_max(res, n_res, x);
                             }
                             if (n_res >= ef) worst_bits = (uint32_t)(res[0] >> 32);
@@ -328,6 +347,8 @@ __device__ inline void slow_walk_list(const SlowParams& P, const uint32_t me, co
                 io.dists[e] = ok ? key_dist(key) : __builtin_inff();
             }
             *io.count = count;
+            if constexpr (FILT)
+                if (cut && !overflow && p.cut_count) atomicAdd(p.cut_count, 1u);
             if (io.stats) {
                 io.stats[0] = n_dist;
                 io.stats[1] = n_expand;
@@ -360,7 +381,7 @@ __device__ __forceinline__ void walker_done(const SlowParams& P) {
 }
 
 // blocks nq.. of a walker launch
-template <int DT, int PV = PV_DENSE>
+template <int DT, int PV = PV_DENSE, bool FILT = false>
 __device__ inline void tail_block(const SlowParams& P, uint8_t* smem) {
     const uint32_t nq = P.sp.nq;
     const uint32_t me = blockIdx.x - nq, n_blocks = gridDim.x - nq;
@@ -370,41 +391,42 @@ __device__ inline void tail_block(const SlowParams& P, uint8_t* smem) {
     }
     __syncthreads();
     const uint32_t n_slow = __hip_atomic_load(P.ctl + CTL_SLOW_COUNT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_slow) slow_walk_list<DT, PV>(P, me, n_blocks, n_slow, smem);
+    if (n_slow) slow_walk_list<DT, PV, FILT>(P, me, n_blocks, n_slow, smem);
     else if (me == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = 0u;
     slow_epilogue(P, n_blocks, n_slow);
 }
 
 // The tail blocks of a split launch (walk_fast.h, fast_kernel's CR): enqueued right behind the walkers' kernel, whose
 // end the stream's order stands for -- nothing spins on CTL_DONE. P.sp.force_slow: every walker handed its query over.
-template <int DT, int PV = PV_DENSE>
+template <int DT, int PV = PV_DENSE, bool FILT = false>
 __global__ __launch_bounds__(64) void tail_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
     const uint32_t n_slow = __hip_atomic_load(P.ctl + CTL_SLOW_COUNT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_slow) slow_walk_list<DT, PV>(P, blockIdx.x, gridDim.x, n_slow, smem);
+    if (n_slow) slow_walk_list<DT, PV, FILT>(P, blockIdx.x, gridDim.x, n_slow, smem);
     else if (blockIdx.x == 0 && threadIdx.x == 0 && P.host_status) P.host_status[1] = 0u;
     slow_epilogue(P, gridDim.x, n_slow);
 }
 
 // every query of the launch on the exact walker (max_search beyond the register walkers, GRANNE_HIP_OPT_FORCE_SLOW)
-template <int DT, int PV = PV_DENSE>
+template <int DT, int PV = PV_DENSE, bool FILT = false>
 __global__ __launch_bounds__(64) void slow_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
-    slow_walk_list<DT, PV>(P, blockIdx.x, gridDim.x, P.sp.nq, smem);
+    slow_walk_list<DT, PV, FILT>(P, blockIdx.x, gridDim.x, P.sp.nq, smem);
     slow_epilogue(P, gridDim.x, P.sp.nq);
 }
 
 // The general walker's launch (search_kernel.h): block b < nq walks query b; the blocks after them are the tail.
 // TRAIL = true is the variant Granne::reorder launches (SearchParams::trail_out): a kernel of its own,
 // so that the search kernel carries one copy of the walker and nothing else.
-template <int DT, int DIM, int S, bool TRAIL = false, int PV = PV_DENSE>
+// FILT = true: the filtered walk (filter.h), general walker and tail alike.
+template <int DT, int DIM, int S, bool TRAIL = false, int PV = PV_DENSE, bool FILT = false>
 __global__ __launch_bounds__(64) void search_kernel(const SlowParams P) {
     extern __shared__ __align__(16) uint8_t smem[];
     if (blockIdx.x < P.sp.nq) {
-        walk_one<DT, DIM, S, TRAIL, PV>(P.sp, blockIdx.x, smem);
+        walk_one<DT, DIM, S, TRAIL, PV, FILT>(P.sp, blockIdx.x, smem);
         walker_done(P);
     } else {
-        tail_block<DT, PV>(P, smem);
+        tail_block<DT, PV, FILT>(P, smem);
     }
 }
 

@@ -439,6 +439,96 @@ class Granne:
                                                    C.c_void_p(d_counts), C.c_void_p(d_stats), C.c_void_p(d_status),
                                                    C.c_void_p(stream)))
 
+    # ---- filtered search: the walk under an id bitmap (granne_amd/filters.py) ------------------------
+    def _filter_arg(self, allowed, nq):
+        """`allowed` as (owner, device pointer, stride in words): a Filter, a bool array of length len(), an integer id
+        array, or a sequence of Filters, one per query (packed with a stride)."""
+        from .filters import Filter, _DeviceBlock, filter_words
+        n = len(self)
+        if isinstance(allowed, Filter):
+            f = allowed
+        elif isinstance(allowed, (list, tuple)) and len(allowed) and all(isinstance(f, Filter) for f in allowed):
+            if len(allowed) != nq:
+                raise ValueError("need one Filter per query")
+            if any(f.n != n or f.device != self.device for f in allowed):
+                raise ValueError("every Filter must cover the index's %d ids on its device" % n)
+            block = _DeviceBlock(nq * filter_words(n) * 4, self.device).upload(np.stack([f.words() for f in allowed]))
+            return block, block.ptr, filter_words(n)
+        else:
+            a = np.asarray(allowed)
+            if a.dtype.kind == "b":
+                if a.shape != (n,):
+                    raise ValueError("a bool filter needs one entry per element")
+                f = Filter.from_mask(a, self.device)
+            elif a.dtype.kind in "iu":
+                f = Filter.from_ids(a, n, self.device)
+            else:
+                raise TypeError("allowed: a Filter, a bool array, an id array or one Filter per query")
+        if f.n != n or f.device != self.device:
+            raise ValueError("the Filter must cover the index's %d ids on its device" % n)
+        return f, f.ptr, 0
+
+    def search_filtered(self, element, allowed, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS, max_expand=0,
+                        prepared=True):
+        """`search` among the ids `allowed` lets through: [(id, distance)] ascending by (distance, id), fewer than
+        num_elements when the walk met fewer allowed ids. max_expand > 0 caps the bottom layer's expansions."""
+        terms = self.element_type == EMBEDDINGS and (len(element) == 0 or np.asarray(element).dtype.kind in "iu")
+        one = [list(element)] if terms else np.asarray(element).reshape(1, -1)
+        ids, dists, counts = self.search_filtered_batch(one, allowed, max_search, num_elements, max_expand, prepared)
+        return [(int(ids[0, i]), float(dists[0, i])) for i in range(int(counts[0]))]
+
+    def search_filtered_batch(self, elements, allowed, max_search=DEFAULT_MAX_SEARCH, num_elements=DEFAULT_NUM_ELEMENTS,
+                              max_expand=0, prepared=True, stats=False, status=False):
+        """nq filtered searches (granne_hip_search_filtered_batch_device). Returns ids [nq,k] uint64, dists [nq,k] float32,
+        counts [nq] uint32, then stats [nq,3] uint64 (stats=True) and the four status words -- [1] walks the exact walker
+        served, [3] walks max_expand cut -- (status=True). `allowed`: see `_filter_arg`."""
+        from ._lib import OK
+        from .filters import _DeviceBlock
+        q = self._prepare(elements, prepared)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        nq, k = q.shape[0], int(num_elements)
+        owner, fptr, stride = self._filter_arg(allowed, nq)
+        up = lambda v: (v + 255) & ~255  # noqa: E731
+        o_ids = up(q.nbytes)
+        o_d = o_ids + up(nq * k * 8)
+        o_c = o_d + up(nq * k * 4)
+        o_s = o_c + up(nq * 4)
+        o_st = o_s + up(nq * 24)
+        block = _DeviceBlock(o_st + 16, self.device)
+        host = np.zeros(o_st + 16, np.uint8)
+        host[:q.nbytes] = q.view(np.uint8).reshape(-1)
+        block.upload(host)
+        rc = OK
+        if nq:
+            rc = lib().granne_hip_search_filtered_batch_device(
+                self._h, C.c_void_p(block.ptr), nq, int(max_search), k, C.c_void_p(fptr), stride, int(max_expand),
+                C.c_void_p(block.ptr + o_ids), C.c_void_p(block.ptr + o_d), C.c_void_p(block.ptr + o_c),
+                C.c_void_p(block.ptr + o_s), C.c_void_p(block.ptr + o_st), None)
+        check(lib().granne_hip_stream_synchronize(None, self.device))
+        check(rc)
+        host = block.download(np.uint8, o_st + 16)
+        del owner
+        st4 = host[o_st:o_st + 16].view(np.uint32).copy()
+        if st4[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact-search scratch exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)")
+        out = [host[o_ids:o_ids + nq * k * 8].view(np.uint64).reshape(nq, k).copy(),
+               host[o_d:o_d + nq * k * 4].view(np.float32).reshape(nq, k).copy(),
+               host[o_c:o_c + nq * 4].view(np.uint32).copy()]
+        if stats:
+            out.append(host[o_s:o_s + nq * 24].view(np.uint64).reshape(nq, 3).copy())
+        if status:
+            out.append(st4)
+        return tuple(out)
+
+    def search_filtered_batch_device(self, d_queries, nq, max_search, num_elements, d_filter, filter_stride_words, max_expand,
+                                     d_ids, d_dists, d_counts, d_stats=0, d_status=0, stream=0):
+        """Device-resident, asynchronous variant: raw device pointers (int); d_filter e.g. a Filter's `ptr`."""
+        check(lib().granne_hip_search_filtered_batch_device(
+            self._h, C.c_void_p(d_queries), int(nq), int(max_search), int(num_elements), C.c_void_p(d_filter),
+            int(filter_stride_words), int(max_expand), C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts),
+            C.c_void_p(d_stats), C.c_void_p(d_status), C.c_void_p(stream)))
+
     def search_batches_device(self, d_queries, nq, max_search, num_elements, d_ids, d_dists, d_counts, d_stats=None,
                               d_status=0, stream=0):
         """Several batches of nq queries through ONE launch (granne_hip_search_batches_device). d_queries, d_ids,

@@ -145,6 +145,82 @@ private:
     granne_hip_build_config c_;
 };
 
+namespace detail {
+// device memory of the library's allocator, freed with the object
+class DeviceMem {
+public:
+    DeviceMem(size_t bytes, int device) : device_(device) { check(granne_hip_device_malloc(&p_, bytes, device)); }
+    DeviceMem(DeviceMem&& o) noexcept : p_(o.p_), device_(o.device_) { o.p_ = nullptr; }
+    DeviceMem(const DeviceMem&) = delete;
+    DeviceMem& operator=(const DeviceMem&) = delete;
+    ~DeviceMem() { granne_hip_device_free(p_, device_); }
+    void* get() const { return p_; }
+    void upload(const void* src, size_t bytes) const {
+        check(granne_hip_copy_to_device(p_, src, bytes, device_, nullptr));
+        check(granne_hip_stream_synchronize(nullptr, device_));
+    }
+    void download(void* dst, size_t bytes, size_t offset = 0) const {
+        check(granne_hip_copy_to_host(dst, (const char*)p_ + offset, bytes, device_, nullptr));
+        check(granne_hip_stream_synchronize(nullptr, device_));
+    }
+
+private:
+    void* p_ = nullptr;
+    int device_;
+};
+} // namespace detail
+
+// An id bitmap in device memory for Granne::search_filtered (granne_hip.h, "filtered search"): bit (id & 31) of u32 word
+// (id >> 5) over the ids 0..n-1, made and counted by the library's kernels.
+class Filter {
+public:
+    // the bits of `ids` set; duplicates are harmless, ids >= n are left out and counted in *bad
+    static Filter from_ids(const std::vector<uint64_t>& ids, size_t n, int device = 0, uint32_t* bad = nullptr) {
+        Filter f(n, device);
+        detail::DeviceMem d_ids(ids.size() * 8 + 8, device), d_bad(4, device);
+        const uint32_t zero = 0;
+        d_ids.upload(ids.data(), ids.size() * 8);
+        d_bad.upload(&zero, 4);
+        check(granne_hip_filter_from_ids_device((const uint64_t*)d_ids.get(), ids.size(), n, f.words(), (uint32_t*)d_bad.get(), device, nullptr));
+        uint32_t b = 0;
+        d_bad.download(&b, 4);
+        if (bad) *bad = b;
+        return f;
+    }
+    // one entry per id, true = allowed
+    static Filter from_mask(const std::vector<bool>& mask, int device = 0) {
+        Filter f(mask.size(), device);
+        std::vector<uint8_t> bytes(mask.begin(), mask.end());
+        detail::DeviceMem d_mask(bytes.size() + 1, device);
+        d_mask.upload(bytes.data(), bytes.size());
+        check(granne_hip_filter_from_mask_device((const uint8_t*)d_mask.get(), mask.size(), f.words(), device, nullptr));
+        check(granne_hip_stream_synchronize(nullptr, device));
+        return f;
+    }
+    // number of allowed ids
+    uint64_t count() const {
+        detail::DeviceMem d_out(8, device_);
+        check(granne_hip_filter_count_device(words(), n_, (uint64_t*)d_out.get(), device_, nullptr));
+        uint64_t c = 0;
+        d_out.download(&c, 8);
+        return c;
+    }
+    size_t len() const { return n_; }
+    int device() const { return device_; }
+    uint32_t* words() const { return (uint32_t*)mem_.get(); } // device pointer
+
+private:
+    Filter(size_t n, int device) : n_(n), device_(device), mem_(words_of(n) * 4, device) {}
+    static size_t words_of(size_t n) {
+        uint64_t w = 0;
+        check(granne_hip_filter_words(n, &w));
+        return (size_t)w;
+    }
+    size_t n_;
+    int device_;
+    detail::DeviceMem mem_;
+};
+
 // Granne (src/index/mod.rs:38-185): search + the Index trait
 template <class Elements>
 class Granne {
@@ -196,6 +272,45 @@ public:
         std::vector<std::vector<std::pair<size_t, float>>> out(nq);
         for (size_t i = 0; i < nq; ++i)
             for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * num_neighbors + j], ds[i * num_neighbors + j]);
+        return out;
+    }
+
+    // `search` among the ids `allowed` lets through (granne_hip.h, "filtered search"): ascending by (distance, id), fewer than
+    // num_neighbors when the walk met fewer allowed ids; max_expand > 0 caps the bottom layer's expansions
+    std::vector<std::pair<size_t, float>> search_filtered(const Element& element, const Filter& allowed, size_t max_search,
+                                                          size_t num_neighbors, uint64_t max_expand = 0) const {
+        return std::move(search_filtered_batch(&element, 1, allowed, max_search, num_neighbors, max_expand)[0]);
+    }
+    std::vector<std::vector<std::pair<size_t, float>>> search_filtered_batch(const Element* elements, size_t nq, const Filter& allowed,
+                                                                             size_t max_search, size_t num_neighbors,
+                                                                             uint64_t max_expand = 0) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed.len() != len() || allowed.device() != device) throw std::runtime_error("the filter must cover the index's ids on its device");
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t k = num_neighbors, qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_st = o_c + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_out.upload(host.data(), total);
+        int rc = granne_hip_search_filtered_batch_device(h_.get(), d_q.get(), (uint32_t)nq, (uint32_t)max_search, (uint32_t)k, allowed.words(), 0,
+                                                         max_expand, (uint64_t*)d_out.get(), (float*)((char*)d_out.get() + o_d),
+                                                         (uint32_t*)((char*)d_out.get() + o_c), nullptr, (uint32_t*)((char*)d_out.get() + o_st), nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error("exact-search scratch exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
         return out;
     }
 

@@ -798,6 +798,60 @@ enum {
 int granne_hip_rw_builder_set_option(granne_hip_rw_builder* rw, int option, uint64_t value);
 int granne_hip_rw_builder_get_option(granne_hip_rw_builder* rw, int option, uint64_t* value);
 
+/* ---- filtered search: the walk under an id bitmap (no reference counterpart) --------
+ * "The nearest neighbours among the ids this bitmap allows". The filter is `allowed`, one bit per element id: u32 words,
+ * bit (id & 31) of word (id >> 5), at least ceil(len / 32) words; bits at positions >= len are ignored. It applies to the
+ * bottom layer's search; find_entrypoint (the upper layers, max_search 1) is unchanged and unfiltered, those nodes only
+ * navigate. The semantic is hnswlib's for a filter functor, written as a change to search_for_neighbors
+ * (src/index/mod.rs:999-1037):
+ *     while let Some((d, idx)) = pq.pop():
+ *         if res.is_full() && d > res.peek().0: break            unchanged; res now holds allowed ids only
+ *         if n_expanded == max_expand && max_expand != 0: break   NEW: work cap, counted in bottom-layer pops
+ *         if allowed(idx): res.push((d, idx))                     NEW: only allowed ids enter res
+ *         n_expanded += 1
+ *         for n in get_neighbors(idx): ...                        unchanged: disallowed nodes are traversed
+ * Results: `res` ascending by (dist, id), count = min(num_neighbors, |res|) -- fewer than num_neighbors when the walk
+ * met fewer allowed ids --, unused slots filled as by granne_hip_search_batch. With every bit set and max_expand = 0 the
+ * result is granne_hip_search_batch's bit for bit, and so are the three counters of d_out_stats: the walkers that serve
+ * these entries keep the exact visited set, n_dist is the reference's count.
+ * Walkers: the general walker (max_search up to 256) or the exact walker, never a register walker;
+ * GRANNE_HIP_OPT_LAST_WALKER reports GRANNE_HIP_WALKER_GENERAL or _EXACT. A very selective filter visits about
+ * max_search / selectivity nodes: the general walker hands such walks to the exact walker, whose containers
+ * GRANNE_HIP_OPT_SLOW_SLOTS bounds (GRANNE_HIP_ERR_OVERFLOW / d_status[0] as for every search); max_expand bounds the work.
+ * Handles: dense f32 and int8 of any dimension and layer width, materialised SumEmbeddings handles. GRANNE_HIP_F16 handles
+ * and compact SumEmbeddings handles are GRANNE_HIP_ERR_INVALID, and so are max_search == 0, a null filter, and a
+ * filter_stride_words that is neither 0 nor >= ceil(len / 32). nq == 0 does nothing.
+ *   d_filter             the bitmap(s) on the index's device
+ *   filter_stride_words  0: one bitmap for all queries; else query q uses d_filter + q * filter_stride_words
+ *   max_expand           0: no cap; else a walk stops before its (max_expand + 1)-th bottom-layer pop and returns what
+ *                        `res` held
+ *   d_status             u32[4] as granne_hip_search_batch_device; [3] += queries cut by max_expand
+ * Every other argument as granne_hip_search_batch_device; asynchronous on `stream`. */
+int granne_hip_search_filtered_batch_device(const granne_hip_index* index, const void* d_queries, uint32_t nq,
+                                            uint32_t max_search, uint32_t num_neighbors, const uint32_t* d_filter,
+                                            uint64_t filter_stride_words, uint64_t max_expand, uint64_t* d_out_ids,
+                                            float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_stats,
+                                            uint32_t* d_status, void* stream);
+/* the same with host buffers in and out (synchronous); filter: ceil(len / 32) words, or nq * filter_stride_words.
+ * out_status: u32[4] (optional), written, not accumulated. GRANNE_HIP_ERR_OVERFLOW as granne_hip_search_batch. These
+ * calls never take part in GRANNE_HIP_OPT_COALESCE. */
+int granne_hip_search_filtered_batch(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t max_search,
+                                     uint32_t num_neighbors, const uint32_t* filter, uint64_t filter_stride_words,
+                                     uint64_t max_expand, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                     uint64_t* out_stats, uint32_t* out_status);
+/* Bitmaps. *out_words = ceil(n_elements / 32). The makers and the count are stream-ordered on `stream` of device_id:
+ * from_ids zeroes the bitmap, then sets the bit of every id < n_elements (duplicates are harmless); ids >= n_elements are
+ * not written and are added to *d_bad (u32 on the device, optional, zeroed by the caller). from_mask takes one byte per
+ * id (non-zero = allowed) and writes every word of the bitmap. count writes the number of set bits among the first
+ * n_elements to *d_out (u64 on the device). */
+int granne_hip_filter_words(uint64_t n_elements, uint64_t* out_words);
+int granne_hip_filter_from_ids_device(const uint64_t* d_ids, uint64_t n_ids, uint64_t n_elements, uint32_t* d_filter,
+                                      uint32_t* d_bad, int device_id, void* stream);
+int granne_hip_filter_from_mask_device(const uint8_t* d_mask, uint64_t n_elements, uint32_t* d_filter, int device_id,
+                                       void* stream);
+int granne_hip_filter_count_device(const uint32_t* d_filter, uint64_t n_elements, uint64_t* d_out, int device_id,
+                                   void* stream);
+
 /* ---- options (per index) ---------------------------------------------------------------------- */
 enum {
     GRANNE_HIP_OPT_VISITED_SLOTS = 1, /* LDS visited-table slots per query: 2^k or 3 * 2^k in [256, 32768]; 0 = auto */
@@ -875,7 +929,7 @@ enum {
                                                the walkers, then the exact walker's tail blocks in a kernel of their own: the
                                                compacted launches of more walks than the chip holds at once. Same bits, same
                                                status words, nothing allocated or waited for; every other launch is one kernel */
-    GRANNE_HIP_OPT_LAST_SCAN = 20           /* read-only: what the index's last exact scan (granne_hip_brute_force*) ran, one packed
+    GRANNE_HIP_OPT_LAST_SCAN = 20,          /* read-only: what the index's last exact scan (granne_hip_brute_force*) ran, one packed
                                                word set on every call before anything is launched; 0 before the first scan.
                                                  bits  0..7   the kernel form, GRANNE_HIP_SCAN_* below
                                                  bits  8..23  G: the element ranges the scan was cut into (1..128)
@@ -884,6 +938,11 @@ enum {
                                                               the pass runs when G >= 32 and Gs >= kk)
                                                  bits 40..47  kk = min(k + 6, 16): the candidates kept per query
                                                GRANNE_HIP_LAST_SCAN_*() take the word apart */
+    GRANNE_HIP_OPT_FORCE_GENERAL = 21       /* 0 [default] / 1: searches a register walker would take go to the general walker
+                                               (max_search up to 256) or the exact walker instead. Results do not depend on
+                                               it; the general walker keeps the exact visited set, so n_dist is the
+                                               reference's count. For tests and measurement: the unfiltered baseline of
+                                               filtered search, which never runs on a register walker */
 };
 #define GRANNE_HIP_LAST_SCAN_FORM(w) ((unsigned)((w) & 0xFFu))
 #define GRANNE_HIP_LAST_SCAN_RANGES(w) ((unsigned)((w) >> 8 & 0xFFFFu))

@@ -196,6 +196,21 @@ extern "C" {
     fn granne_hip_rw_builder_get_index(rw: *mut granne_hip_rw_builder, out: *mut *mut granne_hip_index) -> c_int;
     fn granne_hip_rw_builder_set_option(rw: *mut granne_hip_rw_builder, option: c_int, value: u64) -> c_int;
     fn granne_hip_rw_builder_get_option(rw: *mut granne_hip_rw_builder, option: c_int, value: *mut u64) -> c_int;
+    // filtered search: the walk under an id bitmap; bitmaps
+    fn granne_hip_search_filtered_batch_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        max_search: u32, num_neighbors: u32, d_filter: *const u32, filter_stride_words: u64, max_expand: u64,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_stats: *mut u64,
+        d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_search_filtered_batch(index: *const granne_hip_index, queries: *const c_void, nq: u32,
+        max_search: u32, num_neighbors: u32, filter: *const u32, filter_stride_words: u64, max_expand: u64,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_stats: *mut u64, out_status: *mut u32) -> c_int;
+    fn granne_hip_filter_words(n_elements: u64, out_words: *mut u64) -> c_int;
+    fn granne_hip_filter_from_ids_device(d_ids: *const u64, n_ids: u64, n_elements: u64, d_filter: *mut u32,
+        d_bad: *mut u32, device_id: c_int, stream: *mut c_void) -> c_int;
+    fn granne_hip_filter_from_mask_device(d_mask: *const u8, n_elements: u64, d_filter: *mut u32, device_id: c_int,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_filter_count_device(d_filter: *const u32, n_elements: u64, d_out: *mut u64, device_id: c_int,
+        stream: *mut c_void) -> c_int;
 }
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
@@ -209,6 +224,7 @@ pub const GRANNE_HIP_OPT_COALESCED_QUERIES: c_int = 17;
 pub const GRANNE_HIP_OPT_LAST_COMPACT_ROWS: c_int = 18;
 pub const GRANNE_HIP_OPT_LAST_SPLIT_TAIL: c_int = 19;
 pub const GRANNE_HIP_OPT_LAST_SCAN: c_int = 20;
+pub const GRANNE_HIP_OPT_FORCE_GENERAL: c_int = 21;
 pub const GRANNE_HIP_RW_OPT_SMALL_OPS: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
@@ -565,6 +581,26 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_search_batch_device(self.handle, queries.ptr as *const c_void, nq as u32, max_search as u32,
             out.k as u32, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), std::ptr::null_mut(), stream.raw) })
     }
+    /// `granne_hip_search_filtered_batch_device`: the batch among the ids `filter` allows (one bitmap for all queries),
+    /// ordered on `stream`. `max_expand` > 0 caps a walk's bottom-layer expansions. A result holds fewer than k ids when
+    /// the walk met fewer allowed ones. F16 and compact SumEmbeddings handles are refused.
+    pub fn search_filtered_batch_device(&self, queries: &DeviceBuffer<u8>, nq: usize, max_search: usize, filter: &GpuFilter,
+                                        max_expand: u64, out: &mut DeviceResults, stream: &Stream) -> std::io::Result<()> {
+        out.fits(nq)?;
+        assert_eq!(filter.len(), self.len());
+        check(unsafe { granne_hip_search_filtered_batch_device(self.handle, queries.ptr as *const c_void, nq as u32,
+            max_search as u32, out.k as u32, filter.words.ptr as *const u32, 0, max_expand, out.ids.ptr, out.dists.ptr,
+            out.counts.ptr, std::ptr::null_mut(), std::ptr::null_mut(), stream.raw) })
+    }
+    /// `Granne::search` among the ids `filter` allows: `[(id, distance)]` ascending by (distance, id).
+    pub fn search_filtered(&self, element: &E::Vector, filter: &GpuFilter, max_search: usize, num_neighbors: usize,
+                           max_expand: u64) -> std::io::Result<Vec<(usize, f32)>> {
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(std::slice::from_ref(element), &stream)?;
+        let mut out = DeviceResults::new(1, num_neighbors, self.device())?;
+        self.search_filtered_batch_device(&q, 1, max_search, filter, max_expand, &mut out, &stream)?;
+        Ok(out.to_host(1, &stream)?.remove(0))
+    }
     /// `granne_hip_search_batches_device`: several batches of `nq` queries in ONE launch (the 5.7 M f32 / 21.8 M int8
     /// queries/s path of DESIGN.md 5): walks of later batches take the places of finished ones inside the launch.
     pub fn search_batches_device(&self, queries: &[&DeviceBuffer<u8>], nq: usize, max_search: usize,
@@ -771,6 +807,49 @@ impl<T: Copy> DeviceBuffer<T> {
     }
 }
 impl<T: Copy> Drop for DeviceBuffer<T> { fn drop(&mut self) { unsafe { granne_hip_device_free(self.ptr as *mut c_void, self.device); } } }
+
+/// An id bitmap in HBM for `search_filtered`: bit (id & 31) of u32 word (id >> 5) over the ids 0..n-1.
+pub struct GpuFilter { words: DeviceBuffer<u32>, n: usize }
+impl GpuFilter {
+    fn empty(n: usize, device: i32) -> std::io::Result<Self> {
+        let mut w = 0u64;
+        check(unsafe { granne_hip_filter_words(n as u64, &mut w) })?;
+        Ok(Self { words: DeviceBuffer::new(w as usize, device)?, n })
+    }
+    /// The bits of `ids` set (duplicates are harmless); returns the filter and how many ids were >= n (left out).
+    pub fn from_ids(ids: &[u64], n: usize, device: i32) -> std::io::Result<(Self, u32)> {
+        let (f, stream) = (Self::empty(n, device)?, Stream::new(device)?);
+        let d_ids = DeviceBuffer::<u64>::new(ids.len().max(1), device)?;
+        d_ids.copy_from(ids, &stream)?;
+        let d_bad = DeviceBuffer::<u32>::new(1, device)?;
+        d_bad.copy_from(&[0u32], &stream)?;
+        check(unsafe { granne_hip_filter_from_ids_device(d_ids.ptr as *const u64, ids.len() as u64, n as u64, f.words.ptr,
+            d_bad.ptr, device, stream.raw) })?;
+        let mut bad = [0u32];
+        d_bad.copy_to(&mut bad, &stream)?;
+        Ok((f, bad[0]))
+    }
+    /// One entry per id, `true` = allowed.
+    pub fn from_mask(mask: &[bool], device: i32) -> std::io::Result<Self> {
+        let (f, stream) = (Self::empty(mask.len(), device)?, Stream::new(device)?);
+        let bytes: Vec<u8> = mask.iter().map(|&b| b as u8).collect();
+        let d_mask = DeviceBuffer::<u8>::new(bytes.len().max(1), device)?;
+        d_mask.copy_from(&bytes, &stream)?;
+        check(unsafe { granne_hip_filter_from_mask_device(d_mask.ptr as *const u8, mask.len() as u64, f.words.ptr, device, stream.raw) })?;
+        stream.synchronize()?;
+        Ok(f)
+    }
+    /// Number of allowed ids.
+    pub fn count(&self) -> std::io::Result<u64> {
+        let stream = Stream::new(self.words.device)?;
+        let d_out = DeviceBuffer::<u64>::new(1, self.words.device)?;
+        check(unsafe { granne_hip_filter_count_device(self.words.ptr as *const u32, self.n as u64, d_out.ptr, self.words.device, stream.raw) })?;
+        let mut out = [0u64];
+        d_out.copy_to(&mut out, &stream)?;
+        Ok(out[0])
+    }
+    pub fn len(&self) -> usize { self.n }
+}
 
 /// The results of one batch in HBM: `[nq][k]` ids and distances, `[nq]` counts.
 pub struct DeviceResults { pub ids: DeviceBuffer<u64>, pub dists: DeviceBuffer<f32>, pub counts: DeviceBuffer<u32>, nq: usize, k: usize }

@@ -7,7 +7,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TYPES = {"void": "c_void", "char": "c_char", "int": "c_int", "float": "f32", "uint64_t": "u64", "uint32_t": "u32",
-         "int8_t": "i8", "int64_t": "i64", "uint16_t": "u16"}
+         "int8_t": "i8", "int64_t": "i64", "uint16_t": "u16", "uint8_t": "u8"}
 
 
 def rust_type(c):
