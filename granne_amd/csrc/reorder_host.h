@@ -199,6 +199,10 @@ static int reorder_on(granne_hip_index* ix, uint64_t* out_order, ReorderScratch&
     uint64_t *d_keys_a = S.keys_a.as<uint64_t>(), *d_keys_b = S.keys_b.as<uint64_t>();
     HIP_TRY(hipMemsetAsync(d_inv, 0, inv_len * 4, s));     // vec![0; layer_len(num_layers - 2)], :137
     HIP_TRY(hipMemsetAsync(d_overflow, 0, 16, s));
+    // A walk that exhausts the exact walker's containers writes no trail (slow_kernel.h), and the overflow word is read
+    // only after the last layer: trail_keys_kernel must find node ids in such rows, not what the allocation held
+    // (order_inv[row[c]] with an arbitrary row[c] reads out of bounds). Zeroed once: every later value is a node id.
+    if (widest) HIP_TRY(hipMemsetAsync(d_trail, 0, widest * TRAIL_WIDTH * 4, s));
     hipLaunchKernelGGL(iota_u32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, d_order, n, 0u); // :136
     HIP_TRY(hipGetLastError());
     const SearchTarget T(ix, ix->d_layers.as<LayerDev>(), (uint32_t)ix->layers.size());
@@ -240,6 +244,7 @@ static int reorder_on(granne_hip_index* ix, uint64_t* out_order, ReorderScratch&
     uint32_t h_over[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_over, d_overflow, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    ix->last_slow_count.store(h_over[1]); // hand-overs summed over the trail launches, whether or not one exhausted its containers
     if (h_over[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "a trail walk outgrew the slow-path containers (raise GRANNE_HIP_OPT_SLOW_SLOTS)");
     int r = order_to_host(n, out_order, S, s);
     if (r) return r;

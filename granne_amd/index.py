@@ -378,6 +378,8 @@ class Granne:
         return int(v.value)
 
     def last_slow_count(self):
+        """Queries of the last host search_batch that the exact walker served; after reorder(), done or failed, the trail
+        walks handed over, summed over its trail launches."""
         return int(lib().granne_hip_index_last_slow_count(self._h))
 
     @property

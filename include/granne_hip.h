@@ -871,7 +871,8 @@ enum {
                                          reference's count. (Rounds 3a-3 distinguished three forms of the exact set; one
                                          is left.) Lists beyond 1024 keys and 64-id layers always walk without a set */
     GRANNE_HIP_OPT_VISITED16_LG = 7,  /* retired with the bucket tables it sized: accepted (0..12), ignored */
-    GRANNE_HIP_OPT_LAST_WALKER = 8,   /* read-only (get_option): which kernel the index's last search launch took */
+    GRANNE_HIP_OPT_LAST_WALKER = 8,   /* read-only (get_option): which kernel the index's last search launch took; after
+                                         granne_hip_index_reorder, its last trail launch */
     GRANNE_HIP_OPT_SEARCH_DEPTH = 9,  /* batches that granne_hip_search_begin_device may have in flight: 1..GRANNE_HIP_SEARCH_DEPTH_MAX
                                          [GRANNE_HIP_SEARCH_DEPTH]; cannot change while one is */
     GRANNE_HIP_OPT_INLINE_TAILS = 10, /* f32 indexes of 100 or 200 dimensions whose layers are 32 ids wide keep, for the
@@ -975,7 +976,9 @@ enum {
 int granne_hip_index_set_option(granne_hip_index* index, int option, uint64_t value);
 int granne_hip_index_get_option(const granne_hip_index* index, int option, uint64_t* value);
 /* number of queries of the last search_batch (host variant) that took the slow exact path; with GRANNE_HIP_OPT_COALESCE
- * on, of the last grouped launch: the count of the whole group a call travelled in */
+ * on, of the last grouped launch: the count of the whole group a call travelled in. After granne_hip_index_reorder,
+ * whether it succeeded or returned GRANNE_HIP_ERR_OVERFLOW: the trail walks handed over, summed over the reorder's
+ * trail launches (one per layer above the first) */
 uint64_t granne_hip_index_last_slow_count(const granne_hip_index* index);
 
 #ifdef __cplusplus
