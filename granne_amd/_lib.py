@@ -83,6 +83,7 @@ SIGNATURES = {
     "granne_hip_index_create_device": (i32, [C.POINTER(vp), vp, u64, u32, i32, u32, vp, vp, vp, i32, vp]),
     "granne_hip_index_destroy": (None, [vp]),
     "granne_hip_index_len": (u64, [vp]),
+    "granne_hip_index_num_elements": (u64, [vp]),
     "granne_hip_index_num_layers": (u32, [vp]),
     "granne_hip_index_layer_len": (u64, [vp, u32]),
     "granne_hip_index_dim": (u32, [vp]),
@@ -228,6 +229,9 @@ SIGNATURES = {
     "granne_hip_filter_from_ids_device": (i32, [vp, u64, u64, vp, vp, i32, vp]),
     "granne_hip_filter_from_mask_device": (i32, [vp, u64, vp, i32, vp]),
     "granne_hip_filter_count_device": (i32, [vp, u64, vp, i32, vp]),
+    "granne_hip_filter_to_ids_device": (i32, [vp, u64, vp, vp, i32, vp]),
+    "granne_hip_exact_topk_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
 }
 
 

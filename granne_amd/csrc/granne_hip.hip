@@ -641,6 +641,7 @@ extern "C" void granne_hip_index_destroy(granne_hip_index* index) { destroy_inde
 extern "C" uint64_t granne_hip_index_len(const granne_hip_index* ix) {
     return (ix && !ix->layers.empty()) ? ix->layers.back().len : 0; // src/index/mod.rs:76-83
 }
+extern "C" uint64_t granne_hip_index_num_elements(const granne_hip_index* ix) { return ix ? ix->n_elements : 0; }
 extern "C" uint32_t granne_hip_index_num_layers(const granne_hip_index* ix) { return ix ? (uint32_t)ix->layers.size() : 0; }
 extern "C" uint64_t granne_hip_index_layer_len(const granne_hip_index* ix, uint32_t layer) {
     return (ix && layer < ix->layers.size()) ? ix->layers[layer].len : 0;
@@ -2598,3 +2599,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // filtered search: the walk under an id bitmap; the bitmap makers
 // ------------------------------------------------------------------------------------------------
 #include "filter_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// the exact scan under an id bitmap: a bitmap's ids, exact_topk over the allowed rows
+// ------------------------------------------------------------------------------------------------
+#include "exact_topk_filtered_host.h"

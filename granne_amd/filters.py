@@ -100,6 +100,16 @@ class Filter:
         check(lib().granne_hip_filter_count_device(C.c_void_p(self.ptr), self.n, C.c_void_p(d_out.ptr), self.device, None))
         return int(d_out.download(np.uint64, 1)[0])
 
+    def ids(self):
+        """The allowed ids, ascending, as a uint64 array: what `from_ids` would take back
+        (granne_hip_filter_to_ids_device)."""
+        d_ids = _DeviceBlock(self.n * 8, self.device)
+        d_count = _DeviceBlock(8, self.device)
+        check(lib().granne_hip_filter_to_ids_device(C.c_void_p(self.ptr), self.n, C.c_void_p(d_ids.ptr), C.c_void_p(d_count.ptr),
+                                                    self.device, None))
+        m = int(d_count.download(np.uint64, 1)[0])
+        return d_ids.download(np.uint64, m)
+
     def words(self):
         """The bitmap's u32 words, copied to the host."""
         return self._block.download(np.uint32, filter_words(self.n))

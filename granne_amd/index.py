@@ -442,11 +442,11 @@ class Granne:
                                                    C.c_void_p(stream)))
 
     # ---- filtered search: the walk under an id bitmap (granne_amd/filters.py) ------------------------
-    def _filter_arg(self, allowed, nq):
-        """`allowed` as (owner, device pointer, stride in words): a Filter, a bool array of length len(), an integer id
-        array, or a sequence of Filters, one per query (packed with a stride)."""
+    def _filter_arg(self, allowed, nq, n=None):
+        """`allowed` as (owner, device pointer, stride in words): a Filter, a bool array of length n (len() unless given),
+        an integer id array, or a sequence of Filters, one per query (packed with a stride)."""
         from .filters import Filter, _DeviceBlock, filter_words
-        n = len(self)
+        n = len(self) if n is None else n
         if isinstance(allowed, Filter):
             f = allowed
         elif isinstance(allowed, (list, tuple)) and len(allowed) and all(isinstance(f, Filter) for f in allowed):
@@ -628,6 +628,54 @@ class Granne:
         if status[0]:
             raise GranneHipError(ERR_OVERFLOW, "exact_topk: %d queries have more than %d rows inside one second-level bin "
                                  "at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
+        return out
+
+    def num_elements(self):
+        """Rows of the element set (at least len()): what exact_topk and exact_topk_filtered scan."""
+        return int(lib().granne_hip_index_num_elements(self._h))
+
+    def exact_topk_filtered_device(self, d_queries, nq, k, d_filter, filter_stride_words, d_ids, d_dists, d_counts, d_status=0,
+                                   stream=0):
+        """exact_topk among the ids a bitmap allows (granne_hip_exact_topk_filtered_device): raw device pointers (int);
+        d_filter e.g. a Filter's `ptr` over num_elements() ids with filter_stride_words 0 -- the scan then walks the
+        bitmap's id list and d_status[3] is its length -- or one bitmap per query, filter_stride_words apart.
+        Asynchronous on `stream`."""
+        check(lib().granne_hip_exact_topk_filtered_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_filter),
+                                                          int(filter_stride_words), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                                          C.c_void_p(d_counts), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def exact_topk_filtered(self, queries, k, allowed, prepared=True, stats=False):
+        """The k (up to EXACT_TOPK_KMAX) nearest elements among those `allowed` lets through, exact by construction: ids
+        [nq, k] u64, dists [nq, k] f32, counts [nq] u32 = min(k, allowed ids), ascending by (distance, id), the places past
+        the count UINT64_MAX / +inf. `allowed`: what search_filtered takes (`_filter_arg`), over num_elements() ids. One
+        filter for all queries is scanned as a list of its ids (status[3]: how many); one Filter per query scans all rows
+        under a bit test. Overflow and stats as `exact_topk`."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        k, nq = int(k), q.shape[0]
+        owner, fptr, stride = self._filter_arg(allowed, nq, self.num_elements())
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        self.exact_topk_filtered_device(tq.data_ptr(), nq, k, fptr, stride, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(),
+                                        st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        status = st.cpu().numpy().astype(np.uint32)
+        out = ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk_filtered: %d queries have more than %d rows inside one second-level "
+                                 "bin at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
 
     def dists_device(self, d_queries, nq, d_ids, m, d_out, d_status=0, stream=0):

@@ -205,6 +205,16 @@ public:
         d_out.download(&c, 8);
         return c;
     }
+    // the allowed ids, ascending: what from_ids would take back
+    std::vector<uint64_t> ids() const {
+        detail::DeviceMem d_ids(n_ * 8 + 8, device_), d_count(8, device_);
+        check(granne_hip_filter_to_ids_device(words(), n_, (uint64_t*)d_ids.get(), (uint64_t*)d_count.get(), device_, nullptr));
+        uint64_t m = 0;
+        d_count.download(&m, 8);
+        std::vector<uint64_t> out((size_t)m);
+        if (m) d_ids.download(out.data(), (size_t)m * 8);
+        return out;
+    }
     size_t len() const { return n_; }
     int device() const { return device_; }
     uint32_t* words() const { return (uint32_t*)mem_.get(); } // device pointer
@@ -353,6 +363,43 @@ public:
         return out;
     }
 
+    // exact_topk among the ids `allowed` lets through (granne_hip_exact_topk_filtered_device; one bitmap for all queries,
+    // over num_elements() ids): the scan walks the bitmap's id list -- the tool for a selective filter, where
+    // search_filtered steps over many disallowed nodes per allowed one. A result holds fewer than k ids when fewer are allowed.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_filtered(const Element* elements, size_t nq, size_t k,
+                                                                           const Filter& allowed) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed.len() != num_elements() || allowed.device() != device)
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_st = o_c + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_out.upload(host.data(), total);
+        int rc = granne_hip_exact_topk_filtered_device(h_.get(), d_q.get(), (uint32_t)nq, (uint32_t)k, allowed.words(), 0, (uint64_t*)d_out.get(),
+                                                       (float*)((char*)d_out.get() + o_d), (uint32_t*)((char*)d_out.get() + o_c),
+                                                       (uint32_t*)((char*)d_out.get() + o_st), nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error("exact_topk_filtered: a query has too many rows inside one second-level bin at its k-th distance");
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // A handle over the rows alone (no layers): what RefinedGranne re-ranks by; get_element and the distance operators work
     static Granne from_elements(const Elements& elements, int device = 0) {
         granne_hip_index* h = nullptr;
@@ -363,6 +410,7 @@ public:
 
     // Index trait (mod.rs:54-71)
     size_t len() const { return granne_hip_index_len(h_.get()); }
+    size_t num_elements() const { return granne_hip_index_num_elements(h_.get()); } // rows of the element set (>= len())
     size_t num_layers() const { return granne_hip_index_num_layers(h_.get()); }
     size_t layer_len(size_t layer) const { return granne_hip_index_layer_len(h_.get(), (uint32_t)layer); }
     std::vector<size_t> get_neighbors(size_t index, size_t layer) const {

@@ -103,6 +103,7 @@ void granne_hip_index_destroy(granne_hip_index* index);
 
 /* Index trait (src/index/mod.rs:54-71) */
 uint64_t granne_hip_index_len(const granne_hip_index* index);        /* bottom layer length */
+uint64_t granne_hip_index_num_elements(const granne_hip_index* index); /* rows of the element set (>= len; what exact_topk* scan) */
 uint32_t granne_hip_index_num_layers(const granne_hip_index* index);
 uint64_t granne_hip_index_layer_len(const granne_hip_index* index, uint32_t layer);
 uint32_t granne_hip_index_dim(const granne_hip_index* index);
@@ -851,6 +852,34 @@ int granne_hip_filter_from_mask_device(const uint8_t* d_mask, uint64_t n_element
                                        void* stream);
 int granne_hip_filter_count_device(const uint32_t* d_filter, uint64_t n_elements, uint64_t* d_out, int device_id,
                                    void* stream);
+/* The bitmap's ids, ascending, to d_out_ids (u64, room for n_elements) and their number to *d_out_count (u64 on the
+ * device): the inverse of from_ids. Stream-ordered, nothing is read back. n_elements up to 2^32 - 1. */
+int granne_hip_filter_to_ids_device(const uint32_t* d_filter, uint64_t n_elements, uint64_t* d_out_ids,
+                                    uint64_t* d_out_count, int device_id, void* stream);
+
+/* ---- the exact scan under an id bitmap ---------------------------------------
+ * granne_hip_exact_topk* among the ids a bitmap allows: the k nearest ALLOWED elements of every query, ascending by
+ * (distance bits, id), distances in the reference's arithmetic, count = min(k, allowed ids), the places past it
+ * UINT64_MAX / +inf. Exact by construction, and the tool for a selective filter, where the filtered walk above has to
+ * step over ten or a hundred disallowed nodes per allowed one. The filter covers the handle's n_elements (all rows are
+ * candidates; a handle without layers is fine), laid out as for filtered search.
+ *   filter_stride_words == 0   one bitmap for every query: it is compacted to its m ids on the device and the scan
+ *                              walks that list -- work ~ m x nq. d_status[3] = m.
+ *   filter_stride_words != 0   query q uses d_filter + q * filter_stride_words: the scan over all rows under a bit test,
+ *                              work ~ n_elements x nq. d_status[3] is left alone.
+ * d_status [0], [1], [2] as granne_hip_exact_topk_device. A filter that allows nothing gives count 0 for every query and
+ * GRANNE_HIP_OK. Refused (GRANNE_HIP_ERR_INVALID): what granne_hip_exact_topk refuses -- GRANNE_HIP_F16 and compact
+ * SumEmbeddings handles, k == 0, k > GRANNE_HIP_EXACT_TOPK_KMAX, more than 2^32 - 1 elements --, a null filter, a
+ * filter_stride_words that is neither 0 nor >= ceil(n_elements / 32). nq == 0 does nothing. Asynchronous on `stream`,
+ * no synchronisation and no read-back; scratch (4 bytes per element for the shared form's list) from hipMallocAsync. */
+int granne_hip_exact_topk_filtered_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                          const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,
+                                          float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, void* stream);
+/* the same with host buffers in and out, the filter's words on the host (ceil(n_elements / 32), or nq *
+ * filter_stride_words); synchronous; out_status u32[4] (optional), written; GRANNE_HIP_ERR_OVERFLOW as granne_hip_exact_topk */
+int granne_hip_exact_topk_filtered(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                                   const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
+                                   float* out_dists, uint32_t* out_counts, uint32_t* out_status);
 
 /* ---- options (per index) ---------------------------------------------------------------------- */
 enum {

@@ -60,6 +60,7 @@ extern "C" {
         elements_path: *const c_char, dtype: c_int, device_id: c_int, staging_bytes: u64, out_info: *mut u64) -> c_int;
     fn granne_hip_index_destroy(index: *mut granne_hip_index);
     fn granne_hip_index_len(index: *const granne_hip_index) -> u64;
+    fn granne_hip_index_num_elements(index: *const granne_hip_index) -> u64;
     fn granne_hip_index_num_layers(index: *const granne_hip_index) -> u32;
     fn granne_hip_index_layer_len(index: *const granne_hip_index, layer: u32) -> u64;
     fn granne_hip_index_dim(index: *const granne_hip_index) -> u32;
@@ -211,6 +212,15 @@ extern "C" {
         stream: *mut c_void) -> c_int;
     fn granne_hip_filter_count_device(d_filter: *const u32, n_elements: u64, d_out: *mut u64, device_id: c_int,
         stream: *mut c_void) -> c_int;
+    fn granne_hip_filter_to_ids_device(d_filter: *const u32, n_elements: u64, d_out_ids: *mut u64,
+        d_out_count: *mut u64, device_id: c_int, stream: *mut c_void) -> c_int;
+    // the exact scan under an id bitmap
+    fn granne_hip_exact_topk_filtered_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        k: u32, d_filter: *const u32, filter_stride_words: u64, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_topk_filtered(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
+        filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_status: *mut u32) -> c_int;
 }
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
@@ -523,6 +533,22 @@ impl<E: GpuElements> GpuGranne<E> {
             ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
     }
+    /// `granne_hip_exact_topk_filtered_device`: `exact_topk` among the ids `filter` allows (one bitmap for all queries,
+    /// over `num_elements()` ids): the scan walks the bitmap's id list, exact by construction -- the tool for a selective
+    /// filter. A result holds fewer than `k` ids when fewer are allowed.
+    pub fn exact_topk_filtered(&self, elements: &[E::Vector], k: usize, filter: &GpuFilter) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        if nq == 0 { return Ok(Vec::new()); }
+        assert_eq!(filter.len(), self.num_elements());
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let out = DeviceResults::new(nq, k, self.device())?;
+        check(unsafe { granne_hip_exact_topk_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
+            filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
+    /// Rows of the element set (at least `len()`): what `exact_topk` and `exact_topk_filtered` scan.
+    pub fn num_elements(&self) -> usize { unsafe { granne_hip_index_num_elements(self.handle) as usize } }
     /// `granne_hip_search_refined_batch`: walk `self` (say, int8 rows and their graph), give the walk's `refine_from` best
     /// candidates their distances under `refine`'s rows (say, the f32 rows of the same elements; a handle made with no
     /// layers is enough) and keep the `num_neighbors` best by (distance, id). `walk_elements[i]` and `refine_elements[i]`
@@ -847,6 +873,20 @@ impl GpuFilter {
         let mut out = [0u64];
         d_out.copy_to(&mut out, &stream)?;
         Ok(out[0])
+    }
+    /// The allowed ids, ascending: what `from_ids` would take back.
+    pub fn ids(&self) -> std::io::Result<Vec<u64>> {
+        let stream = Stream::new(self.words.device)?;
+        let d_ids = DeviceBuffer::<u64>::new(self.n.max(1), self.words.device)?;
+        let d_count = DeviceBuffer::<u64>::new(1, self.words.device)?;
+        check(unsafe { granne_hip_filter_to_ids_device(self.words.ptr as *const u32, self.n as u64, d_ids.ptr, d_count.ptr,
+            self.words.device, stream.raw) })?;
+        let mut m = [0u64];
+        d_count.copy_to(&mut m, &stream)?;
+        let mut out = vec![0u64; self.n];
+        d_ids.copy_to(&mut out, &stream)?;
+        out.truncate(m[0] as usize);
+        Ok(out)
     }
     pub fn len(&self) -> usize { self.n }
 }
