@@ -26,10 +26,31 @@
 //             and 2, no collection) first runs over prefixes of the rows, each 16 times the one before, the first
 //             unbounded: a prefix's bound holds for every longer prefix, so a stage counts about 16 k rows per query
 //             whatever its length. The stages are a function of (n) alone: no host decision between kernels.
+//   sources   which (query, row) pairs a pass looks at (EtSrc) -- the one thing in which
+//             granne_hip_exact_topk_filtered_device differs. Distances, keys, selection and ranking are the same code.
+//             ET_ALL   every row of the prefix, for every query.
+//             ET_LIST  one bitmap for every query, compacted to its ids, ascending (filter.h, fl_*): the passes walk that
+//                      list, entry e names row list[e]. Work ~ m x nq for m allowed ids. The candidate key holds list[e],
+//                      the GLOBAL id: et_rank_kernel orders ties by it. m lives on the device only; nothing is read back.
+//                      The grids and the prefixes p_0 < .. < p_last = n stay functions of n; a stage's entries are
+//                      [0, min(p_st, m)). A stage whose predecessor covered the whole list (st > 0 and p_{st-1} >= m) is
+//                      IDLE: its scan blocks return at once, its select leaves bound and sel alone. The stage with
+//                      p_st >= m whose predecessor did not is the FINAL one: its verdicts go to the status words. Stage 0
+//                      is never idle, so sel is always written -- also for m == 0 (target 0: an all-zero EtSel, the bound
+//                      untouched, nothing collected, count 0). A non-final prefix holds p_st >= ET_PRIME_MIN > ET_KMAX
+//                      entries, all allowed: its bound holds k rows. ET_ALL is this rule with the identity list and
+//                      m = n (never idle, the last stage final); its scan reads no list and no m.
+//             ET_BITS  one bitmap per query: the scan over all n rows, a pair counted and collected only if the row's bit
+//                      is set in that query's bitmap. Work ~ n x nq. A block's 32 rows of one step share one filter word
+//                      per query (the step starts at a multiple of 32): lane (l & 31) of every wave loads query l's word
+//                      beside the row, the query loop reads it back by readlane. A query none of the wave's eight rows is
+//                      allowed for is skipped by that wave -- a wave-uniform skip: et_dist shuffles across the wave.
+//                      Priming: see et_select_kernel.
 // Compiled with -ffp-contract=off: every fused operation is an explicit fmaf.
 #pragma once
 
 #include "dist.h"
+#include "filter.h"
 #include "ordered_sum.h"
 
 namespace granne_hip {
@@ -55,18 +76,28 @@ struct EtSel {
     uint32_t over;       // the rows up to (b1, b2) still do
 };
 
+enum EtSrc { ET_ALL, ET_LIST, ET_BITS }; // the pairs a pass looks at (the header, sources)
+
 struct EtParams {
     const uint8_t* elements; // device rows: row_bytes of (zero padded) data every row_stride bytes
-    uint64_t rows;           // the prefix this pass scans
+    uint64_t rows;           // the prefix this pass scans: the stage's p_st (pass 3: n). ET_LIST: of list ENTRIES, clipped
+                             // to *m in the kernel
     uint32_t row_bytes, row_stride, dim;
     const uint8_t* queries;  // dense [nq][dim] (this round's)
     uint32_t nq, q_lds;      // q_lds: bytes of a staged query (a multiple of 16; int8: zero padded to row_bytes)
-    uint64_t per_range;      // rows per blockIdx.y (a multiple of ET_GROUPS)
+    uint64_t per_range;      // rows per blockIdx.y (a multiple of ET_GROUPS). ET_LIST: not read, the kernel splits what is left
     const uint32_t* bound;   // [nq] keys above it are not counted or collected
     const EtSel* sel;        // [nq] (passes 2 and 3)
     uint32_t* hist;          // pass 1: [nq][ET_BINS1], pass 2: [nq][ET_BINS2]
     uint32_t* cnt;           // pass 3: [nq] keys collected
     uint64_t* cand;          // pass 3: [nq][ET_CAP] distance bits << 32 | id
+    // the sources' own fields. (Last on purpose: between q_lds and bound they change how the kernel's arguments are
+    // loaded, and the f32 memory form's collecting pass then takes 66 VGPRs for 46 -- seven waves per SIMD for eight.)
+    const uint32_t* list;    // ET_LIST: the allowed ids, ascending
+    const uint64_t* m;       // ET_LIST: how many, on the device
+    uint64_t prev_rows;      // ET_LIST: p_{st-1}; 0: no predecessor (stage 0 and pass 3 are never idle)
+    const uint32_t* filter;  // ET_BITS: the queries' bitmaps (this round's first)
+    uint64_t filter_stride;  // ET_BITS: words from one query's bitmap to the next
 };
 
 // A group's row. NBLK > 0: its 128-byte blocks in registers, lane `sub` holding the 16-byte piece `sub` of each (pieces
@@ -195,13 +226,21 @@ __device__ __forceinline__ float et_dist(const EtRow<I8, NBLK>& R, const uint8_t
     }
 }
 
-// One pass over rows [0, P.rows): grid = (query tiles of ET_QT, row ranges). PASS 1 counts first-level bins, PASS 2 the
-// second-level bins inside sel.b1 of the queries that need them, PASS 3 collects the keys at or below the bound.
-template <bool I8, int NBLK, int PASS>
+// One pass over the rows (ET_LIST: the list's entries) [0, P.rows): grid = (query tiles of ET_QT, row ranges). PASS 1
+// counts first-level bins, PASS 2 the second-level bins inside sel.b1 of the queries that need them, PASS 3 collects the
+// keys at or below the bound. SRC: where a row index comes from, whether a pair is admitted, what the range is clipped to.
+template <bool I8, int NBLK, int PASS, EtSrc SRC>
 __global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
+    static_assert(ET_GROUPS == 32u && ET_QT <= 32u, "a step's rows share one filter word; a wave's lanes 0..31 hold a tile's words");
     extern __shared__ __align__(16) uint8_t smem_et[];
     __shared__ uint32_t s_bound[ET_QT], s_b1[ET_QT], s_on[ET_QT];
     __shared__ int s_dy[ET_QT];
+    uint64_t rows = P.rows;
+    if constexpr (SRC == ET_LIST) {
+        const uint64_t m = *P.m;
+        if (P.prev_rows != 0 && P.prev_rows >= m) return; // an idle stage (the whole grid alike)
+        if (m < rows) rows = m;
+    }
     const uint32_t tid = threadIdx.x, lane = tid & 63u, sub = lane & 7u, grp = tid >> 3;
     const uint32_t q0 = blockIdx.x * ET_QT;
     const uint32_t qn = P.nq - q0 < ET_QT ? P.nq - q0 : ET_QT;
@@ -221,6 +260,15 @@ __global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
         s_bound[tid] = bound, s_b1[tid] = b1, s_on[tid] = on, s_dy[tid] = 0;
     }
     if (!__syncthreads_or((int)on)) return; // no query of the tile takes part in this pass
+    // The range of blockIdx.y, a multiple of ET_GROUPS rows: `rows` split over the G = gridDim.y ranges launched,
+    // ceil(ceil(rows / G) / 32) * 32. ET_ALL, ET_BITS: the host's P.per_range -- this expression over P.rows, raised to 32
+    // for rows == 0, where r1 = 0 and nothing runs whatever the value. ET_LIST: rows was clipped to *m, known here alone.
+    // (The other two could divide here too and drop the field; measured on the 10M-row f32 scan that costs ~0.15 %.)
+    uint64_t per_range = P.per_range;
+    if constexpr (SRC == ET_LIST) per_range = ((rows + gridDim.y - 1) / gridDim.y + ET_GROUPS - 1) / ET_GROUPS * ET_GROUPS;
+    const uint64_t r0 = (uint64_t)blockIdx.y * per_range;
+    const uint64_t r1 = r0 + per_range < rows ? r0 + per_range : rows;
+    if (r0 >= r1) return; // (the ranges past the last row; ET_LIST: past the m entries)
     if constexpr (NBLK > 0) {
         if constexpr (!I8) {
             float* sq = reinterpret_cast<float*>(smem_et);
@@ -248,19 +296,29 @@ __global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
             __syncthreads();
         }
     }
-    const uint64_t r0 = (uint64_t)blockIdx.y * P.per_range;
-    const uint64_t r1 = r0 + P.per_range < P.rows ? r0 + P.per_range : P.rows;
-    for (uint64_t e0 = r0; e0 < r1; e0 += ET_GROUPS) {
+    for (uint64_t e0 = r0; e0 < r1; e0 += ET_GROUPS) { // e0: a multiple of ET_GROUPS = 32 (per_range is one)
         const uint64_t e = e0 + grp;
         const bool live = e < r1;
+        uint64_t row = live ? e : r1 - 1;
+        if constexpr (SRC == ET_LIST) row = P.list[row];
+        uint32_t fw = 0; // ET_BITS: lane l & 31 holds the word of the tile's query l & 31 with this step's 32 rows
+        if constexpr (SRC == ET_BITS) {
+            if ((lane & 31u) < qn) fw = P.filter[(uint64_t)(q0 + (lane & 31u)) * P.filter_stride + (e0 >> 5)];
+        }
         EtRow<I8, NBLK> R;
-        et_load_row<I8, NBLK>(R, P.elements + (live ? e : r1 - 1) * (uint64_t)P.row_stride, P.row_bytes, lane);
+        et_load_row<I8, NBLK>(R, P.elements + row * (uint64_t)P.row_stride, P.row_bytes, lane);
         for (uint32_t qi = 0; qi < qn; ++qi) {
             if (!s_on[qi]) continue;
+            bool allowed = true;
+            if constexpr (SRC == ET_BITS) {
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)fw, (int)qi);
+                if (((w >> ((tid >> 6) * 8u)) & 0xFFu) == 0u) continue; // none of this wave's eight rows: the whole wave skips
+                allowed = (w >> grp) & 1u;
+            }
             const uint8_t* qp = NBLK > 0 ? smem_et + (size_t)qi * P.q_lds
                                          : P.queries + (size_t)(q0 + qi) * P.dim * (I8 ? 1u : 4u);
             const float d = et_dist<I8, NBLK>(R, qp, s_dy[qi], P.dim, P.row_bytes, lane);
-            if (live && sub == 0u) {
+            if (live && allowed && sub == 0u) {
                 const uint32_t key = et_key(d);
                 if (key <= s_bound[qi]) {
                     const size_t q = q0 + qi;
@@ -270,7 +328,7 @@ __global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
                         if ((key >> 11) == s_b1[qi]) atomicAdd(P.hist + q * ET_BINS2 + (key & 2047u), 1u);
                     } else {
                         const uint32_t pos = atomicAdd(P.cnt + q, 1u);
-                        if (pos < ET_CAP) P.cand[q * ET_CAP + pos] = (uint64_t)__float_as_uint(d) << 32 | (uint64_t)(uint32_t)e;
+                        if (pos < ET_CAP) P.cand[q * ET_CAP + pos] = (uint64_t)__float_as_uint(d) << 32 | (uint64_t)(uint32_t)(SRC == ET_LIST ? row : e);
                     }
                 }
             }
@@ -279,46 +337,57 @@ __global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
 }
 
 // One block per query over the histogram of a counting pass: the first bin whose prefix reaches the target, and what
-// follows from it (the header's rule). `final`: the pass ran over all rows -- its verdicts go to the status words.
-template <int LEVEL>
-__global__ __launch_bounds__(256) void et_select_kernel(const uint32_t* hist, uint32_t k, uint64_t rows, uint32_t* bound, EtSel* sel,
-                                                        uint32_t final, uint32_t* status) {
+// follows from it (the header's rule). `rows`: the stage's prefix p_st; `total`: what the pass counted at or below the
+// query's bound; `final`: the pass saw every row there is -- its verdicts go to the status words.
+//   ET_LIST  m (the list's length: *m_ptr; for ET_ALL, served by this instantiation with no m_ptr, m_all = n) and prev_rows
+//            decide whether the stage is idle (nothing is touched) and whether it is final (the header). The target is
+//            min(k, min(p_st, m)): every entry of the prefix is a row that counts.
+//   ET_BITS  `final` is the host's (the last stage scans all n rows). A prefix may hold fewer than k allowed rows of a
+//            query. A bound taken from those -- a key that min(k, allowed rows OF THE PREFIX) rows are at or below -- would
+//            be too tight for a longer prefix, which may hold allowed rows between it and the true k-th key. So a NON-FINAL
+//            stage narrows only on evidence that lasts: total >= k rows of the prefix at or below the new bound are k rows
+//            of every longer prefix too. With total < k it keeps the bound it has. Only the final stage, which has seen
+//            every row, uses target = min(k, total): a bound below all-ones already holds k allowed rows (total >= k), so
+//            total < k means the bound is all-ones and total is every allowed row of the query.
+// A target of 0 (no row that counts) stores an all-zero EtSel and leaves the bound: pass 3 collects nothing, the count is 0.
+// The second level is reached only past ET_CAP > ET_KMAX rows at or below B1: its target is k - below1 for every source.
+template <int LEVEL, EtSrc SRC>
+__global__ __launch_bounds__(256) void et_select_kernel(const uint32_t* hist, uint32_t k, uint64_t rows, uint64_t prev_rows, const uint64_t* m_ptr,
+                                                        uint64_t m_all, uint32_t* bound, EtSel* sel, uint32_t final, uint32_t* status) {
+    static_assert(SRC != ET_ALL, "all rows: the list rule with m = n by value");
     constexpr uint32_t NB = LEVEL == 1 ? ET_BINS1 : ET_BINS2, PER = NB / 256u;
     __shared__ uint32_t s_wave[4];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    if constexpr (SRC == ET_LIST) {
+        const uint64_t m = m_ptr ? *m_ptr : m_all;
+        if (prev_rows != 0 && prev_rows >= m) return; // idle: bound and sel stay the final stage's
+        final = rows >= m ? 1u : 0u;
+        if (m < rows) rows = m;
+    }
     EtSel s = sel[q];
     if constexpr (LEVEL == 2) {
         if (!s.need2) return;
     } else {
         s.b1 = 0, s.below1 = 0, s.need2 = 0, s.over = 0;
     }
-    uint32_t target = rows < k ? (uint32_t)rows : k;
-    if constexpr (LEVEL == 2) target -= s.below1;
     uint32_t c[PER], mine = 0;
 #pragma unroll
     for (uint32_t i = 0; i < PER; ++i) {
         c[i] = hist[(size_t)q * NB + tid * PER + i];
         mine += c[i];
     }
-    uint32_t incl = mine; // inclusive scan over the wave, then over the four waves
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
-        if (lane >= (uint32_t)o) incl += up;
-    }
-    if (lane == 63u) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, total = 0;
-    for (uint32_t w = 0; w < 4; ++w) {
-        if (w < wave) before += s_wave[w];
-        total += s_wave[w];
-    }
-    if (total < target) { // (cannot happen: the bound holds min(k, rows) rows; then nothing is narrowed)
+    uint32_t total;
+    const uint32_t before = fl_block_exclusive<4>(mine, s_wave, &total);
+    uint32_t target;
+    if constexpr (LEVEL == 2) target = k - s.below1;
+    else if constexpr (SRC == ET_LIST) target = rows < k ? (uint32_t)rows : k;
+    else target = final && total < k ? total : k;
+    // nothing that counts, or (ET_BITS, not final) too few allowed rows yet: nothing is narrowed. (ET_LIST: total < target
+    // cannot happen for target > 0 -- the bound holds min(k, rows) entries.)
+    if (target == 0 || total < target) {
         if (tid == 0) {
-            s.over = total > ET_CAP ? 1u : 0u;
             s.need2 = 0;
             sel[q] = s;
-            if (s.over && final && status) atomicAdd(status + 0, 1u);
         }
         return;
     }
@@ -391,17 +460,30 @@ __global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t
 }
 
 typedef void (*EtScanFn)(const EtParams);
-template <bool I8, int NBLK>
+template <bool I8, int NBLK, EtSrc SRC>
 inline EtScanFn et_scan_pass(int pass) {
-    return pass == 1 ? et_scan_kernel<I8, NBLK, 1> : pass == 2 ? et_scan_kernel<I8, NBLK, 2> : et_scan_kernel<I8, NBLK, 3>;
+    return pass == 1 ? et_scan_kernel<I8, NBLK, 1, SRC> : pass == 2 ? et_scan_kernel<I8, NBLK, 2, SRC> : et_scan_kernel<I8, NBLK, 3, SRC>;
+}
+template <bool I8, EtSrc SRC>
+inline EtScanFn et_scan_blocks(uint32_t nblk, int pass) {
+    return nblk <= 1 ? et_scan_pass<I8, 1, SRC>(pass) : nblk <= 2 ? et_scan_pass<I8, 2, SRC>(pass) : nblk <= 4 ? et_scan_pass<I8, 4, SRC>(pass)
+         : nblk <= 8 ? et_scan_pass<I8, 8, SRC>(pass) : et_scan_pass<I8, 0, SRC>(pass);
+}
+template <bool I8>
+inline EtScanFn et_scan_src(uint32_t nblk, int pass, EtSrc src) {
+    return src == ET_ALL ? et_scan_blocks<I8, ET_ALL>(nblk, pass) : src == ET_LIST ? et_scan_blocks<I8, ET_LIST>(nblk, pass)
+                                                                                    : et_scan_blocks<I8, ET_BITS>(nblk, pass);
 }
 // the pass's kernel for device rows of row_bytes: the fewest register blocks that hold the row, or the memory form
-inline EtScanFn et_scan_fn(bool i8, uint32_t row_bytes, int pass) {
+inline EtScanFn et_scan_fn(bool i8, uint32_t row_bytes, int pass, EtSrc src) {
     const uint32_t nblk = (row_bytes + 127u) / 128u;
-    if (i8) return nblk <= 1 ? et_scan_pass<true, 1>(pass) : nblk <= 2 ? et_scan_pass<true, 2>(pass) : nblk <= 4 ? et_scan_pass<true, 4>(pass)
-                 : nblk <= 8 ? et_scan_pass<true, 8>(pass) : et_scan_pass<true, 0>(pass);
-    return nblk <= 1 ? et_scan_pass<false, 1>(pass) : nblk <= 2 ? et_scan_pass<false, 2>(pass) : nblk <= 4 ? et_scan_pass<false, 4>(pass)
-         : nblk <= 8 ? et_scan_pass<false, 8>(pass) : et_scan_pass<false, 0>(pass);
+    return i8 ? et_scan_src<true>(nblk, pass, src) : et_scan_src<false>(nblk, pass, src);
+}
+// the level's select for the source: ET_ALL is served by the list rule (et_select_kernel)
+typedef void (*EtSelectFn)(const uint32_t*, uint32_t, uint64_t, uint64_t, const uint64_t*, uint64_t, uint32_t*, EtSel*, uint32_t, uint32_t*);
+inline EtSelectFn et_select_fn(int level, EtSrc src) {
+    if (src == ET_BITS) return level == 1 ? et_select_kernel<1, ET_BITS> : et_select_kernel<2, ET_BITS>;
+    return level == 1 ? et_select_kernel<1, ET_LIST> : et_select_kernel<2, ET_LIST>;
 }
 
 } // namespace granne_hip

@@ -21,9 +21,9 @@
 //
 // This file holds the filter's own pieces: the view a walker tests bits through, the second (disallowed) queue of the
 // general walker (search_kernel.h, Walker<.., FILT = true>) with the rule by which it may drop a key, and the kernels that
-// make and count bitmaps. The exact walker's part is in slow_kernel.h. The register walkers (walk_fast.h) have no filtered
-// form: they keep no visited set and find a seen candidate by its rank in one list of max_search keys, which does not
-// survive keys that are expanded but may not be returned.
+// make, count and list bitmaps. The exact walker's part is in slow_kernel.h. The register walkers (walk_fast.h) have no
+// filtered form: they keep no visited set and find a seen candidate by its rank in one list of max_search keys, which
+// does not survive keys that are expanded but may not be returned.
 #pragma once
 
 #include "wave_prims.h"
@@ -105,6 +105,106 @@ __global__ __launch_bounds__(256) void filter_count_kernel(const uint32_t* __res
     }
     for (int o = 32; o > 0; o >>= 1) mine += (uint32_t)__shfl_xor((int)mine, o, 64);
     if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(out, (unsigned long long)mine);
+}
+
+// ---- bitmap -> ascending id list (granne_hip_filter_to_ids_device; the exact scan's list source, exact_topk.h) -------
+// per-block popcounts (fl_count_kernel), one block scanning them (fl_scan_kernel), a scatter (fl_scatter_kernel)
+constexpr uint32_t FL_THREADS = 256, FL_PER = 8;             // words per thread, contiguous: ids come out in order
+constexpr uint32_t FL_BLOCK_WORDS = FL_THREADS * FL_PER;     // 2048 words, 65536 ids per block
+constexpr uint32_t FL_SCAN_THREADS = 1024;
+constexpr uint64_t FL_MAX_BLOCKS = 65536;                    // n up to 2^32 - 1: 2^27 words, one block's scan
+
+__host__ __device__ inline uint64_t fl_blocks(uint64_t n) { return (filter_words(n) + FL_BLOCK_WORDS - 1) / FL_BLOCK_WORDS; }
+
+// word w of the bitmap over n ids, bits at positions >= n (and words past the last) as zeros
+__device__ __forceinline__ uint32_t fl_word(const uint32_t* __restrict__ filter, uint64_t w, uint64_t n) {
+    const uint64_t words = filter_words(n);
+    if (w >= words) return 0u;
+    uint32_t v = filter[w];
+    const uint32_t tail = (uint32_t)(n & 31u);
+    if (w + 1 == words && tail) v &= (1u << tail) - 1u;
+    return v;
+}
+
+// exclusive prefix of `mine` over a block of WAVES waves (every thread calls it); *total: the block's sum
+template <int WAVES, typename T>
+__device__ __forceinline__ T fl_block_exclusive(T mine, T* s_wave, T* total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    T incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(incl, o, 64);
+        if (lane >= (uint32_t)o) incl += up;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    T before = incl - mine, sum = 0;
+    for (uint32_t w = 0; w < (uint32_t)WAVES; ++w) {
+        if (w < wave) before += s_wave[w];
+        sum += s_wave[w];
+    }
+    *total = sum;
+    return before;
+}
+
+// counts[b]: the set bits among block b's FL_BLOCK_WORDS words. grid = fl_blocks(n)
+__global__ __launch_bounds__(FL_THREADS) void fl_count_kernel(const uint32_t* __restrict__ filter, uint64_t n, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t s_wave[FL_THREADS / 64];
+    const uint64_t w0 = (uint64_t)blockIdx.x * FL_BLOCK_WORDS + threadIdx.x * FL_PER;
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < FL_PER; ++i) mine += (uint32_t)__popc(fl_word(filter, w0 + i, n));
+    uint32_t total;
+    (void)fl_block_exclusive<FL_THREADS / 64>(mine, s_wave, &total);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// one block: counts[0 .. blocks) become their exclusive prefix sums in place (each below 2^32: at most 2^32 - 1 ids); the
+// total goes to *out_count and, where asked for, to *out_count32 (the scan's status[3])
+__global__ __launch_bounds__(FL_SCAN_THREADS) void fl_scan_kernel(uint32_t* __restrict__ counts, uint32_t blocks, uint64_t* __restrict__ out_count,
+                                                                  uint32_t* out_count32) {
+    __shared__ uint64_t s_wave[FL_SCAN_THREADS / 64];
+    const uint32_t per = (blocks + FL_SCAN_THREADS - 1) / FL_SCAN_THREADS;
+    const uint32_t b0 = threadIdx.x * per < blocks ? threadIdx.x * per : blocks;
+    const uint32_t b1 = b0 + per < blocks ? b0 + per : blocks;
+    uint64_t mine = 0;
+    for (uint32_t b = b0; b < b1; ++b) mine += counts[b];
+    uint64_t total;
+    uint64_t at = fl_block_exclusive<FL_SCAN_THREADS / 64>(mine, s_wave, &total);
+    for (uint32_t b = b0; b < b1; ++b) { // (a thread rewrites only what it alone read)
+        const uint32_t c = counts[b];
+        counts[b] = (uint32_t)at;
+        at += c;
+    }
+    if (threadIdx.x == 0) {
+        *out_count = total;
+        if (out_count32) *out_count32 = (uint32_t)total;
+    }
+}
+
+// block b writes its ids, ascending, from out[offsets[b]] on. grid = fl_blocks(n)
+template <typename ID>
+__global__ __launch_bounds__(FL_THREADS) void fl_scatter_kernel(const uint32_t* __restrict__ filter, uint64_t n, const uint32_t* __restrict__ offsets,
+                                                                ID* __restrict__ out) {
+    __shared__ uint32_t s_wave[FL_THREADS / 64];
+    const uint64_t w0 = (uint64_t)blockIdx.x * FL_BLOCK_WORDS + threadIdx.x * FL_PER;
+    uint32_t v[FL_PER], mine = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < FL_PER; ++i) {
+        v[i] = fl_word(filter, w0 + i, n);
+        mine += (uint32_t)__popc(v[i]);
+    }
+    uint32_t total;
+    uint64_t pos = (uint64_t)offsets[blockIdx.x] + fl_block_exclusive<FL_THREADS / 64>(mine, s_wave, &total);
+#pragma unroll
+    for (uint32_t i = 0; i < FL_PER; ++i) {
+        uint32_t w = v[i];
+        while (w) { // (set bits only below n: pos stays below the count, the count at most n)
+            const uint32_t b = (uint32_t)__ffs((int)w) - 1u;
+            out[pos++] = (ID)(((w0 + i) << 5) + b);
+            w &= w - 1u;
+        }
+    }
 }
 
 } // namespace granne_hip

@@ -2263,142 +2263,6 @@ extern "C" int granne_hip_brute_force(const granne_hip_index* ix, const void* qu
     return GRANNE_HIP_OK;
 }
 
-// exact k nearest elements in the reference's arithmetic, selected by (distance bits, id) (exact_topk.h)
-static int exact_topk_args(const granne_hip_index* ix, uint32_t nq, uint32_t k, bool buffers) {
-    if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
-    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "exact_topk");
-    GRANNE_HIP_F16_UNSUPPORTED(ix->dtype, "exact_topk");
-    if (nq == 0) return GRANNE_HIP_OK;
-    if (!buffers) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
-    if (k == 0 || k > ET_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "k must be in [1, %u]", ET_KMAX);
-    if (ix->n_elements > 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "exact_topk takes up to 2^32 - 1 elements");
-    return GRANNE_HIP_OK;
-}
-
-extern "C" int granne_hip_exact_topk_device(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k,
-                                            uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status,
-                                            void* stream) {
-    if (const int rc = exact_topk_args(ix, nq, k, d_queries && d_out_ids && d_out_dists && d_out_counts)) return rc;
-    if (nq == 0) return GRANNE_HIP_OK;
-    GRANNE_HIP_ON_DEVICE(ix->device);
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t n = ix->n_elements;
-    const bool i8 = ix->dtype == GRANNE_HIP_I8;
-    const uint32_t qc_max = nq < ET_CHUNK ? nq : ET_CHUNK;
-    // the prefixes the selection runs over, shortest first, the last one all rows (exact_topk.h, priming)
-    uint64_t prefix[16];
-    uint32_t stages = 0;
-    {
-        uint64_t rev[16], p = n;
-        uint32_t m = 0;
-        rev[m++] = p;
-        while (p > 2ull * ET_PRIME_MIN && m < 16) {
-            p /= ET_PRIME_STEP;
-            if (p < ET_PRIME_MIN) p = ET_PRIME_MIN;
-            rev[m++] = p;
-        }
-        while (m) prefix[stages++] = rev[--m];
-    }
-    // scratch: the candidates [qc][ET_CAP] u64 -- the two histograms live in the same bytes, dead before the keys are
-    // collected -- then bound [qc], sel [qc], cnt [qc]
-    const size_t o_big = 0, big = (size_t)qc_max * ET_CAP * 8;
-    static_assert((ET_BINS1 + ET_BINS2) * 4u <= ET_CAP * 8u, "the histograms fit in the candidates' bytes");
-    const size_t o_bound = o_big + big, o_sel = o_bound + (size_t)qc_max * 4, o_cnt = o_sel + (size_t)qc_max * sizeof(EtSel);
-    const size_t total = o_cnt + (size_t)qc_max * 4;
-    uint8_t* scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
-    struct Release {
-        void* p;
-        hipStream_t s;
-        ~Release() { (void)hipFreeAsync(p, s); }
-    } release{scratch, s};
-    const size_t qbytes = (size_t)ix->dim * query_elem_size(ix->dtype);
-    const bool resident = ix->row_bytes <= 1024u;
-    EtParams P;
-    P.elements = ix->d_elements.as<uint8_t>();
-    P.row_bytes = ix->row_bytes;
-    P.row_stride = ix->row_stride;
-    P.dim = ix->dim;
-    P.q_lds = resident ? ix->row_bytes : 0u;
-    P.bound = (const uint32_t*)(scratch + o_bound);
-    P.sel = (const EtSel*)(scratch + o_sel);
-    P.cnt = (uint32_t*)(scratch + o_cnt);
-    P.cand = (uint64_t*)(scratch + o_big);
-    uint32_t* const hist1 = (uint32_t*)(scratch + o_big);
-    const uint32_t lds = ET_QT * P.q_lds;
-    for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
-        const uint32_t qc = nq - c0 < ET_CHUNK ? nq - c0 : ET_CHUNK;
-        uint32_t* const hist2 = hist1 + (size_t)qc * ET_BINS1;
-        const uint32_t tiles = (qc + ET_QT - 1) / ET_QT;
-        P.queries = (const uint8_t*)d_queries + (size_t)c0 * qbytes;
-        P.nq = qc;
-        auto pass = [&](int which, uint64_t rows) -> int {
-            uint64_t G = (rows + ET_GROUPS - 1) / ET_GROUPS;
-            const uint64_t most = 2048u / tiles ? 2048u / tiles : 1u; // ~8 blocks per compute unit
-            if (G > most) G = most;
-            if (G < 1) G = 1;
-            P.rows = rows;
-            P.per_range = ((rows + G - 1) / G + ET_GROUPS - 1) / ET_GROUPS * ET_GROUPS;
-            if (P.per_range < ET_GROUPS) P.per_range = ET_GROUPS;
-            P.hist = which == 1 ? hist1 : hist2;
-            hipLaunchKernelGGL(et_scan_fn(i8, ix->row_bytes, which), dim3(tiles, (uint32_t)G), dim3(ET_THREADS), lds, s, P);
-            HIP_TRY(hipGetLastError());
-            return GRANNE_HIP_OK;
-        };
-        HIP_TRY(hipMemsetAsync(scratch + o_bound, 0xFF, (size_t)qc * 4, s));
-        for (uint32_t st = 0; st < stages; ++st) {
-            const uint32_t final = st + 1 == stages ? 1u : 0u;
-            HIP_TRY(hipMemsetAsync(hist1, 0, (size_t)qc * (ET_BINS1 + ET_BINS2) * 4, s));
-            if (const int rc = pass(1, prefix[st])) return rc;
-            hipLaunchKernelGGL(et_select_kernel<1>, dim3(qc), dim3(256), 0, s, (const uint32_t*)hist1, k, prefix[st],
-                               (uint32_t*)(scratch + o_bound), (EtSel*)(scratch + o_sel), final, d_status);
-            HIP_TRY(hipGetLastError());
-            if (const int rc = pass(2, prefix[st])) return rc;
-            hipLaunchKernelGGL(et_select_kernel<2>, dim3(qc), dim3(256), 0, s, (const uint32_t*)hist2, k, prefix[st],
-                               (uint32_t*)(scratch + o_bound), (EtSel*)(scratch + o_sel), final, d_status);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemsetAsync(scratch + o_cnt, 0, (size_t)qc * 4, s));
-        if (const int rc = pass(3, n)) return rc;
-        hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_big),
-                           (const uint32_t*)(scratch + o_cnt), (const EtSel*)(scratch + o_sel), k, d_out_ids + (size_t)c0 * k,
-                           d_out_dists + (size_t)c0 * k, d_out_counts + c0, d_status);
-        HIP_TRY(hipGetLastError());
-    }
-    return GRANNE_HIP_OK;
-}
-
-// host convenience over the exact selection: host buffers in and out
-extern "C" int granne_hip_exact_topk(const granne_hip_index* ix, const void* queries, uint32_t nq, uint32_t k, uint64_t* out_ids,
-                                     float* out_dists, uint32_t* out_counts, uint32_t* out_status) {
-    if (const int rc = exact_topk_args(ix, nq, k, queries && out_ids && out_dists && out_counts)) return rc;
-    if (nq == 0) return GRANNE_HIP_OK;
-    GRANNE_HIP_ON_DEVICE(ix->device);
-    const size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
-    const size_t o_ids = (qb + 255) & ~(size_t)255, o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + (((size_t)nq * k * 4 + 15) & ~(size_t)15);
-    const size_t o_st = o_c + (((size_t)nq * 4 + 15) & ~(size_t)15), total = o_st + 16;
-    DevBuf block;
-    HIP_TRY(block.alloc(total));
-    struct Settle { // (declared after the block: whatever the passes left running is over before the block is freed)
-        ~Settle() { (void)hipDeviceSynchronize(); }
-    } settle;
-    uint8_t* const buf = block.as<uint8_t>();
-    HIP_TRY(hipMemcpy(buf, queries, qb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(buf + o_st, 0, 16));
-    const int rc = granne_hip_exact_topk_device(ix, buf, nq, k, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c),
-                                                (uint32_t*)(buf + o_st), nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    uint32_t st[4];
-    HIP_TRY(hipMemcpy(out_ids, buf + o_ids, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_dists, buf + o_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_counts, buf + o_c, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(st, buf + o_st, 16, hipMemcpyDeviceToHost));
-    if (out_status) memcpy(out_status, st, 16);
-    if (st[0]) return fail(GRANNE_HIP_ERR_OVERFLOW, "exact_topk: %u queries have more than %u rows inside one second-level bin at their k-th distance", st[0], ET_CAP);
-    return GRANNE_HIP_OK;
-}
-
 extern "C" int granne_hip_synth_rows_device(float* d_out, uint64_t seed, uint64_t row0, uint64_t n, uint32_t dim,
                                             int device_id, void* stream) {
     if (!d_out && n) return fail(GRANNE_HIP_ERR_INVALID, "out is null");
@@ -2601,6 +2465,6 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 #include "filter_host.h"
 
 // ------------------------------------------------------------------------------------------------
-// the exact scan under an id bitmap: a bitmap's ids, exact_topk over the allowed rows
+// the exact selection: exact_topk over all rows or the rows an id bitmap allows; a bitmap's ids
 // ------------------------------------------------------------------------------------------------
-#include "exact_topk_filtered_host.h"
+#include "exact_topk_host.h"

@@ -1,4 +1,4 @@
-"""The host model of exact_topk_filtered (granne_amd/csrc/exact_topk_filtered.h; test infrastructure, a plain module like
+"""The host model of exact_topk_filtered (granne_amd/csrc/exact_topk.h, sources; test infrastructure, a plain module like
 tests/exact_topk_model.py, whose bins, key and two-level rule it reuses):
 
   * the selection over a subset: exact_topk_model.select on the allowed rows' distances, mapped back to global ids;
@@ -77,7 +77,7 @@ def narrow_target(total, k, final, naive=False):
 
 
 def staged_select(dists, mask, k, naive=False):
-    """The per-query form on one query: the bound through every stage (both levels, as etf_select_kernel narrows it), then
+    """The per-query form on one query: the bound through every stage (both levels, as et_select_kernel narrows it), then
     the allowed rows at or below it ranked by (distance bits, id). Returns (global ids, overflow)."""
     d = np.ascontiguousarray(dists, np.float32)
     mask = np.asarray(mask, bool)
