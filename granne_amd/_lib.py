@@ -35,6 +35,7 @@ SEARCH_DEPTH_MAX = 16  # GRANNE_HIP_SEARCH_DEPTH_MAX
 SHARDED_OPT_DEPTH, SHARDED_OPT_EXCHANGE = 1, 2
 SHARDED_EXCHANGE_PEER, SHARDED_EXCHANGE_RCCL = 0, 1
 RW_OPT_SMALL_OPS, RW_OPT_SMALL_LAUNCHES, RW_OPT_SORTED_LAUNCHES = 1, 2, 3  # GRANNE_HIP_RW_OPT_*
+RW_OPT_REMOVED, RW_OPT_FILTERED_SEARCHES = 4, 5  # read-only: removed elements; search calls that ran under the tombstones
 RW_SMALL_OPS = 2048  # GRANNE_HIP_RW_SMALL_OPS
 CODEC_STAGING_DEFAULT = 64 << 20  # GRANNE_HIP_CODEC_STAGING_DEFAULT: the device codec's pinned ring (staging_bytes=0)
 CODEC_STAGING_MIN = 64 << 10  # GRANNE_HIP_CODEC_STAGING_MIN: smaller values are raised to it
@@ -223,6 +224,11 @@ SIGNATURES = {
     "granne_hip_rw_builder_get_index": (i32, [vp, C.POINTER(vp)]),
     "granne_hip_rw_builder_set_option": (i32, [vp, i32, u64]),
     "granne_hip_rw_builder_get_option": (i32, [vp, i32, C.POINTER(u64)]),
+    "granne_hip_rw_builder_remove": (i32, [vp, vp, u64, vp]),
+    "granne_hip_rw_builder_restore": (i32, [vp, vp, u64, vp]),
+    "granne_hip_rw_builder_removed_count": (u64, [vp]),
+    "granne_hip_rw_builder_alive": (i32, [vp, vp, vp]),
+    "granne_hip_rw_builder_compact": (i32, [vp, u64, C.POINTER(vp), vp, C.POINTER(u64)]),
     "granne_hip_search_filtered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_search_filtered_batch": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp]),
     "granne_hip_filter_words": (i32, [u64, C.POINTER(u64)]),

@@ -20,6 +20,13 @@
 #include <condition_variable>
 #include <shared_mutex>
 
+#include "rw_tombstone.h"
+
+// bitmap -> ascending ids (exact_topk_host.h, included after this file)
+template <typename ID>
+static int filter_compact(const uint32_t* d_filter, uint64_t n, uint32_t* d_counts, ID* d_out, uint64_t* d_count, uint32_t* d_count32,
+                          hipStream_t s);
+
 static_assert(RW_SMALL_OPS == GRANNE_HIP_RW_SMALL_OPS, "the header quotes the kernel's constant");
 
 // The handle's reader-writer lock. Writers go first: a search that arrives while an insert waits queues behind it, so
@@ -58,7 +65,7 @@ struct granne_hip_rw_builder {
     granne_hip_builder* b = nullptr;
     uint64_t max_elements = 0;
     uint64_t elem_cap = 0;
-    // insert / promotion hold it exclusively, everything that reads holds it shared, for the whole call
+    // insert / promotion / remove / restore hold it exclusively, everything that reads holds it shared, for the whole call
     RwGate mu;
     hipStream_t stream = nullptr; // inserts
     BuildScratch S;               // sized for batch_cap members (d_layers and selected stay empty in it: they are below)
@@ -68,6 +75,14 @@ struct granne_hip_rw_builder {
     DevBuf d_stage;  // dense rows of an insert call on their way into the element rows
     uint64_t opt_small_ops = RW_SMALL_OPS;
     std::atomic<uint64_t> small_launches{0}, sorted_launches{0};
+    // tombstones (rw_tombstone.h): one bit per element slot, one = alive, all ones when the handle is
+    // made. `removed` counts the zero bits below len; while it is 0 a search is the unfiltered launch it always was.
+    // The insert path never looks at either.
+    DevBuf alive;     // uint32_t [filter_words(elem_cap)]
+    DevBuf d_mark;    // a remove / restore call's counters (u64 [4]), then its ids
+    uint64_t removed = 0;
+    std::atomic<uint64_t> filtered_searches{0};
+    hipEvent_t alive_read = nullptr; // rw_builder_alive: the caller's copy of the bitmap, which the next writer waits for
     // host-pointer searches: a stream and a device buffer per concurrent caller, kept for the life of the handle
     std::mutex call_mu;
     std::vector<granne_hip_index::HostCall*> call_free;
@@ -82,6 +97,7 @@ static void rw_destroy(granne_hip_rw_builder* rw) {
             (void)hipStreamSynchronize(rw->stream);
             (void)hipStreamDestroy(rw->stream);
         }
+        if (rw->alive_read) (void)hipEventDestroy(rw->alive_read);
         for (auto* c : rw->call_free) {
             if (c->stream) (void)hipStreamDestroy(c->stream);
             delete c;
@@ -169,6 +185,9 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
         const size_t eb = (size_t)rw->elem_cap * b->row_stride;
         HIP_TRY(grown.alloc(eb));
         HIP_TRY(hipMemsetAsync(grown.get(), 0, eb, rw->stream));
+        HIP_TRY(rw->alive.alloc((size_t)filter_words(rw->elem_cap) * 4));
+        HIP_TRY(hipMemsetAsync(rw->alive.get(), 0xFF, (size_t)filter_words(rw->elem_cap) * 4, rw->stream));
+        HIP_TRY(hipEventCreateWithFlags(&rw->alive_read, hipEventDisableTiming));
         if (n) HIP_TRY(hipMemcpyAsync(grown.get(), b->d_elements.get(), (size_t)n * b->row_stride, hipMemcpyDeviceToDevice, rw->stream));
         HIP_TRY(hipStreamSynchronize(rw->stream));
         // builder.layers.pop() or an empty layer, resized to max(len, compute_num_elements_in_layer(max_elements,
@@ -192,7 +211,7 @@ extern "C" int granne_hip_rw_builder_create(granne_hip_rw_builder** out, granne_
     // from here on the builder is the handle's
     rw->b = b;
     rw->max_elements = max_elements;
-    b->hbm_bytes += (size_t)(rw->elem_cap - n) * b->row_stride;
+    b->hbm_bytes += (size_t)(rw->elem_cap - n) * b->row_stride + (size_t)filter_words(rw->elem_cap) * 4;
     b->d_elements = std::move(grown);
     if (!b->layers.empty()) {
         b->hbm_bytes -= (size_t)b->layers.back().cap_rows * b->W * 4;
@@ -468,6 +487,10 @@ extern "C" int granne_hip_rw_builder_search_batch(granne_hip_rw_builder* rw, con
     call.stats = (uint64_t*)(buf + o_s);
     call.status = (uint32_t*)(buf + o_st);
     call.stream = s;
+    if (rw->removed != 0) { // the walk under the tombstones (filter.h): removed nodes are traversed, never returned
+        call.filter = rw->alive.as<uint32_t>();
+        rw->filtered_searches.fetch_add(1);
+    }
     int r = search_launch(T, call);
     if (r) return r;
     uint32_t st[4] = {0, 0, 0, 0};
@@ -517,6 +540,144 @@ extern "C" int granne_hip_rw_builder_get_element(granne_hip_rw_builder* rw, uint
     if (idx >= b->n_elements) return fail(GRANNE_HIP_ERR_INVALID, "element index out of range");
     DeviceGuard g(b->device);
     HIP_TRY(hipMemcpy(out, b->d_elements.as<uint8_t>() + idx * b->row_stride, (size_t)b->dim * elem_size(b->dtype), hipMemcpyDeviceToHost));
+    return GRANNE_HIP_OK;
+}
+
+// ---- tombstones (no reference counterpart) -----------------------------------------
+// remove (clear the bits) or restore (set them): out_counts = changed, already so, out of range
+static int rw_mark(granne_hip_rw_builder* rw, const uint64_t* ids, uint64_t n, uint64_t* out_counts, bool remove) {
+    const char* name = remove ? "rw_builder_remove" : "rw_builder_restore";
+    if (!rw) return fail(GRANNE_HIP_ERR_INVALID, "%s: rw builder is null", name);
+    if (!out_counts) return fail(GRANNE_HIP_ERR_INVALID, "%s: out_counts is null", name);
+    out_counts[0] = out_counts[1] = out_counts[2] = 0;
+    if (n == 0) return GRANNE_HIP_OK;
+    if (!ids) return fail(GRANNE_HIP_ERR_INVALID, "%s: ids is null", name);
+    if (n > (1ull << 40)) return fail(GRANNE_HIP_ERR_INVALID, "%s: at most 2^40 ids per call", name);
+    std::unique_lock<RwGate> lk(rw->mu);
+    const granne_hip_builder* b = rw->b;
+    GRANNE_HIP_ON_DEVICE(b->device);
+    hipStream_t s = rw->stream;
+    constexpr size_t head = 32; // the counters
+    if (rw->d_mark.capacity() < head + (size_t)n * 8) {
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(rw->d_mark.reserve(head + (size_t)n * 8));
+    }
+    unsigned long long* d_counters = rw->d_mark.as<unsigned long long>();
+    uint64_t* d_ids = (uint64_t*)(rw->d_mark.as<uint8_t>() + head);
+    HIP_TRY(hipMemsetAsync(d_counters, 0, head, s));
+    HIP_TRY(hipMemcpyAsync(d_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    auto kernel = remove ? tomb_mark_kernel<true> : tomb_mark_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint64_t*)d_ids, n, b->n_elements, rw->alive.as<uint32_t>(),
+                       d_counters);
+    HIP_TRY(hipGetLastError());
+    unsigned long long hc[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(hc, d_counters, sizeof(hc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    rw->removed = remove ? rw->removed + hc[0] : rw->removed - hc[0];
+    out_counts[0] = hc[0], out_counts[1] = hc[1], out_counts[2] = hc[2];
+    return GRANNE_HIP_OK;
+}
+extern "C" int granne_hip_rw_builder_remove(granne_hip_rw_builder* rw, const uint64_t* ids, uint64_t n, uint64_t* out_counts) {
+    return rw_mark(rw, ids, n, out_counts, true);
+}
+extern "C" int granne_hip_rw_builder_restore(granne_hip_rw_builder* rw, const uint64_t* ids, uint64_t n, uint64_t* out_counts) {
+    return rw_mark(rw, ids, n, out_counts, false);
+}
+extern "C" uint64_t granne_hip_rw_builder_removed_count(granne_hip_rw_builder* rw) {
+    if (!rw) return 0;
+    std::shared_lock<RwGate> lk(rw->mu);
+    return rw->removed;
+}
+
+// a copy of the bitmap's first filter_words(len) words, ordered on the caller's stream
+extern "C" int granne_hip_rw_builder_alive(granne_hip_rw_builder* rw, uint32_t* d_filter_out, void* stream) {
+    if (!rw || !d_filter_out) return fail(GRANNE_HIP_ERR_INVALID, "rw_builder_alive: null argument");
+    std::shared_lock<RwGate> lk(rw->mu);
+    const granne_hip_builder* b = rw->b;
+    if (b->n_elements == 0) return GRANNE_HIP_OK;
+    GRANNE_HIP_ON_DEVICE(b->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(d_filter_out, rw->alive.get(), (size_t)filter_words(b->n_elements) * 4, hipMemcpyDeviceToDevice, s));
+    // the copy may still be waiting on the caller's stream when the gate opens: whatever the handle's own stream runs next
+    // -- a remove or restore among it -- waits for it
+    std::lock_guard<std::mutex> ev(rw->call_mu);
+    HIP_TRY(hipEventRecord(rw->alive_read, s));
+    HIP_TRY(hipStreamWaitEvent(rw->stream, rw->alive_read, 0));
+    return GRANNE_HIP_OK;
+}
+
+// the surviving rows, ascending by old id, as a new handle built by the bulk path under this one's config
+extern "C" int granne_hip_rw_builder_compact(granne_hip_rw_builder* rw, uint64_t max_elements, granne_hip_rw_builder** out_rw,
+                                             uint64_t* out_old_ids, uint64_t* out_count) {
+    if (out_rw) *out_rw = nullptr;
+    if (out_count) *out_count = 0;
+    if (!rw || !out_rw || !out_old_ids || !out_count) return fail(GRANNE_HIP_ERR_INVALID, "rw_builder_compact: null argument");
+    if (max_elements == 0) return fail(GRANNE_HIP_ERR_INVALID, "rw_builder_compact: max_elements must be > 0");
+    if (max_elements >= 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "rw_builder_compact: max_elements must be < 2^32 - 1 (src/index/mod.rs:420)");
+    std::shared_lock<RwGate> lk(rw->mu);
+    const granne_hip_builder* b = rw->b;
+    GRANNE_HIP_ON_DEVICE(b->device);
+    const granne_hip_build_config cfg = b->cfg; // (rw_builder_create sets expected_num_elements to the new max_elements)
+    const uint32_t dim = b->dim;
+    const int dtype = b->dtype, device = b->device;
+    const uint64_t n = b->n_elements;
+    const uint32_t dense = dim * (uint32_t)elem_size(dtype);
+    granne_hip_index::HostCall* c = rw_call_acquire(rw);
+    if (!c) return fail(GRANNE_HIP_ERR_HIP, "cannot create a stream");
+    struct Release { // (as search_batch's)
+        granne_hip_rw_builder* rw;
+        granne_hip_index::HostCall* c;
+        ~Release() {
+            (void)hipStreamSynchronize(c->stream);
+            std::lock_guard<std::mutex> lk(rw->call_mu);
+            rw->call_free.push_back(c);
+        }
+    } release{rw, c};
+    hipStream_t s = c->stream;
+    DevBuf d_ids, d_counts, d_count, d_dense;
+    SettleStream settle{s}; // (declared after the four: the stream is idle before an early return frees them)
+    uint64_t m = 0;
+    std::vector<uint32_t> h_ids;
+    if (n) {
+        HIP_TRY(d_ids.alloc((size_t)n * 4));
+        HIP_TRY(d_counts.alloc((size_t)fl_blocks(n) * 4));
+        HIP_TRY(d_count.alloc(8));
+        int rc = filter_compact<uint32_t>(rw->alive.as<uint32_t>(), n, d_counts.as<uint32_t>(), d_ids.as<uint32_t>(), d_count.as<uint64_t>(), nullptr, s);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(&m, d_count.get(), 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m > n) return fail(GRANNE_HIP_ERR_HIP, "rw_builder_compact: %llu survivors of %llu elements", (unsigned long long)m, (unsigned long long)n);
+    }
+    if (m) {
+        HIP_TRY(d_dense.alloc((size_t)m * dense));
+        const uint8_t* rows = b->d_elements.as<uint8_t>();
+        const uint32_t* ids = d_ids.as<uint32_t>();
+        uint8_t* out = d_dense.as<uint8_t>();
+        if (dense % 16u == 0)
+            hipLaunchKernelGGL(gather_dense_rows_kernel<uint4>, dim3(grid_for(m * (dense / 16u), 256)), dim3(256), 0, s, rows, b->row_stride, ids, m, dense, out);
+        else if (dense % 4u == 0)
+            hipLaunchKernelGGL(gather_dense_rows_kernel<uint32_t>, dim3(grid_for(m * (dense / 4u), 256)), dim3(256), 0, s, rows, b->row_stride, ids, m, dense, out);
+        else
+            hipLaunchKernelGGL(gather_dense_rows_kernel<uint8_t>, dim3(grid_for(m * dense, 256)), dim3(256), 0, s, rows, b->row_stride, ids, m, dense, out);
+        HIP_TRY(hipGetLastError());
+        h_ids.resize(m);
+        HIP_TRY(hipMemcpyAsync(h_ids.data(), ids, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    lk.unlock(); // the rows are gathered: the source goes on while the new graph is built
+    granne_hip_builder* nb = nullptr;
+    int rc = granne_hip_builder_create_device(&nb, &cfg, m ? d_dense.get() : nullptr, m, dim, dtype, device, s); // synchronises
+    if (rc) return rc;
+    d_dense.reset();
+    granne_hip_rw_builder* made = nullptr;
+    rc = granne_hip_rw_builder_create(&made, nb, max_elements);
+    if (rc) {
+        destroy_builder(nb);
+        return rc;
+    }
+    for (uint64_t i = 0; i < m; ++i) out_old_ids[i] = h_ids[i];
+    *out_count = m;
+    *out_rw = made;
     return GRANNE_HIP_OK;
 }
 
@@ -574,6 +735,8 @@ extern "C" int granne_hip_rw_builder_get_option(granne_hip_rw_builder* rw, int o
     case GRANNE_HIP_RW_OPT_SMALL_OPS: *value = rw->opt_small_ops; return GRANNE_HIP_OK;
     case GRANNE_HIP_RW_OPT_SMALL_LAUNCHES: *value = rw->small_launches.load(); return GRANNE_HIP_OK;
     case GRANNE_HIP_RW_OPT_SORTED_LAUNCHES: *value = rw->sorted_launches.load(); return GRANNE_HIP_OK;
+    case GRANNE_HIP_RW_OPT_REMOVED: *value = rw->removed; return GRANNE_HIP_OK;
+    case GRANNE_HIP_RW_OPT_FILTERED_SEARCHES: *value = rw->filtered_searches.load(); return GRANNE_HIP_OK;
     }
     return fail(GRANNE_HIP_ERR_INVALID, "unknown option %d", option);
 }

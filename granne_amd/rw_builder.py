@@ -74,9 +74,10 @@ class RwGranneBuilder:
         return int(ids[0]) if len(ids) else None
 
     # ---- search (rw/mod.rs:184-207) ---------------------------------------------------------------
-    def search_batch(self, elements, max_search=DEFAULT_MAX_SEARCH, num_neighbors=DEFAULT_NUM_ELEMENTS):
-        """ids [nq,k] uint64, dists [nq,k] float32, counts [nq] uint32. Without a previous layer every result is empty
-        (the reference's behaviour, rw/mod.rs:198-206)."""
+    def search_batch(self, elements, max_search=DEFAULT_MAX_SEARCH, num_neighbors=DEFAULT_NUM_ELEMENTS, stats=False):
+        """ids [nq,k] uint64, dists [nq,k] float32, counts [nq] uint32 (and stats [nq,3] uint64 = n_dist, n_expand, n_adj
+        when stats=True). Without a previous layer every result is empty (the reference's behaviour, rw/mod.rs:198-206).
+        Removed elements are never returned (`remove`)."""
         q = np.asarray(elements)
         if q.ndim != 2 or (self.dim is not None and q.shape[1] != self.dim):
             raise ValueError("queries must be [nq, %s]" % self.dim)
@@ -84,16 +85,65 @@ class RwGranneBuilder:
         ids = np.full((nq, max(k, 0)), np.iinfo(np.uint64).max, np.uint64)
         dists = np.full((nq, max(k, 0)), np.inf, np.float32)
         counts = np.zeros(nq, np.uint32)
+        st = np.zeros((nq, 3), np.uint64)
         if self._h is None and self._builder is not None:  # nothing inserted, no dimension yet: empty
-            return ids, dists, counts
+            return (ids, dists, counts, st) if stats else (ids, dists, counts)
         q = self._prep(q)
         check(lib().granne_hip_rw_builder_search_batch(self._handle(), _p(q), nq, int(max_search), k, _p(ids), _p(dists),
-                                                       _p(counts), None))
-        return ids, dists, counts
+                                                       _p(counts), _p(st) if stats else None))
+        return (ids, dists, counts, st) if stats else (ids, dists, counts)
 
     def search(self, query, max_search=DEFAULT_MAX_SEARCH, num_neighbors=DEFAULT_NUM_ELEMENTS):
         ids, dists, counts = self.search_batch(np.asarray(query).reshape(1, -1), max_search, num_neighbors)
         return [(int(ids[0, i]), float(dists[0, i])) for i in range(int(counts[0]))]
+
+    # ---- tombstones (include/granne_hip.h, "removing elements") -------------------
+    def _mark(self, fn, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        counts = np.zeros(3, np.uint64)
+        check(fn(self._handle(), _p(ids) if ids.size else None, ids.size, _p(counts)))
+        return int(counts[0]), int(counts[1]), int(counts[2])
+
+    def remove(self, ids):
+        """Marks the elements removed: searches never return them again, the graph keeps them (they are traversed, and
+        inserts may link to them), their slots are not reused. Returns (newly removed, removed already -- repeats within
+        `ids` included --, ids >= len(self), which are ignored)."""
+        return self._mark(lib().granne_hip_rw_builder_remove, ids)
+
+    def restore(self, ids):
+        """The inverse of `remove`: (newly restored, alive already, ids >= len(self))."""
+        return self._mark(lib().granne_hip_rw_builder_restore, ids)
+
+    def removed_count(self):
+        return int(lib().granne_hip_rw_builder_removed_count(self._handle()))
+
+    def alive_filter(self):
+        """A granne_amd.Filter over the len(self) ids with the bits of the elements that are not removed: a copy, for
+        `search_filtered` / `exact_topk_filtered` on a `get_index()` snapshot taken with no insert in between. `save`
+        and `get_index` know nothing of removals: keep `alive_filter().words()` beside the files, or `compact` first."""
+        from .filters import Filter
+        h, n = self._handle(), len(self)
+        f = Filter(max(self.max_elements, n), self.device)  # (room for whatever a concurrent insert adds)
+        f.n = n
+        check(lib().granne_hip_rw_builder_alive(h, C.c_void_p(f.ptr), None))
+        check(lib().granne_hip_stream_synchronize(None, self.device))
+        return f
+
+    def compact(self, max_elements=None):
+        """(a new RwGranneBuilder over the elements that are not removed, in ascending old-id order and built afresh
+        under this one's config; old_ids [len(new)] uint64 with old_ids[new_id] = the element's id here). This handle
+        is left as it is. max_elements: the new handle's (default: this one's)."""
+        h = self._handle()
+        max_elements = self.max_elements if max_elements is None else int(max_elements)
+        old = np.empty(max(self.max_elements, len(self)), np.uint64)
+        count, out = C.c_uint64(0), C.c_void_p()
+        check(lib().granne_hip_rw_builder_compact(h, max_elements, C.byref(out), _p(old), C.byref(count)))
+        new = RwGranneBuilder.__new__(RwGranneBuilder)
+        new.element_type, new.dtype_code, new.np_dtype = self.element_type, self.dtype_code, self.np_dtype
+        new.device, new.config, new.dim = self.device, self.config, self.dim
+        new.max_elements, new._prepared = max_elements, self._prepared
+        new._h, new._builder = out, None
+        return new, old[: count.value].copy()
 
     # ---- accessors --------------------------------------------------------------------------------
     def __len__(self):
@@ -161,3 +211,5 @@ class RwGranneBuilder:
 SMALL_OPS = _lib.RW_OPT_SMALL_OPS
 SMALL_LAUNCHES = _lib.RW_OPT_SMALL_LAUNCHES
 SORTED_LAUNCHES = _lib.RW_OPT_SORTED_LAUNCHES
+REMOVED = _lib.RW_OPT_REMOVED
+FILTERED_SEARCHES = _lib.RW_OPT_FILTERED_SEARCHES

@@ -14,6 +14,7 @@
 // `Vectors<'static>`); a Granne/GranneBuilder owns the device copies.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -170,6 +171,9 @@ private:
 };
 } // namespace detail
 
+template <class Elements>
+class RwGranneBuilder;
+
 // An id bitmap in device memory for Granne::search_filtered (granne_hip.h, "filtered search"): bit (id & 31) of u32 word
 // (id >> 5) over the ids 0..n-1, made and counted by the library's kernels.
 class Filter {
@@ -220,7 +224,9 @@ public:
     uint32_t* words() const { return (uint32_t*)mem_.get(); } // device pointer
 
 private:
+    template <class> friend class RwGranneBuilder; // (alive_filter)
     Filter(size_t n, int device) : n_(n), device_(device), mem_(words_of(n) * 4, device) {}
+    Filter(size_t n, size_t room, int device) : n_(n), device_(device), mem_(words_of(room > n ? room : n) * 4, device) {}
     static size_t words_of(size_t n) {
         uint64_t w = 0;
         check(granne_hip_filter_words(n, &w));
@@ -704,8 +710,52 @@ public:
         return Granne<Elements>(h);
     }
     void set_option(int option, uint64_t value) const { check(granne_hip_rw_builder_set_option(h_.get(), option, value)); }
+    uint64_t get_option(int option) const {
+        uint64_t v = 0;
+        check(granne_hip_rw_builder_get_option(h_.get(), option, &v));
+        return v;
+    }
+
+    // ---- removing elements (granne_hip.h, "removing elements"; no reference counterpart) ----
+    struct MarkCounts {
+        uint64_t changed, already, out_of_range; // ids this call removed (restored); in that state already; >= len, ignored
+    };
+    // search never returns a removed element again; it stays in the graph (traversed, linked to), its slot is not reused
+    MarkCounts remove(const std::vector<uint64_t>& ids) const {
+        uint64_t c[3] = {0, 0, 0};
+        check(granne_hip_rw_builder_remove(h_.get(), ids.data(), ids.size(), c));
+        return {c[0], c[1], c[2]};
+    }
+    MarkCounts restore(const std::vector<uint64_t>& ids) const {
+        uint64_t c[3] = {0, 0, 0};
+        check(granne_hip_rw_builder_restore(h_.get(), ids.data(), ids.size(), c));
+        return {c[0], c[1], c[2]};
+    }
+    size_t removed_count() const { return granne_hip_rw_builder_removed_count(h_.get()); } // (= GRANNE_HIP_RW_OPT_REMOVED)
+    // search calls that ran under the tombstone bitmap so far: one per call made while removed_count() was not 0
+    uint64_t filtered_searches() const { return get_option(GRANNE_HIP_RW_OPT_FILTERED_SEARCHES); }
+    // a copy of the bitmap of the elements that are not removed, over the ids 0..len-1 (`device`: the handle's): the filter
+    // for Granne::search_filtered on a get_index() snapshot taken with no insert in between
+    Filter alive_filter(int device = 0) const {
+        Filter f(len(), max_elements(), device); // (room for whatever a concurrent insert adds)
+        check(granne_hip_rw_builder_alive(h_.get(), f.words(), nullptr));
+        check(granne_hip_stream_synchronize(nullptr, device));
+        return f;
+    }
+    // a new, independent builder over the elements that are not removed, in ascending old-id order, built afresh under
+    // this one's config; (*old_ids)[new_id] = the element's id here. This builder is left as it is.
+    RwGranneBuilder compact(size_t max_elements, std::vector<uint64_t>* old_ids = nullptr) const {
+        std::vector<uint64_t> old(std::max(len(), this->max_elements()) + 1);
+        granne_hip_rw_builder* h = nullptr;
+        uint64_t count = 0;
+        check(granne_hip_rw_builder_compact(h_.get(), max_elements, &h, old.data(), &count));
+        old.resize((size_t)count);
+        if (old_ids) old_ids->swap(old);
+        return RwGranneBuilder(h);
+    }
 
 private:
+    explicit RwGranneBuilder(granne_hip_rw_builder* h) : h_(h, granne_hip_rw_builder_destroy) {}
     std::shared_ptr<granne_hip_rw_builder> h_;
 };
 

@@ -793,11 +793,50 @@ enum {
                                              radix sort: 0 = never, 1 = the default (GRANNE_HIP_RW_SMALL_OPS), any other value
                                              = that threshold, capped at the default. Results do not depend on it */
     GRANNE_HIP_RW_OPT_SMALL_LAUNCHES = 2, /* read-only: sub-batches that took the small path so far */
-    GRANNE_HIP_RW_OPT_SORTED_LAUNCHES = 3 /* read-only: sub-batches that took the radix-sorted path so far */
+    GRANNE_HIP_RW_OPT_SORTED_LAUNCHES = 3, /* read-only: sub-batches that took the radix-sorted path so far */
+    GRANNE_HIP_RW_OPT_REMOVED = 4,         /* read-only: granne_hip_rw_builder_removed_count */
+    GRANNE_HIP_RW_OPT_FILTERED_SEARCHES = 5 /* read-only: search calls that ran under the tombstone bitmap so far (one
+                                              per search / search_batch call made while the removed count was not 0) */
 };
 #define GRANNE_HIP_RW_SMALL_OPS 2048
 int granne_hip_rw_builder_set_option(granne_hip_rw_builder* rw, int option, uint64_t value);
 int granne_hip_rw_builder_get_option(granne_hip_rw_builder* rw, int option, uint64_t* value);
+/* ---- removing elements from a live RwGranneBuilder (no reference counterpart) ------
+ * hnswlib's markDelete, stated as the filter of "filtered search" below: the handle owns a bitmap `alive` over its element
+ * slots (filter layout, one = alive, all ones when the handle is made). A REMOVED element is never returned by the handle's
+ * search / search_batch. It STAYS IN THE GRAPH: it is traversed, it navigates in the upper layers, inserts search through it
+ * and may link to it, exactly as before -- the layers after any mix of inserts, removes and restores are the layers of the
+ * inserts alone, row for row. Removed slots are not reused: len and max_elements count removed elements.
+ * While the removed count is 0 -- also after every removed id has been restored -- search / search_batch run the launch
+ * they always ran. Otherwise they run granne_hip_search_filtered_batch's walk with filter = alive, one bitmap for all
+ * queries, max_expand 0: ids, distances, counts and out_stats are that walk's (the general walker up to max_search 256,
+ * the exact walker beyond; a removed element costs the walk what a disallowed id costs there, and under very heavy
+ * removal the exact walker's table can run out: GRANNE_HIP_ERR_OVERFLOW). Without a previous layer the result is empty,
+ * as before.
+ * remove / restore: ids [n] (host). out_counts [3] (host): [0] ids this call removed (restored), [1] ids that were removed
+ * (alive) already -- a second occurrence of an id within the call included --, [2] ids >= len, counted and not written.
+ * Both hold the handle's lock exclusively for the whole call, like an insert: a search sees whole calls. n = 0 is OK and
+ * needs no ids. GRANNE_HIP_ERR_INVALID: a null handle, null out_counts, null ids with n > 0. */
+int granne_hip_rw_builder_remove(granne_hip_rw_builder* rw, const uint64_t* ids, uint64_t n, uint64_t* out_counts);
+int granne_hip_rw_builder_restore(granne_hip_rw_builder* rw, const uint64_t* ids, uint64_t n, uint64_t* out_counts);
+/* removed elements among the len */
+uint64_t granne_hip_rw_builder_removed_count(granne_hip_rw_builder* rw);
+/* A copy of the bitmap over the ids 0..len-1: ceil(len / 32) words into d_filter_out (device memory on the handle's
+ * device), asynchronous on `stream`; a remove or restore that follows waits for the copy. It is the filter to pass to
+ * granne_hip_search_filtered_batch* / granne_hip_exact_topk_filtered* on a granne_hip_rw_builder_get_index snapshot taken
+ * with no insert in between. Room for ceil(max(max_elements, len) / 32) words is enough whatever is inserted meanwhile.
+ * save and get_index know nothing of tombstones (the reference's files have no place for them): keep these words beside
+ * the files, or compact first. */
+int granne_hip_rw_builder_alive(granne_hip_rw_builder* rw, uint32_t* d_filter_out, void* stream);
+/* Gives the removed rows' space back: a NEW, independent handle over the surviving rows in ascending old-id order, its
+ * graph built afresh by the bulk path under this handle's config -- granne_hip_builder_create_device over the gathered
+ * rows, then granne_hip_rw_builder_create(.., max_elements) -- so nothing of the old graph's links is kept.
+ * out_old_ids[new_id] = old id (host; room for max(this handle's max_elements, len) is enough), *out_count = survivors
+ * = the new handle's len; none gives an empty handle of the same dimension. `rw` is left as it was and stays usable; its
+ * lock is held (shared) only until the rows are gathered, so inserts wait that long and searches never.
+ * GRANNE_HIP_ERR_INVALID: a null argument, max_elements 0 or >= 2^32 - 1. */
+int granne_hip_rw_builder_compact(granne_hip_rw_builder* rw, uint64_t max_elements, granne_hip_rw_builder** out_rw,
+                                  uint64_t* out_old_ids, uint64_t* out_count);
 
 /* ---- filtered search: the walk under an id bitmap (no reference counterpart) --------
  * "The nearest neighbours among the ids this bitmap allows". The filter is `allowed`, one bit per element id: u32 words,

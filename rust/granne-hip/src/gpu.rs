@@ -197,6 +197,12 @@ extern "C" {
     fn granne_hip_rw_builder_get_index(rw: *mut granne_hip_rw_builder, out: *mut *mut granne_hip_index) -> c_int;
     fn granne_hip_rw_builder_set_option(rw: *mut granne_hip_rw_builder, option: c_int, value: u64) -> c_int;
     fn granne_hip_rw_builder_get_option(rw: *mut granne_hip_rw_builder, option: c_int, value: *mut u64) -> c_int;
+    fn granne_hip_rw_builder_remove(rw: *mut granne_hip_rw_builder, ids: *const u64, n: u64, out_counts: *mut u64) -> c_int;
+    fn granne_hip_rw_builder_restore(rw: *mut granne_hip_rw_builder, ids: *const u64, n: u64, out_counts: *mut u64) -> c_int;
+    fn granne_hip_rw_builder_removed_count(rw: *mut granne_hip_rw_builder) -> u64;
+    fn granne_hip_rw_builder_alive(rw: *mut granne_hip_rw_builder, d_filter_out: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_rw_builder_compact(rw: *mut granne_hip_rw_builder, max_elements: u64,
+        out_rw: *mut *mut granne_hip_rw_builder, out_old_ids: *mut u64, out_count: *mut u64) -> c_int;
     // filtered search: the walk under an id bitmap; bitmaps
     fn granne_hip_search_filtered_batch_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
         max_search: u32, num_neighbors: u32, d_filter: *const u32, filter_stride_words: u64, max_expand: u64,
@@ -236,6 +242,8 @@ pub const GRANNE_HIP_OPT_LAST_SPLIT_TAIL: c_int = 19;
 pub const GRANNE_HIP_OPT_LAST_SCAN: c_int = 20;
 pub const GRANNE_HIP_OPT_FORCE_GENERAL: c_int = 21;
 pub const GRANNE_HIP_RW_OPT_SMALL_OPS: c_int = 1;
+pub const GRANNE_HIP_RW_OPT_REMOVED: c_int = 4;
+pub const GRANNE_HIP_RW_OPT_FILTERED_SEARCHES: c_int = 5;
 pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
 pub const GRANNE_HIP_SHARDED_EXCHANGE_PEER: u64 = 0;
@@ -1064,6 +1072,42 @@ impl<E: GpuElements> GpuRwGranneBuilder<E> {
     /// sub-batches of up to this many link-update ops sort them in one workgroup (0: never, 1: the default)
     pub fn set_small_ops(&self, value: u64) -> std::io::Result<()> {
         check(unsafe { granne_hip_rw_builder_set_option(self.handle, GRANNE_HIP_RW_OPT_SMALL_OPS, value) })
+    }
+    /// Marks the elements removed (hnswlib's markDelete): `search` never returns them again; they stay in the graph, are
+    /// traversed and may be linked to, and their slots are not reused. Returns (newly removed, removed already -- repeats
+    /// within `ids` included --, ids >= len, which are ignored).
+    pub fn remove(&self, ids: &[u64]) -> std::io::Result<(u64, u64, u64)> {
+        let mut c = [0u64; 3];
+        check(unsafe { granne_hip_rw_builder_remove(self.handle, ids.as_ptr(), ids.len() as u64, c.as_mut_ptr()) })?;
+        Ok((c[0], c[1], c[2]))
+    }
+    /// The inverse of `remove`: (newly restored, alive already, ids >= len).
+    pub fn restore(&self, ids: &[u64]) -> std::io::Result<(u64, u64, u64)> {
+        let mut c = [0u64; 3];
+        check(unsafe { granne_hip_rw_builder_restore(self.handle, ids.as_ptr(), ids.len() as u64, c.as_mut_ptr()) })?;
+        Ok((c[0], c[1], c[2]))
+    }
+    pub fn removed_count(&self) -> usize { unsafe { granne_hip_rw_builder_removed_count(self.handle) as usize } }
+    /// A copy of the bitmap of the elements that are not removed, over the ids 0..len-1, on `device` (the handle's): the
+    /// filter for `search_filtered` on a snapshot taken with no insert in between.
+    pub fn alive_filter(&self, device: i32) -> std::io::Result<GpuFilter> {
+        let n = self.len();
+        let max = unsafe { granne_hip_rw_builder_max_elements(self.handle) as usize };
+        let (mut f, stream) = (GpuFilter::empty(n.max(max), device)?, Stream::new(device)?); // (room for concurrent inserts)
+        f.n = n;
+        check(unsafe { granne_hip_rw_builder_alive(self.handle, f.words.ptr, stream.raw) })?;
+        stream.synchronize()?;
+        Ok(f)
+    }
+    /// A new, independent builder over the elements that are not removed, in ascending old-id order, its graph built
+    /// afresh under this one's config; and `old_ids[new_id]`. `self` is left as it is.
+    pub fn compact(&self, max_elements: usize) -> std::io::Result<(Self, Vec<u64>)> {
+        let max = unsafe { granne_hip_rw_builder_max_elements(self.handle) as usize };
+        let mut old = vec![0u64; self.len().max(max)];
+        let (mut h, mut count) = (std::ptr::null_mut(), 0u64);
+        check(unsafe { granne_hip_rw_builder_compact(self.handle, max_elements as u64, &mut h, old.as_mut_ptr(), &mut count) })?;
+        old.truncate(count as usize);
+        Ok((Self { handle: h, dim: self.dim, _e: PhantomData }, old))
     }
 }
 impl<E: GpuElements> Drop for GpuRwGranneBuilder<E> { fn drop(&mut self) { unsafe { granne_hip_rw_builder_destroy(self.handle) } } }
