@@ -238,6 +238,14 @@ SIGNATURES = {
     "granne_hip_filter_to_ids_device": (i32, [vp, u64, vp, vp, i32, vp]),
     "granne_hip_exact_topk_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
+    "granne_hip_filter_slice_device": (i32, [vp, u64, u64, u32, u64, u64, vp, u64, i32, vp]),
+    "granne_hip_sharded_id_span": (u64, [vp]),
+    "granne_hip_sharded_search_filtered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_sharded_search_filtered_batch": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp]),
+    "granne_hip_sharded_exact_topk_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_sharded_exact_topk": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
+    "granne_hip_sharded_exact_topk_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_sharded_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
 }
 
 

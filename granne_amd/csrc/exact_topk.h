@@ -425,9 +425,10 @@ __global__ __launch_bounds__(256) void et_select_kernel(const uint32_t* hist, ui
 }
 
 // One block per query: the collected keys sorted in LDS, the first k written; places past the count hold UINT64_MAX / +inf.
+// `over` (optional, u32 per query): 1 where EtSel.over voids the query, else 0 (the partitioned selection carries it on).
 __global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t* cand, const uint32_t* cnt, const EtSel* sel, uint32_t k,
                                                                   uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
-                                                                  uint32_t* status) {
+                                                                  uint32_t* status, uint32_t* over) {
     __shared__ uint64_t keys[ET_CAP];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     uint32_t m = cnt[q] < ET_CAP ? cnt[q] : ET_CAP;
@@ -455,6 +456,7 @@ __global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t
     }
     if (tid == 0) {
         out_counts[q] = count;
+        if (over) over[q] = sel[q].over ? 1u : 0u;
         if (status) atomicMax(status + 2, m);
     }
 }

@@ -68,17 +68,40 @@ static int exact_topk_args(const granne_hip_index* ix, uint32_t nq, uint32_t k, 
     return GRANNE_HIP_OK;
 }
 
+// The selection's scratch: the candidates [qc][ET_CAP] u64 -- the two histograms live in the same bytes, dead before the
+// keys are collected -- then bound [qc], sel [qc], cnt [qc]; then, for the list source, the list's length (u64), the
+// compaction's block counts and the list itself (u32 [n]). qc: the queries of one chunk.
+struct EtScratch {
+    size_t o_big, o_bound, o_sel, o_cnt, o_m, o_blk, o_list, total;
+};
+static EtScratch et_scratch(uint64_t n, uint32_t nq, bool list) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const uint32_t qc_max = nq < ET_CHUNK ? nq : ET_CHUNK;
+    static_assert((ET_BINS1 + ET_BINS2) * 4u <= ET_CAP * 8u, "the histograms fit in the candidates' bytes");
+    EtScratch o;
+    o.o_big = 0;
+    o.o_bound = (size_t)qc_max * ET_CAP * 8;
+    o.o_sel = o.o_bound + (size_t)qc_max * 4;
+    o.o_cnt = o.o_sel + (size_t)qc_max * sizeof(EtSel);
+    o.o_m = up(o.o_cnt + (size_t)qc_max * 4);
+    o.o_blk = o.o_m + 256;
+    o.o_list = o.o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
+    o.total = o.o_list + (list ? (size_t)n * 4 : 0);
+    return o;
+}
+
 // The selection on stream s, arguments checked, nq > 0. d_filter null: all rows (ET_ALL); else filter_stride_words == 0:
-// one bitmap for every query, compacted here to its ids (ET_LIST); else one bitmap per query (ET_BITS).
+// one bitmap for every query, compacted here to its ids (ET_LIST); else one bitmap per query (ET_BITS). d_over (optional,
+// u32[nq]): 1 where the selection overflowed and the query was voided, else 0. d_scratch (optional): et_scratch(..).total
+// bytes of the caller's on the index's device, free for this call on s; null: taken from the stream-ordered allocator.
 static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_filter,
                           uint64_t filter_stride_words, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status,
-                          hipStream_t s) {
+                          hipStream_t s, uint32_t* d_over = nullptr, uint8_t* d_scratch = nullptr) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     const uint64_t n = ix->n_elements;
     const bool i8 = ix->dtype == GRANNE_HIP_I8;
     const EtSrc src = !d_filter ? ET_ALL : filter_stride_words == 0 ? ET_LIST : ET_BITS;
     const bool list = src == ET_LIST;
-    const uint32_t qc_max = nq < ET_CHUNK ? nq : ET_CHUNK;
     // the prefixes the selection runs over, shortest first, the last one all rows (exact_topk.h, priming): a function of n
     // alone -- the list source clips them to the list's length on the device
     uint64_t prefix[16];
@@ -94,22 +117,17 @@ static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uin
         }
         while (m) prefix[stages++] = rev[--m];
     }
-    // scratch: the candidates [qc][ET_CAP] u64 -- the two histograms live in the same bytes, dead before the keys are
-    // collected -- then bound [qc], sel [qc], cnt [qc]; then, for the list source, the list's length (u64), the
-    // compaction's block counts and the list itself (u32 [n])
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_big = 0, big = (size_t)qc_max * ET_CAP * 8;
-    static_assert((ET_BINS1 + ET_BINS2) * 4u <= ET_CAP * 8u, "the histograms fit in the candidates' bytes");
-    const size_t o_bound = o_big + big, o_sel = o_bound + (size_t)qc_max * 4, o_cnt = o_sel + (size_t)qc_max * sizeof(EtSel);
-    const size_t o_m = up(o_cnt + (size_t)qc_max * 4), o_blk = o_m + 256, o_list = o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
-    const size_t total = o_list + (list ? (size_t)n * 4 : 0);
-    uint8_t* scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
+    const EtScratch lay = et_scratch(n, nq, list);
+    const size_t o_big = lay.o_big, o_bound = lay.o_bound, o_sel = lay.o_sel, o_cnt = lay.o_cnt, o_m = lay.o_m, o_blk = lay.o_blk, o_list = lay.o_list;
+    uint8_t* scratch = d_scratch;
+    if (!scratch) HIP_TRY(hipMallocAsync((void**)&scratch, lay.total, s));
     struct Release {
         void* p;
         hipStream_t s;
-        ~Release() { (void)hipFreeAsync(p, s); }
-    } release{scratch, s};
+        ~Release() {
+            if (p) (void)hipFreeAsync(p, s);
+        }
+    } release{d_scratch ? nullptr : scratch, s};
     if (list)
         if (const int rc = filter_compact<uint32_t>(d_filter, n, (uint32_t*)(scratch + o_blk), (uint32_t*)(scratch + o_list),
                                                     (uint64_t*)(scratch + o_m), d_status ? d_status + 3 : nullptr, s))
@@ -169,7 +187,7 @@ static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uin
         if (const int rc = pass(3, n, 0, 0)) return rc;
         hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_big),
                            (const uint32_t*)(scratch + o_cnt), (const EtSel*)(scratch + o_sel), k, d_out_ids + (size_t)c0 * k,
-                           d_out_dists + (size_t)c0 * k, d_out_counts + c0, d_status);
+                           d_out_dists + (size_t)c0 * k, d_out_counts + c0, d_status, d_over ? d_over + c0 : nullptr);
         HIP_TRY(hipGetLastError());
     }
     return GRANNE_HIP_OK;

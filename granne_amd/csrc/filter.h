@@ -26,6 +26,7 @@
 // does not survive keys that are expanded but may not be returned.
 #pragma once
 
+#include "filter_slice.h"
 #include "wave_prims.h"
 
 namespace granne_hip {
@@ -105,6 +106,92 @@ __global__ __launch_bounds__(256) void filter_count_kernel(const uint32_t* __res
     }
     for (int o = 32; o > 0; o >>= 1) mine += (uint32_t)__shfl_xor((int)mine, o, 64);
     if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(out, (unsigned long long)mine);
+}
+
+// ---- bitmap slice (granne_hip_filter_slice_device; the word rule is filter_slice.h's) ---------------------------------
+// out[f][w] = word w of the slice [first_bit, first_bit + n_out_bits) of filter f, for every w < ceil(n_out_bits / 32).
+// grid = (blocks over the output words, filters); both are strided over, so any grid covers any size. One output word per
+// lane; the loop bound is the wave's first word, so a wave stays whole for the hand-over.
+//   !HANDOVER every lane calls filter_slice_word: two loads per lane when unaligned, one when aligned (a guarded copy).
+//             THE FORM THAT RUNS: the second load hits the line the neighbour's first one brings, and measured it is as
+//             fast as the hand-over or faster.
+//   HANDOVER  lane l's second source word is lane l + 1's first: each lane loads one word and takes the other from its
+//             neighbour; only the wave's last lane -- and the lane of the slice's last word, whose neighbour loads
+//             nothing -- load a second one. Kept behind GRANNE_HIP_FILTER_SLICE_HANDOVER for the measurement.
+template <bool HANDOVER>
+__global__ __launch_bounds__(256) void filter_slice_kernel(const uint32_t* __restrict__ src, uint64_t n_bits, uint64_t src_stride,
+                                                           uint32_t n_filters, uint64_t first_bit, uint64_t n_out_bits,
+                                                           uint32_t* __restrict__ out, uint64_t out_stride) {
+    const uint64_t src_words = filter_words(n_bits), out_words = filter_words(n_out_bits);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const bool aligned = (first_bit & 31u) == 0;
+    for (uint32_t f = blockIdx.y; f < n_filters; f += gridDim.y) {
+        const uint32_t* s = src + (uint64_t)f * src_stride;
+        uint32_t* o = out + (uint64_t)f * out_stride;
+        for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); w0 < out_words; w0 += step) {
+            const uint64_t w = w0 + lane;
+            const bool live = w < out_words;
+            if constexpr (HANDOVER) {
+                const uint64_t i = (first_bit >> 5) + w;
+                const uint32_t lo = live ? filter_slice_load(s, src_words, n_bits, i) : 0u;
+                uint32_t hi = 0u;
+                if (!aligned) { // (wave-uniform)
+                    hi = (uint32_t)__shfl_down((int)lo, 1, 64);
+                    if (live && (lane == 63u || w + 1 == out_words)) hi = filter_slice_load(s, src_words, n_bits, i + 1);
+                }
+                if (live) o[w] = filter_slice_combine(lo, hi, first_bit, n_out_bits, w);
+            } else {
+                if (live) o[w] = filter_slice_word(s, src_words, first_bit, n_bits, n_out_bits, w);
+            }
+        }
+    }
+}
+
+// After the merge of a partitioned exact selection. Every shard's block holds, after its packed top-k, four status words
+// (status_off) and one u32 per query (flags_off): non-zero where the shard's selection overflowed for that query. A query
+// flagged by ANY shard is voided in the merged result -- count 0, the row UINT64_MAX / +inf -- so that no list ever
+// misses one shard's rows. (The places past a count are the merge's own fill, which is exact_topk's.) Block 0's first wave
+// folds the status words: [0] += queries voided, [1] += over shards, [2] = max over shards, [3] += over shards.
+// grid = ceil(nq / 256) blocks of 256.
+__global__ __launch_bounds__(256) void sharded_exact_finish_kernel(const uint8_t* gathered, uint64_t stride, uint64_t status_off,
+                                                                   uint64_t flags_off, uint32_t n_shards, uint32_t nq, uint32_t k,
+                                                                   uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    bool voided = false;
+    if (q < nq) {
+        for (uint32_t s = 0; s < n_shards; ++s)
+            voided = voided || reinterpret_cast<const uint32_t*>(gathered + (size_t)s * stride + flags_off)[q] != 0u;
+        if (voided) {
+            out_counts[q] = 0;
+            for (uint32_t j = 0; j < k; ++j) {
+                out_ids[(size_t)q * k + j] = ~0ull;
+                out_dists[(size_t)q * k + j] = __builtin_inff();
+            }
+        }
+    }
+    if (!status) return;
+    const uint32_t mine = (uint32_t)__popcll(wave_ballot(voided));
+    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(status + 0, mine);
+    if (blockIdx.x == 0 && threadIdx.x < 64u) {
+        const uint32_t lane = threadIdx.x;
+        uint32_t b = 0, c = 0, d = 0;
+        if (lane < n_shards) {
+            const uint32_t* st = reinterpret_cast<const uint32_t*>(gathered + (size_t)lane * stride + status_off);
+            b = st[1], c = st[2], d = st[3];
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            b += __shfl_xor(b, o, 64);
+            const uint32_t t = __shfl_xor(c, o, 64);
+            c = t > c ? t : c;
+            d += __shfl_xor(d, o, 64);
+        }
+        if (lane == 0) {
+            if (b) atomicAdd(status + 1, b);
+            if (c) atomicMax(status + 2, c);
+            if (d) atomicAdd(status + 3, d);
+        }
+    }
 }
 
 // ---- bitmap -> ascending id list (granne_hip_filter_to_ids_device; the exact scan's list source, exact_topk.h) -------

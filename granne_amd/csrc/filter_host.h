@@ -126,6 +126,37 @@ extern "C" int granne_hip_filter_from_mask_device(const uint8_t* d_mask, uint64_
     return GRANNE_HIP_OK;
 }
 
+// GRANNE_HIP_FILTER_SLICE_HANDOVER=1: the slice kernel with the lane hand-over instead of two loads per lane (read at
+// every call: the measurement in tools/sharded_filtered_bench.py switches it inside one process)
+static bool filter_slice_handover() {
+    const char* e = getenv("GRANNE_HIP_FILTER_SLICE_HANDOVER");
+    return e && *e && *e != '0';
+}
+
+// bits [first_bit, first_bit + n_out_bits) of n_filters bitmaps over n_bits ids as bitmaps of their own (filter_slice.h)
+extern "C" int granne_hip_filter_slice_device(const uint32_t* d_filter, uint64_t n_bits, uint64_t filter_stride_words, uint32_t n_filters,
+                                              uint64_t first_bit, uint64_t n_out_bits, uint32_t* d_out, uint64_t out_stride_words,
+                                              int device_id, void* stream) {
+    if (first_bit > n_bits) return fail(GRANNE_HIP_ERR_INVALID, "filter_slice: first_bit (%llu) is past the bitmap's %llu bits",
+                                        (unsigned long long)first_bit, (unsigned long long)n_bits);
+    if (n_out_bits == 0) return GRANNE_HIP_OK;
+    if (n_filters == 0) return fail(GRANNE_HIP_ERR_INVALID, "filter_slice: n_filters is 0");
+    if (!d_filter || !d_out) return fail(GRANNE_HIP_ERR_INVALID, "filter_slice: null buffer");
+    if (filter_stride_words == 0 ? n_filters != 1 : filter_stride_words < filter_words(n_bits))
+        return fail(GRANNE_HIP_ERR_INVALID, "filter_slice: filter_stride_words (%llu) must be at least ceil(n_bits / 32) = %llu, or 0 for one filter",
+                    (unsigned long long)filter_stride_words, (unsigned long long)filter_words(n_bits));
+    if (out_stride_words < filter_words(n_out_bits))
+        return fail(GRANNE_HIP_ERR_INVALID, "filter_slice: out_stride_words (%llu) must be at least ceil(n_out_bits / 32) = %llu",
+                    (unsigned long long)out_stride_words, (unsigned long long)filter_words(n_out_bits));
+    GRANNE_HIP_ON_DEVICE(device_id);
+    const dim3 grid(grid_for(filter_words(n_out_bits), 256), n_filters < 1024u ? n_filters : 1024u);
+    auto kernel = filter_slice_handover() ? filter_slice_kernel<true> : filter_slice_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, d_filter, n_bits, filter_stride_words, n_filters, first_bit,
+                       n_out_bits, d_out, out_stride_words);
+    HIP_TRY(hipGetLastError());
+    return GRANNE_HIP_OK;
+}
+
 extern "C" int granne_hip_filter_count_device(const uint32_t* d_filter, uint64_t n_elements, uint64_t* d_out, int device_id,
                                               void* stream) {
     if (!d_out) return fail(GRANNE_HIP_ERR_INVALID, "filter_count: out is null");

@@ -2468,3 +2468,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // the exact selection: exact_topk over all rows or the rows an id bitmap allows; a bitmap's ids
 // ------------------------------------------------------------------------------------------------
 #include "exact_topk_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// partitioned indexes: filtered search and the exact selection over global ids
+// ------------------------------------------------------------------------------------------------
+#include "sharded_ops_host.h"

@@ -110,6 +110,10 @@ struct granne_hip_sharded {
         std::vector<size_t> recv_cap;
         std::vector<uint8_t*> d_q;      // per device other than the merge device: the batch's queries
         std::vector<size_t> q_cap;
+        std::vector<uint8_t*> d_filt;   // per shard, on its device: the shard's slice of a batch's filter(s) (sharded_ops_host.h)
+        std::vector<size_t> filt_cap;
+        std::vector<uint8_t*> d_scan;   // per shard, on its device: the exact selection's scratch
+        std::vector<size_t> scan_cap;
         hipEvent_t ready = nullptr;     // caller's stream: queries (and the previous use of the outputs) are in order
         hipEvent_t merged = nullptr;    // merge stream: the merged result is written
         std::vector<hipEvent_t> searched; // per shard
@@ -154,6 +158,8 @@ static void sharded_free_slot(granne_hip_sharded* sh, granne_hip_sharded::Slot& 
     for (size_t s = 0; s < L.searched.size(); ++s) {
         DeviceGuard g(sh->shards[s].ix->device);
         if (L.searched[s]) (void)hipEventDestroy(L.searched[s]);
+        if (s < L.d_filt.size() && L.d_filt[s]) (void)hipFree(L.d_filt[s]);
+        if (s < L.d_scan.size() && L.d_scan[s]) (void)hipFree(L.d_scan[s]);
     }
     DeviceGuard g(sh->merge_device);
     if (L.ready) (void)hipEventDestroy(L.ready);
@@ -217,6 +223,10 @@ static int sharded_init_slot(granne_hip_sharded* sh, granne_hip_sharded::Slot& L
     L.q_there.assign(nd, nullptr);
     L.xdone.assign(nd, nullptr);
     L.searched.assign(G, nullptr);
+    L.d_filt.assign(G, nullptr);
+    L.filt_cap.assign(G, 0);
+    L.d_scan.assign(G, nullptr);
+    L.scan_cap.assign(G, 0);
     for (size_t d = 0; d < nd; ++d) {
         GRANNE_HIP_ON_DEVICE(sh->devices[d].id);
         HIP_TRY(hipEventCreateWithFlags(&L.q_there[d], hipEventDisableTiming));
@@ -501,9 +511,25 @@ static int slot_grow(uint8_t** p, size_t* cap, size_t want) {
     return GRANNE_HIP_OK;
 }
 
+// ---- what every shard does with a batch ------------------------------------------------------------------------
+// SEARCH is granne_hip_search_batch_packed_device and fold_status_kernel, enqueued here. The others (sharded_ops_host.h)
+// run under the shard's slice of the caller's bitmap(s) and end with a fold or a finishing step of their own; `extra`
+// bytes follow the status words in every shard's block (the exact selection's per-query overflow flags).
+struct ShardedOp {
+    enum Kind { SEARCH, FILTERED, EXACT } kind = SEARCH;
+    const uint32_t* d_filter = nullptr; // on the merge device, over id_span bits; null: EXACT over all rows
+    uint64_t filter_stride = 0;         // words between the queries' bitmaps; 0: one for all
+    uint64_t max_expand = 0;            // FILTERED
+    size_t extra = 0;
+};
+static int sharded_op_enqueue(granne_hip_sharded* sh, granne_hip_sharded::Slot& L, uint32_t s, const ShardedOp& op, const void* q_here,
+                              uint32_t nq, uint32_t max_search, uint32_t k, uint8_t* blk, size_t pb);
+static int sharded_op_finish(granne_hip_sharded* sh, granne_hip_sharded::Slot& L, const ShardedOp& op, uint32_t nq, uint32_t k, size_t pb,
+                             uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status);
+
 // ---- one batch: begin (enqueue everything) / end (order the caller's stream after the merge) -------------------
 // The caller holds sh->mu.
-static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, uint32_t nq, uint32_t max_search,
+static int sharded_begin_locked(granne_hip_sharded* sh, const ShardedOp& op, const void* d_queries, uint32_t nq, uint32_t max_search,
                                 uint32_t num_neighbors, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                                 uint32_t* d_status, hipStream_t stream, uint64_t* out_ticket) {
     using Slot = granne_hip_sharded::Slot;
@@ -522,7 +548,7 @@ static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, u
         return fail(GRANNE_HIP_ERR_INVALID, "%u batches are in flight already (GRANNE_HIP_SHARDED_OPT_DEPTH): end one first", sh->depth);
     Slot& L = sh->slots[si];
     const size_t pb = (size_t)granne_hip_packed_topk_bytes(nq, num_neighbors);
-    const size_t stride = pb + SHARD_STATUS_BYTES;
+    const size_t stride = pb + SHARD_STATUS_BYTES + op.extra;
     const size_t qb = (size_t)nq * sh->dim * elem_size(sh->dtype);
     const bool rccl = sh->exchange == GRANNE_HIP_SHARDED_EXCHANGE_RCCL;
 
@@ -569,8 +595,10 @@ static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, u
             q_here = L.d_q[S.dev];
         }
         uint8_t* blk = block_of(s);
-        HIP_TRY(hipMemsetAsync(blk + pb, 0, SHARD_STATUS_BYTES, S.stream));
-        int rc = granne_hip_search_batch_packed_device(S.ix, q_here, nq, max_search, num_neighbors, blk, (uint32_t*)(blk + pb), S.stream);
+        HIP_TRY(hipMemsetAsync(blk + pb, 0, SHARD_STATUS_BYTES + op.extra, S.stream));
+        int rc = op.kind == ShardedOp::SEARCH
+                     ? granne_hip_search_batch_packed_device(S.ix, q_here, nq, max_search, num_neighbors, blk, (uint32_t*)(blk + pb), S.stream)
+                     : sharded_op_enqueue(sh, L, s, op, q_here, nq, max_search, num_neighbors, blk, pb);
         if (rc) return rc;
         if (!rccl && S.dev != 0)
             HIP_TRY(hipMemcpyPeerAsync(L.d_recv[0] + stride * s, sh->merge_device, blk, S.ix->device, stride, S.stream));
@@ -605,7 +633,10 @@ static int sharded_begin_locked(granne_hip_sharded* sh, const void* d_queries, u
     int rc = granne_hip_merge_topk_packed_strided_device(L.d_recv[0], stride, offs, G, nq, num_neighbors, d_out_ids, d_out_dists,
                                                          d_out_counts, sh->merge_device, sh->merge_stream);
     if (rc) return rc;
-    if (d_status) {
+    if (op.kind != ShardedOp::SEARCH) {
+        rc = sharded_op_finish(sh, L, op, nq, num_neighbors, pb, d_out_ids, d_out_dists, d_out_counts, d_status);
+        if (rc) return rc;
+    } else if (d_status) {
         hipLaunchKernelGGL(fold_status_kernel, dim3(1), dim3(64), 0, sh->merge_stream, (const uint8_t*)L.d_recv[0], (uint64_t)stride,
                            (uint64_t)pb, G, d_status);
         HIP_TRY(hipGetLastError());
@@ -643,7 +674,7 @@ extern "C" int granne_hip_sharded_begin_device(granne_hip_sharded* sh, const voi
     if (nq == 0 || num_neighbors == 0) return fail(GRANNE_HIP_ERR_INVALID, "nq and num_neighbors must be > 0 for a batch in flight");
     if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     std::lock_guard<std::mutex> lk(sh->mu);
-    rc = sharded_begin_locked(sh, d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_status,
+    rc = sharded_begin_locked(sh, ShardedOp(), d_queries, nq, max_search, num_neighbors, d_out_ids, d_out_dists, d_out_counts, d_status,
                               (hipStream_t)stream, out_ticket);
     if (rc) sharded_quiesce(sh); // an error return leaves nothing running on the caller's buffers
     return rc;

@@ -480,4 +480,28 @@ __global__ __launch_bounds__(64) void fold_status_kernel(const uint8_t* gathered
     }
 }
 
+// The status words of the G shards of a partitioned FILTERED search folded into the caller's four: fold_status_kernel's
+// three and [3] += walks cut by max_expand. One wave (G <= 64).
+__global__ __launch_bounds__(64) void fold_status4_kernel(const uint8_t* gathered, uint64_t stride, uint64_t status_off, uint32_t n_shards,
+                                                          uint32_t* out) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t a = 0, b = 0, c = 0, d = 0;
+    if (lane < n_shards) {
+        const uint32_t* st = reinterpret_cast<const uint32_t*>(gathered + (size_t)lane * stride + status_off);
+        a = st[0], b = st[1], c = st[2], d = st[3];
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        a |= __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+        c += __shfl_xor(c, o, 64);
+        d += __shfl_xor(d, o, 64);
+    }
+    if (lane == 0) {
+        if (a) atomicOr(out + 0, 1u);
+        if (b) atomicAdd(out + 1, b);
+        if (c) atomicAdd(out + 2, c);
+        if (d) atomicAdd(out + 3, d);
+    }
+}
+
 } // namespace granne_hip

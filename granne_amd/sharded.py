@@ -429,6 +429,106 @@ class ShardedHost:
         ids, ds, cnt = self.search_batches(q[None], max_search, k)
         return ids[0], ds[0], cnt[0]
 
+    # ---- filters and the exact selection over global ids ------------------------------------------------
+    def id_span(self):
+        """granne_hip_sharded_id_span: the bits of a global filter, max over the shards of offset + num_elements."""
+        return int(self._lib.granne_hip_sharded_id_span(self._h))
+
+    def _filter_arg(self, allowed, nq):
+        """`allowed` as (owner, device pointer, stride in words): what Granne._filter_arg takes, over id_span() ids on
+        self.device -- a Filter, a 1-D bool mask, an id array, one Filter per query -- or a 2-D mask [nq, id_span()]."""
+        from .filters import Filter, _DeviceBlock, filter_words
+        from .index import Granne
+        n = self.id_span()
+        a = None if isinstance(allowed, (Filter, list, tuple)) else np.asarray(allowed)
+        if a is not None and a.ndim == 2:
+            if a.shape != (nq, n):
+                raise ValueError("a 2-D filter needs one row of %d entries per query" % n)
+            words = filter_words(n)
+            bits = np.zeros((nq, words * 32), np.uint8)
+            bits[:, :n] = a != 0
+            packed = np.packbits(bits, axis=1, bitorder="little").view(np.uint32)
+            block = _DeviceBlock(nq * words * 4, self.device).upload(packed)
+            return block, block.ptr, words
+        return Granne._filter_arg(self, allowed, nq, n)
+
+    def _queries(self, queries):
+        q = np.ascontiguousarray(queries, dtype=self.np_dtype)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        return q
+
+    def _run(self, q, k, call, overflow_message, want_status):
+        """Buffers on self.device around one device call `call(d_queries, d_ids, d_dists, d_counts, d_status)`."""
+        from ._lib import ERR_OVERFLOW, GranneHipError
+        from .filters import _DeviceBlock
+        nq = q.shape[0]
+        up = lambda v: (v + 255) & ~255  # noqa: E731
+        o_ids = up(q.nbytes)
+        o_d = o_ids + up(nq * k * 8)
+        o_c = o_d + up(nq * k * 4)
+        o_st = o_c + up(nq * 4)
+        block = _DeviceBlock(o_st + 16, self.device)
+        host = np.zeros(o_st + 16, np.uint8)
+        host[:q.nbytes] = q.view(np.uint8).reshape(-1)
+        block.upload(host)
+        rc = call(block.ptr, block.ptr + o_ids, block.ptr + o_d, block.ptr + o_c, block.ptr + o_st) if nq else 0
+        self._check(self._lib.granne_hip_stream_synchronize(None, self.device))
+        self._check(rc)
+        host = block.download(np.uint8, o_st + 16)
+        st4 = host[o_st:o_st + 16].view(np.uint32).copy()
+        out = (host[o_ids:o_ids + nq * k * 8].view(np.uint64).reshape(nq, k).copy(),
+               host[o_d:o_d + nq * k * 4].view(np.float32).reshape(nq, k).copy(),
+               host[o_c:o_c + nq * 4].view(np.uint32).copy())
+        if want_status:
+            return out + (st4,)
+        if st4[0]:
+            raise GranneHipError(ERR_OVERFLOW, overflow_message % int(st4[0]))
+        return out
+
+    def search_filtered_batch_device(self, d_queries, nq, max_search, k, d_filter, filter_stride_words, max_expand, d_ids, d_dists,
+                                     d_counts, d_status=0, stream=0):
+        """granne_hip_sharded_search_filtered_batch_device: raw device pointers (int) on self.device; d_filter over
+        id_span() bits (filter_stride_words 0: one for all queries). Asynchronous on `stream`."""
+        self._check(self._lib.granne_hip_sharded_search_filtered_batch_device(
+            self._h, C.c_void_p(d_queries), int(nq), int(max_search), int(k), C.c_void_p(d_filter), int(filter_stride_words),
+            int(max_expand), C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def search_filtered_batch(self, queries, allowed, max_search, k, max_expand=0, status=False):
+        """Every shard's filtered walk under its slice of `allowed` (see `_filter_arg`), merged by (distance, global id):
+        ids [nq, k] u64, dists [nq, k] f32, counts [nq] u32, and with status=True the four folded status words ([1] walks
+        the exact walker served, [3] walks max_expand cut, over all shards). max_expand caps each shard's walk."""
+        q, k = self._queries(queries), int(k)
+        owner, fptr, stride = self._filter_arg(allowed, q.shape[0])
+        out = self._run(q, k, lambda dq, di, dd, dc, ds: self._lib.granne_hip_sharded_search_filtered_batch_device(
+            self._h, C.c_void_p(dq), q.shape[0], int(max_search), k, C.c_void_p(fptr), stride, int(max_expand), C.c_void_p(di),
+            C.c_void_p(dd), C.c_void_p(dc), C.c_void_p(ds), None),
+            "%d: a shard's exact-search scratch is exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)", status)
+        del owner
+        return out
+
+    def exact_topk(self, queries, k, stats=False):
+        """The k nearest rows of the whole partitioned set, exact: what Granne.exact_topk gives over the concatenated rows,
+        global ids. A query that overflowed in any shard has count 0 and a filled row; that raises
+        GranneHipError(ERR_OVERFLOW) unless stats=True, which returns the four status words as a fourth value."""
+        q, k = self._queries(queries), int(k)
+        return self._run(q, k, lambda dq, di, dd, dc, ds: self._lib.granne_hip_sharded_exact_topk_device(
+            self._h, C.c_void_p(dq), q.shape[0], k, C.c_void_p(di), C.c_void_p(dd), C.c_void_p(dc), C.c_void_p(ds), None),
+            "sharded exact_topk: %d queries overflowed the selection in a shard", stats)
+
+    def exact_topk_filtered(self, queries, k, allowed, stats=False):
+        """exact_topk among the global ids `allowed` lets through (see `_filter_arg`); with one shared filter status[3] is
+        the number of allowed ids of the whole set. Overflow and stats as `exact_topk`."""
+        q, k = self._queries(queries), int(k)
+        owner, fptr, stride = self._filter_arg(allowed, q.shape[0])
+        out = self._run(q, k, lambda dq, di, dd, dc, ds: self._lib.granne_hip_sharded_exact_topk_filtered_device(
+            self._h, C.c_void_p(dq), q.shape[0], k, C.c_void_p(fptr), stride, C.c_void_p(di), C.c_void_p(dd), C.c_void_p(dc),
+            C.c_void_p(ds), None), "sharded exact_topk_filtered: %d queries overflowed the selection in a shard", stats)
+        del owner
+        return out
+
 
 def replica_query_rows(rank, world_size, n_batches, batch):
     """Replica mode (bench.py --gpus N): rank r searches rows [r*n_batches*batch, (r+1)*...) of the

@@ -598,7 +598,77 @@ public:
         return out;
     }
 
+    // the bits of a global filter: max over the shards of offset + rows (granne_hip_sharded_id_span)
+    size_t id_span() const { return (size_t)granne_hip_sharded_id_span(h_.get()); }
+
+    // `search` among the GLOBAL ids `allowed` lets through (a Filter over id_span() ids on the handle's device): every
+    // shard walks under its slice of the bitmap, the results are merged by (distance, global id); max_expand > 0 caps each
+    // shard's walk
+    std::vector<std::vector<std::pair<size_t, float>>> search_filtered(const Element* elements, size_t nq, const Filter& allowed,
+                                                                       size_t max_search, size_t num_neighbors,
+                                                                       uint64_t max_expand = 0) const {
+        check_filter(allowed);
+        return run(elements, nq, num_neighbors, "a shard's exact-search scratch is exhausted (raise GRANNE_HIP_OPT_SLOW_SLOTS)",
+                   [&](const void* q, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* st) {
+                       return granne_hip_sharded_search_filtered_batch_device(h_.get(), q, (uint32_t)nq, (uint32_t)max_search, (uint32_t)num_neighbors,
+                                                                              allowed.words(), 0, max_expand, ids, ds, counts, st, nullptr);
+                   });
+    }
+    // the k (up to 1024, n_shards * k up to 4096) nearest rows of the whole partitioned set, exact
+    // (granne_hip_sharded_exact_topk_device); throws when a query overflowed the selection in a shard
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk(const Element* elements, size_t nq, size_t k) const {
+        return run(elements, nq, k, "sharded exact_topk: a query overflowed the selection in a shard",
+                   [&](const void* q, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* st) {
+                       return granne_hip_sharded_exact_topk_device(h_.get(), q, (uint32_t)nq, (uint32_t)k, ids, ds, counts, st, nullptr);
+                   });
+    }
+    // the same among the global ids `allowed` lets through
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_filtered(const Element* elements, size_t nq, size_t k,
+                                                                           const Filter& allowed) const {
+        check_filter(allowed);
+        return run(elements, nq, k, "sharded exact_topk_filtered: a query overflowed the selection in a shard",
+                   [&](const void* q, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* st) {
+                       return granne_hip_sharded_exact_topk_filtered_device(h_.get(), q, (uint32_t)nq, (uint32_t)k, allowed.words(), 0, ids, ds,
+                                                                            counts, st, nullptr);
+                   });
+    }
+
 private:
+    // queries up, one device call (queries, ids, dists, counts, status), results down as lists; `overflow`: status[0] != 0
+    template <class Call>
+    std::vector<std::vector<std::pair<size_t, float>>> run(const Element* elements, size_t nq, size_t k, const char* overflow, Call call) const {
+        const size_t dim = granne_hip_index_dim(granne_hip_sharded_shard(h_.get(), 0));
+        const int device = granne_hip_sharded_device(h_.get());
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_st = o_c + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_out.upload(host.data(), total);
+        char* const o = (char*)d_out.get();
+        const int rc = call(d_q.get(), (uint64_t*)o, (float*)(o + o_d), (uint32_t*)(o + o_c), (uint32_t*)(o + o_st));
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error(overflow);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+    void check_filter(const Filter& allowed) const {
+        if (allowed.len() != id_span() || allowed.device() != granne_hip_sharded_device(h_.get()))
+            throw std::runtime_error("the filter must cover the partitioned index's id_span() ids on its device");
+    }
     ShardedGranne() = default;
     std::vector<Granne<Elements>> shards_; // empty when the handle owns its shards (build)
     std::shared_ptr<granne_hip_sharded> h_;

@@ -920,6 +920,58 @@ int granne_hip_exact_topk_filtered(const granne_hip_index* index, const void* qu
                                    const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
                                    float* out_dists, uint32_t* out_counts, uint32_t* out_status);
 
+/* ---- partitioned indexes: filters and the exact selection over GLOBAL ids ----
+ * A bitmap slice: output bit i (i < n_out_bits) of filter f is source bit first_bit + i of filter f; source bits at
+ * positions >= n_bits read as 0 and no source word at or past ceil(n_bits / 32) is read; the bits past n_out_bits of the
+ * last output word are written as 0, so slices compare bytewise. Filter f is d_filter + f * filter_stride_words
+ * (filter_stride_words == 0: one filter only) and goes to d_out + f * out_stride_words, out_stride_words >=
+ * ceil(n_out_bits / 32). Stream-ordered, nothing is read back; n_out_bits == 0 does nothing. GRANNE_HIP_ERR_INVALID:
+ * first_bit > n_bits, and for a non-empty slice n_filters == 0, a null pointer or a stride that is too small.           */
+int granne_hip_filter_slice_device(const uint32_t* d_filter, uint64_t n_bits, uint64_t filter_stride_words,
+                                   uint32_t n_filters, uint64_t first_bit, uint64_t n_out_bits, uint32_t* d_out,
+                                   uint64_t out_stride_words, int device_id, void* stream);
+/* max over the shards of id_offsets[s] + granne_hip_index_num_elements(shard s): the bits of a global filter. It has
+ * ceil(id_span / 32) words (or nq * filter_stride_words), laid out as for filtered search, on granne_hip_sharded_device.
+ * Bits of ids in gaps between shards are ignored. Shard s searches under the bits [id_offsets[s], id_offsets[s] +
+ * num_elements) -- a pointer into the caller's words where it can be, else a slice made on the shard's stream.          */
+uint64_t granne_hip_sharded_id_span(const granne_hip_sharded* sharded);
+/* Every shard's granne_hip_search_filtered_batch_device under its slice, merged by (dist, global id): count[q] =
+ * min(num_neighbors, sum of the shards' counts). max_expand caps each shard's walk separately. d_status (u32[4],
+ * optional, zeroed by the caller): [0] |=, [1] +=, [2] += as granne_hip_sharded_search_batch_device, [3] += walks cut by
+ * max_expand, over all shards. Refused before anything is enqueued: what the single index refuses (max_search == 0, a
+ * null filter, a stride that is neither 0 nor >= ceil(id_span / 32), compact SumEmbeddings shards) and n_shards *
+ * num_neighbors > 4096. nq == 0 does nothing. Full calls only (no begin / end pair).                                    */
+int granne_hip_sharded_search_filtered_batch_device(granne_hip_sharded* sharded, const void* d_queries, uint32_t nq,
+                                                    uint32_t max_search, uint32_t num_neighbors, const uint32_t* d_filter,
+                                                    uint64_t filter_stride_words, uint64_t max_expand, uint64_t* d_out_ids,
+                                                    float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status,
+                                                    void* stream);
+/* host buffers (synchronous), the filter's words on the host; out_status u32[4] (optional), written;
+ * GRANNE_HIP_ERR_OVERFLOW as granne_hip_sharded_search_batch                                                           */
+int granne_hip_sharded_search_filtered_batch(granne_hip_sharded* sharded, const void* queries, uint32_t nq,
+                                             uint32_t max_search, uint32_t num_neighbors, const uint32_t* filter,
+                                             uint64_t filter_stride_words, uint64_t max_expand, uint64_t* out_ids,
+                                             float* out_dists, uint32_t* out_counts, uint32_t* out_status);
+/* granne_hip_exact_topk / granne_hip_exact_topk_filtered over the whole partitioned set: every shard selects its k, the
+ * merge keeps the k best by (distance bits, global id). The result is the scan's over the concatenated rows: count =
+ * min(k, rows) or min(k, allowed rows), the places past it UINT64_MAX / +inf. A query whose selection overflowed in ANY
+ * shard has count 0 and a filled row -- never a list that misses one shard's rows. k <= GRANNE_HIP_EXACT_TOPK_KMAX and
+ * n_shards * k <= 4096. d_status (u32[4], optional, zeroed by the caller): [0] += queries voided in the merged result,
+ * [1] += the shards' [1], [2] = max of the shards' [2], [3] += the shards' list lengths (one shared filter: the allowed
+ * ids of the whole set). The host forms return GRANNE_HIP_ERR_OVERFLOW, outputs written, when [0] != 0.               */
+int granne_hip_sharded_exact_topk_device(granne_hip_sharded* sharded, const void* d_queries, uint32_t nq, uint32_t k,
+                                         uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                         uint32_t* d_status, void* stream);
+int granne_hip_sharded_exact_topk(granne_hip_sharded* sharded, const void* queries, uint32_t nq, uint32_t k,
+                                  uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status);
+int granne_hip_sharded_exact_topk_filtered_device(granne_hip_sharded* sharded, const void* d_queries, uint32_t nq,
+                                                  uint32_t k, const uint32_t* d_filter, uint64_t filter_stride_words,
+                                                  uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                                  uint32_t* d_status, void* stream);
+int granne_hip_sharded_exact_topk_filtered(granne_hip_sharded* sharded, const void* queries, uint32_t nq, uint32_t k,
+                                           const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
+                                           float* out_dists, uint32_t* out_counts, uint32_t* out_status);
+
 /* ---- options (per index) ---------------------------------------------------------------------- */
 enum {
     GRANNE_HIP_OPT_VISITED_SLOTS = 1, /* LDS visited-table slots per query: 2^k or 3 * 2^k in [256, 32768]; 0 = auto */

@@ -227,6 +227,26 @@ extern "C" {
     fn granne_hip_exact_topk_filtered(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
         out_status: *mut u32) -> c_int;
+    // partitioned indexes: the bitmap slice, filtered search and the exact selection over global ids
+    fn granne_hip_filter_slice_device(d_filter: *const u32, n_bits: u64, filter_stride_words: u64, n_filters: u32,
+        first_bit: u64, n_out_bits: u64, d_out: *mut u32, out_stride_words: u64, device_id: c_int, stream: *mut c_void) -> c_int;
+    fn granne_hip_sharded_id_span(sharded: *const granne_hip_sharded) -> u64;
+    fn granne_hip_sharded_search_filtered_batch_device(sharded: *mut granne_hip_sharded, d_queries: *const c_void, nq: u32,
+        max_search: u32, num_neighbors: u32, d_filter: *const u32, filter_stride_words: u64, max_expand: u64,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_sharded_search_filtered_batch(sharded: *mut granne_hip_sharded, queries: *const c_void, nq: u32,
+        max_search: u32, num_neighbors: u32, filter: *const u32, filter_stride_words: u64, max_expand: u64,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_sharded_exact_topk_device(sharded: *mut granne_hip_sharded, d_queries: *const c_void, nq: u32, k: u32,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_sharded_exact_topk(sharded: *mut granne_hip_sharded, queries: *const c_void, nq: u32, k: u32,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_sharded_exact_topk_filtered_device(sharded: *mut granne_hip_sharded, d_queries: *const c_void, nq: u32,
+        k: u32, d_filter: *const u32, filter_stride_words: u64, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_sharded_exact_topk_filtered(sharded: *mut granne_hip_sharded, queries: *const c_void, nq: u32, k: u32,
+        filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_status: *mut u32) -> c_int;
 }
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
@@ -1181,6 +1201,57 @@ impl<E: GpuElements> GpuShardedGranne<E> {
             max_search as u32, out.k as u32, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })
     }
     pub fn device(&self) -> i32 { unsafe { granne_hip_sharded_device(self.handle) } }
+    /// `granne_hip_sharded_id_span`: the bits of a global filter, max over the shards of offset + rows.
+    pub fn id_span(&self) -> usize { unsafe { granne_hip_sharded_id_span(self.handle) as usize } }
+    fn upload_queries(&self, elements: &[E::Vector], stream: &Stream) -> std::io::Result<DeviceBuffer<u8>> {
+        let mut q = Vec::new();
+        for e in elements { assert_eq!(E::query_len(e), self.dim); E::append_query(&mut q, e); }
+        let buf = DeviceBuffer::<u8>::new(q.len().max(1), self.device())?;
+        buf.copy_from(&q, stream)?;
+        stream.synchronize()?; // (`q` is dropped at the end of this function: the copy has to be over)
+        Ok(buf)
+    }
+    /// `granne_hip_sharded_search_filtered_batch_device`: `search_batch` among the GLOBAL ids `filter` allows (one bitmap
+    /// over `id_span()` ids on `device()`): every shard walks under its slice, merged by (distance, global id).
+    /// `max_expand > 0` caps each shard's walk.
+    pub fn search_filtered(&mut self, elements: &[E::Vector], filter: &GpuFilter, max_search: usize, num_neighbors: usize,
+                           max_expand: u64) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        if nq == 0 { return Ok(Vec::new()); }
+        assert_eq!(filter.len(), self.id_span());
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let out = DeviceResults::new(nq, num_neighbors, self.device())?;
+        check(unsafe { granne_hip_sharded_search_filtered_batch_device(self.handle, q.ptr as *const c_void, nq as u32,
+            max_search as u32, num_neighbors as u32, filter.words.ptr as *const u32, 0, max_expand, out.ids.ptr, out.dists.ptr,
+            out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
+    /// `granne_hip_sharded_exact_topk`: the `k` nearest rows of the whole partitioned set, exact, global ids
+    /// (`k <= 1024`, `num_shards() * k <= 4096`). An error when a query overflowed the selection in a shard.
+    pub fn exact_topk(&mut self, elements: &[E::Vector], k: usize) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        let mut q = Vec::new();
+        for e in elements { assert_eq!(E::query_len(e), self.dim); E::append_query(&mut q, e); }
+        let (mut ids, mut ds) = (vec![0u64; nq * k], vec![0f32; nq * k]);
+        let mut counts = vec![0u32; nq];
+        check(unsafe { granne_hip_sharded_exact_topk(self.handle, q.as_ptr() as *const c_void, nq as u32, k as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
+    }
+    /// `granne_hip_sharded_exact_topk_filtered_device`: `exact_topk` among the global ids `filter` allows.
+    pub fn exact_topk_filtered(&mut self, elements: &[E::Vector], k: usize, filter: &GpuFilter)
+        -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        if nq == 0 { return Ok(Vec::new()); }
+        assert_eq!(filter.len(), self.id_span());
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let out = DeviceResults::new(nq, k, self.device())?;
+        check(unsafe { granne_hip_sharded_exact_topk_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
+            filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
     /// `granne_hip_sharded_begin_device` / `_end_device`: batch b + 1 is searched while batch b is exchanged and merged.
     /// The ticket's borrow keeps the buffers alive; `ShardedInFlight::end` (or drop) orders `stream` after the merge.
     pub fn begin<'a>(&'a self, queries: &'a DeviceBuffer<u8>, nq: usize, max_search: usize, out: &'a mut DeviceResults,
