@@ -27,6 +27,9 @@ OPT_FORCE_GENERAL = 21  # 1: no register walker (tests and measurement: the unfi
  SCAN_F32_100_2, SCAN_F32_128_1) = range(11)
 EXACT_TOPK_KMAX = 1024  # GRANNE_HIP_EXACT_TOPK_KMAX
 EXACT_TOPK_CAP = 4096  # GRANNE_HIP_EXACT_TOPK_CAP: candidates ranked per query
+PF_MAX_STAGES = 8  # GRANNE_HIP_PF_MAX_STAGES: post-filtered search (Granne.search_postfiltered_batch)
+PF_FALLBACK_SHORT, PF_FALLBACK_EXACT = 0, 1  # GRANNE_HIP_PF_FALLBACK_*
+PF_STAGE_EXACT, PF_STAGE_SHORT = 0xFFFFFFFF, 0xFFFFFFFE  # GRANNE_HIP_PF_STAGE_*: out_stage of a query no stage finished
 COALESCE_CALL_MAX = 64  # GRANNE_HIP_COALESCE_CALL_MAX
 COALESCE_MAX = 1024  # GRANNE_HIP_COALESCE_MAX
 WALKER_NONE, WALKER_REGISTER, WALKER_REGISTER_WIDE, WALKER_GENERAL, WALKER_EXACT = 0, 1, 2, 3, 4
@@ -238,6 +241,8 @@ SIGNATURES = {
     "granne_hip_filter_to_ids_device": (i32, [vp, u64, vp, vp, i32, vp]),
     "granne_hip_exact_topk_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
+    "granne_hip_search_postfiltered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_search_postfiltered_batch": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp]),
     "granne_hip_filter_slice_device": (i32, [vp, u64, u64, u32, u64, u64, vp, u64, i32, vp]),
     "granne_hip_sharded_id_span": (u64, [vp]),
     "granne_hip_sharded_search_filtered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp]),

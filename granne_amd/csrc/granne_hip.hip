@@ -2473,3 +2473,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // partitioned indexes: filtered search and the exact selection over global ids
 // ------------------------------------------------------------------------------------------------
 #include "sharded_ops_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// post-filtered search: staged over-fetch on the ordinary search, the exact scan for what is left
+// ------------------------------------------------------------------------------------------------
+#include "postfilter_host.h"

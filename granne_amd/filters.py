@@ -16,6 +16,43 @@ def filter_words(n):
     return int(w.value)
 
 
+PF_MAX_STAGES = 8  # GRANNE_HIP_PF_MAX_STAGES
+# postfilter_stages' default over-fetch: the smallest margin of tools/postfilter_bench.py's sweep whose recall is not
+# below the filtered walk's at selectivity 0.1 and 0.01 (profiles/postfiltered_search.json): every margin
+# of the sweep, 1.0 included, reached it on f32 and on int8 rows
+PF_DEFAULT_MARGIN = 1.0
+
+
+def postfilter_stages(min_allowed, selectivity=None, e_max=8192, n_stages=4, margin=PF_DEFAULT_MARGIN):
+    """The stages E_0 < E_1 < .. of a post-filtered search (Granne.search_postfiltered_batch): list lengths of the ordinary
+    search, tried in turn by the queries whose list held fewer than min_allowed allowed ids. Pure Python.
+
+    With a selectivity (the allowed share of the ids, 0..1): a list of E holds about E * selectivity allowed ids, so
+    E_0 = margin * min_allowed / selectivity, rounded up to a multiple of 64 and kept within [min_allowed, e_max], then
+    doubled up to e_max. Without one: min_allowed * (1, 4, 16, 64), capped at e_max. Always strictly ascending, at most
+    min(n_stages, 8) entries, E_0 >= min_allowed."""
+    min_allowed, e_max, n_stages = int(min_allowed), int(e_max), int(n_stages)
+    if min_allowed < 1 or n_stages < 1 or margin <= 0:
+        raise ValueError("min_allowed >= 1, n_stages >= 1 and margin > 0")
+    if selectivity is not None and not 0.0 <= selectivity <= 1.0:
+        raise ValueError("selectivity is a share: 0..1")
+    e_max = max(e_max, min_allowed)
+    n_stages = min(n_stages, PF_MAX_STAGES)
+    if selectivity is None:
+        want = [min_allowed * 4 ** i for i in range(n_stages)]
+    else:
+        e0 = e_max if selectivity * e_max <= margin * min_allowed else -(-margin * min_allowed / selectivity // 64) * 64
+        e0 = min(max(int(e0), min_allowed), e_max)
+        want = [e0 << i for i in range(n_stages)]
+    out = []
+    for e in want:
+        e = min(e, e_max)
+        if out and e <= out[-1]:
+            break
+        out.append(e)
+    return out
+
+
 class _DeviceBlock:
     """Device memory from granne_hip_device_malloc, freed with the object."""
 

@@ -531,6 +531,78 @@ class Granne:
             int(filter_stride_words), int(max_expand), C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts),
             C.c_void_p(d_stats), C.c_void_p(d_status), C.c_void_p(stream)))
 
+    # ---- post-filtered search: staged over-fetch on the ordinary search (include/granne_hip.h) ------
+    def search_postfiltered(self, element, num_elements, allowed, min_allowed=50, stages=None, fallback="exact", prepared=True):
+        """`search_postfiltered_batch` for one query: [(id, distance)] ascending by (distance, id)."""
+        terms = self.element_type == EMBEDDINGS and (len(element) == 0 or np.asarray(element).dtype.kind in "iu")
+        one = [list(element)] if terms else np.asarray(element).reshape(1, -1)
+        ids, dists, counts = self.search_postfiltered_batch(one, num_elements, allowed, min_allowed, stages, fallback, prepared=prepared)
+        return [(int(ids[0, i]), float(dists[0, i])) for i in range(int(counts[0]))]
+
+    def search_postfiltered_batch(self, queries, num_elements, allowed, min_allowed=50, stages=None, fallback="exact", scratch_bytes=0,
+                                  return_stage=False, status=False, prepared=True):
+        """The k = num_elements nearest ALLOWED ids by the ordinary search with a long list and a filter of its result
+        (granne_hip_search_postfiltered_batch_device): a query's list of stages[s] entries answers it once it holds
+        min_allowed allowed ids (or the walk ran out of graph), else the query goes on to the next stage; what no stage
+        finishes gets the exact scan under the filter (fallback="exact") or its short answer (fallback="short").
+        `allowed`: see `_filter_arg`. stages=None: `filters.postfilter_stages`, from the filter's count where one filter
+        serves all queries. Returns ids [nq,k] uint64, dists [nq,k] float32, counts [nq] uint32, then the stage that answered
+        each query (return_stage=True; _lib.PF_STAGE_EXACT / PF_STAGE_SHORT for the fallback) and the four status words --
+        [3] the queries no stage finished -- (status=True)."""
+        from ._lib import OK, PF_FALLBACK_EXACT, PF_FALLBACK_SHORT
+        from .filters import Filter, _DeviceBlock, postfilter_stages
+        q = self._prepare(queries, prepared)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        fb = {"exact": PF_FALLBACK_EXACT, "short": PF_FALLBACK_SHORT}.get(fallback, fallback)
+        nq, k = q.shape[0], int(num_elements)
+        owner, fptr, stride = self._filter_arg(allowed, nq, self.num_elements())
+        if stages is None:
+            sel = owner.count() / max(owner.n, 1) if isinstance(owner, Filter) else None
+            stages = postfilter_stages(int(min_allowed), sel)
+        st_arr = (C.c_uint32 * max(len(stages), 1))(*[int(e) for e in stages])
+        up = lambda v: (v + 255) & ~255  # noqa: E731
+        o_ids = up(q.nbytes)
+        o_d = o_ids + up(nq * max(k, 0) * 8)
+        o_c = o_d + up(nq * max(k, 0) * 4)
+        o_sg = o_c + up(nq * 4)
+        o_st = o_sg + up(nq * 4)
+        block = _DeviceBlock(o_st + 16, self.device)
+        host = np.zeros(o_st + 16, np.uint8)
+        host[:q.nbytes] = q.view(np.uint8).reshape(-1)
+        block.upload(host)
+        rc = lib().granne_hip_search_postfiltered_batch_device(
+            self._h, C.c_void_p(block.ptr), nq, k, int(min_allowed), st_arr, len(stages), int(fb), C.c_void_p(fptr), stride,
+            int(scratch_bytes), C.c_void_p(block.ptr + o_ids), C.c_void_p(block.ptr + o_d), C.c_void_p(block.ptr + o_c),
+            C.c_void_p(block.ptr + o_sg), C.c_void_p(block.ptr + o_st), None)
+        check(lib().granne_hip_stream_synchronize(None, self.device))
+        check(rc)
+        host = block.download(np.uint8, o_st + 16)
+        del owner
+        st4 = host[o_st:o_st + 16].view(np.uint32).copy()
+        if st4[0]:
+            raise GranneHipError(ERR_OVERFLOW, "search_postfiltered: a walk ran out of exact-search scratch (raise "
+                                 "GRANNE_HIP_OPT_SLOW_SLOTS) or the fallback's selection overflowed")
+        out = [host[o_ids:o_ids + nq * k * 8].view(np.uint64).reshape(nq, k).copy(),
+               host[o_d:o_d + nq * k * 4].view(np.float32).reshape(nq, k).copy(),
+               host[o_c:o_c + nq * 4].view(np.uint32).copy()]
+        if return_stage:
+            out.append(host[o_sg:o_sg + nq * 4].view(np.uint32).copy())
+        if status:
+            out.append(st4)
+        return tuple(out)
+
+    def search_postfiltered_batch_device(self, d_queries, nq, num_elements, min_allowed, stages, fallback, d_filter,
+                                         filter_stride_words, d_ids, d_dists, d_counts, d_stage=0, d_status=0, scratch_bytes=0,
+                                         stream=0):
+        """Device-resident variant: raw device pointers (int); `stages` a sequence on the host, `fallback`
+        _lib.PF_FALLBACK_*. Stream-ordered, but the call waits on `stream` once per stage it goes beyond."""
+        st_arr = (C.c_uint32 * max(len(stages), 1))(*[int(e) for e in stages])
+        check(lib().granne_hip_search_postfiltered_batch_device(
+            self._h, C.c_void_p(d_queries), int(nq), int(num_elements), int(min_allowed), st_arr, len(stages), int(fallback),
+            C.c_void_p(d_filter), int(filter_stride_words), int(scratch_bytes), C.c_void_p(d_ids), C.c_void_p(d_dists),
+            C.c_void_p(d_counts), C.c_void_p(d_stage), C.c_void_p(d_status), C.c_void_p(stream)))
+
     def search_batches_device(self, d_queries, nq, max_search, num_elements, d_ids, d_dists, d_counts, d_stats=None,
                               d_status=0, stream=0):
         """Several batches of nq queries through ONE launch (granne_hip_search_batches_device). d_queries, d_ids,

@@ -406,6 +406,54 @@ public:
         return out;
     }
 
+    // The num_neighbors nearest ALLOWED ids by the ordinary search with a long list and a filter of its result
+    // (granne_hip.h, "post-filtered search"): a query's list of stages[s] entries answers it once it holds min_allowed
+    // allowed ids or the walk ran out of graph, else the query goes on to the next stage; what no stage finishes gets the
+    // exact scan under the filter (GRANNE_HIP_PF_FALLBACK_EXACT) or its short answer (_SHORT). out_stage (optional): the
+    // stage that answered each query, or GRANNE_HIP_PF_STAGE_EXACT / _SHORT.
+    std::vector<std::vector<std::pair<size_t, float>>> search_postfiltered(const Element* elements, size_t nq, size_t num_neighbors,
+                                                                           const Filter& allowed, size_t min_allowed,
+                                                                           const std::vector<uint32_t>& stages,
+                                                                           int fallback = GRANNE_HIP_PF_FALLBACK_EXACT,
+                                                                           std::vector<uint32_t>* out_stage = nullptr,
+                                                                           uint64_t scratch_bytes = 0) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed.len() != num_elements() || allowed.device() != device)
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t k = num_neighbors, qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_sg = o_c + nq * 4, o_st = o_sg + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_out.upload(host.data(), total);
+        char* const o = (char*)d_out.get();
+        int rc = granne_hip_search_postfiltered_batch_device(h_.get(), d_q.get(), (uint32_t)nq, (uint32_t)k, (uint32_t)min_allowed, stages.data(),
+                                                             (uint32_t)stages.size(), fallback, allowed.words(), 0, scratch_bytes, (uint64_t*)o,
+                                                             (float*)(o + o_d), (uint32_t*)(o + o_c), (uint32_t*)(o + o_sg), (uint32_t*)(o + o_st),
+                                                             nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (out_stage) out_stage->assign(nq, 0);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        if (*(const uint32_t*)(host.data() + o_st))
+            throw std::runtime_error("search_postfiltered: a walk ran out of exact-search scratch or the fallback's selection overflowed");
+        if (out_stage) std::memcpy(out_stage->data(), host.data() + o_sg, nq * 4);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // A handle over the rows alone (no layers): what RefinedGranne re-ranks by; get_element and the distance operators work
     static Granne from_elements(const Elements& elements, int device = 0) {
         granne_hip_index* h = nullptr;

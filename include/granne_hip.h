@@ -920,6 +920,65 @@ int granne_hip_exact_topk_filtered(const granne_hip_index* index, const void* qu
                                    const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
                                    float* out_dists, uint32_t* out_counts, uint32_t* out_status);
 
+/* ---- post-filtered search: staged over-fetch on the ordinary search -----------
+ * "The nearest neighbours among the ids this bitmap allows", answered by the ORDINARY search with a long list and a filter
+ * of its result: no walker knows about the filter, so the register walkers serve it, and so do GRANNE_HIP_F16 and compact
+ * SumEmbeddings handles. The filter is laid out as for filtered search (one bitmap, or one per query with
+ * filter_stride_words). k = num_neighbors; min_allowed: how many allowed ids a walk's list must hold before its first k
+ * count as the answer (what max_search means to the filtered walk, whose `res` holds max_search allowed keys); stages: an
+ * ascending list E_0 < E_1 < ... of list lengths, on the HOST. The model is the definition:
+ *     postfiltered(q):
+ *       for s in 0 .. n_stages-1:
+ *           L = Granne::search(q, max_search = E_s, num_neighbors = E_s)     the ordinary search, unfiltered
+ *           A = [x for x in L if allowed(x.id)]                              order of L kept: ascending (dist, id)
+ *           if len(A) >= min_allowed or len(L) < E_s:                        enough allowed ids, or the walk ran out of graph
+ *               return A[:k], stage = s
+ *       if fallback == EXACT: return exact_topk_filtered(q, k), stage = GRANNE_HIP_PF_STAGE_EXACT
+ *       else:                 return A[:k] of the last stage, stage = GRANNE_HIP_PF_STAGE_SHORT
+ * Escalation is per query: a stage runs only the queries the stages before it did not finish. count = min(k, len(A)) (the
+ * exact scan's count in the fallback); unused places are UINT64_MAX / +inf. All bits set: every query ends at stage 0, and
+ * the result is granne_hip_search_batch(E_0, k) bit for bit. Nothing allowed: count 0 and GRANNE_HIP_OK. Bits at positions
+ * >= len are ignored; slots of L past its count are never bit-tested.
+ *   stages               HOST array of n_stages (1 .. GRANNE_HIP_PF_MAX_STAGES) values, strictly ascending, none 0
+ *   fallback             GRANNE_HIP_PF_FALLBACK_EXACT: granne_hip_exact_topk_filtered_device on the unfinished queries (the
+ *                        list form for one bitmap, the bit-tested form for per-query bitmaps); it inherits that entry's
+ *                        limits. GRANNE_HIP_PF_FALLBACK_SHORT: the last stage's allowed entries, fewer than min_allowed
+ *   scratch_bytes        bound on the stage lists' scratch (12 * E_s bytes per pending query): the pending queries are
+ *                        taken in chunks that fit; 0 = 256 MiB; never below one query's list. Same result for any value
+ *   d_out_stage          u32[nq], optional: the stage that answered the query, or GRANNE_HIP_PF_STAGE_EXACT / _SHORT
+ *   d_status             u32[4], optional, zeroed by the caller: [0], [1], [2] accumulate over the stages' searches as for
+ *                        granne_hip_search_batch_device ([0] also += the fallback scan's overflowed queries); [3] += the
+ *                        queries no stage finished
+ * Refused with GRANNE_HIP_ERR_INVALID, each with its own message: n_stages 0 or > GRANNE_HIP_PF_MAX_STAGES; stages null, not
+ * strictly ascending or containing 0; num_neighbors == 0; num_neighbors > min_allowed; min_allowed > stages[0]; a fallback
+ * outside {0, 1}; EXACT with num_neighbors > GRANNE_HIP_EXACT_TOPK_KMAX; a null index (also with nq == 0); a null filter; a
+ * filter_stride_words that is neither 0 nor >= ceil(len / 32); EXACT on a handle the exact scan refuses (GRANNE_HIP_F16,
+ * compact SumEmbeddings). nq == 0 otherwise does nothing.
+ * The device entry is stream-ordered but WAITS on `stream` once per stage it goes beyond: the number of pending queries
+ * (one u32) is read back to size the next stage and to stop at 0. After the last stage nothing is read back with SHORT; with
+ * EXACT one count sizes the scan. Scratch comes from hipMallocAsync on `stream`. GRANNE_HIP_OPT_LAST_WALKER reports the last
+ * stage's walker. */
+#define GRANNE_HIP_PF_MAX_STAGES 8
+#define GRANNE_HIP_PF_FALLBACK_SHORT 0
+#define GRANNE_HIP_PF_FALLBACK_EXACT 1
+#define GRANNE_HIP_PF_STAGE_EXACT 0xFFFFFFFFu
+#define GRANNE_HIP_PF_STAGE_SHORT 0xFFFFFFFEu
+int granne_hip_search_postfiltered_batch_device(const granne_hip_index* index, const void* d_queries, uint32_t nq,
+                                                uint32_t num_neighbors, uint32_t min_allowed, const uint32_t* stages,
+                                                uint32_t n_stages, int fallback, const uint32_t* d_filter,
+                                                uint64_t filter_stride_words, uint64_t scratch_bytes, uint64_t* d_out_ids,
+                                                float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_stage,
+                                                uint32_t* d_status, void* stream);
+/* the same with host buffers in and out (synchronous), the filter's words on the host (ceil(len / 32), or nq *
+ * filter_stride_words); out_stage optional; out_status u32[4] (optional), written, not accumulated.
+ * GRANNE_HIP_ERR_OVERFLOW, outputs written, when status[0] != 0. These calls never take part in GRANNE_HIP_OPT_COALESCE. */
+int granne_hip_search_postfiltered_batch(const granne_hip_index* index, const void* queries, uint32_t nq,
+                                         uint32_t num_neighbors, uint32_t min_allowed, const uint32_t* stages,
+                                         uint32_t n_stages, int fallback, const uint32_t* filter,
+                                         uint64_t filter_stride_words, uint64_t scratch_bytes, uint64_t* out_ids,
+                                         float* out_dists, uint32_t* out_counts, uint32_t* out_stage,
+                                         uint32_t* out_status);
+
 /* ---- partitioned indexes: filters and the exact selection over GLOBAL ids ----
  * A bitmap slice: output bit i (i < n_out_bits) of filter f is source bit first_bit + i of filter f; source bits at
  * positions >= n_bits read as 0 and no source word at or past ceil(n_bits / 32) is read; the bits past n_out_bits of the

@@ -247,7 +247,22 @@ extern "C" {
     fn granne_hip_sharded_exact_topk_filtered(sharded: *mut granne_hip_sharded, queries: *const c_void, nq: u32, k: u32,
         filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
         out_status: *mut u32) -> c_int;
+    // post-filtered search: staged over-fetch on the ordinary search
+    fn granne_hip_search_postfiltered_batch_device(index: *const granne_hip_index, d_queries: *const c_void,
+        nq: u32, num_neighbors: u32, min_allowed: u32, stages: *const u32, n_stages: u32, fallback: c_int,
+        d_filter: *const u32, filter_stride_words: u64, scratch_bytes: u64, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_stage: *mut u32, d_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_search_postfiltered_batch(index: *const granne_hip_index, queries: *const c_void, nq: u32,
+        num_neighbors: u32, min_allowed: u32, stages: *const u32, n_stages: u32, fallback: c_int,
+        filter: *const u32, filter_stride_words: u64, scratch_bytes: u64, out_ids: *mut u64, out_dists: *mut f32,
+        out_counts: *mut u32, out_stage: *mut u32, out_status: *mut u32) -> c_int;
 }
+pub const GRANNE_HIP_PF_MAX_STAGES: usize = 8;
+pub const GRANNE_HIP_PF_FALLBACK_SHORT: c_int = 0;
+pub const GRANNE_HIP_PF_FALLBACK_EXACT: c_int = 1;
+pub const GRANNE_HIP_PF_STAGE_EXACT: u32 = 0xFFFF_FFFF;
+pub const GRANNE_HIP_PF_STAGE_SHORT: u32 = 0xFFFF_FFFE;
 pub const GRANNE_HIP_OPT_SEARCH_DEPTH: c_int = 9;
 pub const GRANNE_HIP_OPT_INLINE_TAILS: c_int = 10;
 pub const GRANNE_HIP_OPT_SEEN_MIN: c_int = 11;
@@ -573,6 +588,25 @@ impl<E: GpuElements> GpuGranne<E> {
         let out = DeviceResults::new(nq, k, self.device())?;
         check(unsafe { granne_hip_exact_topk_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
             filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
+    /// `granne_hip_search_postfiltered_batch_device`: the `num_neighbors` nearest ids `filter` allows, by the ordinary
+    /// search with lists of `stages[s]` entries and a filter of its result. A query is answered by the first stage whose
+    /// list holds `min_allowed` allowed ids (or whose walk ran out of graph); what no stage finishes gets the exact scan
+    /// under the filter (`GRANNE_HIP_PF_FALLBACK_EXACT`) or its short answer (`_SHORT`). The call waits on its stream once
+    /// per stage it goes beyond.
+    pub fn search_postfiltered(&self, elements: &[E::Vector], num_neighbors: usize, filter: &GpuFilter, min_allowed: usize,
+                               stages: &[u32], fallback: c_int) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        if nq == 0 { return Ok(Vec::new()); }
+        assert_eq!(filter.len(), self.num_elements());
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let out = DeviceResults::new(nq, num_neighbors, self.device())?;
+        check(unsafe { granne_hip_search_postfiltered_batch_device(self.handle, q.ptr as *const c_void, nq as u32,
+            num_neighbors as u32, min_allowed as u32, stages.as_ptr(), stages.len() as u32, fallback,
+            filter.words.ptr as *const u32, 0, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(),
+            std::ptr::null_mut(), stream.raw) })?;
         out.to_host(nq, &stream)
     }
     /// Rows of the element set (at least `len()`): what `exact_topk` and `exact_topk_filtered` scan.
