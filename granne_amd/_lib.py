@@ -30,6 +30,10 @@ EXACT_TOPK_CAP = 4096  # GRANNE_HIP_EXACT_TOPK_CAP: candidates ranked per query
 PF_MAX_STAGES = 8  # GRANNE_HIP_PF_MAX_STAGES: post-filtered search (Granne.search_postfiltered_batch)
 PF_FALLBACK_SHORT, PF_FALLBACK_EXACT = 0, 1  # GRANNE_HIP_PF_FALLBACK_*
 PF_STAGE_EXACT, PF_STAGE_SHORT = 0xFFFFFFFF, 0xFFFFFFFE  # GRANNE_HIP_PF_STAGE_*: out_stage of a query no stage finished
+RANGE_CAP_MAX = 1024  # GRANNE_HIP_RANGE_CAP_MAX: range search (Granne.exact_range, Granne.search_range_batch)
+RG_MAX_STAGES = 8  # GRANNE_HIP_RG_MAX_STAGES
+RG_FALLBACK_SHORT, RG_FALLBACK_EXACT = 0, 1  # GRANNE_HIP_RG_FALLBACK_*
+RG_STAGE_EXACT, RG_STAGE_SHORT = 0xFFFFFFFF, 0xFFFFFFFE  # GRANNE_HIP_RG_STAGE_*: out_stage of a query no stage finished
 COALESCE_CALL_MAX = 64  # GRANNE_HIP_COALESCE_CALL_MAX
 COALESCE_MAX = 1024  # GRANNE_HIP_COALESCE_MAX
 WALKER_NONE, WALKER_REGISTER, WALKER_REGISTER_WIDE, WALKER_GENERAL, WALKER_EXACT = 0, 1, 2, 3, 4
@@ -243,6 +247,10 @@ SIGNATURES = {
     "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_range_device": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_range": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_search_range_batch_device": (i32, [vp, vp, u32, vp, u32, vp, u32, i32, u64, vp, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_search_range_batch": (i32, [vp, vp, u32, vp, u32, vp, u32, i32, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_filter_slice_device": (i32, [vp, u64, u64, u32, u64, u64, vp, u64, i32, vp]),
     "granne_hip_sharded_id_span": (u64, [vp]),
     "granne_hip_sharded_search_filtered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp]),

@@ -424,18 +424,12 @@ __global__ __launch_bounds__(256) void et_select_kernel(const uint32_t* hist, ui
     }
 }
 
-// One block per query: the collected keys sorted in LDS, the first k written; places past the count hold UINT64_MAX / +inf.
-// `over` (optional, u32 per query): 1 where EtSel.over voids the query, else 0 (the partitioned selection carries it on).
-__global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t* cand, const uint32_t* cnt, const EtSel* sel, uint32_t k,
-                                                                  uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
-                                                                  uint32_t* status, uint32_t* over) {
-    __shared__ uint64_t keys[ET_CAP];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    uint32_t m = cnt[q] < ET_CAP ? cnt[q] : ET_CAP;
-    if (sel[q].over) m = 0;
+// The first m (<= ET_CAP) keys of `cand` into `keys` (LDS, ET_CAP entries), sorted ascending (bitonic, padded with all-ones
+// to a power of two); every thread of a block of ET_RANK_THREADS calls it, and the keys are in place when it returns.
+__device__ __forceinline__ void et_sort_keys(uint64_t* keys, const uint64_t* cand, uint32_t m, uint32_t tid) {
     uint32_t n2 = 2;
     while (n2 < m) n2 <<= 1;
-    for (uint32_t i = tid; i < n2; i += ET_RANK_THREADS) keys[i] = i < m ? cand[(size_t)q * ET_CAP + i] : ~0ull;
+    for (uint32_t i = tid; i < n2; i += ET_RANK_THREADS) keys[i] = i < m ? cand[i] : ~0ull;
     for (uint32_t size = 2; size <= n2; size <<= 1) {
         for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
             __syncthreads();
@@ -448,6 +442,18 @@ __global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t
         }
     }
     __syncthreads();
+}
+
+// One block per query: the collected keys sorted in LDS, the first k written; places past the count hold UINT64_MAX / +inf.
+// `over` (optional, u32 per query): 1 where EtSel.over voids the query, else 0 (the partitioned selection carries it on).
+__global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t* cand, const uint32_t* cnt, const EtSel* sel, uint32_t k,
+                                                                  uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                                                  uint32_t* status, uint32_t* over) {
+    __shared__ uint64_t keys[ET_CAP];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    uint32_t m = cnt[q] < ET_CAP ? cnt[q] : ET_CAP;
+    if (sel[q].over) m = 0;
+    et_sort_keys(keys, cand + (size_t)q * ET_CAP, m, tid);
     const uint32_t count = m < k ? m : k;
     for (uint32_t i = tid; i < k; i += ET_RANK_THREADS) {
         const uint64_t key = i < count ? keys[i] : 0;

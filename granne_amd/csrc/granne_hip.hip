@@ -2478,3 +2478,9 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // post-filtered search: staged over-fetch on the ordinary search, the exact scan for what is left
 // ------------------------------------------------------------------------------------------------
 #include "postfilter_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// range search: every element within a radius, by the exact scan and by the staged walk
+// ------------------------------------------------------------------------------------------------
+#include "exact_range_host.h"
+#include "range_host.h"

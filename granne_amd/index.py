@@ -12,10 +12,13 @@ import os
 
 import numpy as np
 
-from ._lib import ERR_OVERFLOW, EXACT_TOPK_CAP, F16, F32, I8, GranneHipError, check, lib
+from ._lib import ERR_INVALID, ERR_OVERFLOW, EXACT_TOPK_CAP, F16, F32, I8, RANGE_CAP_MAX, GranneHipError, check, lib
 
 DEFAULT_MAX_SEARCH = 200   # py/src/lib.rs:14
 DEFAULT_NUM_ELEMENTS = 10  # py/src/lib.rs:15
+# search_range_batch's list lengths: of the ascending subsets of the register walkers' list sizes 60 / 124 / 252 / 508 / 1020
+# the cheapest whose recall was not below search_batch(1020, 1020)'s at any radius (tools/range_bench.py)
+RANGE_DEFAULT_STAGES = (252, 1020)
 
 # "angular_f16": rows of IEEE halves; the element a row stands for is Vector::from(widen(row)) -- normalised where it is
 # read -- and queries are prepared float32 rows, as for "angular"
@@ -749,6 +752,117 @@ class Granne:
             raise GranneHipError(ERR_OVERFLOW, "exact_topk_filtered: %d queries have more than %d rows inside one second-level "
                                  "bin at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
+
+    # ---- range search: all elements within a radius, by scan and by walk (include/granne_hip.h) -----
+    def _radii(self, radius, nq):
+        """`radius` -- a scalar or one value per query -- as float32 [nq]; a NaN is refused here as by the host entries"""
+        r = np.array(np.broadcast_to(np.asarray(radius, np.float32), (nq,)) if np.ndim(radius) == 0 else radius, np.float32, order="C")
+        if r.shape != (nq,):
+            raise ValueError("radius: a scalar or one value per query")
+        if np.isnan(r).any():
+            raise GranneHipError(ERR_INVALID, "range search: the radius of query %d is NaN" % int(np.argmax(np.isnan(r))))
+        return r
+
+    def exact_range_device(self, d_queries, nq, d_radii, max_results, d_filter, filter_stride_words, d_ids, d_dists, d_counts,
+                           d_totals, d_status=0, stream=0):
+        """Every element within d_radii[q] of query q (granne_hip_exact_range_device): raw device pointers (int); d_filter 0
+        for all rows, else as exact_topk_filtered_device. Stream-ordered, but the call waits on `stream` once."""
+        check(lib().granne_hip_exact_range_device(self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_radii), int(max_results),
+                                                  C.c_void_p(d_filter), int(filter_stride_words), C.c_void_p(d_ids),
+                                                  C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_totals),
+                                                  C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def exact_range(self, queries, radius, max_results=RANGE_CAP_MAX, allowed=None, prepared=True, stats=False):
+        """The elements within `radius` (a scalar or one value per query) of every query, exact by construction: ids
+        [nq, max_results] u64 and dists f32 -- the nearest min(total, max_results), ascending by (distance, id), the places
+        past the count UINT64_MAX / +inf --, counts [nq] u32 and totals [nq] u32, the exact number within the radius also
+        beyond max_results (up to RANGE_CAP_MAX). `allowed`: None for all rows, else what exact_topk_filtered takes. A query
+        voided by the selection's overflow (status[0]; only with total > EXACT_TOPK_CAP) has count 0 and its exact total:
+        with stats=False that raises GranneHipError(ERR_OVERFLOW); with stats=True the four status words are returned last."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        cap, nq = int(max_results), q.shape[0]
+        r = self._radii(radius, nq)
+        owner, fptr, stride = (None, 0, 0) if allowed is None else self._filter_arg(allowed, nq, self.num_elements())
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        tr = torch.from_numpy(r).to(dev)
+        ids = torch.empty((nq, max(cap, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(cap, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        tot = torch.empty(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        self.exact_range_device(tq.data_ptr(), nq, tr.data_ptr(), cap, fptr, stride, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(),
+                                tot.data_ptr(), st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        status = st.cpu().numpy().view(np.uint32)
+        out = (ids.cpu().numpy().view(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), tot.cpu().numpy().view(np.uint32))
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact_range: %d queries have more than %d rows inside one second-level bin at "
+                                 "their cap-th distance" % (int(status[0]), EXACT_TOPK_CAP))
+        return out
+
+    def search_range(self, element, radius, max_results=DEFAULT_NUM_ELEMENTS, stages=None, fallback="exact", prepared=True):
+        """`search_range_batch` for one query: [(id, distance)] ascending by (distance, id), every distance <= radius."""
+        terms = self.element_type == EMBEDDINGS and (len(element) == 0 or np.asarray(element).dtype.kind in "iu")
+        one = [list(element)] if terms else np.asarray(element).reshape(1, -1)
+        ids, dists, counts = self.search_range_batch(one, radius, max_results, stages, fallback, prepared=prepared)[:3]
+        return [(int(ids[0, i]), float(dists[0, i])) for i in range(int(counts[0]))]
+
+    def search_range_batch(self, queries, radius, max_results, stages=None, fallback="exact", scratch_bytes=0, prepared=True,
+                           stats=False):
+        """The elements within `radius` of every query by the ordinary search with a long list, cut at the radius
+        (granne_hip_search_range_batch_device): a query's list of stages[s] entries answers it once it holds an entry beyond
+        the radius (or the walk ran out of graph), else the query goes on to the next stage; what no stage finishes gets
+        the exact scan (fallback="exact") or its short answer (fallback="short"). stages=None: RANGE_DEFAULT_STAGES. Returns
+        ids [nq, max_results] uint64, dists float32, counts [nq] uint32, found [nq] uint32 (the entries within the radius
+        of the answering list, or the exact total), stage [nq] uint32 (_lib.RG_STAGE_EXACT / RG_STAGE_SHORT for the
+        fallback), then the four status words -- [3] the queries no stage finished -- (stats=True)."""
+        import torch
+        from ._lib import RG_FALLBACK_EXACT, RG_FALLBACK_SHORT
+        q = self._prepare(queries, prepared)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        fb = {"exact": RG_FALLBACK_EXACT, "short": RG_FALLBACK_SHORT}.get(fallback, fallback)
+        nq, cap = q.shape[0], int(max_results)
+        r = self._radii(radius, nq)
+        stages = RANGE_DEFAULT_STAGES if stages is None else stages
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        tr = torch.from_numpy(r).to(dev)
+        ids = torch.empty((nq, max(cap, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(cap, 0)), dtype=torch.float32, device=dev)
+        cnt, found, stage = (torch.empty(nq, dtype=torch.int32, device=dev) for _ in range(3))
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.search_range_batch_device(tq.data_ptr(), nq, tr.data_ptr(), cap, stages, fb, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(),
+                                       found.data_ptr(), stage.data_ptr(), st.data_ptr(), scratch_bytes, stream)
+        torch.cuda.synchronize(dev)
+        status = st.cpu().numpy().view(np.uint32)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "search_range: a walk ran out of exact-search scratch (raise GRANNE_HIP_OPT_SLOW_SLOTS) "
+                                 "or the fallback's selection overflowed")
+        out = (ids.cpu().numpy().view(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().view(np.uint32),
+               found.cpu().numpy().view(np.uint32), stage.cpu().numpy().view(np.uint32))
+        return out + (status,) if stats else out
+
+    def search_range_batch_device(self, d_queries, nq, d_radii, max_results, stages, fallback, d_ids, d_dists, d_counts, d_found=0,
+                                  d_stage=0, d_status=0, scratch_bytes=0, stream=0):
+        """Device-resident variant: raw device pointers (int); `stages` a sequence on the host, `fallback`
+        _lib.RG_FALLBACK_*. Stream-ordered, but the call waits on `stream` once per stage it goes beyond."""
+        st_arr = (C.c_uint32 * max(len(stages), 1))(*[int(e) for e in stages])
+        check(lib().granne_hip_search_range_batch_device(
+            self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_radii), int(max_results), st_arr, len(stages), int(fallback),
+            int(scratch_bytes), C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_found),
+            C.c_void_p(d_stage), C.c_void_p(d_status), C.c_void_p(stream)))
 
     def dists_device(self, d_queries, nq, d_ids, m, d_out, d_status=0, stream=0):
         """ElementContainer::dists (src/elements/mod.rs:35-39) batched on device: out[q, j] =

@@ -454,6 +454,39 @@ public:
         return out;
     }
 
+    // Every element within radii[i] of query i, exact by construction (granne_hip.h, "range search"): the nearest cap (up to
+    // GRANNE_HIP_RANGE_CAP_MAX) of them ascending by (distance, id); out_totals (optional): the exact number within the
+    // radius, also beyond cap. allowed: null for all rows, else the rows one bitmap allows.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_range(const Element* elements, size_t nq, const float* radii, size_t cap,
+                                                                   const Filter* allowed = nullptr,
+                                                                   std::vector<uint32_t>* out_totals = nullptr) const {
+        if (allowed && (allowed->len() != num_elements() || allowed->device() != granne_hip_index_device(h_.get())))
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        return range_call(elements, nq, radii, cap, out_totals, nullptr, "exact_range: a query has too many rows inside one second-level bin at its cap-th distance",
+                          [&](const void* q, const float* r, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* found, uint32_t*, uint32_t* status) {
+                              return granne_hip_exact_range_device(h_.get(), q, (uint32_t)nq, r, (uint32_t)cap, allowed ? allowed->words() : nullptr, 0, ids,
+                                                                   ds, counts, found, status, nullptr);
+                          });
+    }
+
+    // The elements within radii[i] of query i by the ordinary search with lists of stages[s] entries, cut at the radius
+    // (granne_hip.h, "range search"): a list answers its query once it holds an entry beyond the radius or the walk ran out
+    // of graph, else the query goes on to the next stage; what no stage finishes gets the exact scan
+    // (GRANNE_HIP_RG_FALLBACK_EXACT) or its short answer (_SHORT). out_found / out_stage (optional): the entries within the
+    // radius (the exact total after the scan), and the stage that answered, or GRANNE_HIP_RG_STAGE_EXACT / _SHORT.
+    std::vector<std::vector<std::pair<size_t, float>>> search_range(const Element* elements, size_t nq, const float* radii, size_t cap,
+                                                                    const std::vector<uint32_t>& stages,
+                                                                    int fallback = GRANNE_HIP_RG_FALLBACK_EXACT,
+                                                                    std::vector<uint32_t>* out_found = nullptr,
+                                                                    std::vector<uint32_t>* out_stage = nullptr,
+                                                                    uint64_t scratch_bytes = 0) const {
+        return range_call(elements, nq, radii, cap, out_found, out_stage, "search_range: a walk ran out of exact-search scratch or the fallback's selection overflowed",
+                          [&](const void* q, const float* r, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* found, uint32_t* stage, uint32_t* status) {
+                              return granne_hip_search_range_batch_device(h_.get(), q, (uint32_t)nq, r, (uint32_t)cap, stages.data(), (uint32_t)stages.size(),
+                                                                          fallback, scratch_bytes, ids, ds, counts, found, stage, status, nullptr);
+                          });
+    }
+
     // A handle over the rows alone (no layers): what RefinedGranne re-ranks by; get_element and the distance operators work
     static Granne from_elements(const Elements& elements, int device = 0) {
         granne_hip_index* h = nullptr;
@@ -544,6 +577,47 @@ public:
 
 private:
     static constexpr int dtype() { return detail::dtype_of<typename decltype(Element::data)::value_type>::value; }
+    // what exact_range and search_range share: queries and radii up, `call` on device buffers (ids, dists, counts, found,
+    // stage, status), the answer down; out_found / out_stage optional; a non-zero status[0] throws `overflow`
+    template <class Call>
+    std::vector<std::vector<std::pair<size_t, float>>> range_call(const Element* elements, size_t nq, const float* radii, size_t cap,
+                                                                  std::vector<uint32_t>* out_found, std::vector<uint32_t>* out_stage,
+                                                                  const char* overflow, Call call) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            if (radii[i] != radii[i]) throw std::runtime_error("range search: a radius is NaN");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * cap * 8, o_c = o_d + nq * cap * 4, o_fn = o_c + nq * 4, o_sg = o_fn + nq * 4, o_st = o_sg + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_r(nq * 4 + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_r.upload(radii, nq * 4);
+        d_out.upload(host.data(), total);
+        char* const o = (char*)d_out.get();
+        int rc = call((const void*)d_q.get(), (const float*)d_r.get(), (uint64_t*)o, (float*)(o + o_d), (uint32_t*)(o + o_c), (uint32_t*)(o + o_fn),
+                      (uint32_t*)(o + o_sg), (uint32_t*)(o + o_st));
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (out_found) out_found->assign(nq, 0);
+        if (out_stage) out_stage->assign(nq, 0);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        if (out_found) std::memcpy(out_found->data(), host.data() + o_fn, nq * 4);
+        if (out_stage) std::memcpy(out_stage->data(), host.data() + o_sg, nq * 4);
+        if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error(overflow);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * cap + j], ds[i * cap + j]);
+        return out;
+    }
     std::shared_ptr<granne_hip_index> h_;
 };
 

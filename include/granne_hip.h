@@ -979,6 +979,93 @@ int granne_hip_search_postfiltered_batch(const granne_hip_index* index, const vo
                                          float* out_dists, uint32_t* out_counts, uint32_t* out_stage,
                                          uint32_t* out_status);
 
+/* ---- range search: all elements within a radius, by scan and by walk ----------
+ * "Which elements lie within distance r of this query, and how many are there?" Distances are the reference's own values,
+ * as granne_hip_exact_topk's; compares are f32 compares on them; a radius is one f32 PER QUERY (d_radii: f32[nq]). The
+ * models are the definitions.
+ *
+ * granne_hip_exact_range*: the scan. With allowed(q, i) = true where no filter is given,
+ *     W      = { i < n_elements : allowed(q, i) and dist(i, q) <= r }
+ *     total  = |W|                                  always exact, also beyond cap
+ *     answer = the first min(total, cap) members of W ordered by (distance bits, id)
+ * cap in [1, GRANNE_HIP_RANGE_CAP_MAX]; count = min(total, cap); places past the count hold UINT64_MAX / +inf. A negative
+ * radius gives count 0 and total 0; a +inf radius gives W = every allowed row. A NaN radius is refused by the host-pointer
+ * entry (GRANNE_HIP_ERR_INVALID, the message names the first such query); the device-pointer entry cannot see it: the
+ * compare is false and the answer is empty. The filter follows granne_hip_exact_topk_filtered's convention: d_filter null:
+ * all rows; filter_stride_words == 0: one bitmap for all queries, compacted to its id list (work ~ allowed ids x nq;
+ * d_status[3] = their number); otherwise one bitmap per query. Nothing allowed, or nothing within the radius: count 0,
+ * total 0, GRANNE_HIP_OK.
+ * One pass over the rows collects up to GRANNE_HIP_EXACT_TOPK_CAP keys per query and counts every hit. A query with
+ * total > GRANNE_HIP_EXACT_TOPK_CAP is answered by granne_hip_exact_topk[_filtered](k = cap): more than cap rows lie within
+ * the radius, so the cap nearest rows all do. That is the ONLY way a query is voided: the selection's own overflow, more than
+ * GRANNE_HIP_EXACT_TOPK_CAP rows inside one second-level bin at the cap-th distance. Such a query is voided, not partially
+ * answered -- count 0 and a filled row --, its total is still exact, it is counted in d_status[0], and the host entry returns
+ * GRANNE_HIP_ERR_OVERFLOW with every output written, as granne_hip_exact_topk does.
+ *   d_out_totals   u32[nq]: |W|
+ *   d_status       u32[4], optional, zeroed by the caller: [0] += queries voided by the selection's overflow; [1] += queries
+ *                  the selection answered (total > GRANNE_HIP_EXACT_TOPK_CAP); [2] = max(, most keys ranked for one query);
+ *                  [3] = with one shared bitmap, the number of allowed ids
+ * Refused (GRANNE_HIP_ERR_INVALID), in this order: a null index; GRANNE_HIP_F16 and compact SumEmbeddings handles, with
+ * granne_hip_exact_topk's messages and for the same reason; then, for nq > 0: a null buffer; cap == 0 or
+ * cap > GRANNE_HIP_RANGE_CAP_MAX; more than 2^32 - 1 elements; a filter_stride_words that is neither 0 nor
+ * >= ceil(n_elements / 32). nq == 0 does nothing. The device entry is stream-ordered but WAITS on `stream` ONCE: the number of
+ * queries with total > GRANNE_HIP_EXACT_TOPK_CAP (one u32) is read back; 0 ends the call. Scratch from hipMallocAsync.
+ *
+ * granne_hip_search_range_batch*: the walk, approximate by nature, defined by
+ *     search_range(q):
+ *       for s in 0 .. n_stages-1:
+ *           L = Granne::search(q, max_search = E_s, num_neighbors = E_s)     the ordinary search, whatever walker the plan picks
+ *           within = number of entries of L with distance <= r               a prefix: L ascends by (distance, id)
+ *           if within < len(L) or len(L) < E_s:                              the list reaches past the radius, or the walk ran out of graph
+ *               return L[:min(within, cap)], found = within, stage = s
+ *       if fallback == EXACT: return exact_range(q, r, cap), found = total, stage = GRANNE_HIP_RG_STAGE_EXACT
+ *       else:                 return L[:min(within, cap)] of the last stage, found = within, stage = GRANNE_HIP_RG_STAGE_SHORT
+ * No walker sees the radius: the register walkers serve the stages, and GRANNE_HIP_F16 and compact SumEmbeddings handles
+ * work with GRANNE_HIP_RG_FALLBACK_SHORT. Escalation is per query. The call takes no filter.
+ *   stages         HOST array of n_stages (1 .. GRANNE_HIP_RG_MAX_STAGES) values, strictly ascending, none 0
+ *   scratch_bytes  bound on the stage lists' scratch, as granne_hip_search_postfiltered_batch_device's: same result for any value
+ *   d_out_found    u32[nq], optional: `within` of the answering list, or the exact total
+ *   d_out_stage    u32[nq], optional: the stage that answered the query, or GRANNE_HIP_RG_STAGE_EXACT / _SHORT
+ *   d_status       u32[4], optional, zeroed by the caller: [0], [1], [2] accumulate over the stages' searches as for
+ *                  granne_hip_search_batch_device ([0] also += the fallback scan's voided queries); [3] += the queries no
+ *                  stage finished
+ * Refused with GRANNE_HIP_ERR_INVALID, each with its own message, in this order: n_stages 0 or > GRANNE_HIP_RG_MAX_STAGES;
+ * stages null, not strictly ascending or containing 0; cap == 0 or cap > GRANNE_HIP_RANGE_CAP_MAX; a fallback outside {0, 1};
+ * for nq > 0 a null buffer; (host entry) a NaN radius, naming the first such query; a null index (also with nq == 0); EXACT on
+ * a handle the exact scan refuses (GRANNE_HIP_F16, compact SumEmbeddings, more than 2^32 - 1 elements). nq == 0 otherwise does
+ * nothing.
+ * The device entry is stream-ordered but WAITS on `stream` once per stage it goes beyond: the number of pending queries (one
+ * u32) is read back to size the next stage and to stop at 0. After the last stage nothing is read back with SHORT; with EXACT
+ * one count sizes the scan, which waits once itself. These calls never take part in GRANNE_HIP_OPT_COALESCE.
+ *
+ * Out of scope: granne_hip_rw_builder_*, the partitioned handles (granne_hip_sharded_*), refined search, and a filter on
+ * granne_hip_search_range_batch*. */
+#define GRANNE_HIP_RANGE_CAP_MAX 1024
+#define GRANNE_HIP_RG_MAX_STAGES 8
+#define GRANNE_HIP_RG_FALLBACK_SHORT 0
+#define GRANNE_HIP_RG_FALLBACK_EXACT 1
+#define GRANNE_HIP_RG_STAGE_EXACT 0xFFFFFFFFu
+#define GRANNE_HIP_RG_STAGE_SHORT 0xFFFFFFFEu
+int granne_hip_exact_range_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, const float* d_radii,
+                                  uint32_t cap, const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,
+                                  float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_status,
+                                  void* stream);
+/* the same with host buffers in and out (synchronous), the filter's words on the host; out_status u32[4] (optional), written */
+int granne_hip_exact_range(const granne_hip_index* index, const void* queries, uint32_t nq, const float* radii, uint32_t cap,
+                           const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids, float* out_dists,
+                           uint32_t* out_counts, uint32_t* out_totals, uint32_t* out_status);
+int granne_hip_search_range_batch_device(const granne_hip_index* index, const void* d_queries, uint32_t nq,
+                                         const float* d_radii, uint32_t cap, const uint32_t* stages, uint32_t n_stages,
+                                         int fallback, uint64_t scratch_bytes, uint64_t* d_out_ids, float* d_out_dists,
+                                         uint32_t* d_out_counts, uint32_t* d_out_found, uint32_t* d_out_stage,
+                                         uint32_t* d_status, void* stream);
+/* the same with host buffers in and out (synchronous); out_found, out_stage optional; out_status u32[4] (optional), written,
+ * not accumulated. GRANNE_HIP_ERR_OVERFLOW, outputs written, when status[0] != 0. */
+int granne_hip_search_range_batch(const granne_hip_index* index, const void* queries, uint32_t nq, const float* radii,
+                                  uint32_t cap, const uint32_t* stages, uint32_t n_stages, int fallback,
+                                  uint64_t scratch_bytes, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                  uint32_t* out_found, uint32_t* out_stage, uint32_t* out_status);
+
 /* ---- partitioned indexes: filters and the exact selection over GLOBAL ids ----
  * A bitmap slice: output bit i (i < n_out_bits) of filter f is source bit first_bit + i of filter f; source bits at
  * positions >= n_bits read as 0 and no source word at or past ceil(n_bits / 32) is read; the bits past n_out_bits of the

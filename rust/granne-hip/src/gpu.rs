@@ -257,7 +257,29 @@ extern "C" {
         num_neighbors: u32, min_allowed: u32, stages: *const u32, n_stages: u32, fallback: c_int,
         filter: *const u32, filter_stride_words: u64, scratch_bytes: u64, out_ids: *mut u64, out_dists: *mut f32,
         out_counts: *mut u32, out_stage: *mut u32, out_status: *mut u32) -> c_int;
+    // range search: all elements within a radius, by the exact scan and by the staged walk
+    fn granne_hip_exact_range_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        d_radii: *const f32, cap: u32, d_filter: *const u32, filter_stride_words: u64, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_totals: *mut u32, d_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_range(index: *const granne_hip_index, queries: *const c_void, nq: u32, radii: *const f32,
+        cap: u32, filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32,
+        out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_search_range_batch_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        d_radii: *const f32, cap: u32, stages: *const u32, n_stages: u32, fallback: c_int, scratch_bytes: u64,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_found: *mut u32,
+        d_out_stage: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_search_range_batch(index: *const granne_hip_index, queries: *const c_void, nq: u32,
+        radii: *const f32, cap: u32, stages: *const u32, n_stages: u32, fallback: c_int, scratch_bytes: u64,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_found: *mut u32, out_stage: *mut u32,
+        out_status: *mut u32) -> c_int;
 }
+pub const GRANNE_HIP_RANGE_CAP_MAX: usize = 1024;
+pub const GRANNE_HIP_RG_MAX_STAGES: usize = 8;
+pub const GRANNE_HIP_RG_FALLBACK_SHORT: c_int = 0;
+pub const GRANNE_HIP_RG_FALLBACK_EXACT: c_int = 1;
+pub const GRANNE_HIP_RG_STAGE_EXACT: u32 = 0xFFFF_FFFF;
+pub const GRANNE_HIP_RG_STAGE_SHORT: u32 = 0xFFFF_FFFE;
 pub const GRANNE_HIP_PF_MAX_STAGES: usize = 8;
 pub const GRANNE_HIP_PF_FALLBACK_SHORT: c_int = 0;
 pub const GRANNE_HIP_PF_FALLBACK_EXACT: c_int = 1;
@@ -608,6 +630,52 @@ impl<E: GpuElements> GpuGranne<E> {
             filter.words.ptr as *const u32, 0, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(),
             std::ptr::null_mut(), stream.raw) })?;
         out.to_host(nq, &stream)
+    }
+    /// `granne_hip_exact_range_device`: every element within `radii[i]` of query i, exact by construction -- the nearest
+    /// `cap` (up to `GRANNE_HIP_RANGE_CAP_MAX`) of them ascending by (distance, id), and `totals[i]`, the exact number
+    /// within the radius also beyond `cap`. `filter`: `None` for all rows, else the rows one bitmap allows. The call
+    /// waits on its stream once.
+    pub fn exact_range(&self, elements: &[E::Vector], radii: &[f32], cap: usize, filter: Option<&GpuFilter>)
+                       -> std::io::Result<(Vec<Vec<(usize, f32)>>, Vec<u32>)> {
+        let nq = elements.len();
+        assert_eq!(nq, radii.len());
+        if nq == 0 { return Ok((Vec::new(), Vec::new())); }
+        if let Some(f) = filter { assert_eq!(f.len(), self.num_elements()); }
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let r = DeviceBuffer::<f32>::new(nq, self.device())?;
+        r.copy_from(radii, &stream)?;
+        let out = DeviceResults::new(nq, cap, self.device())?;
+        let totals = DeviceBuffer::<u32>::new(nq, self.device())?;
+        check(unsafe { granne_hip_exact_range_device(self.handle, q.ptr as *const c_void, nq as u32, r.ptr as *const f32,
+            cap as u32, filter.map_or(std::ptr::null(), |f| f.words.ptr as *const u32), 0, out.ids.ptr, out.dists.ptr,
+            out.counts.ptr, totals.ptr, std::ptr::null_mut(), stream.raw) })?;
+        let mut t = vec![0u32; nq];
+        totals.copy_to(&mut t, &stream)?;
+        Ok((out.to_host(nq, &stream)?, t))
+    }
+    /// `granne_hip_search_range_batch_device`: the elements within `radii[i]` of query i by the ordinary search with
+    /// lists of `stages[s]` entries, cut at the radius. A query is answered by the first stage whose list holds an entry
+    /// beyond the radius (or whose walk ran out of graph); what no stage finishes gets the exact scan
+    /// (`GRANNE_HIP_RG_FALLBACK_EXACT`) or its short answer (`_SHORT`). Returns the answers and, per query, how many
+    /// entries lay within the radius (`found`). The call waits on its stream once per stage it goes beyond.
+    pub fn search_range(&self, elements: &[E::Vector], radii: &[f32], cap: usize, stages: &[u32], fallback: c_int)
+                        -> std::io::Result<(Vec<Vec<(usize, f32)>>, Vec<u32>)> {
+        let nq = elements.len();
+        assert_eq!(nq, radii.len());
+        if nq == 0 { return Ok((Vec::new(), Vec::new())); }
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let r = DeviceBuffer::<f32>::new(nq, self.device())?;
+        r.copy_from(radii, &stream)?;
+        let out = DeviceResults::new(nq, cap, self.device())?;
+        let found = DeviceBuffer::<u32>::new(nq, self.device())?;
+        check(unsafe { granne_hip_search_range_batch_device(self.handle, q.ptr as *const c_void, nq as u32,
+            r.ptr as *const f32, cap as u32, stages.as_ptr(), stages.len() as u32, fallback, 0, out.ids.ptr, out.dists.ptr,
+            out.counts.ptr, found.ptr, std::ptr::null_mut(), std::ptr::null_mut(), stream.raw) })?;
+        let mut f = vec![0u32; nq];
+        found.copy_to(&mut f, &stream)?;
+        Ok((out.to_host(nq, &stream)?, f))
     }
     /// Rows of the element set (at least `len()`): what `exact_topk` and `exact_topk_filtered` scan.
     pub fn num_elements(&self) -> usize { unsafe { granne_hip_index_num_elements(self.handle) as usize } }
