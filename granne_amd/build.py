@@ -8,6 +8,7 @@ the GPU box; it is git-ignored.
 import os
 import subprocess
 import sys
+import tempfile
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -23,6 +24,14 @@ FLAGS = [
     "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math",
     "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
 ]
+# sources built with flags of their own, after FLAGS. The screened exact selection is compiled without the packed f32
+# instructions (v_pk_*_f32): its scan kernels then hold their operands in fewer registers (count forms: 238 VGPRs for 256 at
+# 16 x 13 components, 220 for 240 at 16 x 7, int8 162 for 176; no scratch either way). The switch is a device feature: the
+# host pass of the same command does not know it and says so. tools/build_variant.sh builds every source with one set of
+# flags, so a variant library carries these kernels in the higher-register form.
+SOURCE_FLAGS = {
+    "exact_topk_screened.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _sources():
@@ -49,10 +58,24 @@ def build_library(force=False, use_dpp=None, verbose=False):
     if use_dpp is None:
         use_dpp = int(os.environ.get("GRANNE_HIP_USE_DPP", "1"))
     extra = os.environ.get("GRANNE_HIP_EXTRA_FLAGS", "").split()  # kernel experiments, e.g. -DGRANNE_HIP_PQ_MERGE_MIN=99
-    cmd = [HIPCC] + FLAGS + ["-DGRANNE_HIP_USE_DPP=%d" % int(use_dpp)] + extra + ["-I", INCLUDE] + _sources() + ["-o", LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    common = [f for f in FLAGS if f != "-shared"] + ["-DGRANNE_HIP_USE_DPP=%d" % int(use_dpp)] + extra + ["-I", INCLUDE]
+    # one object per source (each with its own flags), compiled side by side in a scratch directory, then linked
+    with tempfile.TemporaryDirectory(prefix="granne_hip_build_") as tmp:
+        jobs = []
+        for src in _sources():
+            name = os.path.basename(src)
+            obj = os.path.join(tmp, name + ".o")
+            cmd = [HIPCC] + common + SOURCE_FLAGS.get(name, []) + ["-c", src, "-o", obj]
+            if verbose:
+                print(" ".join(cmd))
+            jobs.append((cmd, obj, subprocess.Popen(cmd)))
+        failed = [cmd for cmd, _, p in jobs if p.wait() != 0]
+        if failed:
+            raise subprocess.CalledProcessError(1, failed[0])
+        link = [HIPCC] + [f for f in FLAGS if f.startswith("--offload-arch")] + ["-fPIC", "-shared"] + [o for _, o, _ in jobs] + ["-o", LIB_PATH]
+        if verbose:
+            print(" ".join(link))
+        subprocess.check_call(link)
     return LIB_PATH
 
 

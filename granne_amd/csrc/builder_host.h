@@ -524,7 +524,21 @@ extern "C" int granne_hip_builder_get_layer(const granne_hip_builder* b, uint32_
     DeviceGuard g(b->device);
     const BuilderLayer& L = b->layers[layer];
     const uint32_t nn = b->cfg.num_neighbors;
-    HIP_TRY(hipMemcpy2D(out_rows, (size_t)nn * 4, L.d_adj.get(), (size_t)b->W * 4, (size_t)nn * 4, L.len, hipMemcpyDeviceToHost));
+    // The lists are packed on the device, a million at a time, and come down as plain copies: a strided copy straight into
+    // pageable host memory moves one short row per transfer (17 MB/s measured).
+    if (b->W == nn) {
+        if (L.len) HIP_TRY(hipMemcpy(out_rows, L.d_adj.get(), (size_t)L.len * nn * 4, hipMemcpyDeviceToHost));
+        return GRANNE_HIP_OK;
+    }
+    const uint64_t chunk = 1u << 20;
+    DevBuf packed;
+    if (L.len) HIP_TRY(packed.alloc((size_t)(L.len < chunk ? L.len : chunk) * nn * 4));
+    for (uint64_t r0 = 0; r0 < L.len; r0 += chunk) {
+        const uint64_t rows = L.len - r0 < chunk ? L.len - r0 : chunk;
+        HIP_TRY(hipMemcpy2D(packed.get(), (size_t)nn * 4, L.d_adj.as<uint8_t>() + (size_t)r0 * b->W * 4, (size_t)b->W * 4, (size_t)nn * 4, rows,
+                            hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(out_rows + (size_t)r0 * nn, packed.get(), (size_t)rows * nn * 4, hipMemcpyDeviceToHost));
+    }
     return GRANNE_HIP_OK;
 }
 

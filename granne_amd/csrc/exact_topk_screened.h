@@ -1,0 +1,96 @@
+// exact_topk_screened.h -- exact_topk's answer at matrix-core speed (granne_hip_exact_topk_screened_device; DESIGN.md
+// 3.7b). The matrix cores give every (query, row) pair a cheap SCREEN SCORE s; a proven bound eps on |s - r|, r = 1 - the
+// reference's distance, turns the score into a screen that no row of the true top-k can fail; only the survivors -- a few
+// times k per query -- get the reference's arithmetic (dists_kernel) and exact_topk's (distance bits, id) ranking
+// (et_rank_kernel). This header is what the two sides share: the kernels and their launchers are exact_topk_screened.hip
+// (a translation unit of its own: it is compiled without the packed f32 instructions), the driver is
+// exact_topk_screened_host.h.
+//
+//   score    f32 rows: every component in two bf16 pieces, x = xh + xl (+ a residual below 2^-18 |x|), a product as three
+//            v_mfma_f32_32x32x16_bf16 (xh qh + xh ql + xl qh) accumulated in f32 -- brute_force.h's bf_b16_kernel operand
+//            layout: a tile of rows split on its way to LDS, the wave's 32 queries in registers for the whole range, a
+//            lane owns one query (column) and sees 16 rows per 32-row block. int8 rows: v_mfma_i32_32x32x32_i8, the exact
+//            integer dot, times the row's 1 / |x| (the index's d_inv_norm) times the query's 1 / |q|.
+//   bound    ets_epsilon(dtype, dim), derived in DESIGN.md 3.7b, made on the host, passed in. f32: for rows and queries
+//            of squared norm at most ETS_NORM2_MAX (prepared rows are; ets_max_norm2_kernel looks once per index,
+//            ets_init_kernel at every query) -- a handle or a query outside that is answered by exact_topk's own scan.
+//   floor    per query a score `lo` that at least k rows reach; it starts at ETS_LO0, below every score there is. A
+//            COUNT pass puts every score >= lo of a prefix of the rows into one of ETS_BUCKETS linear buckets between lo
+//            and 1, edge(j) = lo + w j, w = (1 - lo) / 64 -- per (block, query) in LDS (ds_add; [bucket][query], the
+//            lanes of a wave on different banks), the non-zero buckets added to the query's global histogram at the end
+//            of the block's range. ets_select_kernel raises lo to the highest edge with k rows at or above it: those k
+//            rows are rows of every longer prefix. The prefixes are exact_topk's (16 times the one before, the last one
+//            all rows; a set of one stage is counted twice, the second time between the first floor and 1).
+//   collect  the same kernel, the other epilogue: every row with s >= lo - 2 eps goes to the query's candidate list (u32
+//            ids, ETS_CAP of them). Why 2 eps: the k witnesses of lo have r >= lo - eps, so the k-th best r is at least
+//            that; a row of the true top-k (ties at the k-th included) has r >= the k-th best, and its own s is within
+//            eps of its r. The place in the list: one atomic per (wave, query, 32-row block) that has hits, the lane
+//            pair of a query sharing it; the count keeps running past ETS_CAP.
+//   rank     ets_pad_kernel closes the lists (unused places: an id no handle has, which dists_kernel answers +inf) and
+//            puts a query with more than ETS_CAP candidates, or outside the norm bound, on the fallback list;
+//            dists_kernel gives the candidates their distances in the reference's arithmetic, ets_keys_kernel makes the
+//            keys (distance bits << 32 | id), et_rank_kernel sorts them and writes the first k.
+// Only comparisons against `lo` decide what is counted and collected, and count and select evaluate edge(j) by one
+// expression (ets_edge; compiled with -ffp-contract=off): a bucket's count vouches for s >= its edge.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace granne_hip {
+
+constexpr uint32_t ETS_BUCKETS = 64;
+constexpr uint32_t ETS_THREADS = 512, ETS_QT = 256; // 8 waves x 32 queries
+constexpr uint32_t ETS_CAP = 4096;                  // = ET_CAP: candidates per query
+constexpr float ETS_LO0 = -1.25f;                   // below every screen score: |s| <= (1 + 2^-10) + eps
+constexpr float ETS_NORM2_MAX = 1.0f + 0x1p-10f;    // f32: the bound holds for |x|^2, |q|^2 up to here
+constexpr float ETS_NORM2_TEST = 1.0f + 0x1p-10f - 0x1p-14f; // what an f32 sum of <= 208 squares is held to (its own rounding: 208 x 2^-24)
+constexpr uint32_t ETS_F32_DIM_MAX = 208, ETS_I8_DIM_MAX = 128;
+enum { ETS_FORM_ROUTED = 0, ETS_FORM_B16_7x4 = 1, ETS_FORM_B16_13x2 = 2, ETS_FORM_I8 = 3 };
+constexpr uint32_t ETS_VOIDED = 0x80000000u; // status[3]: exact_topk's own selection overflowed for a query handed to it
+
+// The bound on |screen score - (1 - reference distance)|; 0: the shape has no screen.
+static inline float ets_epsilon(int i8, uint32_t dim) {
+    if (dim == 0) return 0.0f;
+    if (i8) return dim <= ETS_I8_DIM_MAX ? 0x1p-20f : 0.0f;
+    if (dim > ETS_F32_DIM_MAX) return 0.0f;
+    const double kpad = dim <= 112 ? 112.0 : 208.0;         // components the matrix form sums (zero padded)
+    const double split = 3.1 * 0x1p-18;                     // xl ql, x qr, xr q: the dropped term and the residuals
+    const double mfma = 3.0 * kpad * 0x1p-23 * 1.02;        // 3 kpad exact products summed in f32, any order, rounded or truncated
+    const double ref = (double)dim * 0x1p-24 * 1.01;        // the reference's dim fused steps, 32 accumulators, ordered sum
+    return (float)((split + mfma + ref) * (1.0 + 0x1p-10) + 0x1p-22); // |x||q| <= 1 + 2^-10; 1 - dot, lo - 2 eps rounded
+}
+
+struct EtsParams {
+    const uint8_t* elements;
+    uint64_t n;              // the rows this pass scans (a prefix, or all)
+    uint32_t row_bytes, row_stride, dim;
+    const uint8_t* queries;  // dense [nq][dim] (this round's)
+    uint32_t nq;
+    uint64_t per_range;      // rows per range (a multiple of the tile)
+    const float* inv_norm;   // int8: [n] 1 / |x|
+    const float* inv_gmax;   // int8: [ceil(n / 32)][2] (brute_force.h)
+    const float* lo;         // [nq] the floor; +inf: the query takes no part (outside the norm bound)
+    uint32_t* hist;          // COUNT: [nq][ETS_BUCKETS]
+    uint32_t* cnt;           // COLLECT: [nq]
+    uint32_t* cand;          // COLLECT: [nq][ETS_CAP]
+    float eps2;              // COLLECT: 2 eps
+};
+
+// the launchers (exact_topk_screened.hip); every one is ordered on s and returns what the launch left
+uint32_t ets_tile_rows(uint32_t form); // rows per tile of the form's scan
+hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s);
+hipError_t ets_max_norm2(const uint8_t* elements, uint64_t n, uint32_t row_bytes, uint32_t row_stride, uint32_t* out, hipStream_t s);
+hipError_t ets_init(bool i8, const uint8_t* queries, uint32_t nq, uint32_t dim, float* lo, uint32_t* hist, uint32_t* cnt, hipStream_t s);
+hipError_t ets_select(uint32_t* hist, uint32_t nq, uint32_t k, float* lo, hipStream_t s);
+// sel: [nq][4] u32, exact_topk's EtSel (word 3: the query is voided for et_rank_kernel -- here: it is on the fallback list)
+hipError_t ets_pad(uint32_t* cand, const uint32_t* cnt, const float* lo, uint32_t nq, uint32_t q_base, uint32_t* sel, uint32_t* fb_count,
+                   uint32_t* fb_list, uint32_t* status, hipStream_t s);
+hipError_t ets_keys(const uint32_t* cand, const float* dists, const uint32_t* cnt, uint32_t nq, uint64_t* keys, hipStream_t s);
+hipError_t ets_gather(const uint8_t* queries, uint32_t qbytes, const uint32_t* fb_list, uint32_t nfb, uint8_t* out, hipStream_t s);
+hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const uint64_t* ids, const float* dists, const uint32_t* counts,
+                       const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s);
+hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s);
+
+} // namespace granne_hip

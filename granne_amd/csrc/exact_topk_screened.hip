@@ -1,0 +1,527 @@
+// exact_topk_screened.hip -- the kernels of the screened exact selection and their launchers (exact_topk_screened.h has
+// the method and what this file shares with the driver). A translation unit of its own: granne_amd/build.py compiles it
+// without the packed f32 instructions. It needs nothing of the library's other kernels but dist.h's dot4_i8.
+#include "exact_topk_screened.h"
+#include "dist.h"
+
+namespace granne_hip {
+
+typedef float ets_f32x16 __attribute__((ext_vector_type(16)));
+typedef int ets_i32x16 __attribute__((ext_vector_type(16)));
+typedef int ets_i32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 ets_b16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 ets_b16x4 __attribute__((ext_vector_type(4)));
+
+// Which (query tile, row range) a block takes: brute_force.h's bf_block -- workgroups go to the 8 XCDs round robin by
+// their linear id, so with a multiple of 8 ranges the query tiles that stream one range share an XCD and its L2.
+struct EtsBlock { uint32_t qt, range; };
+__device__ __forceinline__ EtsBlock ets_block() {
+    const uint32_t nqt = gridDim.x, G = gridDim.y;
+    const uint32_t L = blockIdx.y * nqt + blockIdx.x; // dispatch order: x fastest
+    EtsBlock b;
+    if ((G & 7u) == 0u) {
+        const uint32_t xcd = L & 7u, slot = L >> 3;
+        b.range = xcd * (G >> 3) + slot / nqt;
+        b.qt = slot % nqt;
+    } else {
+        b.qt = blockIdx.x;
+        b.range = blockIdx.y;
+    }
+    return b;
+}
+
+__device__ __forceinline__ float ets_width(float lo) { return (1.0f - lo) * (1.0f / (float)ETS_BUCKETS); }
+__device__ __forceinline__ float ets_edge(float lo, float w, int j) { return lo + w * (float)j; }
+
+// A lane's view of its query's floor
+struct EtsFloor {
+    float thr, lo, w, inv_w;
+    template <bool COLLECT>
+    __device__ __forceinline__ void init(const EtsParams& P, uint32_t q, bool qlive) {
+        lo = qlive ? P.lo[q] : __builtin_inff();
+        w = ets_width(lo);
+        inv_w = 1.0f / w;
+        thr = COLLECT ? lo - P.eps2 : lo;
+    }
+};
+
+// The 16 scores a lane holds of one 32-row block: rows e_blk + 8 (v / 4) + v % 4 + 4 h, its query in column `col`.
+// COUNT: into the block's LDS histogram (hq: the query's column of it). COLLECT: into the query's candidate list.
+template <bool COLLECT>
+__device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
+                                           bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq) {
+    if constexpr (!COLLECT) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
+            if (sc[v] >= F.thr && (whole || e < r1)) {
+                int j = (int)__builtin_fminf((sc[v] - F.lo) * F.inv_w, (float)(ETS_BUCKETS - 1));
+                j = j < 0 ? 0 : j;
+                while (j > 0 && sc[v] < ets_edge(F.lo, F.w, j)) --j; // never round up into a bucket
+                atomicAdd(hq + (uint32_t)j * ETS_QT, 1u);
+            }
+        }
+    } else {
+        uint32_t mask = 0;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
+            mask |= (sc[v] >= F.thr && (whole || e < r1)) ? 1u << v : 0u;
+        }
+        const uint32_t mine = (uint32_t)__builtin_popcount(mask);
+        const uint32_t other = (uint32_t)__shfl_xor((int)mine, 32, 64);
+        uint32_t base = 0;
+        if (h == 0u && mine + other > 0u) base = atomicAdd(P.cnt + q, mine + other); // (hits: q is a live query)
+        base = (uint32_t)__shfl((int)base, (int)col, 64);
+        uint32_t pos = base + (h ? other : 0u); // the pair's lower lane first
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            if (mask >> v & 1u) {
+                if (pos < ETS_CAP) P.cand[(size_t)q * ETS_CAP + pos] = (uint32_t)(e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h);
+                ++pos;
+            }
+        }
+    }
+}
+
+// a block's LDS histogram: cleared before its range, its non-zero buckets added to the queries' global ones after it
+__device__ __forceinline__ void ets_hist_clear(uint32_t* lh, uint32_t tid) {
+    for (uint32_t i = tid; i < ETS_BUCKETS * ETS_QT; i += ETS_THREADS) lh[i] = 0u;
+}
+__device__ __forceinline__ void ets_hist_flush(const EtsParams& P, const uint32_t* lh, uint32_t q0, uint32_t tid) {
+    __syncthreads();
+    for (uint32_t i = tid; i < ETS_BUCKETS * ETS_QT; i += ETS_THREADS) {
+        const uint32_t c = lh[i], q = q0 + (i & (ETS_QT - 1u));
+        if (c != 0u && q < P.nq) atomicAdd(P.hist + (size_t)q * ETS_BUCKETS + (i / ETS_QT), c);
+    }
+}
+
+// f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order.
+template <int KG, int R, bool COLLECT>
+__global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P) {
+    extern __shared__ __align__(16) uint8_t smem_ets[];
+    constexpr uint32_t ET = 32u * R;                // rows per tile
+    constexpr uint32_t COMPS = 16u * KG;            // components per (zero padded) row
+    constexpr uint32_t STRIDE_B = 2u * COMPS + 16u; // bytes per LDS row of one piece: an odd number of 16-byte units
+    uint8_t* tile_hi = smem_ets;
+    uint8_t* tile_lo = smem_ets + (size_t)ET * STRIDE_B;
+    uint32_t* lh = reinterpret_cast<uint32_t*>(smem_ets + 2u * (size_t)ET * STRIDE_B); // COUNT: [ETS_BUCKETS][ETS_QT]
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t col = lane & 31u, h = lane >> 5;
+    const EtsBlock blk = ets_block();
+    const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
+    const bool qlive = q < P.nq;
+    if constexpr (!COLLECT) ets_hist_clear(lh, tid); // (the first tile's barriers stand between this and the first count)
+
+    ets_b16x8 qh[KG], ql[KG]; // the lane's half of its query as bf16 pieces, in registers for the whole range
+    {
+        const float* qp = reinterpret_cast<const float*>(P.queries) + (size_t)(qlive ? q : 0u) * P.dim;
+#pragma unroll
+        for (int g = 0; g < KG; ++g) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t c = h * 8u * KG + (uint32_t)g * 8u + (uint32_t)j;
+                const float v = (qlive && c < P.dim) ? qp[c] : 0.0f;
+                const __bf16 hi = (__bf16)v;
+                qh[g][j] = hi;
+                ql[g][j] = (__bf16)(v - (float)hi);
+            }
+        }
+    }
+    EtsFloor F;
+    F.init<COLLECT>(P, q, qlive);
+
+    const uint64_t r0 = (uint64_t)blk.range * P.per_range;
+    const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
+    const uint32_t row_f4 = P.row_bytes / 16u; // float4 units of a device row that hold data
+    constexpr uint32_t UNITS = COMPS / 4u;     // float4 units per (padded) row
+    constexpr uint32_t NPF = (ET * UNITS + ETS_THREADS - 1u) / ETS_THREADS;
+    float4 pf[NPF]; // the next tile, on its way from memory while this one is scored
+    auto fetch = [&](uint64_t e0) {
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) {
+            const uint32_t u = tid + ETS_THREADS * j;
+            const uint32_t row = u / UNITS, c4 = u - row * UNITS;
+            pf[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (u < ET * UNITS && e0 + row < r1 && c4 < row_f4)
+                pf[j] = *reinterpret_cast<const float4*>(P.elements + (e0 + row) * P.row_stride + c4 * 16u);
+        }
+    };
+    if (r0 < r1) fetch(r0);
+    for (uint64_t e0 = r0; e0 < r1; e0 += ET) {
+        __syncthreads(); // the previous tile has been consumed
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) { // split into the two pieces on the way to LDS
+            const uint32_t u = tid + ETS_THREADS * j;
+            const uint32_t row = u / UNITS, c4 = u - row * UNITS;
+            if (u < ET * UNITS) {
+                ets_b16x4 hi, lo;
+                const float v[4] = {pf[j].x, pf[j].y, pf[j].z, pf[j].w};
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    hi[t] = (__bf16)v[t];
+                    lo[t] = (__bf16)(v[t] - (float)hi[t]);
+                }
+                *reinterpret_cast<ets_b16x4*>(tile_hi + (size_t)row * STRIDE_B + c4 * 8u) = hi;
+                *reinterpret_cast<ets_b16x4*>(tile_lo + (size_t)row * STRIDE_B + c4 * 8u) = lo;
+            }
+        }
+        __syncthreads();
+        if (e0 + ET < r1) fetch(e0 + ET);
+        ets_f32x16 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[r][v] = 0.0f;
+        // the fragments of the next (step, block) are read while the matrix cores work on this one
+        const size_t off0 = (size_t)col * STRIDE_B + (size_t)h * 16u * KG;
+        constexpr int NF = KG * R;
+        ets_b16x8 ah[2], al[2];
+        ah[0] = *reinterpret_cast<const ets_b16x8*>(tile_hi + off0);
+        al[0] = *reinterpret_cast<const ets_b16x8*>(tile_lo + off0);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int g = i / R, r = i % R;
+            if (i + 1 < NF) {
+                const int gn = (i + 1) / R, rn = (i + 1) % R;
+                ah[(i + 1) & 1] = *reinterpret_cast<const ets_b16x8*>(tile_hi + off0 + (size_t)rn * 32u * STRIDE_B + (size_t)gn * 16u);
+                al[(i + 1) & 1] = *reinterpret_cast<const ets_b16x8*>(tile_lo + off0 + (size_t)rn * 32u * STRIDE_B + (size_t)gn * 16u);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], qh[g], acc[r], 0, 0, 0);
+            acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], ql[g], acc[r], 0, 0, 0);
+            acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i & 1], qh[g], acc[r], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // result block r: acc[r][v] ~ dot(row e0 + r*32 + 8*(v/4) + 4*h + v%4, query `col` of this wave). Few blocks hold
+        // a score at or above a lane's floor: one max over the block decides for the wave.
+        const bool whole = e0 + ET <= r1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float mx = acc[r][0];
+#pragma unroll
+            for (int v = 1; v < 16; ++v) mx = __builtin_fmaxf(mx, acc[r][v]);
+            if (__ballot(mx >= F.thr)) {
+                float sc[16];
+#pragma unroll
+                for (int v = 0; v < 16; ++v) sc[v] = acc[r][v];
+                ets_take16<COLLECT>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col);
+            }
+        }
+    }
+    if constexpr (!COLLECT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+}
+
+template <int KG, int R>
+constexpr uint32_t ets_b16_lds(bool collect) {
+    return 2u * (32u * R) * (2u * 16u * KG + 16u) + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u); // tile_hi, tile_lo, the histogram
+}
+
+// int8 rows of up to 128 bytes: score = ((float)dot * (1 / |x|)) * (1 / |q|), the dot exact in i32
+constexpr uint32_t ETS_I8_R = 4, ETS_I8_ROWS = 32u * ETS_I8_R, ETS_I8_STRIDE = 128u + 16u;
+template <bool COLLECT>
+__global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) {
+    extern __shared__ __align__(16) uint8_t smem_ets[];
+    constexpr int R = (int)ETS_I8_R;
+    constexpr uint32_t ET = ETS_I8_ROWS, STRIDE = ETS_I8_STRIDE;
+    uint8_t* tile = smem_ets;
+    float* inv = reinterpret_cast<float*>(smem_ets + (size_t)ET * STRIDE); // [ET] 1 / |x|
+    float* gm = inv + ET;                                                   // [2][R] inv_gmax of the tile's blocks, by lane half
+    uint32_t* lh = reinterpret_cast<uint32_t*>(gm + 2 * R);                 // COUNT: [ETS_BUCKETS][ETS_QT]
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t col = lane & 31u, h = lane >> 5;
+    const EtsBlock blk = ets_block();
+    const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
+    const bool qlive = q < P.nq;
+    if constexpr (!COLLECT) ets_hist_clear(lh, tid);
+    ets_i32x4 qr[4]; // bytes 32 g + 16 h .. + 15 of the query (bf_i8_kernel's operand)
+    float qinv = 0.0f;
+    {
+        const uint8_t* qp = P.queries + (size_t)(qlive ? q : 0u) * P.dim;
+        const uint32_t last = P.dim - 1u;
+        int dy = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const uint32_t c = (uint32_t)g * 32u + h * 16u + (uint32_t)w * 4u + (uint32_t)b;
+                    const uint32_t raw = qp[c < last ? c : last];
+                    const uint32_t keep = (qlive && c < P.dim) ? 0xFFu : 0u;
+                    v |= (raw & keep) << (8 * b);
+                }
+                qr[g][w] = (int)v;
+                dy = dot4_i8(v, v, dy);
+            }
+        }
+        dy += __shfl_xor(dy, 32, 64); // the other half of the vector
+        qinv = dy > 0 ? 1.0f / __builtin_sqrtf((float)dy) : 0.0f;
+    }
+    EtsFloor F;
+    F.init<COLLECT>(P, q, qlive);
+
+    const uint64_t r0 = (uint64_t)blk.range * P.per_range;
+    const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
+    // 8 threads per row (16 bytes each; device rows shorter than 128 bytes are zero extended): 64 rows per round
+    constexpr uint32_t NPF = ET * 8u / ETS_THREADS;
+    const uint32_t my_row = tid >> 3, my_c = tid & 7u;
+    const bool col_live = my_c < P.row_bytes / 16u;
+    uint4 pf[NPF];
+    float pfn[NPF], pfg = 0.0f;
+    auto fetch = [&](uint64_t e0) {
+        if (tid < 2u * R) pfg = e0 + 32u * (tid >> 1) < r1 ? P.inv_gmax[((e0 >> 5) + (tid >> 1)) * 2u + (tid & 1u)] : 0.0f;
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) {
+            const uint64_t row = e0 + my_row + (ETS_THREADS / 8u) * j;
+            pf[j] = make_uint4(0, 0, 0, 0);
+            pfn[j] = 0.0f;
+            if (row < r1 && col_live) pf[j] = *reinterpret_cast<const uint4*>(P.elements + row * P.row_stride + my_c * 16u);
+            if (row < r1 && my_c == 0u) pfn[j] = P.inv_norm[row];
+        }
+    };
+    if (r0 < r1) fetch(r0);
+    for (uint64_t e0 = r0; e0 < r1; e0 += ET) {
+        __syncthreads();
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) {
+            const uint32_t row = my_row + (ETS_THREADS / 8u) * j;
+            *reinterpret_cast<uint4*>(tile + (size_t)row * STRIDE + my_c * 16u) = pf[j];
+            if (my_c == 0u) inv[row] = pfn[j];
+        }
+        if (tid < 2u * R) gm[(tid & 1u) * R + (tid >> 1)] = pfg;
+        __syncthreads();
+        if (e0 + ET < r1) fetch(e0 + ET);
+        ets_i32x16 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[r][v] = 0;
+        ets_i32x4 afrag[2][R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) afrag[0][r] = *reinterpret_cast<const ets_i32x4*>(tile + (size_t)(r * 32 + col) * STRIDE + h * 16);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (g + 1 < 4) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    afrag[(g + 1) & 1][r] = *reinterpret_cast<const ets_i32x4*>(tile + (size_t)(r * 32 + col) * STRIDE + (g + 1) * 32 + h * 16);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[g & 1][r], qr[g], acc[r], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the largest dot of the lane's 16 rows times the largest 1 / |x| among them bounds their scores from above
+        // (products of non-negative floats are monotone; a negative dot's score is <= 0 <= the bound)
+        const bool whole = e0 + ET <= r1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int im = 0;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) im = max(im, acc[r][v]);
+            if (!__ballot(((float)im * gm[h * R + r]) * qinv >= F.thr)) continue;
+            float sc[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) { // rows r*32 + 8*g4 + 4*h + 0..3: their 1 / |x| in one read
+                const float4 iv = *reinterpret_cast<const float4*>(inv + r * 32 + 8 * g4 + 4 * h);
+                sc[g4 * 4 + 0] = ((float)acc[r][g4 * 4 + 0] * iv.x) * qinv;
+                sc[g4 * 4 + 1] = ((float)acc[r][g4 * 4 + 1] * iv.y) * qinv;
+                sc[g4 * 4 + 2] = ((float)acc[r][g4 * 4 + 2] * iv.z) * qinv;
+                sc[g4 * 4 + 3] = ((float)acc[r][g4 * 4 + 3] * iv.w) * qinv;
+            }
+            ets_take16<COLLECT>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col);
+        }
+    }
+    if constexpr (!COLLECT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+}
+
+constexpr uint32_t ets_i8_lds(bool collect) {
+    return ETS_I8_ROWS * ETS_I8_STRIDE + ETS_I8_ROWS * 4u + 2u * ETS_I8_R * 4u + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u);
+}
+
+__global__ void ets_clear_kernel(uint32_t* p, uint32_t n) {
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
+}
+
+// f32 handles, once per index: the largest squared norm of a row, as the bits of a non-negative float (a NaN's bits lie
+// above +inf's: it fails the test it is held to). Eight lanes per row.
+__global__ void ets_max_norm2_kernel(const uint8_t* __restrict__ elements, uint64_t n, uint32_t row_bytes, uint32_t row_stride,
+                                                     uint32_t* __restrict__ out) {
+    const uint32_t c = threadIdx.x & 7u, units = row_bytes / 16u;
+    float worst = 0.0f;
+    uint32_t nan = 0;
+    for (uint64_t row = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; row < ((n + 7u) & ~7ull); row += ((uint64_t)gridDim.x * blockDim.x) >> 3) {
+        float s = 0.0f;
+        for (uint32_t u = c; u < units; u += 8u) {
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (row < n) v = *reinterpret_cast<const float4*>(elements + row * row_stride + (size_t)u * 16u);
+            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        nan |= s != s ? 1u : 0u;
+        worst = __builtin_fmaxf(worst, s);
+    }
+    if (c == 0u && (worst > 0.0f || nan)) atomicMax(out, nan ? 0x7FC00000u : __float_as_uint(worst));
+}
+
+// Per query of a round, before its first pass: the floor's start (+inf: an f32 query outside the norm bound, which takes no
+// part in the screen), its histogram and its candidate count cleared.
+template <bool I8>
+__global__ void ets_init_kernel(const uint8_t* __restrict__ queries, uint32_t nq, uint32_t dim, float* __restrict__ lo,
+                                                uint32_t* __restrict__ hist, uint32_t* __restrict__ cnt) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    bool ok = true;
+    if constexpr (!I8) {
+        const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
+        float s = 0.0f;
+        for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
+        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+    }
+    lo[q] = ok ? ETS_LO0 : __builtin_inff();
+    for (uint32_t j = 0; j < ETS_BUCKETS; ++j) hist[(size_t)q * ETS_BUCKETS + j] = 0u;
+    cnt[q] = 0u;
+}
+
+// One wave per query after a COUNT pass: lane j holds bucket j. The floor rises to the highest edge with k rows at or
+// above it; fewer than k rows counted in all (a set of fewer than k rows): it stays. The histogram is left cleared.
+__global__ __launch_bounds__(64) void ets_select_kernel(uint32_t* __restrict__ hist, uint32_t k, float* __restrict__ lo) {
+    static_assert(ETS_BUCKETS == 64u, "one bucket per lane");
+    const uint32_t q = blockIdx.x, lane = threadIdx.x;
+    const uint32_t c = hist[(size_t)q * ETS_BUCKETS + lane];
+    hist[(size_t)q * ETS_BUCKETS + lane] = 0u;
+    uint32_t above = 0; // rows in the buckets lane .. 63
+    for (uint32_t j = 0; j < ETS_BUCKETS; ++j) {
+        const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)j);
+        above += j >= lane ? o : 0u;
+    }
+    const uint64_t have = __ballot(above >= k);
+    if (lane == 0u && have != 0ull) {
+        const float l = lo[q];
+        if (l < 1.0f) lo[q] = ets_edge(l, ets_width(l), 63 - __builtin_clzll(have));
+    }
+}
+
+// One block per query of a round, after the collecting pass: the places of its list past the count get an id that no
+// handle has (dists_kernel answers +inf for it); a query with more than ETS_CAP candidates, or a floor of +inf, goes to
+// the fallback list and is voided for et_rank_kernel (its row is written again by ets_scatter_kernel). q_base: the
+// round's first query among the call's.
+__global__ __launch_bounds__(256) void ets_pad_kernel(uint32_t* __restrict__ cand, const uint32_t* __restrict__ cnt, const float* __restrict__ lo,
+                                                      uint32_t q_base, uint32_t* __restrict__ sel, uint32_t* fb_count, uint32_t* fb_list,
+                                                      uint32_t* status) {
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t m = cnt[q];
+    const bool screened = lo[q] < 1.0f;
+    const bool fallback = !screened || m > ETS_CAP;
+    for (uint32_t i = (fallback ? 0u : m) + tid; i < ETS_CAP; i += 256u) cand[(size_t)q * ETS_CAP + i] = 0xFFFFFFFFu;
+    if (tid == 0u) {
+        sel[4u * q + 0u] = 0u, sel[4u * q + 1u] = 0u, sel[4u * q + 2u] = 0u, sel[4u * q + 3u] = fallback ? 1u : 0u;
+        if (status && screened) atomicMax(status + 2, m);
+        if (fallback) {
+            fb_list[atomicAdd(fb_count, 1u)] = q_base + q;
+            if (status) atomicAdd(status + 0, 1u);
+        }
+    }
+}
+
+// the candidates' keys for et_rank_kernel: distance bits << 32 | id
+__global__ void ets_keys_kernel(const uint32_t* __restrict__ cand, const float* __restrict__ dists, const uint32_t* __restrict__ cnt,
+                                uint32_t nq, uint64_t* __restrict__ keys) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nq * ETS_CAP; i += (uint64_t)gridDim.x * blockDim.x)
+        if ((uint32_t)(i & (ETS_CAP - 1u)) < cnt[i / ETS_CAP]) keys[i] = (uint64_t)__float_as_uint(dists[i]) << 32 | (uint64_t)cand[i];
+}
+
+// the fallback: the listed queries, dense, for exact_topk's scan -- and its answers back into their places
+__global__ void ets_gather_kernel(const uint8_t* __restrict__ queries, uint32_t qbytes, const uint32_t* __restrict__ fb_list,
+                                                  uint32_t nfb, uint8_t* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nfb * qbytes; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t f = (uint32_t)(i / qbytes), b = (uint32_t)(i - (uint64_t)f * qbytes);
+        out[i] = queries[(size_t)fb_list[f] * qbytes + b];
+    }
+}
+__global__ void ets_scatter_kernel(const uint32_t* __restrict__ fb_list, uint32_t nfb, uint32_t k, const uint64_t* __restrict__ ids,
+                                                   const float* __restrict__ dists, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ xs,
+                                                   uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nfb * k; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t f = (uint32_t)(i / k), j = (uint32_t)(i - (uint64_t)f * k);
+        const size_t q = fb_list[f];
+        out_ids[q * k + j] = ids[i];
+        out_dists[q * k + j] = dists[i];
+        if (j == 0u) out_counts[q] = counts[f];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && status && xs[0]) atomicOr(status + 3, ETS_VOIDED);
+}
+// the status words of a call: [1] queries routed by their shape, [3] the form
+__global__ void ets_status_kernel(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs) {
+    atomicAdd(status + 1, routed);
+    atomicOr(status + 3, form | (xs && xs[0] ? ETS_VOIDED : 0u));
+}
+
+// ---- launchers ----
+typedef void (*EtsScanFn)(const EtsParams);
+static uint32_t ets_grid(uint64_t work) {
+    const uint64_t g = (work + 255) / 256;
+    return (uint32_t)(g > 8192 ? 8192 : g < 1 ? 1 : g);
+}
+
+uint32_t ets_tile_rows(uint32_t form) { return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : ETS_I8_ROWS; }
+
+hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    EtsScanFn fn;
+    uint32_t lds;
+    if (form == ETS_FORM_B16_7x4) fn = collect ? ets_b16_kernel<7, 4, true> : ets_b16_kernel<7, 4, false>, lds = ets_b16_lds<7, 4>(collect);
+    else if (form == ETS_FORM_B16_13x2) fn = collect ? ets_b16_kernel<13, 2, true> : ets_b16_kernel<13, 2, false>, lds = ets_b16_lds<13, 2>(collect);
+    else if (form == ETS_FORM_I8) fn = collect ? ets_i8_kernel<true> : ets_i8_kernel<false>, lds = ets_i8_lds(collect);
+    else return hipErrorInvalidValue;
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(fn, dim3(tiles, ranges), dim3(ETS_THREADS), lds, s, P);
+    return hipGetLastError();
+}
+hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s) {
+    hipLaunchKernelGGL(ets_clear_kernel, dim3(1), dim3(64), 0, s, p, n);
+    return hipGetLastError();
+}
+hipError_t ets_max_norm2(const uint8_t* elements, uint64_t n, uint32_t row_bytes, uint32_t row_stride, uint32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(ets_max_norm2_kernel, dim3(ets_grid(n * 8)), dim3(256), 0, s, elements, n, row_bytes, row_stride, out);
+    return hipGetLastError();
+}
+hipError_t ets_init(bool i8, const uint8_t* queries, uint32_t nq, uint32_t dim, float* lo, uint32_t* hist, uint32_t* cnt, hipStream_t s) {
+    hipLaunchKernelGGL(i8 ? ets_init_kernel<true> : ets_init_kernel<false>, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, dim, lo, hist, cnt);
+    return hipGetLastError();
+}
+hipError_t ets_select(uint32_t* hist, uint32_t nq, uint32_t k, float* lo, hipStream_t s) {
+    hipLaunchKernelGGL(ets_select_kernel, dim3(nq), dim3(64), 0, s, hist, k, lo);
+    return hipGetLastError();
+}
+hipError_t ets_pad(uint32_t* cand, const uint32_t* cnt, const float* lo, uint32_t nq, uint32_t q_base, uint32_t* sel, uint32_t* fb_count,
+                   uint32_t* fb_list, uint32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(ets_pad_kernel, dim3(nq), dim3(256), 0, s, cand, cnt, lo, q_base, sel, fb_count, fb_list, status);
+    return hipGetLastError();
+}
+hipError_t ets_keys(const uint32_t* cand, const float* dists, const uint32_t* cnt, uint32_t nq, uint64_t* keys, hipStream_t s) {
+    hipLaunchKernelGGL(ets_keys_kernel, dim3(ets_grid((uint64_t)nq * ETS_CAP)), dim3(256), 0, s, cand, dists, cnt, nq, keys);
+    return hipGetLastError();
+}
+hipError_t ets_gather(const uint8_t* queries, uint32_t qbytes, const uint32_t* fb_list, uint32_t nfb, uint8_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(ets_gather_kernel, dim3(ets_grid((uint64_t)nfb * qbytes)), dim3(256), 0, s, queries, qbytes, fb_list, nfb, out);
+    return hipGetLastError();
+}
+hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const uint64_t* ids, const float* dists, const uint32_t* counts,
+                       const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(ets_scatter_kernel, dim3(ets_grid((uint64_t)nfb * k)), dim3(256), 0, s, fb_list, nfb, k, ids, dists, counts, xs, out_ids,
+                       out_dists, out_counts, status);
+    return hipGetLastError();
+}
+hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s) {
+    hipLaunchKernelGGL(ets_status_kernel, dim3(1), dim3(1), 0, s, status, routed, form, xs);
+    return hipGetLastError();
+}
+
+} // namespace granne_hip

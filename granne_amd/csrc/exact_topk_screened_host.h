@@ -1,0 +1,227 @@
+// exact_topk_screened_host.h -- host side of the screened exact selection (included by granne_hip.hip after
+// exact_topk_host.h): granne_hip_exact_topk_screened*, granne_hip_exact_topk_screen_epsilon. The kernels and the method:
+// exact_topk_screened.h; DESIGN.md 3.7b.
+#pragma once
+
+#include "exact_topk_screened.h"
+
+static_assert(ETS_CAP == ET_CAP && sizeof(EtSel) == 16 && offsetof(EtSel, over) == 12, "ets_pad_kernel writes exact_topk's EtSel; one cap");
+
+extern "C" float granne_hip_exact_topk_screen_epsilon(int dtype, uint32_t dim) {
+    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return 0.0f;
+    return ets_epsilon(dtype == GRANNE_HIP_I8, dim);
+}
+
+static int exact_topk_screened_args(const granne_hip_index* ix, uint32_t nq, uint32_t k, bool buffers) {
+    if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "exact_topk_screened: index is null");
+    GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "exact_topk_screened");
+    GRANNE_HIP_F16_UNSUPPORTED(ix->dtype, "exact_topk_screened");
+    if (nq == 0) return GRANNE_HIP_OK;
+    if (!buffers) return fail(GRANNE_HIP_ERR_INVALID, "exact_topk_screened: null buffer");
+    if (k == 0 || k > ET_KMAX) return fail(GRANNE_HIP_ERR_INVALID, "exact_topk_screened: k must be in [1, %u]", ET_KMAX);
+    if (ix->n_elements > 0xFFFFFFFFull) return fail(GRANNE_HIP_ERR_INVALID, "exact_topk_screened takes up to 2^32 - 1 elements");
+    return GRANNE_HIP_OK;
+}
+
+// The form that screens the handle's rows, or ETS_FORM_ROUTED: rows too long for the register forms, or f32 rows beyond
+// the norm the bound is proven for. The largest squared norm is looked up once per handle (one pass over the rows and one
+// wait on s, under norm_mu); every later call reads the verdict.
+static int ets_form(const granne_hip_index* ix, hipStream_t s, uint32_t* form) {
+    *form = ETS_FORM_ROUTED;
+    if (ix->dtype == GRANNE_HIP_I8) {
+        if (ix->dim <= ETS_I8_DIM_MAX && ix->row_bytes <= 128u) *form = ETS_FORM_I8;
+        return GRANNE_HIP_OK;
+    }
+    if (ix->dim > ETS_F32_DIM_MAX) return GRANNE_HIP_OK;
+    granne_hip_index* mix = const_cast<granne_hip_index*>(ix);
+    int verdict = mix->screen_rows.load();
+    if (verdict == 0) {
+        std::lock_guard<std::mutex> lk(mix->norm_mu);
+        verdict = mix->screen_rows.load();
+        if (verdict == 0) {
+            uint32_t* d_max = nullptr;
+            uint32_t bits = 0;
+            HIP_TRY(hipMallocAsync((void**)&d_max, 4, s));
+            hipError_t e = ets_clear(d_max, 1u, s);
+            if (e == hipSuccess) e = ets_max_norm2(ix->d_elements.as<uint8_t>(), ix->n_elements, ix->row_bytes, ix->row_stride, d_max, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(&bits, d_max, 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            (void)hipFreeAsync(d_max, s);
+            HIP_TRY(e);
+            float worst;
+            memcpy(&worst, &bits, 4);
+            verdict = worst <= ETS_NORM2_TEST ? 1 : 2; // (a NaN compares false)
+            mix->screen_rows.store(verdict);
+        }
+    }
+    if (verdict == 1) *form = ix->dim <= 112u ? ETS_FORM_B16_7x4 : ETS_FORM_B16_13x2;
+    return GRANNE_HIP_OK;
+}
+
+// int8: the rows' 1 / |x| are made with the index (make_scan_norms); a handle that has none yet gets them here, and the call
+// waits for them once, since other streams may scan the handle next
+static int ets_scan_norms(const granne_hip_index* ix, hipStream_t s) {
+    if (ix->d_inv_norm) return GRANNE_HIP_OK;
+    if (const int rc = make_scan_norms(const_cast<granne_hip_index*>(ix), s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return GRANNE_HIP_OK;
+}
+
+// The selection on stream s, arguments checked, nq > 0. Everything is ordered on s; the call waits on s once, after the
+// last round, for one word: the number of queries on the fallback list (and runs exact_topk's scan over them if any).
+static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
+                                   float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s) {
+    GRANNE_HIP_ON_DEVICE(ix->device);
+    uint32_t form = ETS_FORM_ROUTED;
+    if (const int rc = ets_form(ix, s, &form)) return rc;
+    const uint64_t n = ix->n_elements;
+    const bool i8 = ix->dtype == GRANNE_HIP_I8;
+    const size_t qbytes = (size_t)ix->dim * query_elem_size(ix->dtype);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const uint32_t qc_max = nq < ET_CHUNK ? nq : ET_CHUNK;
+    // scratch: xs (exact_topk's status words for what is handed to it) and the fallback count; the fallback list; then a
+    // round's floors, histograms, counts, EtSel words, candidates, their distances and their keys
+    const size_t o_xs = 0, o_fbn = 16, o_fbl = 256, o_lo = o_fbl + up((size_t)nq * 4), o_hist = o_lo + up((size_t)qc_max * 4);
+    const size_t o_cnt = o_hist + up((size_t)qc_max * ETS_BUCKETS * 4), o_sel = o_cnt + up((size_t)qc_max * 4);
+    const size_t o_cand = o_sel + up((size_t)qc_max * sizeof(EtSel)), o_dist = o_cand + (size_t)qc_max * ET_CAP * 4;
+    const size_t o_keys = o_dist + (size_t)qc_max * ET_CAP * 4;
+    const size_t total = form == ETS_FORM_ROUTED ? 256 : o_keys + (size_t)qc_max * ET_CAP * 8;
+    uint8_t* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
+    struct Release {
+        void* p;
+        hipStream_t s;
+        ~Release() {
+            if (p) (void)hipFreeAsync(p, s);
+        }
+    } release{scratch, s};
+    uint32_t* const xs = (uint32_t*)(scratch + o_xs);
+    HIP_TRY(ets_clear(xs, 8u, s)); // words 0..3: xs; word 4 (o_fbn = 16 bytes): the fallback count
+    if (form == ETS_FORM_ROUTED) {
+        if (const int rc = exact_topk_run(ix, d_queries, nq, k, nullptr, 0, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+        if (d_status) HIP_TRY(ets_status(d_status, nq, (uint32_t)ETS_FORM_ROUTED, xs, s));
+        return GRANNE_HIP_OK;
+    }
+    if (i8)
+        if (const int rc = ets_scan_norms(ix, s)) return rc;
+    const uint64_t tile = ets_tile_rows(form);
+    // the prefixes the floor is raised over, shortest first, the last one all rows (exact_topk's); one stage: counted twice
+    uint64_t prefix[17];
+    uint32_t stages = 0;
+    {
+        uint64_t rev[16], p = n;
+        uint32_t m = 0;
+        rev[m++] = p;
+        while (p > 2ull * ET_PRIME_MIN && m < 16) {
+            p /= ET_PRIME_STEP;
+            if (p < ET_PRIME_MIN) p = ET_PRIME_MIN;
+            rev[m++] = p;
+        }
+        while (m) prefix[stages++] = rev[--m];
+        if (stages == 1) prefix[stages++] = n;
+    }
+    EtsParams P;
+    P.elements = ix->d_elements.as<uint8_t>();
+    P.row_bytes = ix->row_bytes;
+    P.row_stride = ix->row_stride;
+    P.dim = ix->dim;
+    P.inv_norm = i8 ? ix->d_inv_norm.as<float>() : nullptr;
+    P.inv_gmax = i8 ? P.inv_norm + ((n + 31u) & ~31ull) : nullptr;
+    P.lo = (const float*)(scratch + o_lo);
+    P.hist = (uint32_t*)(scratch + o_hist);
+    P.cnt = (uint32_t*)(scratch + o_cnt);
+    P.cand = (uint32_t*)(scratch + o_cand);
+    P.eps2 = 2.0f * ets_epsilon(i8, ix->dim);
+    uint32_t* const fb_count = (uint32_t*)(scratch + o_fbn);
+    uint32_t* const fb_list = (uint32_t*)(scratch + o_fbl);
+    for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
+        const uint32_t qc = nq - c0 < ET_CHUNK ? nq - c0 : ET_CHUNK;
+        const uint32_t tiles = (qc + ETS_QT - 1) / ETS_QT;
+        P.queries = (const uint8_t*)d_queries + (size_t)c0 * qbytes;
+        P.nq = qc;
+        auto pass = [&](bool collect, uint64_t rows) -> int {
+            // one block per compute unit (the tile and the histogram fill its LDS), four rounds of them; a multiple of 8
+            // ranges so that the tiles of a range share an XCD (bf_block)
+            uint64_t G = (rows + tile - 1) / tile;
+            const uint64_t most = 1024u / tiles;
+            if (G > most) G = most;
+            if (G >= 8) G &= ~7ull;
+            if (G < 1) G = 1;
+            P.n = rows;
+            P.per_range = ((rows + G - 1) / G + tile - 1) / tile * tile;
+            HIP_TRY(ets_scan(form, collect, tiles, (uint32_t)G, P, s));
+            return GRANNE_HIP_OK;
+        };
+        HIP_TRY(ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
+        for (uint32_t st = 0; st < stages; ++st) {
+            if (const int rc = pass(false, prefix[st])) return rc;
+            HIP_TRY(ets_select(P.hist, qc, k, (float*)(scratch + o_lo), s));
+        }
+        if (const int rc = pass(true, n)) return rc;
+        // the survivors' distances in the reference's arithmetic, then exact_topk's ranking by (distance bits, id)
+        HIP_TRY(ets_pad(P.cand, P.cnt, P.lo, qc, c0, (uint32_t*)(scratch + o_sel), fb_count, fb_list, d_status, s));
+        if (const int rc = dists_launch(ix, P.queries, nullptr, ET_CAP, P.cand, (uint64_t)qc * ET_CAP, (float*)(scratch + o_dist), nullptr, s)) return rc;
+        HIP_TRY(ets_keys(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, (uint64_t*)(scratch + o_keys), s));
+        hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_keys), (const uint32_t*)P.cnt,
+                           (const EtSel*)(scratch + o_sel), k, d_out_ids + (size_t)c0 * k, d_out_dists + (size_t)c0 * k, d_out_counts + c0,
+                           (uint32_t*)nullptr, (uint32_t*)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_status) HIP_TRY(ets_status(d_status, 0u, form, nullptr, s));
+    uint32_t nfb = 0;
+    HIP_TRY(hipMemcpyAsync(&nfb, fb_count, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (nfb == 0) return GRANNE_HIP_OK;
+    // the fallback: the listed queries by exact_topk's own scan, the answers into their places
+    const size_t f_ids = up((size_t)nfb * qbytes), f_d = f_ids + (size_t)nfb * k * 8, f_c = f_d + up((size_t)nfb * k * 4);
+    uint8_t* fb = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&fb, f_c + (size_t)nfb * 4, s));
+    Release release_fb{fb, s};
+    HIP_TRY(ets_gather((const uint8_t*)d_queries, (uint32_t)qbytes, fb_list, nfb, fb, s));
+    if (const int rc = exact_topk_run(ix, fb, nfb, k, nullptr, 0, (uint64_t*)(fb + f_ids), (float*)(fb + f_d), (uint32_t*)(fb + f_c), xs, s)) return rc;
+    HIP_TRY(ets_scatter(fb_list, nfb, k, (const uint64_t*)(fb + f_ids), (const float*)(fb + f_d), (const uint32_t*)(fb + f_c), xs, d_out_ids,
+                        d_out_dists, d_out_counts, d_status, s));
+    return GRANNE_HIP_OK;
+}
+
+// exact_topk's answer, the matrix cores screening the rows first (exact_topk_screened.h)
+extern "C" int granne_hip_exact_topk_screened_device(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k,
+                                                     uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status,
+                                                     void* stream) {
+    if (const int rc = exact_topk_screened_args(ix, nq, k, d_queries && d_out_ids && d_out_dists && d_out_counts)) return rc;
+    if (nq == 0) return GRANNE_HIP_OK;
+    return exact_topk_screened_run(ix, d_queries, nq, k, d_out_ids, d_out_dists, d_out_counts, d_status, (hipStream_t)stream);
+}
+
+// host buffers in and out; GRANNE_HIP_ERR_OVERFLOW (outputs and status still written) where exact_topk itself would give it
+extern "C" int granne_hip_exact_topk_screened(const granne_hip_index* ix, const void* queries, uint32_t nq, uint32_t k, uint64_t* out_ids,
+                                              float* out_dists, uint32_t* out_counts, uint32_t* out_status) {
+    if (const int rc = exact_topk_screened_args(ix, nq, k, queries && out_ids && out_dists && out_counts)) return rc;
+    if (nq == 0) return GRANNE_HIP_OK;
+    GRANNE_HIP_ON_DEVICE(ix->device);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t qb = (size_t)nq * ix->dim * query_elem_size(ix->dtype);
+    const size_t o_ids = up(qb), o_d = o_ids + (size_t)nq * k * 8, o_c = o_d + up((size_t)nq * k * 4), o_st = o_c + up((size_t)nq * 4);
+    DevBuf block;
+    HIP_TRY(block.alloc(o_st + 16));
+    struct Settle { // (declared after the block: whatever the passes left running is over before the block is freed)
+        ~Settle() { (void)hipDeviceSynchronize(); }
+    } settle;
+    uint8_t* const buf = block.as<uint8_t>();
+    HIP_TRY(hipMemcpy(buf, queries, qb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(buf + o_st, 0, 16));
+    if (const int rc = exact_topk_screened_run(ix, buf, nq, k, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c),
+                                               (uint32_t*)(buf + o_st), nullptr))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t st[4];
+    HIP_TRY(hipMemcpy(out_ids, buf + o_ids, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_dists, buf + o_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counts, buf + o_c, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st, buf + o_st, 16, hipMemcpyDeviceToHost));
+    if (out_status) memcpy(out_status, st, 16);
+    if (st[3] & ETS_VOIDED)
+        return fail(GRANNE_HIP_ERR_OVERFLOW, "exact_topk_screened: exact_topk's own selection overflowed for a query handed to it (more than %u rows "
+                    "inside one second-level bin at its k-th distance)", ET_CAP);
+    return GRANNE_HIP_OK;
+}

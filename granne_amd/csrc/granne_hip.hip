@@ -194,6 +194,8 @@ struct granne_hip_index {
     // the exact scan of int8 rows (brute_force.h): 1 / |x| per row, made at the first scan
     std::mutex norm_mu;
     DevBuf d_inv_norm;
+    // exact_topk_screened over f32 rows: 0 not looked yet, 1 every row's squared norm is within the screen's bound, 2 not
+    std::atomic<int> screen_rows{0};
     // f32 rows of the sketched shapes: one SKETCH_LINE per row (search_kernel.h), made with the index, or null
     DevBuf d_sketch;
     // host-pointer searches (granne_hip_search / _search_batch): a stream, a device buffer and a pinned
@@ -2484,3 +2486,8 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // ------------------------------------------------------------------------------------------------
 #include "exact_range_host.h"
 #include "range_host.h"
+
+// ------------------------------------------------------------------------------------------------
+// the exact selection behind a matrix-core screen
+// ------------------------------------------------------------------------------------------------
+#include "exact_topk_screened_host.h"

@@ -705,6 +705,43 @@ class Granne:
                                  "at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
 
+    def exact_topk_screened_device(self, d_queries, nq, k, d_ids, d_dists, d_counts, d_status=0, stream=0):
+        """exact_topk's answer with the matrix cores screening the rows first (granne_hip_exact_topk_screened_device). Raw
+        device pointers (int; d_status: u32[4] zeroed by the caller, or 0); ordered on `stream`, which the call waits on
+        once at its end."""
+        check(lib().granne_hip_exact_topk_screened_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_ids),
+                                                          C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_status),
+                                                          C.c_void_p(stream)))
+
+    def exact_topk_screened(self, queries, k, prepared=True, stats=False):
+        """Host convenience over exact_topk_screened_device: the returns of `exact_topk`, the same bytes. The status words
+        (stats=True): [0] queries answered by exact_topk's scan after the screen, [1] queries routed to it by the handle's
+        shape, [2] the largest number of survivors of one query, [3] the form that ran, bit 31 set where exact_topk itself
+        voided a query (count 0) -- with stats=False that raises GranneHipError(ERR_OVERFLOW) as `exact_topk` does."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        k = int(k)
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(q.shape[0], -1)).to(dev)
+        ids = torch.empty((q.shape[0], max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((q.shape[0], max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(q.shape[0], dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.exact_topk_screened_device(tq.data_ptr(), q.shape[0], k, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(), st.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        status = st.cpu().numpy().astype(np.uint32)
+        out = ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+        if stats:
+            return out + (status,)
+        if status[3] & 0x80000000:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk_screened: exact_topk's selection overflowed for a query handed to it")
+        return out
+
     def num_elements(self):
         """Rows of the element set (at least len()): what exact_topk and exact_topk_filtered scan."""
         return int(lib().granne_hip_index_num_elements(self._h))

@@ -369,6 +369,29 @@ public:
         return out;
     }
 
+    // exact_topk's answer, the same ids and distance bytes, with the matrix cores screening the rows first under a proven
+    // bound on the screen score (granne_hip_exact_topk_screened); shapes without a screen and queries with too many
+    // survivors are answered by exact_topk's scan inside the call. Throws where exact_topk throws. `status` (optional):
+    // the four status words of the call.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_screened(const Element* elements, size_t nq, size_t k,
+                                                                           std::vector<uint32_t>* status = nullptr) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        std::vector<uint64_t> ids(nq * k);
+        std::vector<float> ds(nq * k);
+        std::vector<uint32_t> counts(nq), st(4, 0u);
+        check(granne_hip_exact_topk_screened(h_.get(), q.data(), (uint32_t)nq, (uint32_t)k, ids.data(), ds.data(), counts.data(), st.data()));
+        if (status) *status = st;
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // exact_topk among the ids `allowed` lets through (granne_hip_exact_topk_filtered_device; one bitmap for all queries,
     // over num_elements() ids): the scan walks the bitmap's id list -- the tool for a selective filter, where
     // search_filtered steps over many disallowed nodes per allowed one. A result holds fewer than k ids when fewer are allowed.

@@ -435,6 +435,38 @@ int granne_hip_exact_topk_device(const granne_hip_index* index, const void* d_qu
 int granne_hip_exact_topk(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
                           uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
 
+/* granne_hip_exact_topk's answer -- the same ids, distance bytes and counts, k up to GRANNE_HIP_EXACT_TOPK_KMAX -- with
+ * the matrix cores in front: every (query, row) pair gets a cheap screen score (f32 rows: two bf16 pieces per component,
+ * three matrix instructions per 16 components; int8 rows: the exact integer dot times the two inverse norms), a PROVEN
+ * bound eps on |score - (1 - reference distance)| (granne_hip_exact_topk_screen_epsilon) makes the score a screen that no
+ * row of the true top-k fails, and only the survivors, a few times k per query, get the reference's arithmetic and the
+ * (distance bits, id) ranking (granne_amd/csrc/exact_topk_screened.h).
+ *   screened   f32 rows of up to 208 components whose squared norms are at most 1 + 2^-10 (prepared rows are; looked up
+ *              once per handle, on the first call: one pass over the rows and one wait on `stream`), int8 rows of up to 128.
+ *   routed     every other handle is answered by granne_hip_exact_topk_device inside the call. GRANNE_HIP_F16 and compact
+ *              SumEmbeddings handles, k == 0, k > GRANNE_HIP_EXACT_TOPK_KMAX and null buffers are refused as
+ *              granne_hip_exact_topk refuses them; nq == 0 does nothing.
+ *   fallback   a query with more than GRANNE_HIP_EXACT_TOPK_CAP survivors (thousands of copies of a row, near-ties denser
+ *              than a score bucket) or, f32, of squared norm above 1 + 2^-10 is answered by granne_hip_exact_topk_device
+ *              too, after the screen: the two paths' answers are the same bytes. Where that scan itself overflows, the
+ *              query's row is voided as it voids it (count 0).
+ *   d_status   u32[4], optional, zeroed by the caller: [0] queries answered by the fallback, [1] queries routed by the
+ *              handle's shape (0 or nq), [2] the largest number of survivors of one query (it counts on past the cap),
+ *              [3] the form that ran (0 routed, 1 and 2 the f32 forms for up to 112 and 208 components, 3 int8), bit 31
+ *              set where exact_topk voided a query handed to it.
+ * Stream-ordered; the call waits on `stream` once, at its end, for one word (the length of the fallback list). Scratch
+ * from hipMallocAsync, about 64 MB for a round of 1024 queries (candidates 16 MB, their distances 16 MB, keys 32 MB) plus, where
+ * queries fall back, granne_hip_exact_topk_device's own. Neither entry writes GRANNE_HIP_OPT_LAST_SCAN. */
+int granne_hip_exact_topk_screened_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                          uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                          uint32_t* d_status /* u32[4], optional, zeroed by the caller */, void* stream);
+/* the same with host buffers in and out (synchronous). GRANNE_HIP_ERR_OVERFLOW when bit 31 of status[3] is set: the
+ * outputs (and out_status, optional) are still written. */
+int granne_hip_exact_topk_screened(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                                   uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
+/* the screen's bound for rows of `dtype` and `dim` components -- the number the kernels are given; 0: no screen for the shape */
+float granne_hip_exact_topk_screen_epsilon(int dtype, uint32_t dim);
+
 /* The per-shard top-k of one batch as ONE buffer -- what a rank contributes to the single exchange
  * step of the partitioned mode (one all-gather, or one peer copy):
  *   [nq*k u64 local ids][nq*k f32 dists][nq u32 counts], padded to 16 bytes.                      */

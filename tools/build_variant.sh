@@ -5,4 +5,4 @@ cd "$(dirname "$0")/.."
 NAME=$1; shift
 exec /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
   -fno-fast-math -fPIC -shared -Wall -Wno-unused-function -DGRANNE_HIP_USE_DPP=1 "$@" -I include \
-  granne_amd/csrc/granne_hip.hip -o granne_amd/lib/libgranne_hip_$NAME.so
+  granne_amd/csrc/granne_hip.hip granne_amd/csrc/exact_topk_screened.hip -o granne_amd/lib/libgranne_hip_$NAME.so
