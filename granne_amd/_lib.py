@@ -248,6 +248,8 @@ SIGNATURES = {
     "granne_hip_filter_to_ids_device": (i32, [vp, u64, vp, vp, i32, vp]),
     "granne_hip_exact_topk_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_screened_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_screened_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_range_device": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp]),

@@ -48,6 +48,10 @@ constexpr float ETS_NORM2_TEST = 1.0f + 0x1p-10f - 0x1p-14f; // what an f32 sum 
 constexpr uint32_t ETS_F32_DIM_MAX = 208, ETS_I8_DIM_MAX = 128;
 enum { ETS_FORM_ROUTED = 0, ETS_FORM_B16_7x4 = 1, ETS_FORM_B16_13x2 = 2, ETS_FORM_I8 = 3 };
 constexpr uint32_t ETS_VOIDED = 0x80000000u; // status[3]: exact_topk's own selection overflowed for a query handed to it
+// What a scan runs over (granne_hip_exact_topk_screened_filtered*): all rows; the positions of the id list
+// one shared bitmap compacts to; or all rows under a bit test, one bitmap per query -- a 32-row result block is one word of
+// it, read only for the blocks that pass the wave's floor test.
+enum { ETS_ALL = 0, ETS_LIST = 1, ETS_BITS = 2 };
 
 // The bound on |screen score - (1 - reference distance)|; 0: the shape has no screen.
 static inline float ets_epsilon(int i8, uint32_t dim) {
@@ -75,11 +79,16 @@ struct EtsParams {
     uint32_t* cnt;           // COLLECT: [nq]
     uint32_t* cand;          // COLLECT: [nq][ETS_CAP]
     float eps2;              // COLLECT: 2 eps
+    const uint32_t* list = nullptr;   // ETS_LIST: the allowed ids, ascending; n counts its positions
+    const uint32_t* filter = nullptr; // ETS_BITS: this round's bitmaps, query q's at filter + q * filter_stride
+    uint64_t filter_stride = 0;       // ETS_BITS: in words
 };
 
 // the launchers (exact_topk_screened.hip); every one is ordered on s and returns what the launch left
 uint32_t ets_tile_rows(uint32_t form); // rows per tile of the form's scan
 hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+hipError_t ets_empty(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s);
 hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s);
 hipError_t ets_max_norm2(const uint8_t* elements, uint64_t n, uint32_t row_bytes, uint32_t row_stride, uint32_t* out, hipStream_t s);
 hipError_t ets_init(bool i8, const uint8_t* queries, uint32_t nq, uint32_t dim, float* lo, uint32_t* hist, uint32_t* cnt, hipStream_t s);

@@ -47,14 +47,18 @@ struct EtsFloor {
 
 // The 16 scores a lane holds of one 32-row block: rows e_blk + 8 (v / 4) + v % 4 + 4 h, its query in column `col`.
 // COUNT: into the block's LDS histogram (hq: the query's column of it). COLLECT: into the query's candidate list.
-template <bool COLLECT>
+// ETS_BITS: `word` is the block's word of the query's bitmap -- rows e_blk .. e_blk + 31 are its bits 0 .. 31 -- and only
+// allowed rows are counted or collected. ETS_LIST: the rows are list positions; what is collected is the id at the position.
+template <bool COLLECT, int SRC>
 __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
-                                           bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq) {
+                                           bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq, uint32_t word) {
+    const uint32_t wv = word >> (4u * h); // the lane's row v: bit 8 (v / 4) + v % 4 of it
+    auto allowed = [&](int v) { return SRC != ETS_BITS || (wv >> (8 * (v / 4) + v % 4) & 1u) != 0u; };
     if constexpr (!COLLECT) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
-            if (sc[v] >= F.thr && (whole || e < r1)) {
+            if (sc[v] >= F.thr && (whole || e < r1) && allowed(v)) {
                 int j = (int)__builtin_fminf((sc[v] - F.lo) * F.inv_w, (float)(ETS_BUCKETS - 1));
                 j = j < 0 ? 0 : j;
                 while (j > 0 && sc[v] < ets_edge(F.lo, F.w, j)) --j; // never round up into a bucket
@@ -66,7 +70,7 @@ __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
-            mask |= (sc[v] >= F.thr && (whole || e < r1)) ? 1u << v : 0u;
+            mask |= (sc[v] >= F.thr && (whole || e < r1) && allowed(v)) ? 1u << v : 0u;
         }
         const uint32_t mine = (uint32_t)__builtin_popcount(mask);
         const uint32_t other = (uint32_t)__shfl_xor((int)mine, 32, 64);
@@ -77,7 +81,10 @@ __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             if (mask >> v & 1u) {
-                if (pos < ETS_CAP) P.cand[(size_t)q * ETS_CAP + pos] = (uint32_t)(e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h);
+                if (pos < ETS_CAP) {
+                    const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
+                    P.cand[(size_t)q * ETS_CAP + pos] = SRC == ETS_LIST ? P.list[e] : (uint32_t)e;
+                }
                 ++pos;
             }
         }
@@ -96,8 +103,19 @@ __device__ __forceinline__ void ets_hist_flush(const EtsParams& P, const uint32_
     }
 }
 
-// f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order.
-template <int KG, int R, bool COLLECT>
+// The word of query q's bitmap for the 32-row block at e_blk (ETS_BITS), read by the lanes the block's test passed for
+// (`hit`: a live query's); a block past the range's end (zero rows, which can pass a floor below 0) reads nothing.
+template <int SRC>
+__device__ __forceinline__ uint32_t ets_word(const EtsParams& P, uint32_t q, uint64_t e_blk, uint64_t r1, bool hit) {
+    if constexpr (SRC == ETS_BITS) {
+        if (hit && e_blk < r1) return P.filter[(size_t)q * P.filter_stride + (e_blk >> 5)];
+    }
+    return 0u;
+}
+
+// f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order. SRC: the rows are all
+// rows (ETS_ALL, ETS_BITS: P.n of them) or the rows at the positions [0, P.n) of P.list (ETS_LIST).
+template <int KG, int R, bool COLLECT, int SRC = ETS_ALL>
 __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr uint32_t ET = 32u * R;                // rows per tile
@@ -143,8 +161,11 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
             const uint32_t u = tid + ETS_THREADS * j;
             const uint32_t row = u / UNITS, c4 = u - row * UNITS;
             pf[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (u < ET * UNITS && e0 + row < r1 && c4 < row_f4)
-                pf[j] = *reinterpret_cast<const float4*>(P.elements + (e0 + row) * P.row_stride + c4 * 16u);
+            if (u < ET * UNITS && e0 + row < r1 && c4 < row_f4) {
+                uint64_t id = e0 + row;
+                if constexpr (SRC == ETS_LIST) id = P.list[id];
+                pf[j] = *reinterpret_cast<const float4*>(P.elements + id * P.row_stride + c4 * 16u);
+            }
         }
     };
     if (r0 < r1) fetch(r0);
@@ -205,7 +226,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
                 float sc[16];
 #pragma unroll
                 for (int v = 0; v < 16; ++v) sc[v] = acc[r][v];
-                ets_take16<COLLECT>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col);
+                const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && mx >= F.thr);
+                ets_take16<COLLECT, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
             }
         }
     }
@@ -219,7 +241,9 @@ constexpr uint32_t ets_b16_lds(bool collect) {
 
 // int8 rows of up to 128 bytes: score = ((float)dot * (1 / |x|)) * (1 / |q|), the dot exact in i32
 constexpr uint32_t ETS_I8_R = 4, ETS_I8_ROWS = 32u * ETS_I8_R, ETS_I8_STRIDE = 128u + 16u;
-template <bool COLLECT>
+// ETS_LIST: a gathered block has no entry in inv_gmax; its bound is made from the block's own 1 / |x| on their way into
+// LDS (gm, two copies by the tile's parity: one is read while the next tile's is being made).
+template <bool COLLECT, int SRC = ETS_ALL>
 __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr int R = (int)ETS_I8_R;
@@ -228,12 +252,16 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
     float* inv = reinterpret_cast<float*>(smem_ets + (size_t)ET * STRIDE); // [ET] 1 / |x|
     float* gm = inv + ET;                                                   // [2][R] inv_gmax of the tile's blocks, by lane half
     uint32_t* lh = reinterpret_cast<uint32_t*>(gm + 2 * R);                 // COUNT: [ETS_BUCKETS][ETS_QT]
+    uint32_t* gml = lh + (COLLECT ? 0u : ETS_BUCKETS * ETS_QT);             // ETS_LIST: [2][2][R] float bits, by parity
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t col = lane & 31u, h = lane >> 5;
     const EtsBlock blk = ets_block();
     const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
     const bool qlive = q < P.nq;
     if constexpr (!COLLECT) ets_hist_clear(lh, tid);
+    if constexpr (SRC == ETS_LIST) {
+        if (tid < 4u * R) gml[tid] = 0u; // (the first tile's first barrier stands between this and the first maximum)
+    }
     ets_i32x4 qr[4]; // bytes 32 g + 16 h .. + 15 of the query (bf_i8_kernel's operand)
     float qinv = 0.0f;
     {
@@ -271,17 +299,22 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
     uint4 pf[NPF];
     float pfn[NPF], pfg = 0.0f;
     auto fetch = [&](uint64_t e0) {
-        if (tid < 2u * R) pfg = e0 + 32u * (tid >> 1) < r1 ? P.inv_gmax[((e0 >> 5) + (tid >> 1)) * 2u + (tid & 1u)] : 0.0f;
+        if constexpr (SRC != ETS_LIST) {
+            if (tid < 2u * R) pfg = e0 + 32u * (tid >> 1) < r1 ? P.inv_gmax[((e0 >> 5) + (tid >> 1)) * 2u + (tid & 1u)] : 0.0f;
+        }
 #pragma unroll
         for (uint32_t j = 0; j < NPF; ++j) {
             const uint64_t row = e0 + my_row + (ETS_THREADS / 8u) * j;
             pf[j] = make_uint4(0, 0, 0, 0);
             pfn[j] = 0.0f;
-            if (row < r1 && col_live) pf[j] = *reinterpret_cast<const uint4*>(P.elements + row * P.row_stride + my_c * 16u);
-            if (row < r1 && my_c == 0u) pfn[j] = P.inv_norm[row];
+            uint64_t id = row;
+            if constexpr (SRC == ETS_LIST) id = row < r1 ? P.list[row] : 0u;
+            if (row < r1 && col_live) pf[j] = *reinterpret_cast<const uint4*>(P.elements + id * P.row_stride + my_c * 16u);
+            if (row < r1 && my_c == 0u) pfn[j] = P.inv_norm[id];
         }
     };
     if (r0 < r1) fetch(r0);
+    uint32_t par = 0; // ETS_LIST: which copy of gml this tile's maxima go to
     for (uint64_t e0 = r0; e0 < r1; e0 += ET) {
         __syncthreads();
 #pragma unroll
@@ -289,9 +322,19 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
             const uint32_t row = my_row + (ETS_THREADS / 8u) * j;
             *reinterpret_cast<uint4*>(tile + (size_t)row * STRIDE + my_c * 16u) = pf[j];
             if (my_c == 0u) inv[row] = pfn[j];
+            if constexpr (SRC == ETS_LIST) { // row = 32 r + 8 g4 + 4 h + t: non-negative floats order as their bits
+                if (my_c == 0u) atomicMax(gml + par * 2u * R + (row >> 2 & 1u) * R + (row >> 5), __float_as_uint(pfn[j]));
+            }
         }
-        if (tid < 2u * R) gm[(tid & 1u) * R + (tid >> 1)] = pfg;
+        if constexpr (SRC != ETS_LIST) {
+            if (tid < 2u * R) gm[(tid & 1u) * R + (tid >> 1)] = pfg;
+        }
         __syncthreads();
+        if constexpr (SRC == ETS_LIST) {
+            gm = reinterpret_cast<float*>(gml + par * 2u * R);
+            par ^= 1u;
+            if (tid < 2u * R) gml[par * 2u * R + tid] = 0u; // the next tile's copy: last read before this tile's first barrier
+        }
         if (e0 + ET < r1) fetch(e0 + ET);
         ets_i32x16 acc[R];
 #pragma unroll
@@ -321,7 +364,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
             int im = 0;
 #pragma unroll
             for (int v = 0; v < 16; ++v) im = max(im, acc[r][v]);
-            if (!__ballot(((float)im * gm[h * R + r]) * qinv >= F.thr)) continue;
+            const bool hit = ((float)im * gm[h * R + r]) * qinv >= F.thr;
+            if (!__ballot(hit)) continue;
             float sc[16];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) { // rows r*32 + 8*g4 + 4*h + 0..3: their 1 / |x| in one read
@@ -331,14 +375,16 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
                 sc[g4 * 4 + 2] = ((float)acc[r][g4 * 4 + 2] * iv.z) * qinv;
                 sc[g4 * 4 + 3] = ((float)acc[r][g4 * 4 + 3] * iv.w) * qinv;
             }
-            ets_take16<COLLECT>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col);
+            const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && hit);
+            ets_take16<COLLECT, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
         }
     }
     if constexpr (!COLLECT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
 }
 
-constexpr uint32_t ets_i8_lds(bool collect) {
-    return ETS_I8_ROWS * ETS_I8_STRIDE + ETS_I8_ROWS * 4u + 2u * ETS_I8_R * 4u + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u);
+constexpr uint32_t ets_i8_lds(bool collect, bool list = false) {
+    return ETS_I8_ROWS * ETS_I8_STRIDE + ETS_I8_ROWS * 4u + 2u * ETS_I8_R * 4u + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u) +
+           (list ? 4u * ETS_I8_R * 4u : 0u);
 }
 
 __global__ void ets_clear_kernel(uint32_t* p, uint32_t n) {
@@ -455,6 +501,14 @@ __global__ void ets_scatter_kernel(const uint32_t* __restrict__ fb_list, uint32_
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && status && xs[0]) atomicOr(status + 3, ETS_VOIDED);
 }
+// a filter that allows nothing: every query's answer is empty
+__global__ void ets_empty_kernel(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nq * k; i += (uint64_t)gridDim.x * blockDim.x) {
+        out_ids[i] = 0xFFFFFFFFFFFFFFFFull;
+        out_dists[i] = __builtin_inff();
+        if (i < nq) out_counts[i] = 0u; // (k >= 1)
+    }
+}
 // the status words of a call: [1] queries routed by their shape, [3] the form
 __global__ void ets_status_kernel(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs) {
     atomicAdd(status + 1, routed);
@@ -470,13 +524,24 @@ static uint32_t ets_grid(uint64_t work) {
 
 uint32_t ets_tile_rows(uint32_t form) { return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : ETS_I8_ROWS; }
 
+template <int SRC>
+static EtsScanFn ets_scan_fn(uint32_t form, bool collect, uint32_t* lds) {
+    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(collect), collect ? ets_b16_kernel<7, 4, true, SRC> : ets_b16_kernel<7, 4, false, SRC>;
+    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(collect), collect ? ets_b16_kernel<13, 2, true, SRC> : ets_b16_kernel<13, 2, false, SRC>;
+    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(collect, SRC == ETS_LIST), collect ? ets_i8_kernel<true, SRC> : ets_i8_kernel<false, SRC>;
+    return nullptr;
+}
+
 hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
-    EtsScanFn fn;
-    uint32_t lds;
-    if (form == ETS_FORM_B16_7x4) fn = collect ? ets_b16_kernel<7, 4, true> : ets_b16_kernel<7, 4, false>, lds = ets_b16_lds<7, 4>(collect);
-    else if (form == ETS_FORM_B16_13x2) fn = collect ? ets_b16_kernel<13, 2, true> : ets_b16_kernel<13, 2, false>, lds = ets_b16_lds<13, 2>(collect);
-    else if (form == ETS_FORM_I8) fn = collect ? ets_i8_kernel<true> : ets_i8_kernel<false>, lds = ets_i8_lds(collect);
-    else return hipErrorInvalidValue;
+    return ets_scan_src(form, collect, ETS_ALL, tiles, ranges, P, s);
+}
+hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = src == ETS_ALL    ? ets_scan_fn<ETS_ALL>(form, collect, &lds)
+                         : src == ETS_LIST ? ets_scan_fn<ETS_LIST>(form, collect, &lds)
+                         : src == ETS_BITS ? ets_scan_fn<ETS_BITS>(form, collect, &lds)
+                                           : nullptr;
+    if (!fn) return hipErrorInvalidValue;
     if (lds > 64u * 1024u) {
         const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -517,6 +582,10 @@ hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const 
                        const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(ets_scatter_kernel, dim3(ets_grid((uint64_t)nfb * k)), dim3(256), 0, s, fb_list, nfb, k, ids, dists, counts, xs, out_ids,
                        out_dists, out_counts, status);
+    return hipGetLastError();
+}
+hipError_t ets_empty(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s) {
+    hipLaunchKernelGGL(ets_empty_kernel, dim3(ets_grid((uint64_t)nq * k)), dim3(256), 0, s, nq, k, out_ids, out_dists, out_counts);
     return hipGetLastError();
 }
 hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s) {

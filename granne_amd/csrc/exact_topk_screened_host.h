@@ -67,14 +67,27 @@ static int ets_scan_norms(const granne_hip_index* ix, hipStream_t s) {
     return GRANNE_HIP_OK;
 }
 
+// the fallback list's queries under their own bitmaps (exact_topk_screened_filtered_host.h)
+static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_queries, const uint32_t* d_fb_list, uint32_t nfb, uint32_t k,
+                             const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                             uint32_t* d_xs, hipStream_t s);
+
 // The selection on stream s, arguments checked, nq > 0. Everything is ordered on s; the call waits on s once, after the
 // last round, for one word: the number of queries on the fallback list (and runs exact_topk's scan over them if any).
+// d_filter (exact_topk_screened_filtered_host.h; null: all rows, and nothing below differs from the unfiltered call):
+// filter_stride_words == 0 is one bitmap for every query, compacted here to its ascending id list, whose length m the call
+// reads back once, at its start -- the prefixes and the grids are then made from m as they are made from n, and the
+// kernels scan list positions (ETS_LIST); any other stride is one bitmap per query, tested in the kernels (ETS_BITS).
+// What is handed to exact_topk_run, routed or on the fallback list, goes there with its filter.
 static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
-                                   float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s) {
+                                   float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s,
+                                   const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
     if (const int rc = ets_form(ix, s, &form)) return rc;
-    const uint64_t n = ix->n_elements;
+    const int src = !d_filter ? ETS_ALL : filter_stride_words == 0 ? ETS_LIST : ETS_BITS;
+    const bool list = src == ETS_LIST && form != ETS_FORM_ROUTED;
+    uint64_t n = ix->n_elements; // ETS_LIST: the list's length, once it is known
     const bool i8 = ix->dtype == GRANNE_HIP_I8;
     const size_t qbytes = (size_t)ix->dim * query_elem_size(ix->dtype);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -85,7 +98,9 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     const size_t o_cnt = o_hist + up((size_t)qc_max * ETS_BUCKETS * 4), o_sel = o_cnt + up((size_t)qc_max * 4);
     const size_t o_cand = o_sel + up((size_t)qc_max * sizeof(EtSel)), o_dist = o_cand + (size_t)qc_max * ET_CAP * 4;
     const size_t o_keys = o_dist + (size_t)qc_max * ET_CAP * 4;
-    const size_t total = form == ETS_FORM_ROUTED ? 256 : o_keys + (size_t)qc_max * ET_CAP * 8;
+    // ETS_LIST: the list's length (u64), the compaction's block counts, the list
+    const size_t o_m = o_keys + (size_t)qc_max * ET_CAP * 8, o_blk = o_m + 256, o_list = o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
+    const size_t total = form == ETS_FORM_ROUTED ? 256 : list ? o_list + (size_t)n * 4 : o_m;
     uint8_t* scratch = nullptr;
     HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
     struct Release {
@@ -98,9 +113,22 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     uint32_t* const xs = (uint32_t*)(scratch + o_xs);
     HIP_TRY(ets_clear(xs, 8u, s)); // words 0..3: xs; word 4 (o_fbn = 16 bytes): the fallback count
     if (form == ETS_FORM_ROUTED) {
-        if (const int rc = exact_topk_run(ix, d_queries, nq, k, nullptr, 0, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+        if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s))
+            return rc;
         if (d_status) HIP_TRY(ets_status(d_status, nq, (uint32_t)ETS_FORM_ROUTED, xs, s));
         return GRANNE_HIP_OK;
+    }
+    if (list) {
+        if (const int rc = filter_compact<uint32_t>(d_filter, n, (uint32_t*)(scratch + o_blk), (uint32_t*)(scratch + o_list),
+                                                    (uint64_t*)(scratch + o_m), nullptr, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&n, scratch + o_m, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n == 0) { // nothing is allowed: no scan
+            HIP_TRY(ets_empty(nq, k, d_out_ids, d_out_dists, d_out_counts, s));
+            if (d_status) HIP_TRY(ets_status(d_status, 0u, form, nullptr, s));
+            return GRANNE_HIP_OK;
+        }
     }
     if (i8)
         if (const int rc = ets_scan_norms(ix, s)) return rc;
@@ -126,12 +154,14 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     P.row_stride = ix->row_stride;
     P.dim = ix->dim;
     P.inv_norm = i8 ? ix->d_inv_norm.as<float>() : nullptr;
-    P.inv_gmax = i8 ? P.inv_norm + ((n + 31u) & ~31ull) : nullptr;
+    P.inv_gmax = i8 ? P.inv_norm + ((ix->n_elements + 31u) & ~31ull) : nullptr;
     P.lo = (const float*)(scratch + o_lo);
     P.hist = (uint32_t*)(scratch + o_hist);
     P.cnt = (uint32_t*)(scratch + o_cnt);
     P.cand = (uint32_t*)(scratch + o_cand);
     P.eps2 = 2.0f * ets_epsilon(i8, ix->dim);
+    P.list = list ? (const uint32_t*)(scratch + o_list) : nullptr;
+    P.filter_stride = filter_stride_words;
     uint32_t* const fb_count = (uint32_t*)(scratch + o_fbn);
     uint32_t* const fb_list = (uint32_t*)(scratch + o_fbl);
     for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
@@ -139,6 +169,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
         const uint32_t tiles = (qc + ETS_QT - 1) / ETS_QT;
         P.queries = (const uint8_t*)d_queries + (size_t)c0 * qbytes;
         P.nq = qc;
+        P.filter = src == ETS_BITS ? d_filter + (size_t)c0 * filter_stride_words : nullptr;
         auto pass = [&](bool collect, uint64_t rows) -> int {
             // one block per compute unit (the tile and the histogram fill its LDS), four rounds of them; a multiple of 8
             // ranges so that the tiles of a range share an XCD (bf_block)
@@ -149,7 +180,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
             if (G < 1) G = 1;
             P.n = rows;
             P.per_range = ((rows + G - 1) / G + tile - 1) / tile * tile;
-            HIP_TRY(ets_scan(form, collect, tiles, (uint32_t)G, P, s));
+            HIP_TRY(ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s));
             return GRANNE_HIP_OK;
         };
         HIP_TRY(ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
@@ -172,13 +203,18 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     HIP_TRY(hipMemcpyAsync(&nfb, fb_count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (nfb == 0) return GRANNE_HIP_OK;
-    // the fallback: the listed queries by exact_topk's own scan, the answers into their places
+    // the fallback: the listed queries by exact_topk's own scan (under their filter), the answers into their places
     const size_t f_ids = up((size_t)nfb * qbytes), f_d = f_ids + (size_t)nfb * k * 8, f_c = f_d + up((size_t)nfb * k * 4);
     uint8_t* fb = nullptr;
     HIP_TRY(hipMallocAsync((void**)&fb, f_c + (size_t)nfb * 4, s));
     Release release_fb{fb, s};
     HIP_TRY(ets_gather((const uint8_t*)d_queries, (uint32_t)qbytes, fb_list, nfb, fb, s));
-    if (const int rc = exact_topk_run(ix, fb, nfb, k, nullptr, 0, (uint64_t*)(fb + f_ids), (float*)(fb + f_d), (uint32_t*)(fb + f_c), xs, s)) return rc;
+    if (src != ETS_BITS) {
+        if (const int rc = exact_topk_run(ix, fb, nfb, k, d_filter, 0, (uint64_t*)(fb + f_ids), (float*)(fb + f_d), (uint32_t*)(fb + f_c), xs, s))
+            return rc;
+    } else if (const int rc = ets_fallback_bits(ix, fb, fb_list, nfb, k, d_filter, filter_stride_words, (uint64_t*)(fb + f_ids), (float*)(fb + f_d),
+                                                (uint32_t*)(fb + f_c), xs, s))
+        return rc;
     HIP_TRY(ets_scatter(fb_list, nfb, k, (const uint64_t*)(fb + f_ids), (const float*)(fb + f_d), (const uint32_t*)(fb + f_c), xs, d_out_ids,
                         d_out_dists, d_out_counts, d_status, s));
     return GRANNE_HIP_OK;

@@ -2491,3 +2491,4 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // the exact selection behind a matrix-core screen
 // ------------------------------------------------------------------------------------------------
 #include "exact_topk_screened_host.h"
+#include "exact_topk_screened_filtered_host.h"

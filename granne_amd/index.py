@@ -790,6 +790,47 @@ class Granne:
                                  "bin at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
 
+    def exact_topk_screened_filtered_device(self, d_queries, nq, k, d_filter, filter_stride_words, d_ids, d_dists, d_counts,
+                                            d_status=0, stream=0):
+        """exact_topk_filtered's answer with the matrix cores screening the rows first
+        (granne_hip_exact_topk_screened_filtered_device): raw device pointers (int), the filter as exact_topk_filtered_device
+        takes it; d_status: u32[4] zeroed by the caller, or 0 (exact_topk_screened's words). Ordered on `stream`, which the
+        call waits on at its end, and for one shared bitmap once at its start (the length of its id list)."""
+        check(lib().granne_hip_exact_topk_screened_filtered_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_filter),
+                                                                   int(filter_stride_words), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                                                   C.c_void_p(d_counts), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def exact_topk_screened_filtered(self, queries, k, allowed, prepared=True, stats=False):
+        """Host convenience over exact_topk_screened_filtered_device: the returns of `exact_topk_filtered`, the same bytes;
+        `allowed` as it takes it. The status words (stats=True) are `exact_topk_screened`'s; with stats=False bit 31 of
+        status[3] raises GranneHipError(ERR_OVERFLOW) as `exact_topk_filtered` does."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        k, nq = int(k), q.shape[0]
+        owner, fptr, stride = self._filter_arg(allowed, nq, self.num_elements())
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        self.exact_topk_screened_filtered_device(tq.data_ptr(), nq, k, fptr, stride, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(),
+                                                 st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        status = st.cpu().numpy().astype(np.uint32)
+        out = ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+        if stats:
+            return out + (status,)
+        if status[3] & 0x80000000:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk_screened_filtered: exact_topk's selection overflowed for a query handed to it")
+        return out
+
     # ---- range search: all elements within a radius, by scan and by walk (include/granne_hip.h, DESIGN.md 3.10e) -----
     def _radii(self, radius, nq):
         """`radius` -- a scalar or one value per query -- as float32 [nq]; a NaN is refused here as by the host entries"""

@@ -429,6 +429,47 @@ public:
         return out;
     }
 
+    // exact_topk_filtered's answer, the same ids and distance bytes, with exact_topk_screened's matrix-core screen in front
+    // (granne_hip_exact_topk_screened_filtered_device; one bitmap for all queries: the screen scans the bitmap's id list).
+    // Throws where exact_topk_filtered throws. `status` (optional): the four status words of the call.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_screened_filtered(const Element* elements, size_t nq, size_t k,
+                                                                                    const Filter& allowed,
+                                                                                    std::vector<uint32_t>* status = nullptr) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed.len() != num_elements() || allowed.device() != device)
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t qb = q.size() * sizeof(q[0]);
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_st = o_c + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_out.upload(host.data(), total);
+        int rc = granne_hip_exact_topk_screened_filtered_device(h_.get(), d_q.get(), (uint32_t)nq, (uint32_t)k, allowed.words(), 0,
+                                                                (uint64_t*)d_out.get(), (float*)((char*)d_out.get() + o_d),
+                                                                (uint32_t*)((char*)d_out.get() + o_c), (uint32_t*)((char*)d_out.get() + o_st),
+                                                                nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        const uint32_t* st = (const uint32_t*)(host.data() + o_st);
+        if (status) status->assign(st, st + 4);
+        if (st[3] & 0x80000000u) throw std::runtime_error("exact_topk_screened_filtered: exact_topk's selection overflowed for a query handed to it");
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // The num_neighbors nearest ALLOWED ids by the ordinary search with a long list and a filter of its result
     // (granne_hip.h, "post-filtered search"): a query's list of stages[s] entries answers it once it holds min_allowed
     // allowed ids or the walk ran out of graph, else the query goes on to the next stage; what no stage finishes gets the

@@ -952,6 +952,39 @@ int granne_hip_exact_topk_filtered(const granne_hip_index* index, const void* qu
                                    const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
                                    float* out_dists, uint32_t* out_counts, uint32_t* out_status);
 
+/* granne_hip_exact_topk_filtered's answer -- the same ids, distance bytes and counts for the same arguments, no tolerance
+ * anywhere -- with granne_hip_exact_topk_screened's matrix-core screen in front. count = min(k, allowed
+ * ids), the places past it UINT64_MAX / +inf; a filter that allows nothing gives count 0 and GRANNE_HIP_OK. The filter
+ * follows granne_hip_exact_topk_filtered's convention (bits past n_elements in the last word do not matter):
+ *   filter_stride_words == 0   one bitmap for every query: compacted to its m ascending ids, and the screen scans the
+ *                              list's positions -- work ~ m x nq. The call reads m back ONCE AT ITS START (one wait on
+ *                              `stream`) to size the prefixes and the grids; m == 0 is answered without a scan.
+ *   filter_stride_words != 0   query q uses d_filter + q * filter_stride_words: the screen scans all rows; a 32-row result
+ *                              block is one word of the bitmap, read only for the blocks that pass the floor test.
+ *   routed     handles that granne_hip_exact_topk_screened routes (f32 rows beyond 208 components or off the proven norm
+ *              range, int8 rows beyond 128) are answered by granne_hip_exact_topk_filtered_device inside the call.
+ *   fallback   a query with more than GRANNE_HIP_EXACT_TOPK_CAP survivors, or an f32 query of squared norm above
+ *              1 + 2^-10, is answered by granne_hip_exact_topk_filtered_device under its own filter, after the screen.
+ *   d_status   u32[4], optional, zeroed by the caller, as granne_hip_exact_topk_screened's: [0] queries answered by the
+ *              fallback, [1] queries routed (0 or nq), [2] the largest survivor count of one query (counting on past the
+ *              cap), [3] the form that ran (0 / 1 / 2 / 3), bit 31 set where exact_topk's own selection voided a query
+ *              handed to it.
+ * Refused (GRANNE_HIP_ERR_INVALID, the message naming exact_topk_screened_filtered): what granne_hip_exact_topk_filtered
+ * refuses -- GRANNE_HIP_F16 and compact SumEmbeddings handles, k == 0, k > GRANNE_HIP_EXACT_TOPK_KMAX, more than 2^32 - 1
+ * elements, a null filter, a filter_stride_words that is neither 0 nor >= ceil(n_elements / 32), null buffers. nq == 0
+ * does nothing. Stream-ordered; besides the shared form's read of m the call waits on `stream` once, at its end, for the
+ * length of the fallback list. Scratch from hipMallocAsync: granne_hip_exact_topk_screened's plus 4 bytes per element for
+ * the shared form's list. */
+int granne_hip_exact_topk_screened_filtered_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                                   const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,
+                                                   float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, void* stream);
+/* the same with host buffers in and out, the filter's words on the host (ceil(n_elements / 32), or nq *
+ * filter_stride_words); synchronous. GRANNE_HIP_ERR_OVERFLOW when bit 31 of status[3] is set: the outputs (and out_status,
+ * optional) are still written. */
+int granne_hip_exact_topk_screened_filtered(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                                            const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
+                                            float* out_dists, uint32_t* out_counts, uint32_t* out_status);
+
 /* ---- post-filtered search: staged over-fetch on the ordinary search -----------
  * "The nearest neighbours among the ids this bitmap allows", answered by the ORDINARY search with a long list and a filter
  * of its result: no walker knows about the filter, so the register walkers serve it, and so do GRANNE_HIP_F16 and compact

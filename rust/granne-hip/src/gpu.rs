@@ -227,6 +227,12 @@ extern "C" {
     fn granne_hip_exact_topk_filtered(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
         out_status: *mut u32) -> c_int;
+    fn granne_hip_exact_topk_screened_filtered_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        k: u32, d_filter: *const u32, filter_stride_words: u64, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_topk_screened_filtered(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
+        filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_status: *mut u32) -> c_int;
     // partitioned indexes: the bitmap slice, filtered search and the exact selection over global ids
     fn granne_hip_filter_slice_device(d_filter: *const u32, n_bits: u64, filter_stride_words: u64, n_filters: u32,
         first_bit: u64, n_out_bits: u64, d_out: *mut u32, out_stride_words: u64, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -627,6 +633,20 @@ impl<E: GpuElements> GpuGranne<E> {
         let q = self.upload_queries(elements, &stream)?;
         let out = DeviceResults::new(nq, k, self.device())?;
         check(unsafe { granne_hip_exact_topk_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
+            filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
+    /// `granne_hip_exact_topk_screened_filtered_device`: `exact_topk_filtered`'s answer, the same ids and distance bytes,
+    /// with the matrix cores screening the rows of the bitmap's id list first. The call waits on its stream once for the
+    /// list's length and once at its end.
+    pub fn exact_topk_screened_filtered(&self, elements: &[E::Vector], k: usize, filter: &GpuFilter) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        if nq == 0 { return Ok(Vec::new()); }
+        assert_eq!(filter.len(), self.num_elements());
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let out = DeviceResults::new(nq, k, self.device())?;
+        check(unsafe { granne_hip_exact_topk_screened_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
             filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
         out.to_host(nq, &stream)
     }
