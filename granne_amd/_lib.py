@@ -254,6 +254,8 @@ SIGNATURES = {
     "granne_hip_search_postfiltered_batch": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_range_device": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_exact_range": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_range_screened_device": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_range_screened": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp]),
     "granne_hip_search_range_batch_device": (i32, [vp, vp, u32, vp, u32, vp, u32, i32, u64, vp, vp, vp, vp, vp, vp, vp]),
     "granne_hip_search_range_batch": (i32, [vp, vp, u32, vp, u32, vp, u32, i32, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_filter_slice_device": (i32, [vp, u64, u64, u32, u64, u64, vp, u64, i32, vp]),

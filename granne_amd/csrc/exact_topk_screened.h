@@ -52,6 +52,10 @@ constexpr uint32_t ETS_VOIDED = 0x80000000u; // status[3]: exact_topk's own sele
 // one shared bitmap compacts to; or all rows under a bit test, one bitmap per query -- a 32-row result block is one word of
 // it, read only for the blocks that pass the wave's floor test.
 enum { ETS_ALL = 0, ETS_LIST = 1, ETS_BITS = 2 };
+// The epilogue of a scan: the histogram of the scores at or above the floor; the candidates at or above it; or, for a
+// radius (granne_hip_exact_range_screened*), one pass that counts and lists the rows at or above `hi` and
+// lists the rows between `lo` and `hi`.
+enum { ETS_COUNT = 0, ETS_COLLECT = 1, ETS_RADIUS = 2 };
 
 // The bound on |screen score - (1 - reference distance)|; 0: the shape has no screen.
 static inline float ets_epsilon(int i8, uint32_t dim) {
@@ -79,6 +83,9 @@ struct EtsParams {
     uint32_t* cnt;           // COLLECT: [nq]
     uint32_t* cand;          // COLLECT: [nq][ETS_CAP]
     float eps2;              // COLLECT: 2 eps
+    const float* hi = nullptr;        // ETS_RADIUS: [nq] the upper threshold (lo: the lower one); cand is [nq][2][ETS_CAP]
+    uint32_t* sure = nullptr;         // ETS_RADIUS: [nq] the rows with s >= hi, exact however many (cnt: the places asked for)
+    uint32_t* bcnt = nullptr;         // ETS_RADIUS: [nq] the rows with lo <= s < hi
     const uint32_t* list = nullptr;   // ETS_LIST: the allowed ids, ascending; n counts its positions
     const uint32_t* filter = nullptr; // ETS_BITS: this round's bitmaps, query q's at filter + q * filter_stride
     uint64_t filter_stride = 0;       // ETS_BITS: in words
@@ -88,6 +95,7 @@ struct EtsParams {
 uint32_t ets_tile_rows(uint32_t form); // rows per tile of the form's scan
 hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
 hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+hipError_t ets_scan_radius(uint32_t form, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
 hipError_t ets_empty(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s);
 hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s);
 hipError_t ets_max_norm2(const uint8_t* elements, uint64_t n, uint32_t row_bytes, uint32_t row_stride, uint32_t* out, hipStream_t s);
@@ -101,5 +109,28 @@ hipError_t ets_gather(const uint8_t* queries, uint32_t qbytes, const uint32_t* f
 hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const uint64_t* ids, const float* dists, const uint32_t* counts,
                        const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s);
 hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s);
+
+// ---- the radius scan (exact_range_screened_host.h) ----
+// What the queries of a call that path A does not answer are listed in: n[0] queries for exact_topk_screened(k = cap)
+// (their totals are known), n[1] for exact_range's own scan; the lists hold their places among the call's queries.
+struct ErsLists {
+    uint32_t* n;    // [2]
+    uint32_t* b;    // [nq]
+    uint32_t* c;    // [nq]
+};
+// per query of a round: the f32 norm test, lo and hi (outside the norm bound: lo = +inf, hi = -inf), sure / cnt / bcnt cleared
+hipError_t ers_radius(bool i8, const uint8_t* queries, const float* radii, uint32_t nq, uint32_t dim, float eps, float* lo, float* hi,
+                      uint32_t* sure, uint32_t* cnt, uint32_t* bcnt, hipStream_t s);
+// the unused places of both lists of every query: an id no handle has; list (ETS_LIST, else null): positions become ids
+hipError_t ers_pad(uint32_t* cand, const uint32_t* sure, const uint32_t* bcnt, const uint32_t* list, uint32_t nq, hipStream_t s);
+// after dists_kernel: keys [nq][ETS_CAP] (distance bits << 32 | id) of the listed rows with d <= r, totals [nq] for
+// er_rank_kernel (path A: the keys; path B: the exact total, above ETS_CAP; path C: ETS_CAP + 1), the lists, the status words
+hipError_t ers_keys(const uint32_t* cand, const float* dists, const float* radii, const float* lo, const float* hi, const uint32_t* sure,
+                    const uint32_t* bcnt, uint32_t nq, uint32_t q_base, uint64_t* keys, uint32_t* totals, ErsLists lists, uint32_t* status,
+                    hipStream_t s);
+// status[0] += the queries of a dense answer with count 0 (voided by exact_topk's overflow), ETS_VOIDED into status[3]
+hipError_t ers_voided(const uint32_t* counts, uint32_t np, uint32_t* status, hipStream_t s);
+// status[0] += xs[0] (xs optional; ETS_VOIDED into [3] with it), status[1] += not_a, status[3] |= form
+hipError_t ers_status(uint32_t* status, const uint32_t* xs, uint32_t not_a, uint32_t form, hipStream_t s);
 
 } // namespace granne_hip

@@ -33,15 +33,15 @@ __device__ __forceinline__ EtsBlock ets_block() {
 __device__ __forceinline__ float ets_width(float lo) { return (1.0f - lo) * (1.0f / (float)ETS_BUCKETS); }
 __device__ __forceinline__ float ets_edge(float lo, float w, int j) { return lo + w * (float)j; }
 
-// A lane's view of its query's floor
+// A lane's view of its query's floor. ETS_RADIUS: thr = lo is the lower threshold; w and inv_w are not used.
 struct EtsFloor {
     float thr, lo, w, inv_w;
-    template <bool COLLECT>
+    template <int MODE>
     __device__ __forceinline__ void init(const EtsParams& P, uint32_t q, bool qlive) {
         lo = qlive ? P.lo[q] : __builtin_inff();
         w = ets_width(lo);
         inv_w = 1.0f / w;
-        thr = COLLECT ? lo - P.eps2 : lo;
+        thr = MODE == ETS_COLLECT ? lo - P.eps2 : lo;
     }
 };
 
@@ -49,12 +49,12 @@ struct EtsFloor {
 // COUNT: into the block's LDS histogram (hq: the query's column of it). COLLECT: into the query's candidate list.
 // ETS_BITS: `word` is the block's word of the query's bitmap -- rows e_blk .. e_blk + 31 are its bits 0 .. 31 -- and only
 // allowed rows are counted or collected. ETS_LIST: the rows are list positions; what is collected is the id at the position.
-template <bool COLLECT, int SRC>
+template <int MODE, int SRC>
 __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
                                            bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq, uint32_t word) {
     const uint32_t wv = word >> (4u * h); // the lane's row v: bit 8 (v / 4) + v % 4 of it
     auto allowed = [&](int v) { return SRC != ETS_BITS || (wv >> (8 * (v / 4) + v % 4) & 1u) != 0u; };
-    if constexpr (!COLLECT) {
+    if constexpr (MODE == ETS_COUNT) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
@@ -91,6 +91,63 @@ __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F
     }
 }
 
+// ETS_RADIUS, the third epilogue (exact_range_screened): of the lane's 16 scores, the SURE rows (s >= hi:
+// within the radius whatever the reference's arithmetic says) are counted in `sure` and listed by COLLECT's placement in
+// P.cand[q][0 .. ETS_CAP) -- until the pair has seen the list full (the places asked for reached ETS_CAP: ETS_SURE_FULL in
+// `sure`, whose count goes on) --; `sure` is the thread's own word of LDS, not a register: the 16 x 13 form over a list has
+// none left for a value that lives through the scan loop. The BAND rows (lo <= s < hi) are listed in P.cand[q][ETS_CAP .. 2 ETS_CAP) by an atomic of
+// the lane's own, taken only by a lane that has one. hi is read here, by the lanes with a row at or above lo: the scan
+// loop holds one register less. Rows and bits as ets_take16's.
+constexpr uint32_t ETS_SURE_FULL = 0x80000000u; // (a block's range has fewer rows than that)
+template <int SRC>
+__device__ __forceinline__ void ets_radius16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
+                                             bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t word, uint32_t* my_sure) {
+    const uint32_t wv = word >> (4u * h);
+    uint32_t in = 0, top = 0;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const uint64_t e = e_blk + (uint32_t)(8 * (v / 4) + v % 4) + 4u * h;
+        const bool ok = (whole || e < r1) && (SRC != ETS_BITS || (wv >> (8 * (v / 4) + v % 4) & 1u) != 0u);
+        in |= (sc[v] >= F.lo && ok) ? 1u << v : 0u;
+    }
+    const float hi = in ? P.hi[q] : __builtin_inff(); // (a row at or above lo: q is a live query)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) top |= sc[v] >= hi ? 1u << v : 0u;
+    top &= in;
+    const uint32_t band = in & ~top;
+    uint32_t bpos = 0;
+    if (band != 0u) bpos = atomicAdd(P.bcnt + q, (uint32_t)__builtin_popcount(band));
+    const uint32_t mine = (uint32_t)__builtin_popcount(top);
+    const uint32_t other = (uint32_t)__shfl_xor((int)mine, 32, 64);
+    uint32_t sure = *my_sure + mine;
+    uint32_t base = ETS_CAP; // (no place)
+    if (h == 0u && mine + other > 0u && !(sure & ETS_SURE_FULL)) base = atomicAdd(P.cnt + q, mine + other);
+    base = (uint32_t)__shfl((int)base, (int)col, 64);
+    if (mine + other > 0u && base + mine + other >= ETS_CAP) sure |= ETS_SURE_FULL; // (the same for both lanes of the pair)
+    *my_sure = sure;
+    uint32_t pos = base + (h ? other : 0u); // the pair's lower lane first
+    uint32_t* const lists = P.cand + (size_t)q * (2u * ETS_CAP);
+    // Both lists in one loop over the set bits, not unrolled: the scores are not needed any more, and the unrolled form's
+    // sixteen store addresses cost the 16 x 13 form its last registers. ETS_LIST: the position is listed, not the id at
+    // it (ers_pad_kernel reads the ids). Rows and positions fit 32 bits: the host refuses more elements.
+    for (uint32_t m = in; m != 0u; m &= m - 1u) {
+        const uint32_t v = (uint32_t)__builtin_ctz(m);
+        const bool t = top >> v & 1u;
+        const uint32_t at = t ? pos : bpos;
+        if (at < ETS_CAP) lists[(t ? 0u : ETS_CAP) + at] = (uint32_t)e_blk + 8u * (v >> 2) + (v & 3u) + 4u * h;
+        pos += t ? 1u : 0u, bpos += t ? 0u : 1u;
+    }
+}
+// after the block's range: the lane pair's count of sure rows in one atomic per (block, query) that has any
+__device__ __forceinline__ void ets_sure_flush(const EtsParams& P, uint32_t q, uint32_t h, uint32_t sure) {
+    sure &= ~ETS_SURE_FULL;
+    sure += (uint32_t)__shfl_xor((int)sure, 32, 64);
+    if (h == 0u && sure != 0u) atomicAdd(P.sure + q, sure);
+}
+
+// the words of LDS an epilogue keeps beside the tile: the histogram, nothing, or a count per thread
+constexpr uint32_t ets_mode_words(int mode) { return mode == ETS_COUNT ? ETS_BUCKETS * ETS_QT : mode == ETS_RADIUS ? ETS_THREADS : 0u; }
+
 // a block's LDS histogram: cleared before its range, its non-zero buckets added to the queries' global ones after it
 __device__ __forceinline__ void ets_hist_clear(uint32_t* lh, uint32_t tid) {
     for (uint32_t i = tid; i < ETS_BUCKETS * ETS_QT; i += ETS_THREADS) lh[i] = 0u;
@@ -115,7 +172,7 @@ __device__ __forceinline__ uint32_t ets_word(const EtsParams& P, uint32_t q, uin
 
 // f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order. SRC: the rows are all
 // rows (ETS_ALL, ETS_BITS: P.n of them) or the rows at the positions [0, P.n) of P.list (ETS_LIST).
-template <int KG, int R, bool COLLECT, int SRC = ETS_ALL>
+template <int KG, int R, int MODE, int SRC = ETS_ALL>
 __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr uint32_t ET = 32u * R;                // rows per tile
@@ -123,13 +180,13 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
     constexpr uint32_t STRIDE_B = 2u * COMPS + 16u; // bytes per LDS row of one piece: an odd number of 16-byte units
     uint8_t* tile_hi = smem_ets;
     uint8_t* tile_lo = smem_ets + (size_t)ET * STRIDE_B;
-    uint32_t* lh = reinterpret_cast<uint32_t*>(smem_ets + 2u * (size_t)ET * STRIDE_B); // COUNT: [ETS_BUCKETS][ETS_QT]
+    uint32_t* lh = reinterpret_cast<uint32_t*>(smem_ets + 2u * (size_t)ET * STRIDE_B); // COUNT: [ETS_BUCKETS][ETS_QT]; RADIUS: [ETS_THREADS]
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t col = lane & 31u, h = lane >> 5;
     const EtsBlock blk = ets_block();
     const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
     const bool qlive = q < P.nq;
-    if constexpr (!COLLECT) ets_hist_clear(lh, tid); // (the first tile's barriers stand between this and the first count)
+    if constexpr (MODE == ETS_COUNT) ets_hist_clear(lh, tid); // (the first tile's barriers stand between this and the first count)
 
     ets_b16x8 qh[KG], ql[KG]; // the lane's half of its query as bf16 pieces, in registers for the whole range
     {
@@ -147,7 +204,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
         }
     }
     EtsFloor F;
-    F.init<COLLECT>(P, q, qlive);
+    F.init<MODE>(P, q, qlive);
+    if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
 
     const uint64_t r0 = (uint64_t)blk.range * P.per_range;
     const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
@@ -227,23 +285,27 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) sc[v] = acc[r][v];
                 const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && mx >= F.thr);
-                ets_take16<COLLECT, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+                if constexpr (MODE == ETS_RADIUS)
+                    ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
+                else
+                    ets_take16<MODE, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
             }
         }
     }
-    if constexpr (!COLLECT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_COUNT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_RADIUS) ets_sure_flush(P, q, h, lh[tid]);
 }
 
 template <int KG, int R>
-constexpr uint32_t ets_b16_lds(bool collect) {
-    return 2u * (32u * R) * (2u * 16u * KG + 16u) + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u); // tile_hi, tile_lo, the histogram
+constexpr uint32_t ets_b16_lds(int mode) {
+    return 2u * (32u * R) * (2u * 16u * KG + 16u) + ets_mode_words(mode) * 4u; // tile_hi, tile_lo, the mode's words
 }
 
 // int8 rows of up to 128 bytes: score = ((float)dot * (1 / |x|)) * (1 / |q|), the dot exact in i32
 constexpr uint32_t ETS_I8_R = 4, ETS_I8_ROWS = 32u * ETS_I8_R, ETS_I8_STRIDE = 128u + 16u;
 // ETS_LIST: a gathered block has no entry in inv_gmax; its bound is made from the block's own 1 / |x| on their way into
 // LDS (gm, two copies by the tile's parity: one is read while the next tile's is being made).
-template <bool COLLECT, int SRC = ETS_ALL>
+template <int MODE, int SRC = ETS_ALL>
 __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr int R = (int)ETS_I8_R;
@@ -251,14 +313,14 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
     uint8_t* tile = smem_ets;
     float* inv = reinterpret_cast<float*>(smem_ets + (size_t)ET * STRIDE); // [ET] 1 / |x|
     float* gm = inv + ET;                                                   // [2][R] inv_gmax of the tile's blocks, by lane half
-    uint32_t* lh = reinterpret_cast<uint32_t*>(gm + 2 * R);                 // COUNT: [ETS_BUCKETS][ETS_QT]
-    uint32_t* gml = lh + (COLLECT ? 0u : ETS_BUCKETS * ETS_QT);             // ETS_LIST: [2][2][R] float bits, by parity
+    uint32_t* lh = reinterpret_cast<uint32_t*>(gm + 2 * R);                 // COUNT: [ETS_BUCKETS][ETS_QT]; RADIUS: [ETS_THREADS]
+    uint32_t* gml = lh + ets_mode_words(MODE);             // ETS_LIST: [2][2][R] float bits, by parity
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t col = lane & 31u, h = lane >> 5;
     const EtsBlock blk = ets_block();
     const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
     const bool qlive = q < P.nq;
-    if constexpr (!COLLECT) ets_hist_clear(lh, tid);
+    if constexpr (MODE == ETS_COUNT) ets_hist_clear(lh, tid);
     if constexpr (SRC == ETS_LIST) {
         if (tid < 4u * R) gml[tid] = 0u; // (the first tile's first barrier stands between this and the first maximum)
     }
@@ -288,7 +350,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
         qinv = dy > 0 ? 1.0f / __builtin_sqrtf((float)dy) : 0.0f;
     }
     EtsFloor F;
-    F.init<COLLECT>(P, q, qlive);
+    F.init<MODE>(P, q, qlive);
+    if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
 
     const uint64_t r0 = (uint64_t)blk.range * P.per_range;
     const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
@@ -376,14 +439,18 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
                 sc[g4 * 4 + 3] = ((float)acc[r][g4 * 4 + 3] * iv.w) * qinv;
             }
             const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && hit);
-            ets_take16<COLLECT, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+            if constexpr (MODE == ETS_RADIUS)
+                ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
+            else
+                ets_take16<MODE, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
         }
     }
-    if constexpr (!COLLECT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_COUNT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_RADIUS) ets_sure_flush(P, q, h, lh[tid]);
 }
 
-constexpr uint32_t ets_i8_lds(bool collect, bool list = false) {
-    return ETS_I8_ROWS * ETS_I8_STRIDE + ETS_I8_ROWS * 4u + 2u * ETS_I8_R * 4u + (collect ? 0u : ETS_BUCKETS * ETS_QT * 4u) +
+constexpr uint32_t ets_i8_lds(int mode, bool list = false) {
+    return ETS_I8_ROWS * ETS_I8_STRIDE + ETS_I8_ROWS * 4u + 2u * ETS_I8_R * 4u + ets_mode_words(mode) * 4u +
            (list ? 4u * ETS_I8_R * 4u : 0u);
 }
 
@@ -515,7 +582,133 @@ __global__ void ets_status_kernel(uint32_t* status, uint32_t routed, uint32_t fo
     atomicOr(status + 3, form | (xs && xs[0] ? ETS_VOIDED : 0u));
 }
 
+// ---- the radius scan's small kernels ----
+// Per query of a round, in ets_init_kernel's place: the thresholds of its radius, made in double and rounded outward,
+//   lo = 1 - r - eps rounded down: every row with d <= r scores s >= lo;  hi = 1 - r + eps rounded up: s >= hi has d <= r.
+// r < 0 or NaN: no distance is within it (distances are clamped at 0): lo = hi = +inf, nothing passes, the answer is
+// empty. r = +inf: lo = hi = -inf, every row is sure. An f32 query outside the norm bound: lo = +inf, hi = -inf (the only
+// way hi < lo comes about), for exact_range's own scan. The query's three counters are cleared.
+template <bool I8>
+__global__ void ets_radius_kernel(const uint8_t* __restrict__ queries, const float* __restrict__ radii, uint32_t nq, uint32_t dim, float eps,
+                                  float* __restrict__ lo, float* __restrict__ hi, uint32_t* __restrict__ sure, uint32_t* __restrict__ cnt,
+                                  uint32_t* __restrict__ bcnt) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    bool ok = true;
+    if constexpr (!I8) {
+        const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
+        float s = 0.0f;
+        for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
+        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+    }
+    const float r = radii[q];
+    float l = __builtin_inff(), u = ok ? __builtin_inff() : -__builtin_inff();
+    if (ok && r >= 0.0f) { // (false for a NaN)
+        const double dl = 1.0 - (double)r - (double)eps, du = 1.0 - (double)r + (double)eps;
+        l = (float)dl, u = (float)du;
+        if ((double)l > dl) l = nextafterf(l, -__builtin_inff());
+        if ((double)u < du) u = nextafterf(u, __builtin_inff());
+    }
+    lo[q] = l, hi[q] = u;
+    sure[q] = 0u, cnt[q] = 0u, bcnt[q] = 0u;
+}
+
+// One block per query of a round, before dists_kernel: the places of both lists past their counts get an id that no
+// handle has. A list that ran over (or a query outside the bound) is not read afterwards: all of it is padded. `list`
+// (ETS_LIST, else null): the scan listed positions of it; they become the ids at those positions.
+__global__ __launch_bounds__(256) void ers_pad_kernel(uint32_t* __restrict__ cand, const uint32_t* __restrict__ sure, const uint32_t* __restrict__ bcnt,
+                                                      const uint32_t* __restrict__ list) {
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t S = sure[q] <= ETS_CAP ? sure[q] : 0u, B = bcnt[q] <= ETS_CAP ? bcnt[q] : 0u;
+    uint32_t* const mine = cand + (size_t)q * (2u * ETS_CAP);
+    for (uint32_t i = tid; i < ETS_CAP; i += 256u) {
+        if (i >= S) mine[i] = 0xFFFFFFFFu;
+        else if (list) mine[i] = list[mine[i]];
+        if (i >= B) mine[ETS_CAP + i] = 0xFFFFFFFFu;
+        else if (list) mine[ETS_CAP + i] = list[mine[ETS_CAP + i]];
+    }
+}
+
+// One block per query of a round, after dists_kernel has given both lists the reference's distances: the keys (distance
+// bits << 32 | id) of the listed rows with d <= r, dense in keys[q] in any order (er_rank_kernel sorts them), and the
+// query's path. S sure rows, B band rows, of which b_in lie within r:
+//   C  outside the norm bound, or B > ETS_CAP (the band's list ran over)      -> lists.c, totals = ETS_CAP + 1
+//   total = S + b_in is exact otherwise (S <= ETS_CAP: the sure list is whole and its rows are counted as keys)
+//   A  total <= ETS_CAP: the keys are all of W, totals = total               B  otherwise -> lists.b, totals = total
+// status (optional): [1] += 1 unless A, [2] raised to S + B of a query inside the bound.
+__global__ __launch_bounds__(256) void ers_keys_kernel(const uint32_t* __restrict__ cand, const float* __restrict__ dists, const float* __restrict__ radii,
+                                                       const float* __restrict__ lo, const float* __restrict__ hi, const uint32_t* __restrict__ sure,
+                                                       const uint32_t* __restrict__ bcnt, uint32_t q_base, uint64_t* __restrict__ keys,
+                                                       uint32_t* __restrict__ totals, ErsLists lists, uint32_t* status) {
+    __shared__ uint32_t n_keys, n_band;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t S = sure[q], B = bcnt[q];
+    const bool screened = !(hi[q] < lo[q]);
+    const float r = radii[q];
+    if (tid == 0u) n_keys = 0u, n_band = 0u;
+    __syncthreads();
+    const uint32_t ns = screened && S <= ETS_CAP ? S : 0u, nb = screened && B <= ETS_CAP ? B : 0u;
+    const size_t base = (size_t)q * (2u * ETS_CAP);
+    for (uint32_t i = tid; i < ns + nb; i += 256u) {
+        const size_t at = base + (i < ns ? i : ETS_CAP + (i - ns));
+        const float d = dists[at];
+        if (d <= r) {
+            if (i >= ns) atomicAdd(&n_band, 1u);
+            const uint32_t p = atomicAdd(&n_keys, 1u);
+            if (p < ETS_CAP) keys[(size_t)q * ETS_CAP + p] = (uint64_t)__float_as_uint(d) << 32 | (uint64_t)cand[at];
+        }
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const bool c = !screened || B > ETS_CAP;
+    const uint32_t total = S <= ETS_CAP ? n_keys : S + n_band;
+    const bool a = !c && total <= ETS_CAP;
+    totals[q] = c ? ETS_CAP + 1u : total;
+    if (c) lists.c[atomicAdd(lists.n + 1, 1u)] = q_base + q;
+    else if (!a) lists.b[atomicAdd(lists.n + 0, 1u)] = q_base + q;
+    if (status) {
+        if (!a) atomicAdd(status + 1, 1u);
+        if (screened) atomicMax(status + 2, S + B < S ? 0xFFFFFFFFu : S + B);
+    }
+}
+
+__global__ void ers_voided_kernel(const uint32_t* __restrict__ counts, uint32_t np, uint32_t* status) {
+    uint32_t v = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) v += counts[i] == 0u ? 1u : 0u;
+    if (v) atomicAdd(status + 0, v), atomicOr(status + 3, ETS_VOIDED);
+}
+__global__ void ers_status_kernel(uint32_t* status, const uint32_t* xs, uint32_t not_a, uint32_t form) {
+    if (xs && xs[0]) atomicAdd(status + 0, xs[0]);
+    atomicAdd(status + 1, not_a);
+    atomicOr(status + 3, form | (xs && xs[0] ? ETS_VOIDED : 0u));
+}
+
 // ---- launchers ----
+hipError_t ers_radius(bool i8, const uint8_t* queries, const float* radii, uint32_t nq, uint32_t dim, float eps, float* lo, float* hi,
+                      uint32_t* sure, uint32_t* cnt, uint32_t* bcnt, hipStream_t s) {
+    hipLaunchKernelGGL(i8 ? ets_radius_kernel<true> : ets_radius_kernel<false>, dim3((nq + 255) / 256), dim3(256), 0, s, queries, radii, nq, dim, eps,
+                       lo, hi, sure, cnt, bcnt);
+    return hipGetLastError();
+}
+hipError_t ers_pad(uint32_t* cand, const uint32_t* sure, const uint32_t* bcnt, const uint32_t* list, uint32_t nq, hipStream_t s) {
+    hipLaunchKernelGGL(ers_pad_kernel, dim3(nq), dim3(256), 0, s, cand, sure, bcnt, list);
+    return hipGetLastError();
+}
+hipError_t ers_keys(const uint32_t* cand, const float* dists, const float* radii, const float* lo, const float* hi, const uint32_t* sure,
+                    const uint32_t* bcnt, uint32_t nq, uint32_t q_base, uint64_t* keys, uint32_t* totals, ErsLists lists, uint32_t* status,
+                    hipStream_t s) {
+    hipLaunchKernelGGL(ers_keys_kernel, dim3(nq), dim3(256), 0, s, cand, dists, radii, lo, hi, sure, bcnt, q_base, keys, totals, lists, status);
+    return hipGetLastError();
+}
+hipError_t ers_voided(const uint32_t* counts, uint32_t np, uint32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(ers_voided_kernel, dim3((np + 255) / 256 < 64 ? (np + 255) / 256 : 64), dim3(256), 0, s, counts, np, status);
+    return hipGetLastError();
+}
+hipError_t ers_status(uint32_t* status, const uint32_t* xs, uint32_t not_a, uint32_t form, hipStream_t s) {
+    hipLaunchKernelGGL(ers_status_kernel, dim3(1), dim3(1), 0, s, status, xs, not_a, form);
+    return hipGetLastError();
+}
+
 typedef void (*EtsScanFn)(const EtsParams);
 static uint32_t ets_grid(uint64_t work) {
     const uint64_t g = (work + 255) / 256;
@@ -524,23 +717,21 @@ static uint32_t ets_grid(uint64_t work) {
 
 uint32_t ets_tile_rows(uint32_t form) { return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : ETS_I8_ROWS; }
 
-template <int SRC>
-static EtsScanFn ets_scan_fn(uint32_t form, bool collect, uint32_t* lds) {
-    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(collect), collect ? ets_b16_kernel<7, 4, true, SRC> : ets_b16_kernel<7, 4, false, SRC>;
-    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(collect), collect ? ets_b16_kernel<13, 2, true, SRC> : ets_b16_kernel<13, 2, false, SRC>;
-    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(collect, SRC == ETS_LIST), collect ? ets_i8_kernel<true, SRC> : ets_i8_kernel<false, SRC>;
+template <int MODE, int SRC>
+static EtsScanFn ets_scan_fn(uint32_t form, uint32_t* lds) {
+    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC>;
+    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC>;
+    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC>;
     return nullptr;
 }
-
-hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
-    return ets_scan_src(form, collect, ETS_ALL, tiles, ranges, P, s);
+template <int MODE>
+static EtsScanFn ets_scan_mode(uint32_t form, int src, uint32_t* lds) {
+    return src == ETS_ALL    ? ets_scan_fn<MODE, ETS_ALL>(form, lds)
+           : src == ETS_LIST ? ets_scan_fn<MODE, ETS_LIST>(form, lds)
+           : src == ETS_BITS ? ets_scan_fn<MODE, ETS_BITS>(form, lds)
+                             : nullptr;
 }
-hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
-    uint32_t lds = 0;
-    const EtsScanFn fn = src == ETS_ALL    ? ets_scan_fn<ETS_ALL>(form, collect, &lds)
-                         : src == ETS_LIST ? ets_scan_fn<ETS_LIST>(form, collect, &lds)
-                         : src == ETS_BITS ? ets_scan_fn<ETS_BITS>(form, collect, &lds)
-                                           : nullptr;
+static hipError_t ets_scan_launch(EtsScanFn fn, uint32_t lds, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
     if (!fn) return hipErrorInvalidValue;
     if (lds > 64u * 1024u) {
         const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -548,6 +739,20 @@ hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, ui
     }
     hipLaunchKernelGGL(fn, dim3(tiles, ranges), dim3(ETS_THREADS), lds, s, P);
     return hipGetLastError();
+}
+
+hipError_t ets_scan(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    return ets_scan_src(form, collect, ETS_ALL, tiles, ranges, P, s);
+}
+hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = collect ? ets_scan_mode<ETS_COLLECT>(form, src, &lds) : ets_scan_mode<ETS_COUNT>(form, src, &lds);
+    return ets_scan_launch(fn, lds, tiles, ranges, P, s);
+}
+hipError_t ets_scan_radius(uint32_t form, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = ets_scan_mode<ETS_RADIUS>(form, src, &lds);
+    return ets_scan_launch(fn, lds, tiles, ranges, P, s);
 }
 hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s) {
     hipLaunchKernelGGL(ets_clear_kernel, dim3(1), dim3(64), 0, s, p, n);

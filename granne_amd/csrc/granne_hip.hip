@@ -2492,3 +2492,4 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // ------------------------------------------------------------------------------------------------
 #include "exact_topk_screened_host.h"
 #include "exact_topk_screened_filtered_host.h"
+#include "exact_range_screened_host.h"

@@ -888,6 +888,52 @@ class Granne:
                                  "their cap-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
 
+    def exact_range_screened_device(self, d_queries, nq, d_radii, max_results, d_filter, filter_stride_words, d_ids, d_dists,
+                                    d_counts, d_totals, d_status=0, stream=0):
+        """exact_range_device's answer with the matrix cores screening the rows first
+        (granne_hip_exact_range_screened_device): the same arguments; d_status: u32[4] zeroed by the caller, or 0."""
+        check(lib().granne_hip_exact_range_screened_device(self._h, C.c_void_p(d_queries), int(nq), C.c_void_p(d_radii),
+                                                           int(max_results), C.c_void_p(d_filter), int(filter_stride_words),
+                                                           C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts),
+                                                           C.c_void_p(d_totals), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def exact_range_screened(self, queries, radius, max_results=RANGE_CAP_MAX, filter=None, prepared=True, stats=False):
+        """`exact_range`'s returns, the same bytes, by one matrix-core pass over the rows: only rows within the screen's
+        bound of the radius get the reference's arithmetic. `filter` is what `exact_range` takes as `allowed`. The status
+        words (stats=True): [0] queries voided by the selection's overflow, which raises GranneHipError(ERR_OVERFLOW) with
+        stats=False as in `exact_range`; [1] queries not answered by the pass alone (a total beyond EXACT_TOPK_CAP, a band
+        beyond it, a query or a handle without a screen); [2] the most rows listed for one query; [3] the form, 0: routed."""
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        cap, nq = int(max_results), q.shape[0]
+        r = self._radii(radius, nq)
+        owner, fptr, stride = (None, 0, 0) if filter is None else self._filter_arg(filter, nq, self.num_elements())
+        dev = torch.device("cuda", self.device)
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        tr = torch.from_numpy(r).to(dev)
+        ids = torch.empty((nq, max(cap, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(cap, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        tot = torch.empty(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        self.exact_range_screened_device(tq.data_ptr(), nq, tr.data_ptr(), cap, fptr, stride, ids.data_ptr(), ds.data_ptr(),
+                                         cnt.data_ptr(), tot.data_ptr(), st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        status = st.cpu().numpy().view(np.uint32)
+        out = (ids.cpu().numpy().view(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), tot.cpu().numpy().view(np.uint32))
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact_range_screened: %d queries have more than %d rows inside one second-level "
+                                 "bin at their cap-th distance" % (int(status[0]), EXACT_TOPK_CAP))
+        return out
+
     def search_range(self, element, radius, max_results=DEFAULT_NUM_ELEMENTS, stages=None, fallback="exact", prepared=True):
         """`search_range_batch` for one query: [(id, distance)] ascending by (distance, id), every distance <= radius."""
         terms = self.element_type == EMBEDDINGS and (len(element) == 0 or np.asarray(element).dtype.kind in "iu")

@@ -533,6 +533,21 @@ public:
                           });
     }
 
+    // exact_range's answer, the same ids, distance bytes and totals, by one matrix-core pass over the rows: only rows within
+    // the screen's bound of the radius get the reference's arithmetic (granne_hip_exact_range_screened_device).
+    std::vector<std::vector<std::pair<size_t, float>>> exact_range_screened(const Element* elements, size_t nq, const float* radii, size_t cap,
+                                                                            const Filter* allowed = nullptr,
+                                                                            std::vector<uint32_t>* out_totals = nullptr) const {
+        if (allowed && (allowed->len() != num_elements() || allowed->device() != granne_hip_index_device(h_.get())))
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        return range_call(elements, nq, radii, cap, out_totals, nullptr,
+                          "exact_range_screened: a query has too many rows inside one second-level bin at its cap-th distance",
+                          [&](const void* q, const float* r, uint64_t* ids, float* ds, uint32_t* counts, uint32_t* found, uint32_t*, uint32_t* status) {
+                              return granne_hip_exact_range_screened_device(h_.get(), q, (uint32_t)nq, r, (uint32_t)cap,
+                                                                            allowed ? allowed->words() : nullptr, 0, ids, ds, counts, found, status, nullptr);
+                          });
+    }
+
     // The elements within radii[i] of query i by the ordinary search with lists of stages[s] entries, cut at the radius
     // (granne_hip.h, "range search"): a list answers its query once it holds an entry beyond the radius or the walk ran out
     // of graph, else the query goes on to the next stage; what no stage finishes gets the exact scan

@@ -1119,6 +1119,33 @@ int granne_hip_exact_range_device(const granne_hip_index* index, const void* d_q
 int granne_hip_exact_range(const granne_hip_index* index, const void* queries, uint32_t nq, const float* radii, uint32_t cap,
                            const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids, float* out_dists,
                            uint32_t* out_counts, uint32_t* out_totals, uint32_t* out_status);
+/* granne_hip_exact_range's answer -- its arguments in its order, the same ids, distance bytes, counts and totals, the same
+ * refusals (the messages name exact_range_screened) and the same GRANNE_HIP_ERR_OVERFLOW from the host entry -- with
+ * granne_hip_exact_topk_screened's matrix-core screen in front. The radius is a floor known before the
+ * scan: ONE pass over the rows gives every query S, the exact number of rows whose screen score vouches for d <= r, the
+ * first GRANNE_HIP_EXACT_TOPK_CAP of their ids, and the B rows of the band within the screen's bound of the radius, which
+ * alone get the reference's arithmetic to decide. With total = S + (band rows with d <= r):
+ *   A  total <= GRANNE_HIP_EXACT_TOPK_CAP: the listed rows within r are ranked by (distance bits, id)
+ *   B  otherwise, B <= GRANNE_HIP_EXACT_TOPK_CAP: granne_hip_exact_topk_screened[_filtered](k = cap) answers, the total is known
+ *   C  B > GRANNE_HIP_EXACT_TOPK_CAP, or an f32 query of squared norm above 1 + 2^-10: granne_hip_exact_range's own scan
+ * Handles that granne_hip_exact_topk_screened routes are answered by granne_hip_exact_range's scan outright.
+ *   d_status   u32[4], optional, zeroed by the caller: [0] += queries voided by the selection's overflow, as
+ *              granne_hip_exact_range's [0]; [1] += queries not answered by path A (B, C and routed ones); [2] = max(, S + B
+ *              of a screened query); [3] |= the form (GRANNE_HIP_ETS_FORM_*; 0: routed), GRANNE_HIP_ETS_VOIDED with [0] != 0
+ * The device entry is stream-ordered but waits on `stream` once, for the numbers of B and C queries (two u32, one copy), and
+ * with one shared bitmap once more at its start, for the length of its id list; what it hands on waits as documented there. */
+#define GRANNE_HIP_ETS_FORM_ROUTED 0u
+#define GRANNE_HIP_ETS_FORM_B16_7x4 1u
+#define GRANNE_HIP_ETS_FORM_B16_13x2 2u
+#define GRANNE_HIP_ETS_FORM_I8 3u
+#define GRANNE_HIP_ETS_VOIDED 0x80000000u
+int granne_hip_exact_range_screened_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, const float* d_radii,
+                                           uint32_t cap, const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,
+                                           float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_status,
+                                           void* stream);
+int granne_hip_exact_range_screened(const granne_hip_index* index, const void* queries, uint32_t nq, const float* radii, uint32_t cap,
+                                    const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids, float* out_dists,
+                                    uint32_t* out_counts, uint32_t* out_totals, uint32_t* out_status);
 int granne_hip_search_range_batch_device(const granne_hip_index* index, const void* d_queries, uint32_t nq,
                                          const float* d_radii, uint32_t cap, const uint32_t* stages, uint32_t n_stages,
                                          int fallback, uint64_t scratch_bytes, uint64_t* d_out_ids, float* d_out_dists,

@@ -271,6 +271,13 @@ extern "C" {
     fn granne_hip_exact_range(index: *const granne_hip_index, queries: *const c_void, nq: u32, radii: *const f32,
         cap: u32, filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32,
         out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_exact_range_screened_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        d_radii: *const f32, cap: u32, d_filter: *const u32, filter_stride_words: u64, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_totals: *mut u32, d_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_range_screened(index: *const granne_hip_index, queries: *const c_void, nq: u32, radii: *const f32,
+        cap: u32, filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32,
+        out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_search_range_batch_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
         d_radii: *const f32, cap: u32, stages: *const u32, n_stages: u32, fallback: c_int, scratch_bytes: u64,
         d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_found: *mut u32,
@@ -688,6 +695,27 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_exact_range_device(self.handle, q.ptr as *const c_void, nq as u32, r.ptr as *const f32,
             cap as u32, filter.map_or(std::ptr::null(), |f| f.words.ptr as *const u32), 0, out.ids.ptr, out.dists.ptr,
             out.counts.ptr, totals.ptr, std::ptr::null_mut(), stream.raw) })?;
+        let mut t = vec![0u32; nq];
+        totals.copy_to(&mut t, &stream)?;
+        Ok((out.to_host(nq, &stream)?, t))
+    }
+    /// `granne_hip_exact_range_screened_device`: `exact_range`'s answer, the same ids, distance bytes and totals, by one
+    /// matrix-core pass over the rows; only rows within the screen's bound of the radius get the reference's arithmetic.
+    pub fn exact_range_screened(&self, elements: &[E::Vector], radii: &[f32], cap: usize, filter: Option<&GpuFilter>)
+                                -> std::io::Result<(Vec<Vec<(usize, f32)>>, Vec<u32>)> {
+        let nq = elements.len();
+        assert_eq!(nq, radii.len());
+        if nq == 0 { return Ok((Vec::new(), Vec::new())); }
+        if let Some(f) = filter { assert_eq!(f.len(), self.num_elements()); }
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let r = DeviceBuffer::<f32>::new(nq, self.device())?;
+        r.copy_from(radii, &stream)?;
+        let out = DeviceResults::new(nq, cap, self.device())?;
+        let totals = DeviceBuffer::<u32>::new(nq, self.device())?;
+        check(unsafe { granne_hip_exact_range_screened_device(self.handle, q.ptr as *const c_void, nq as u32,
+            r.ptr as *const f32, cap as u32, filter.map_or(std::ptr::null(), |f| f.words.ptr as *const u32), 0, out.ids.ptr,
+            out.dists.ptr, out.counts.ptr, totals.ptr, std::ptr::null_mut(), stream.raw) })?;
         let mut t = vec![0u32; nq];
         totals.copy_to(&mut t, &stream)?;
         Ok((out.to_host(nq, &stream)?, t))
