@@ -56,6 +56,10 @@ enum { ETS_ALL = 0, ETS_LIST = 1, ETS_BITS = 2 };
 // radius (granne_hip_exact_range_screened*), one pass that counts and lists the rows at or above `hi` and
 // lists the rows between `lo` and `hi`.
 enum { ETS_COUNT = 0, ETS_COLLECT = 1, ETS_RADIUS = 2 };
+// Where a scan takes its queries from: the caller's dense matrix; or the handle's own rows (granne_hip_knn_graph*;
+// DESIGN.md 3.7e) -- query q of a round is element q_first + q, its fragments are read from the row where it lies, and the
+// score of a row with itself is replaced by -inf before anything looks at it: an element is no witness of its own floor.
+enum { ETS_Q_DENSE = 0, ETS_Q_ROWS = 1 };
 
 // The bound on |screen score - (1 - reference distance)|; 0: the shape has no screen.
 static inline float ets_epsilon(int i8, uint32_t dim) {
@@ -89,6 +93,7 @@ struct EtsParams {
     const uint32_t* list = nullptr;   // ETS_LIST: the allowed ids, ascending; n counts its positions
     const uint32_t* filter = nullptr; // ETS_BITS: this round's bitmaps, query q's at filter + q * filter_stride
     uint64_t filter_stride = 0;       // ETS_BITS: in words
+    uint64_t q_first = 0;             // ETS_Q_ROWS: the element that is this round's query 0 (queries is not read)
 };
 
 // the launchers (exact_topk_screened.hip); every one is ordered on s and returns what the launch left
@@ -109,6 +114,17 @@ hipError_t ets_gather(const uint8_t* queries, uint32_t qbytes, const uint32_t* f
 hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const uint64_t* ids, const float* dists, const uint32_t* counts,
                        const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s);
 hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s);
+
+// ---- the handle's own rows as queries (knn_graph_host.h) ----
+// ets_scan over all rows with the queries of ETS_Q_ROWS: P.q_first, P.nq; ets_init with queries == nullptr starts them
+hipError_t ets_scan_rows(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+// rows first + p -- p = list[f], or p_base + f where list is null -- f < m, as dense queries of qbytes each
+hipError_t ets_gather_rows(const uint8_t* elements, uint32_t row_stride, uint32_t qbytes, uint64_t first, const uint32_t* list, uint32_t p_base,
+                           uint32_t m, uint8_t* out, hipStream_t s);
+// exact_topk's k + 1 nearest of the same m rows ([m][k + 1], counts [m]) -> the k nearest OTHERS, into place p of the outputs:
+// the element dropped where it is listed, the last entry where it is not
+hipError_t kg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t k, const uint64_t* ids, const float* dists,
+                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s);
 
 // ---- the radius scan (exact_range_screened_host.h) ----
 // What the queries of a call that path A does not answer are listed in: n[0] queries for exact_topk_screened(k = cap)

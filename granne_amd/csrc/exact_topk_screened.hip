@@ -170,9 +170,21 @@ __device__ __forceinline__ uint32_t ets_word(const EtsParams& P, uint32_t q, uin
     return 0u;
 }
 
+// ETS_Q_ROWS: the place of the diagonal in a 32-row result block -- the v of the lane's 16 scores that is the score of its
+// query (element qid) with itself, 16 where the block's rows e_blk .. e_blk + 31 do not hold it or the lane's half does not
+// (rows 8 (v / 4) + v % 4 + 4 h). Ids and rows fit 32 bits (the host refuses more elements); a block past qid wraps to a
+// large difference. `any`: some lane of the wave has its diagonal in the block -- the wave's 32 queries are consecutive
+// elements, so of all the blocks of a scan at most two, and only they run the replacement.
+__device__ __forceinline__ uint32_t ets_diag(uint32_t qid, bool qlive, uint64_t e_blk, uint32_t h, bool* any) {
+    const uint32_t d = qid - (uint32_t)e_blk;
+    *any = __ballot(d < 32u) != 0ull;
+    return (qlive && d < 32u && (d >> 2 & 1u) == h) ? 4u * (d >> 3) + (d & 3u) : 16u;
+}
+
 // f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order. SRC: the rows are all
-// rows (ETS_ALL, ETS_BITS: P.n of them) or the rows at the positions [0, P.n) of P.list (ETS_LIST).
-template <int KG, int R, int MODE, int SRC = ETS_ALL>
+// rows (ETS_ALL, ETS_BITS: P.n of them) or the rows at the positions [0, P.n) of P.list (ETS_LIST). QSRC: the queries are
+// the caller's dense ones, or the elements P.q_first + q (ETS_Q_ROWS), split into their pieces straight from their rows.
+template <int KG, int R, int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE>
 __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr uint32_t ET = 32u * R;                // rows per tile
@@ -190,7 +202,11 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
 
     ets_b16x8 qh[KG], ql[KG]; // the lane's half of its query as bf16 pieces, in registers for the whole range
     {
-        const float* qp = reinterpret_cast<const float*>(P.queries) + (size_t)(qlive ? q : 0u) * P.dim;
+        const float* qp;
+        if constexpr (QSRC == ETS_Q_ROWS)
+            qp = reinterpret_cast<const float*>(P.elements + (P.q_first + (qlive ? q : 0u)) * P.row_stride);
+        else
+            qp = reinterpret_cast<const float*>(P.queries) + (size_t)(qlive ? q : 0u) * P.dim;
 #pragma unroll
         for (int g = 0; g < KG; ++g) {
 #pragma unroll
@@ -277,6 +293,14 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
         const bool whole = e0 + ET <= r1;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
+            if constexpr (QSRC == ETS_Q_ROWS) { // the diagonal: before the block's max, the ballot and the epilogue
+                bool any;
+                const uint32_t vd = ets_diag((uint32_t)P.q_first + q, qlive, e0 + (uint32_t)(r * 32), h, &any);
+                if (any) {
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) acc[r][v] = (uint32_t)v == vd ? -__builtin_inff() : acc[r][v];
+                }
+            }
             float mx = acc[r][0];
 #pragma unroll
             for (int v = 1; v < 16; ++v) mx = __builtin_fmaxf(mx, acc[r][v]);
@@ -305,7 +329,9 @@ constexpr uint32_t ets_b16_lds(int mode) {
 constexpr uint32_t ETS_I8_R = 4, ETS_I8_ROWS = 32u * ETS_I8_R, ETS_I8_STRIDE = 128u + 16u;
 // ETS_LIST: a gathered block has no entry in inv_gmax; its bound is made from the block's own 1 / |x| on their way into
 // LDS (gm, two copies by the tile's parity: one is read while the next tile's is being made).
-template <int MODE, int SRC = ETS_ALL>
+// ETS_Q_ROWS: the lane's 16-byte groups of element P.q_first + q are the operand as they lie (device rows are zero padded),
+// its 1 / |q| is the row's own P.inv_norm.
+template <int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE>
 __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) {
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr int R = (int)ETS_I8_R;
@@ -326,7 +352,17 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
     }
     ets_i32x4 qr[4]; // bytes 32 g + 16 h .. + 15 of the query (bf_i8_kernel's operand)
     float qinv = 0.0f;
-    {
+    if constexpr (QSRC == ETS_Q_ROWS) {
+        const uint64_t id = P.q_first + (qlive ? q : 0u);
+        const uint8_t* qp = P.elements + id * P.row_stride;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint32_t off = (uint32_t)g * 32u + h * 16u;
+            qr[g] = ets_i32x4{0, 0, 0, 0};
+            if (qlive && off < P.row_bytes) qr[g] = *reinterpret_cast<const ets_i32x4*>(qp + off);
+        }
+        qinv = qlive ? P.inv_norm[id] : 0.0f;
+    } else {
         const uint8_t* qp = P.queries + (size_t)(qlive ? q : 0u) * P.dim;
         const uint32_t last = P.dim - 1u;
         int dy = 0;
@@ -424,6 +460,15 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
         const bool whole = e0 + ET <= r1;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
+            uint32_t vd = 16u;
+            bool diag = false;
+            if constexpr (QSRC == ETS_Q_ROWS) { // the diagonal: out of the block's bound here, out of its scores below
+                vd = ets_diag((uint32_t)P.q_first + q, qlive, e0 + (uint32_t)(r * 32), h, &diag);
+                if (diag) {
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) acc[r][v] = (uint32_t)v == vd ? (int)0x80000000 : acc[r][v];
+                }
+            }
             int im = 0;
 #pragma unroll
             for (int v = 0; v < 16; ++v) im = max(im, acc[r][v]);
@@ -437,6 +482,12 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
                 sc[g4 * 4 + 1] = ((float)acc[r][g4 * 4 + 1] * iv.y) * qinv;
                 sc[g4 * 4 + 2] = ((float)acc[r][g4 * 4 + 2] * iv.z) * qinv;
                 sc[g4 * 4 + 3] = ((float)acc[r][g4 * 4 + 3] * iv.w) * qinv;
+            }
+            if constexpr (QSRC == ETS_Q_ROWS) {
+                if (diag) {
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) sc[v] = (uint32_t)v == vd ? -__builtin_inff() : sc[v];
+                }
             }
             const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && hit);
             if constexpr (MODE == ETS_RADIUS)
@@ -490,10 +541,12 @@ __global__ void ets_init_kernel(const uint8_t* __restrict__ queries, uint32_t nq
     if (q >= nq) return;
     bool ok = true;
     if constexpr (!I8) {
-        const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
-        float s = 0.0f;
-        for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
-        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+        if (queries) { // (null: the queries are the handle's rows, ETS_Q_ROWS, which its verdict covers)
+            const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
+            float s = 0.0f;
+            for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
+            ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+        }
     }
     lo[q] = ok ? ETS_LO0 : __builtin_inff();
     for (uint32_t j = 0; j < ETS_BUCKETS; ++j) hist[(size_t)q * ETS_BUCKETS + j] = 0u;
@@ -580,6 +633,43 @@ __global__ void ets_empty_kernel(uint32_t nq, uint32_t k, uint64_t* out_ids, flo
 __global__ void ets_status_kernel(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs) {
     atomicAdd(status + 1, routed);
     atomicOr(status + 3, form | (xs && xs[0] ? ETS_VOIDED : 0u));
+}
+
+// ---- the handle's own rows as queries ----
+// ets_gather_kernel's sibling: the rows first + p, p = list[f] or p_base + f, dense for exact_topk's scan
+__global__ void ets_gather_rows_kernel(const uint8_t* __restrict__ elements, uint32_t row_stride, uint32_t qbytes, uint64_t first,
+                                       const uint32_t* __restrict__ list, uint32_t p_base, uint32_t m, uint8_t* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)m * qbytes; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t f = (uint32_t)(i / qbytes), b = (uint32_t)(i - (uint64_t)f * qbytes);
+        out[i] = elements[(first + (list ? list[f] : p_base + f)) * row_stride + b];
+    }
+}
+// One block per row f of a scan with k + 1: element e = first + p among its own k + 1 nearest is dropped where it is listed
+// (at `at`, found by the block), the last entry where it is not (more than k bit-copies with smaller ids); the k entries,
+// the places past the count padded, and the count go to place p. A voided answer (count 0) stays empty.
+__global__ __launch_bounds__(256) void kg_drop_self_kernel(uint64_t first, const uint32_t* __restrict__ list, uint32_t p_base, uint32_t k,
+                                                           const uint64_t* __restrict__ ids, const float* __restrict__ dists,
+                                                           const uint32_t* __restrict__ counts, uint64_t* __restrict__ out_ids,
+                                                           float* __restrict__ out_dists, uint32_t* __restrict__ out_counts) {
+    __shared__ uint32_t at;
+    const uint32_t f = blockIdx.x, tid = threadIdx.x;
+    const size_t p = list ? list[f] : p_base + f;
+    const uint64_t e = first + p;
+    const uint32_t c = counts[f] <= k + 1u ? counts[f] : k + 1u;
+    const uint64_t* const in_ids = ids + (size_t)f * (k + 1u);
+    const float* const in_dists = dists + (size_t)f * (k + 1u);
+    if (tid == 0u) at = c ? c - 1u : 0u;
+    __syncthreads();
+    for (uint32_t j = tid; j < c; j += 256u)
+        if (in_ids[j] == e) at = j; // (an id is listed once)
+    __syncthreads();
+    const uint32_t drop = at, count = c ? c - 1u : 0u;
+    for (uint32_t j = tid; j < k; j += 256u) {
+        const uint32_t src = j < drop ? j : j + 1u;
+        out_ids[p * k + j] = j < count ? in_ids[src] : 0xFFFFFFFFFFFFFFFFull;
+        out_dists[p * k + j] = j < count ? in_dists[src] : __builtin_inff();
+    }
+    if (tid == 0u) out_counts[p] = count;
 }
 
 // ---- the radius scan's small kernels ----
@@ -748,6 +838,29 @@ hipError_t ets_scan_src(uint32_t form, bool collect, int src, uint32_t tiles, ui
     uint32_t lds = 0;
     const EtsScanFn fn = collect ? ets_scan_mode<ETS_COLLECT>(form, src, &lds) : ets_scan_mode<ETS_COUNT>(form, src, &lds);
     return ets_scan_launch(fn, lds, tiles, ranges, P, s);
+}
+hipError_t ets_scan_rows(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    EtsScanFn fn = nullptr;
+    uint32_t lds = 0;
+    const int mode = collect ? ETS_COLLECT : ETS_COUNT;
+    if (form == ETS_FORM_B16_7x4)
+        lds = ets_b16_lds<7, 4>(mode), fn = collect ? ets_b16_kernel<7, 4, ETS_COLLECT, ETS_ALL, ETS_Q_ROWS> : ets_b16_kernel<7, 4, ETS_COUNT, ETS_ALL, ETS_Q_ROWS>;
+    else if (form == ETS_FORM_B16_13x2)
+        lds = ets_b16_lds<13, 2>(mode), fn = collect ? ets_b16_kernel<13, 2, ETS_COLLECT, ETS_ALL, ETS_Q_ROWS> : ets_b16_kernel<13, 2, ETS_COUNT, ETS_ALL, ETS_Q_ROWS>;
+    else if (form == ETS_FORM_I8)
+        lds = ets_i8_lds(mode), fn = collect ? ets_i8_kernel<ETS_COLLECT, ETS_ALL, ETS_Q_ROWS> : ets_i8_kernel<ETS_COUNT, ETS_ALL, ETS_Q_ROWS>;
+    return ets_scan_launch(fn, lds, tiles, ranges, P, s);
+}
+hipError_t ets_gather_rows(const uint8_t* elements, uint32_t row_stride, uint32_t qbytes, uint64_t first, const uint32_t* list, uint32_t p_base,
+                           uint32_t m, uint8_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(ets_gather_rows_kernel, dim3(ets_grid((uint64_t)m * qbytes)), dim3(256), 0, s, elements, row_stride, qbytes, first, list,
+                       p_base, m, out);
+    return hipGetLastError();
+}
+hipError_t kg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t k, const uint64_t* ids, const float* dists,
+                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s) {
+    hipLaunchKernelGGL(kg_drop_self_kernel, dim3(m), dim3(256), 0, s, first, list, p_base, k, ids, dists, counts, out_ids, out_dists, out_counts);
+    return hipGetLastError();
 }
 hipError_t ets_scan_radius(uint32_t form, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
     uint32_t lds = 0;

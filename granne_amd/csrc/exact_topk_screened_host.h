@@ -71,6 +71,10 @@ static int ets_scan_norms(const granne_hip_index* ix, hipStream_t s) {
 static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_queries, const uint32_t* d_fb_list, uint32_t nfb, uint32_t k,
                              const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
                              uint32_t* d_xs, hipStream_t s);
+// the handle's own rows first + p (p = d_list[f], or f where d_list is null; f < m) by exact_topk's scan with k + 1, the
+// row itself dropped (knn_graph_host.h)
+static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, uint32_t k, uint64_t* d_out_ids,
+                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_xs, hipStream_t s);
 
 // The selection on stream s, arguments checked, nq > 0. Everything is ordered on s; the call waits on s once, after the
 // last round, for one word: the number of queries on the fallback list (and runs exact_topk's scan over them if any).
@@ -79,9 +83,13 @@ static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_que
 // reads back once, at its start -- the prefixes and the grids are then made from m as they are made from n, and the
 // kernels scan list positions (ETS_LIST); any other stride is one bitmap per query, tested in the kernels (ETS_BITS).
 // What is handed to exact_topk_run, routed or on the fallback list, goes there with its filter.
+// own_first (knn_graph_host.h; null: the caller's queries, and nothing below differs): the queries are the handle's own
+// rows *own_first .. + nq - 1, d_queries and the filter are null, and the answer is every row's k nearest OTHER rows --
+// the scans read their queries where the rows lie and take the diagonal out (ETS_Q_ROWS), dists_kernel strides over the
+// rows, and what exact_topk's scan answers is asked for k + 1 and has the row itself dropped (kg_by_scan).
 static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
                                    float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s,
-                                   const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0) {
+                                   const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0, const uint64_t* own_first = nullptr) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
     if (const int rc = ets_form(ix, s, &form)) return rc;
@@ -113,7 +121,9 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     uint32_t* const xs = (uint32_t*)(scratch + o_xs);
     HIP_TRY(ets_clear(xs, 8u, s)); // words 0..3: xs; word 4 (o_fbn = 16 bytes): the fallback count
     if (form == ETS_FORM_ROUTED) {
-        if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s))
+        if (own_first) {
+            if (const int rc = kg_by_scan(ix, *own_first, nullptr, nq, k, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+        } else if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s))
             return rc;
         if (d_status) HIP_TRY(ets_status(d_status, nq, (uint32_t)ETS_FORM_ROUTED, xs, s));
         return GRANNE_HIP_OK;
@@ -167,7 +177,8 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
         const uint32_t qc = nq - c0 < ET_CHUNK ? nq - c0 : ET_CHUNK;
         const uint32_t tiles = (qc + ETS_QT - 1) / ETS_QT;
-        P.queries = (const uint8_t*)d_queries + (size_t)c0 * qbytes;
+        P.queries = own_first ? nullptr : (const uint8_t*)d_queries + (size_t)c0 * qbytes;
+        P.q_first = own_first ? *own_first + c0 : 0;
         P.nq = qc;
         P.filter = src == ETS_BITS ? d_filter + (size_t)c0 * filter_stride_words : nullptr;
         auto pass = [&](bool collect, uint64_t rows) -> int {
@@ -180,7 +191,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
             if (G < 1) G = 1;
             P.n = rows;
             P.per_range = ((rows + G - 1) / G + tile - 1) / tile * tile;
-            HIP_TRY(ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s));
+            HIP_TRY(own_first ? ets_scan_rows(form, collect, tiles, (uint32_t)G, P, s) : ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s));
             return GRANNE_HIP_OK;
         };
         HIP_TRY(ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
@@ -191,7 +202,10 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
         if (const int rc = pass(true, n)) return rc;
         // the survivors' distances in the reference's arithmetic, then exact_topk's ranking by (distance bits, id)
         HIP_TRY(ets_pad(P.cand, P.cnt, P.lo, qc, c0, (uint32_t*)(scratch + o_sel), fb_count, fb_list, d_status, s));
-        if (const int rc = dists_launch(ix, P.queries, nullptr, ET_CAP, P.cand, (uint64_t)qc * ET_CAP, (float*)(scratch + o_dist), nullptr, s)) return rc;
+        const uint8_t* const dq = own_first ? P.elements + P.q_first * ix->row_stride : P.queries; // (a row is a prepared query)
+        if (const int rc = dists_launch(ix, dq, nullptr, ET_CAP, P.cand, (uint64_t)qc * ET_CAP, (float*)(scratch + o_dist), nullptr, s,
+                                        own_first ? ix->row_stride : 0u))
+            return rc;
         HIP_TRY(ets_keys(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, (uint64_t*)(scratch + o_keys), s));
         hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_keys), (const uint32_t*)P.cnt,
                            (const EtSel*)(scratch + o_sel), k, d_out_ids + (size_t)c0 * k, d_out_dists + (size_t)c0 * k, d_out_counts + c0,
@@ -203,6 +217,11 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     HIP_TRY(hipMemcpyAsync(&nfb, fb_count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (nfb == 0) return GRANNE_HIP_OK;
+    if (own_first) {
+        if (const int rc = kg_by_scan(ix, *own_first, fb_list, nfb, k, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+        if (d_status) HIP_TRY(ets_status(d_status, 0u, form, xs, s)); // (ETS_VOIDED where exact_topk voided one of them)
+        return GRANNE_HIP_OK;
+    }
     // the fallback: the listed queries by exact_topk's own scan (under their filter), the answers into their places
     const size_t f_ids = up((size_t)nfb * qbytes), f_d = f_ids + (size_t)nfb * k * 8, f_c = f_d + up((size_t)nfb * k * 4);
     uint8_t* fb = nullptr;

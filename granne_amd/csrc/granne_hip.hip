@@ -1989,27 +1989,28 @@ extern "C" int granne_hip_f16_to_f32(const uint16_t* rows16, float* out, uint64_
 }
 
 static int dists_launch(const granne_hip_index* ix, const void* d_queries, const uint32_t* d_qidx, uint32_t m,
-                        const uint32_t* d_ids, uint64_t n_pairs, float* d_out, uint32_t* d_status, void* stream) {
+                        const uint32_t* d_ids, uint64_t n_pairs, float* d_out, uint32_t* d_status, void* stream, uint32_t q_stride = 0) {
     if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "index is null");
     GRANNE_HIP_COMPACT_UNSUPPORTED(ix, "dists");
     if (n_pairs == 0) return GRANNE_HIP_OK;
     if (!d_queries || !d_ids || !d_out) return fail(GRANNE_HIP_ERR_INVALID, "null buffer");
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t* st = d_status; // optional: count of out-of-range ids
+    if (q_stride == 0) q_stride = ix->dim * query_elem_size(ix->dtype); // dense queries (else: bytes from one to the next)
     // eight lanes per pair, 32 pairs per 256-thread block; enough blocks to cover the chip many times
     uint64_t blocks = (n_pairs + 31) / 32;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
     if (ix->dtype == GRANNE_HIP_F16)
         hipLaunchKernelGGL(dists_kernel<DT_F16>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
-                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
+                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, q_stride, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     else if (ix->dtype == GRANNE_HIP_F32)
         hipLaunchKernelGGL(dists_kernel<0>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
-                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
+                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, q_stride, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     else
         hipLaunchKernelGGL(dists_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, ix->d_elements.as<uint8_t>(),
-                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, d_qidx, m, d_ids, n_pairs,
+                           ix->n_elements, ix->row_bytes, ix->row_stride, ix->dim, (const uint8_t*)d_queries, q_stride, d_qidx, m, d_ids, n_pairs,
                            d_out, st);
     HIP_TRY(hipGetLastError());
     return GRANNE_HIP_OK;
@@ -2493,3 +2494,4 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 #include "exact_topk_screened_host.h"
 #include "exact_topk_screened_filtered_host.h"
 #include "exact_range_screened_host.h"
+#include "knn_graph_host.h"

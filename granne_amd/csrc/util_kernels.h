@@ -249,12 +249,13 @@ __global__ void quantize_rows_kernel(const float* __restrict__ rows, int8_t* __r
 // fetches eight rows with fully used 128-byte lines -- the same lane layout as the walk's
 // fast_rows. f32 keeps the reference's association: lane `sub` owns accumulators 4*sub..4*sub+3
 // of the 32, the ordered sum runs down the eight lanes, the tail is folded by sequential fmas.
-// (lane_shr1 and the ordered sum down the eight lanes: ordered_sum.h)
+// (lane_shr1 and the ordered sum down the eight lanes: ordered_sum.h) q_stride: bytes from one query to the next -- dense
+// queries, or the index's own rows as they lie (knn_graph_host.h).
 
 template <int DT>
 __global__ __launch_bounds__(256) void dists_kernel(const uint8_t* __restrict__ elements, uint64_t n_elements,
                                                     uint32_t row_bytes, uint32_t row_stride, uint32_t dim,
-                                                    const uint8_t* __restrict__ queries,
+                                                    const uint8_t* __restrict__ queries, uint32_t q_stride,
                                                     const uint32_t* __restrict__ qidx, uint32_t m,
                                                     const uint32_t* __restrict__ ids, uint64_t n_pairs,
                                                     float* __restrict__ out, uint32_t* __restrict__ status) {
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(256) void dists_kernel(const uint8_t* __restrict__ 
         const uint8_t* row = elements + (uint64_t)(valid ? id : 0u) * row_stride;
         float d;
         if constexpr (DT == 0) {
-            const float* q = reinterpret_cast<const float*>(queries) + qi * dim;
+            const float* q = reinterpret_cast<const float*>(queries + qi * q_stride);
             const uint32_t nfull = dim >> 5, tail = dim & 31u;
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
 #pragma unroll 4
@@ -298,10 +299,10 @@ __global__ __launch_bounds__(256) void dists_kernel(const uint8_t* __restrict__ 
         } else if constexpr (DT == DT_F16) { // rows of halves, f32 queries (f16.h)
             const uint8_t* one[1] = {row};
             float d1[1];
-            f16_dist_group<1>(one, reinterpret_cast<const float*>(queries) + qi * dim, dim, row_bytes, lane, d1);
+            f16_dist_group<1>(one, reinterpret_cast<const float*>(queries + qi * q_stride), dim, row_bytes, lane, d1);
             d = d1[0];
         } else {
-            const int8_t* q = reinterpret_cast<const int8_t*>(queries) + qi * dim;
+            const int8_t* q = reinterpret_cast<const int8_t*>(queries + qi * q_stride);
             int r = 0, dx = 0, dy = 0;
             for (uint32_t b = sub * 16u; b < row_bytes; b += 128u) {
                 const uint4 v = *reinterpret_cast<const uint4*>(row + b);

@@ -742,6 +742,39 @@ class Granne:
             raise GranneHipError(ERR_OVERFLOW, "exact_topk_screened: exact_topk's selection overflowed for a query handed to it")
         return out
 
+    def knn_graph_device(self, first, count, k, d_ids, d_dists, d_counts, d_status=0, stream=0):
+        """Every element's exact k nearest OTHER elements for the elements first .. first + count - 1
+        (granne_hip_knn_graph_device). Raw device pointers (int; d_status: u32[4] zeroed by the caller, or 0); ordered on
+        `stream`, which the call waits on once at its end."""
+        check(lib().granne_hip_knn_graph_device(self._h, int(first), int(count), int(k), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                                C.c_void_p(d_counts), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def knn_graph(self, k, first=0, count=None, stats=False):
+        """The exact k-NN graph of the index's own elements: for each element e of first .. first + count - 1 (count=None:
+        to the last one) the first k (up to EXACT_TOPK_KMAX - 1) of all OTHER elements by (distance bits, id) -- what
+        `exact_topk(get_element(e), k + 1)` gives with e left out, also where more than k bit-copies of e have smaller
+        ids. Returns ids [count, k] u64, dists [count, k] f32, counts [count] u32 (min(k, num_elements() - 1); unused
+        places hold 2^64 - 1 and +inf) and, with stats=True, `exact_topk_screened`'s status words; with stats=False a
+        voided element raises GranneHipError(ERR_OVERFLOW) as `exact_topk` does."""
+        import torch
+        first, k = int(first), int(k)
+        count = self.num_elements() - first if count is None else int(count)
+        dev = torch.device("cuda", self.device)
+        ids = torch.empty((max(count, 0), max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((max(count, 0), max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(max(count, 0), dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.knn_graph_device(first, count, k, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(), st.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        status = st.cpu().numpy().astype(np.uint32)
+        out = ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+        if stats:
+            return out + (status,)
+        if status[3] & 0x80000000:
+            raise GranneHipError(ERR_OVERFLOW, "knn_graph: exact_topk's selection overflowed for an element handed to it")
+        return out
+
     def num_elements(self):
         """Rows of the element set (at least len()): what exact_topk and exact_topk_filtered scan."""
         return int(lib().granne_hip_index_num_elements(self._h))

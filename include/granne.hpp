@@ -392,6 +392,23 @@ public:
         return out;
     }
 
+    // The exact k-NN graph of the index's own elements (granne_hip_knn_graph): for every element of [first, first + count)
+    // its k (up to 1023) nearest OTHER elements by (distance bits, id) -- exact_topk of the element's own row with the
+    // element left out, the matrix cores screening the rows first. Throws where exact_topk throws. `status` (optional):
+    // exact_topk_screened's four status words.
+    std::vector<std::vector<std::pair<size_t, float>>> knn_graph(size_t k, size_t first, size_t count,
+                                                                 std::vector<uint32_t>* status = nullptr) const {
+        std::vector<uint64_t> ids(count * k);
+        std::vector<float> ds(count * k);
+        std::vector<uint32_t> counts(count), st(4, 0u);
+        check(granne_hip_knn_graph(h_.get(), (uint64_t)first, (uint64_t)count, (uint32_t)k, ids.data(), ds.data(), counts.data(), st.data()));
+        if (status) *status = st;
+        std::vector<std::vector<std::pair<size_t, float>>> out(count);
+        for (size_t i = 0; i < count; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
+        return out;
+    }
+
     // exact_topk among the ids `allowed` lets through (granne_hip_exact_topk_filtered_device; one bitmap for all queries,
     // over num_elements() ids): the scan walks the bitmap's id list -- the tool for a selective filter, where
     // search_filtered steps over many disallowed nodes per allowed one. A result holds fewer than k ids when fewer are allowed.

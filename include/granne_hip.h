@@ -467,6 +467,33 @@ int granne_hip_exact_topk_screened(const granne_hip_index* index, const void* qu
 /* the screen's bound for rows of `dtype` and `dim` components -- the number the kernels are given; 0: no screen for the shape */
 float granne_hip_exact_topk_screen_epsilon(int dtype, uint32_t dim);
 
+/* The exact k-NN graph of the handle's own elements: for every e in [first, first + count), all elements j != e are
+ * ranked by (distance bits of dist(element e, element j), j) and the first k are written to row e - first of the outputs.
+ * The distance is the one granne_hip_exact_topk gives when element e is the query -- f32: the stored row as a prepared
+ * query; int8: the stored int8 row, angular_int::Vector::dist between two rows. Equivalently: granne_hip_exact_topk(row e,
+ * k + 1) with e dropped where it is listed and the last entry dropped where it is not (more than k bit-copies of e with
+ * smaller ids). d_out_counts[e - first] = min(k, n_elements - 1); unused places hold UINT64_MAX and +inf.
+ *   screened   handles that granne_hip_exact_topk_screened screens: its scan with the queries read from the rows where they
+ *              lie (no dense copy of them is made) and the score of a row with itself taken out before the floor, the
+ *              histogram or the candidate list sees it -- an element is no witness of its own floor.
+ *   routed     every other handle (f32 beyond 208 components or off the proven norm bound, int8 beyond 128): the rows are
+ *              gathered as queries for granne_hip_exact_topk_device with k + 1, and the element is dropped from its answer.
+ *   fallback   an element with more than GRANNE_HIP_EXACT_TOPK_CAP survivors goes the same way after the screen.
+ *   d_status   u32[4], optional, zeroed by the caller, granne_hip_exact_topk_screened's words: [0] elements answered by the
+ *              fallback, [1] elements routed by the handle's shape (0 or count), [2] the largest number of survivors of one
+ *              element, [3] the form that ran, bit 31 set where exact_topk voided an element handed to it (count 0).
+ * Refused (GRANNE_HIP_ERR_INVALID, the message naming knn_graph): a null index, first + count > n_elements, null buffers,
+ * k == 0, k > GRANNE_HIP_EXACT_TOPK_KMAX - 1 (what exact_topk's scan answers is asked for k + 1), GRANNE_HIP_F16 and compact
+ * SumEmbeddings handles; count == 0 does nothing. Stream-ordered; the call waits on `stream` once, at its end, for one
+ * word. Scratch from hipMallocAsync as granne_hip_exact_topk_screened's. Neither entry writes GRANNE_HIP_OPT_LAST_SCAN. */
+int granne_hip_knn_graph_device(const granne_hip_index* index, uint64_t first, uint64_t count, uint32_t k,
+                                uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                uint32_t* d_status /* u32[4], optional, zeroed by the caller */, void* stream);
+/* the same with host buffers out (synchronous). GRANNE_HIP_ERR_OVERFLOW when bit 31 of status[3] is set: the outputs (and
+ * out_status, optional) are still written. */
+int granne_hip_knn_graph(const granne_hip_index* index, uint64_t first, uint64_t count, uint32_t k,
+                         uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
+
 /* The per-shard top-k of one batch as ONE buffer -- what a rank contributes to the single exchange
  * step of the partitioned mode (one all-gather, or one peer copy):
  *   [nq*k u64 local ids][nq*k f32 dists][nq u32 counts], padded to 16 bytes.                      */

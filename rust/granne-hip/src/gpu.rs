@@ -412,6 +412,10 @@ extern "C" {
     fn granne_hip_exact_topk_screened(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_exact_topk_screen_epsilon(dtype: c_int, dim: u32) -> f32;
+    fn granne_hip_knn_graph_device(index: *const granne_hip_index, first: u64, count: u64, k: u32, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_knn_graph(index: *const granne_hip_index, first: u64, count: u64, k: u32, out_ids: *mut u64,
+        out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_merge_topk_device(d_ids: *const u64, d_dists: *const f32, d_counts: *const u32,
         shard_offsets: *const u64, n_shards: u32, nq: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
         d_out_counts: *mut u32, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -628,6 +632,16 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_exact_topk_screened(self.handle, q.as_ptr() as *const c_void, nq as u32, k as u32,
             ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
+    }
+    /// `granne_hip_knn_graph`: for every element of `first .. first + count` its exact `k` (up to 1023) nearest OTHER
+    /// elements by (distance bits, id) -- `exact_topk` of the element's own row with the element left out, the matrix
+    /// cores screening the rows first. An `Err` where `exact_topk` gives one.
+    pub fn knn_graph(&self, k: usize, first: usize, count: usize) -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let (mut ids, mut ds) = (vec![0u64; count * k], vec![0f32; count * k]);
+        let mut counts = vec![0u32; count];
+        check(unsafe { granne_hip_knn_graph(self.handle, first as u64, count as u64, k as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok((0..count).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
     }
     /// `granne_hip_exact_topk_filtered_device`: `exact_topk` among the ids `filter` allows (one bitmap for all queries,
     /// over `num_elements()` ids): the scan walks the bitmap's id list, exact by construction -- the tool for a selective
