@@ -144,6 +144,21 @@ hipError_t ers_pad(uint32_t* cand, const uint32_t* sure, const uint32_t* bcnt, c
 hipError_t ers_keys(const uint32_t* cand, const float* dists, const float* radii, const float* lo, const float* hi, const uint32_t* sure,
                     const uint32_t* bcnt, uint32_t nq, uint32_t q_base, uint64_t* keys, uint32_t* totals, ErsLists lists, uint32_t* status,
                     hipStream_t s);
+// ---- every element's neighbours within a radius (range_graph_host.h) ----
+// ets_scan_radius over all rows with the queries of ETS_Q_ROWS (P.q_first, P.nq): the diagonal is -inf before the block's
+// max, so an element is in neither of its lists and in none of its counts. ers_radius with queries == nullptr starts them.
+hipError_t ets_scan_radius_rows(uint32_t form, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+// for the elements first + p -- p = list[f], or p_base + f where list is null -- f < m: their ids (dists_kernel's one
+// candidate per element: d(e, e)) and their radii, dense
+hipError_t rg_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, const float* radii, uint32_t* self_ids, float* out_radii,
+                   hipStream_t s);
+// exact_range's answer for cap + 1 over the same m rows as queries ([m][cap + 1], counts [m], totals [m]) -> the neighbours
+// within the radius, into place p of the outputs: the total less one where self[f] = d(e, e) <= radii[f]; the element
+// dropped where it is listed, the last entry where it is not and the listing is full
+hipError_t rg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t cap, const uint64_t* ids, const float* dists,
+                        const uint32_t* counts, const uint32_t* totals, const float* self, const float* radii, uint64_t* out_ids, float* out_dists,
+                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s);
+
 // status[0] += the queries of a dense answer with count 0 (voided by exact_topk's overflow), ETS_VOIDED into status[3]
 hipError_t ers_voided(const uint32_t* counts, uint32_t np, uint32_t* status, hipStream_t s);
 // status[0] += xs[0] (xs optional; ETS_VOIDED into [3] with it), status[1] += not_a, status[3] |= form

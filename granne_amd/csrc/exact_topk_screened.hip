@@ -686,10 +686,12 @@ __global__ void ets_radius_kernel(const uint8_t* __restrict__ queries, const flo
     if (q >= nq) return;
     bool ok = true;
     if constexpr (!I8) {
-        const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
-        float s = 0.0f;
-        for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
-        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+        if (queries) { // (null: the queries are the handle's rows, ETS_Q_ROWS, which its verdict covers, as in ets_init_kernel)
+            const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
+            float s = 0.0f;
+            for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
+            ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+        }
     }
     const float r = radii[q];
     float l = __builtin_inff(), u = ok ? __builtin_inff() : -__builtin_inff();
@@ -698,6 +700,9 @@ __global__ void ets_radius_kernel(const uint8_t* __restrict__ queries, const flo
         l = (float)dl, u = (float)du;
         if ((double)l > dl) l = nextafterf(l, -__builtin_inff());
         if ((double)u < du) u = nextafterf(u, __builtin_inff());
+        // Rows as queries (range_graph_host.h): the score of a row with itself is -inf, and -inf >= -inf would let r = +inf
+        // admit it. No threshold goes below ETS_LO0: every real score is above it, so nothing else changes.
+        if (!queries) l = __builtin_fmaxf(l, ETS_LO0), u = __builtin_fmaxf(u, ETS_LO0);
     }
     lo[q] = l, hi[q] = u;
     sure[q] = 0u, cnt[q] = 0u, bcnt[q] = 0u;
@@ -773,7 +778,67 @@ __global__ void ers_status_kernel(uint32_t* status, const uint32_t* xs, uint32_t
     atomicOr(status + 3, form | (xs && xs[0] ? ETS_VOIDED : 0u));
 }
 
+// ---- every element's neighbours within a radius (range_graph_host.h) ----
+// The elements exact_range's own scan answers (path C, routed handles), a round of them: element first + p, p = list[f] or
+// p_base + f, gets its id as the one candidate of dists_kernel -- d(e, e) in the reference's arithmetic -- and its radius
+// dense beside its gathered row.
+__global__ void rg_self_kernel(uint64_t first, const uint32_t* __restrict__ list, uint32_t p_base, uint32_t m, const float* __restrict__ radii,
+                               uint32_t* __restrict__ self_ids, float* __restrict__ out_radii) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= m) return;
+    const uint32_t p = list ? list[f] : p_base + f;
+    self_ids[f] = (uint32_t)(first + p);
+    out_radii[f] = radii[p];
+}
+// kg_drop_self_kernel's rule with a radius. One block per row f of exact_range's answer for cap + 1 ([m][cap + 1], counts,
+// totals): element e = first + p was counted by that scan exactly when self[f] = d(e, e) <= r (the scan's own compare; false
+// for a NaN radius), and then the total drops by one. e is dropped from the listing where it is listed (at `at`, found by
+// the block); where it is not and the listing is full (cap + 1 entries, all of them others that come before e or e outside
+// the radius) the last entry is; a shorter listing without e is whole. A voided answer (count 0) stays empty.
+__global__ __launch_bounds__(256) void rg_drop_self_kernel(uint64_t first, const uint32_t* __restrict__ list, uint32_t p_base, uint32_t cap,
+                                                           const uint64_t* __restrict__ ids, const float* __restrict__ dists,
+                                                           const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
+                                                           const float* __restrict__ self, const float* __restrict__ radii,
+                                                           uint64_t* __restrict__ out_ids, float* __restrict__ out_dists,
+                                                           uint32_t* __restrict__ out_counts, uint32_t* __restrict__ out_totals) {
+    __shared__ uint32_t at;
+    const uint32_t f = blockIdx.x, tid = threadIdx.x;
+    const size_t p = list ? list[f] : p_base + f;
+    const uint64_t e = first + p;
+    const uint32_t c = counts[f] <= cap + 1u ? counts[f] : cap + 1u;
+    const uint64_t* const in_ids = ids + (size_t)f * (cap + 1u);
+    const float* const in_dists = dists + (size_t)f * (cap + 1u);
+    if (tid == 0u) at = c == cap + 1u ? cap : 0xFFFFFFFFu;
+    __syncthreads();
+    for (uint32_t j = tid; j < c; j += 256u)
+        if (in_ids[j] == e) at = j; // (an id is listed once)
+    __syncthreads();
+    const uint32_t drop = at, count = drop < c ? c - 1u : c;
+    for (uint32_t j = tid; j < cap; j += 256u) {
+        const uint32_t src = j < drop ? j : j + 1u;
+        out_ids[p * cap + j] = j < count ? in_ids[src] : 0xFFFFFFFFFFFFFFFFull;
+        out_dists[p * cap + j] = j < count ? in_dists[src] : __builtin_inff();
+    }
+    if (tid == 0u) {
+        const bool within = self[f] <= radii[f];
+        out_counts[p] = count;
+        out_totals[p] = totals[f] - (within && totals[f] ? 1u : 0u);
+    }
+}
+
 // ---- launchers ----
+hipError_t rg_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, const float* radii, uint32_t* self_ids, float* out_radii,
+                   hipStream_t s) {
+    hipLaunchKernelGGL(rg_self_kernel, dim3((m + 255) / 256), dim3(256), 0, s, first, list, p_base, m, radii, self_ids, out_radii);
+    return hipGetLastError();
+}
+hipError_t rg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t cap, const uint64_t* ids, const float* dists,
+                        const uint32_t* counts, const uint32_t* totals, const float* self, const float* radii, uint64_t* out_ids, float* out_dists,
+                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s) {
+    hipLaunchKernelGGL(rg_drop_self_kernel, dim3(m), dim3(256), 0, s, first, list, p_base, cap, ids, dists, counts, totals, self, radii, out_ids,
+                       out_dists, out_counts, out_totals);
+    return hipGetLastError();
+}
 hipError_t ers_radius(bool i8, const uint8_t* queries, const float* radii, uint32_t nq, uint32_t dim, float eps, float* lo, float* hi,
                       uint32_t* sure, uint32_t* cnt, uint32_t* bcnt, hipStream_t s) {
     hipLaunchKernelGGL(i8 ? ets_radius_kernel<true> : ets_radius_kernel<false>, dim3((nq + 255) / 256), dim3(256), 0, s, queries, radii, nq, dim, eps,
@@ -865,6 +930,14 @@ hipError_t kg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, u
 hipError_t ets_scan_radius(uint32_t form, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
     uint32_t lds = 0;
     const EtsScanFn fn = ets_scan_mode<ETS_RADIUS>(form, src, &lds);
+    return ets_scan_launch(fn, lds, tiles, ranges, P, s);
+}
+hipError_t ets_scan_radius_rows(uint32_t form, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    EtsScanFn fn = nullptr;
+    uint32_t lds = 0;
+    if (form == ETS_FORM_B16_7x4) lds = ets_b16_lds<7, 4>(ETS_RADIUS), fn = ets_b16_kernel<7, 4, ETS_RADIUS, ETS_ALL, ETS_Q_ROWS>;
+    else if (form == ETS_FORM_B16_13x2) lds = ets_b16_lds<13, 2>(ETS_RADIUS), fn = ets_b16_kernel<13, 2, ETS_RADIUS, ETS_ALL, ETS_Q_ROWS>;
+    else if (form == ETS_FORM_I8) lds = ets_i8_lds(ETS_RADIUS), fn = ets_i8_kernel<ETS_RADIUS, ETS_ALL, ETS_Q_ROWS>;
     return ets_scan_launch(fn, lds, tiles, ranges, P, s);
 }
 hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s) {

@@ -2495,3 +2495,4 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 #include "exact_topk_screened_filtered_host.h"
 #include "exact_range_screened_host.h"
 #include "knn_graph_host.h"
+#include "range_graph_host.h"

@@ -775,6 +775,45 @@ class Granne:
             raise GranneHipError(ERR_OVERFLOW, "knn_graph: exact_topk's selection overflowed for an element handed to it")
         return out
 
+    def range_graph_device(self, first, count, d_radii, cap, d_ids, d_dists, d_counts, d_totals, d_status=0, stream=0):
+        """Every element's exact neighbours within its radius for the elements first .. first + count - 1
+        (granne_hip_range_graph_device). Raw device pointers (int; d_radii: f32[count]; d_status: u32[4] zeroed by the
+        caller, or 0); ordered on `stream`, which the call waits on."""
+        check(lib().granne_hip_range_graph_device(self._h, int(first), int(count), C.c_void_p(d_radii), int(cap), C.c_void_p(d_ids),
+                                                  C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_totals), C.c_void_p(d_status),
+                                                  C.c_void_p(stream)))
+
+    def range_graph(self, radius, max_results=1024, first=0, count=None, stats=False):
+        """For each element e of first .. first + count - 1 (count=None: to the last one) the OTHER elements within
+        `radius` of it (a scalar, or one value per element of the window; d <= r on exact_range's own distances): what
+        `exact_range(get_element(e), r, max_results)` gives with e struck out -- the total one less where e was counted,
+        bit-copies of e kept in id order. Returns ids [count, max_results] u64, dists f32, counts [count] u32 and totals
+        [count] u32 (exact however large; unused places hold 2^64 - 1 and +inf) and, with stats=True,
+        `exact_range_screened`'s status words; with stats=False a voided element raises GranneHipError(ERR_OVERFLOW)."""
+        import torch
+        first, cap = int(first), int(max_results)
+        count = self.num_elements() - first if count is None else int(count)
+        shape = max(count, 0)
+        dev = torch.device("cuda", self.device)
+        r = np.array(np.broadcast_to(np.asarray(radius, dtype=np.float32), (shape,)))  # (a copy: one value per element)
+        d_r = torch.from_numpy(r).to(dev)
+        ids = torch.empty((shape, max(cap, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((shape, max(cap, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(shape, dtype=torch.int32, device=dev)
+        tot = torch.empty(shape, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.range_graph_device(first, count, d_r.data_ptr(), cap, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(), tot.data_ptr(),
+                                st.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        status = st.cpu().numpy().astype(np.uint32)
+        out = (ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32),
+               tot.cpu().numpy().astype(np.uint32))
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "range_graph: exact_topk's selection overflowed for an element handed to it")
+        return out
+
     def num_elements(self):
         """Rows of the element set (at least len()): what exact_topk and exact_topk_filtered scan."""
         return int(lib().granne_hip_index_num_elements(self._h))

@@ -409,6 +409,29 @@ public:
         return out;
     }
 
+    // Every element's exact neighbours within a radius (granne_hip_range_graph): for every element e of [first, first +
+    // count) the OTHER elements within radii[e - first] of it (one radius per element, or one for all), nearest first by
+    // (distance bits, id), at most max_results of them listed -- exact_range of the element's own row with the element
+    // struck out. `totals` (optional): the exact number of such elements, however many are listed. `status` (optional):
+    // exact_range_screened's four status words. Throws where exact_range throws.
+    std::vector<std::vector<std::pair<size_t, float>>> range_graph(const std::vector<float>& radii, size_t max_results, size_t first,
+                                                                   size_t count, std::vector<uint32_t>* totals = nullptr,
+                                                                   std::vector<uint32_t>* status = nullptr) const {
+        if (radii.size() != count && radii.size() != 1) throw std::invalid_argument("range_graph: one radius, or one per element");
+        const std::vector<float> r = radii.size() == count ? radii : std::vector<float>(count, radii[0]);
+        std::vector<uint64_t> ids(count * max_results);
+        std::vector<float> ds(count * max_results);
+        std::vector<uint32_t> counts(count), tot(count), st(4, 0u);
+        check(granne_hip_range_graph(h_.get(), (uint64_t)first, (uint64_t)count, r.data(), (uint32_t)max_results, ids.data(), ds.data(),
+                                     counts.data(), tot.data(), st.data()));
+        if (totals) *totals = tot;
+        if (status) *status = st;
+        std::vector<std::vector<std::pair<size_t, float>>> out(count);
+        for (size_t i = 0; i < count; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * max_results + j], ds[i * max_results + j]);
+        return out;
+    }
+
     // exact_topk among the ids `allowed` lets through (granne_hip_exact_topk_filtered_device; one bitmap for all queries,
     // over num_elements() ids): the scan walks the bitmap's id list -- the tool for a selective filter, where
     // search_filtered steps over many disallowed nodes per allowed one. A result holds fewer than k ids when fewer are allowed.

@@ -494,6 +494,39 @@ int granne_hip_knn_graph_device(const granne_hip_index* index, uint64_t first, u
 int granne_hip_knn_graph(const granne_hip_index* index, uint64_t first, uint64_t count, uint32_t k,
                          uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
 
+/* Every element's exact neighbours within a radius: for every e in [first, first + count) and its radius r_e =
+ * d_radii[e - first] (one f32 per element of the window),
+ *   W'(e)    = { x < n_elements : x != e and dist(element e, x) <= r_e }   (granne_hip_exact_range's distances and compare)
+ *   total[e] = |W'(e)|, ALWAYS exact; the listing = the first min(total, cap) members of W' by (distance bits, id)
+ * into row e - first of the outputs; unused places hold UINT64_MAX and +inf, as granne_hip_exact_range pads them. The model:
+ * granne_hip_exact_range(row e as the query, r_e, cap) with id e struck out -- where e was counted, which is exactly when
+ * dist(e, e) <= r_e in the reference's arithmetic (dist(e, e) is not always 0), the total is one less; bit-copies of e stay,
+ * in id order. A NaN or negative radius admits nothing.
+ *   path A     handles that granne_hip_exact_range_screened screens: its one radius pass with the queries read from the rows
+ *              where they lie and the score of a row with itself taken out before anything counts or lists it (DESIGN.md
+ *              3.7f). Rows whose score vouches for d <= r are counted exactly and the first GRANNE_HIP_EXACT_TOPK_CAP listed;
+ *              the band around the radius is decided by the reference's arithmetic. Up to that many neighbours: ranked.
+ *   path B     more neighbours than that: the total is the pass's; the cap nearest by the screened selection with cap + 1
+ *              over the element's gathered row, the element dropped as granne_hip_knn_graph drops it.
+ *   path C     a band beyond GRANNE_HIP_EXACT_TOPK_CAP, or a handle without a screen (f32 beyond 208 components or off the
+ *              proven norm bound, int8 beyond 128): granne_hip_exact_range's own scan with cap + 1 over the gathered rows;
+ *              dist(e, e) <= r_e is evaluated once, the total corrected and the element dropped.
+ *   d_status   u32[4], optional, zeroed by the caller, granne_hip_exact_range_screened's words: [0] elements voided (count 0,
+ *              total exact), [1] elements not answered by path A, [2] the largest sure + band count of one element, [3] the
+ *              form that ran (GRANNE_HIP_ETS_FORM_*), bit 31 (GRANNE_HIP_ETS_VOIDED) with [0].
+ * Refused (GRANNE_HIP_ERR_INVALID, the message naming range_graph): a null index, first + count > n_elements, null buffers,
+ * cap outside [1, GRANNE_HIP_RANGE_CAP_MAX], GRANNE_HIP_F16 and compact SumEmbeddings handles; count == 0 does nothing.
+ * Stream-ordered; the call waits on `stream` once for two words (and where paths B and C wait). Scratch from hipMallocAsync. */
+int granne_hip_range_graph_device(const granne_hip_index* index, uint64_t first, uint64_t count, const float* d_radii,
+                                  uint32_t cap, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                  uint32_t* d_out_totals, uint32_t* d_status /* u32[4], optional, zeroed by the caller */,
+                                  void* stream);
+/* the same with host buffers in and out (synchronous); a NaN radius is refused. GRANNE_HIP_ERR_OVERFLOW when status[0] is
+ * not 0: the outputs (and out_status, optional) are still written. */
+int granne_hip_range_graph(const granne_hip_index* index, uint64_t first, uint64_t count, const float* radii, uint32_t cap,
+                           uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_totals,
+                           uint32_t* out_status /* optional */);
+
 /* The per-shard top-k of one batch as ONE buffer -- what a rank contributes to the single exchange
  * step of the partitioned mode (one all-gather, or one peer copy):
  *   [nq*k u64 local ids][nq*k f32 dists][nq u32 counts], padded to 16 bytes.                      */

@@ -416,6 +416,11 @@ extern "C" {
         d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
     fn granne_hip_knn_graph(index: *const granne_hip_index, first: u64, count: u64, k: u32, out_ids: *mut u64,
         out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_range_graph_device(index: *const granne_hip_index, first: u64, count: u64, d_radii: *const f32,
+        cap: u32, d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_totals: *mut u32,
+        d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_range_graph(index: *const granne_hip_index, first: u64, count: u64, radii: *const f32, cap: u32,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_merge_topk_device(d_ids: *const u64, d_dists: *const f32, d_counts: *const u32,
         shard_offsets: *const u64, n_shards: u32, nq: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
         d_out_counts: *mut u32, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -642,6 +647,18 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_knn_graph(self.handle, first as u64, count as u64, k as u32,
             ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok((0..count).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
+    }
+    /// `granne_hip_range_graph`: for every element `e` of `first .. first + count` the OTHER elements within
+    /// `radii[e - first]` of it, nearest first by (distance bits, id), at most `cap` listed -- `exact_range` of the
+    /// element's own row with the element struck out -- and the exact number of them, however many are listed.
+    pub fn range_graph(&self, radii: &[f32], cap: usize, first: usize, count: usize)
+                       -> std::io::Result<(Vec<Vec<(usize, f32)>>, Vec<u32>)> {
+        assert_eq!(count, radii.len());
+        let (mut ids, mut ds) = (vec![0u64; count * cap], vec![0f32; count * cap]);
+        let (mut counts, mut totals) = (vec![0u32; count], vec![0u32; count]);
+        check(unsafe { granne_hip_range_graph(self.handle, first as u64, count as u64, radii.as_ptr(), cap as u32,
+            ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), totals.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok(((0..count).map(|i| (0..counts[i] as usize).map(|j| (ids[i * cap + j] as usize, ds[i * cap + j])).collect()).collect(), totals))
     }
     /// `granne_hip_exact_topk_filtered_device`: `exact_topk` among the ids `filter` allows (one bitmap for all queries,
     /// over `num_elements()` ids): the scan walks the bitmap's id list, exact by construction -- the tool for a selective
