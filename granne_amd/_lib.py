@@ -159,6 +159,10 @@ SIGNATURES = {
     "granne_hip_knn_graph": (i32, [vp, u64, u64, u32, vp, vp, vp, vp]),
     "granne_hip_range_graph_device": (i32, [vp, u64, u64, vp, u32, vp, vp, vp, vp, vp, vp]),
     "granne_hip_range_graph": (i32, [vp, u64, u64, vp, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_knn_graph_filtered_device": (i32, [vp, vp, u64, u64, u32, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_knn_graph_filtered": (i32, [vp, vp, u64, u64, u32, vp, vp, vp, vp, vp]),
+    "granne_hip_range_graph_filtered_device": (i32, [vp, vp, u64, u64, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "granne_hip_range_graph_filtered": (i32, [vp, vp, u64, u64, vp, u32, vp, vp, vp, vp, vp, vp]),
     "granne_hip_merge_topk_device": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp]),
     "granne_hip_packed_topk_bytes": (u64, [u32, u32]),
     "granne_hip_search_batch_packed_device": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),

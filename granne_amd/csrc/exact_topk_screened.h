@@ -93,7 +93,8 @@ struct EtsParams {
     const uint32_t* list = nullptr;   // ETS_LIST: the allowed ids, ascending; n counts its positions
     const uint32_t* filter = nullptr; // ETS_BITS: this round's bitmaps, query q's at filter + q * filter_stride
     uint64_t filter_stride = 0;       // ETS_BITS: in words
-    uint64_t q_first = 0;             // ETS_Q_ROWS: the element that is this round's query 0 (queries is not read)
+    uint64_t q_first = 0;             // ETS_Q_ROWS: the element that is this round's query 0 (queries is not read); with
+                                      // ETS_LIST: its position in the list
 };
 
 // the launchers (exact_topk_screened.hip); every one is ordered on s and returns what the launch left
@@ -118,13 +119,16 @@ hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const ui
 // ---- the handle's own rows as queries (knn_graph_host.h) ----
 // ets_scan over all rows with the queries of ETS_Q_ROWS: P.q_first, P.nq; ets_init with queries == nullptr starts them
 hipError_t ets_scan_rows(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
-// rows first + p -- p = list[f], or p_base + f where list is null -- f < m, as dense queries of qbytes each
+// rows first + p -- p = list[f], or p_base + f where list is null -- f < m, as dense queries of qbytes each.
+// `allowed`, here and in kg_drop_self, rg_self and rg_drop_self (graph_filtered_host.h): a filter's id
+// list -- first + p is then a position of it and the element is allowed[first + p]; the outputs' places stay p.
 hipError_t ets_gather_rows(const uint8_t* elements, uint32_t row_stride, uint32_t qbytes, uint64_t first, const uint32_t* list, uint32_t p_base,
-                           uint32_t m, uint8_t* out, hipStream_t s);
+                           uint32_t m, uint8_t* out, hipStream_t s, const uint32_t* allowed = nullptr);
 // exact_topk's k + 1 nearest of the same m rows ([m][k + 1], counts [m]) -> the k nearest OTHERS, into place p of the outputs:
 // the element dropped where it is listed, the last entry where it is not
 hipError_t kg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t k, const uint64_t* ids, const float* dists,
-                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s);
+                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s,
+                        const uint32_t* allowed = nullptr);
 
 // ---- the radius scan (exact_range_screened_host.h) ----
 // What the queries of a call that path A does not answer are listed in: n[0] queries for exact_topk_screened(k = cap)
@@ -151,13 +155,22 @@ hipError_t ets_scan_radius_rows(uint32_t form, uint32_t tiles, uint32_t ranges, 
 // for the elements first + p -- p = list[f], or p_base + f where list is null -- f < m: their ids (dists_kernel's one
 // candidate per element: d(e, e)) and their radii, dense
 hipError_t rg_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, const float* radii, uint32_t* self_ids, float* out_radii,
-                   hipStream_t s);
+                   hipStream_t s, const uint32_t* allowed = nullptr);
 // exact_range's answer for cap + 1 over the same m rows as queries ([m][cap + 1], counts [m], totals [m]) -> the neighbours
 // within the radius, into place p of the outputs: the total less one where self[f] = d(e, e) <= radii[f]; the element
 // dropped where it is listed, the last entry where it is not and the listing is full
 hipError_t rg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t cap, const uint64_t* ids, const float* dists,
                         const uint32_t* counts, const uint32_t* totals, const float* self, const float* radii, uint64_t* out_ids, float* out_dists,
-                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s);
+                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s, const uint32_t* allowed = nullptr);
+
+// ---- the graphs of a subset (graph_filtered_host.h) ----
+// The scans over the positions [0, P.n) of P.list (ETS_LIST) with the queries of ETS_Q_ROWS: query q of a round is POSITION
+// P.q_first + q of the list, read from row P.list[P.q_first + q]; the diagonal is found by comparing positions, which is
+// what the scanned rows are too. COLLECT lists ids, RADIUS positions, as the ETS_LIST scans with dense queries do.
+hipError_t ets_scan_rows_list(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+hipError_t ets_scan_radius_rows_list(uint32_t form, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+// out[p] = allowed[first + p], p < count
+hipError_t gf_elements(const uint32_t* allowed, uint64_t first, uint32_t count, uint64_t* out, hipStream_t s);
 
 // status[0] += the queries of a dense answer with count 0 (voided by exact_topk's overflow), ETS_VOIDED into status[3]
 hipError_t ers_voided(const uint32_t* counts, uint32_t np, uint32_t* status, hipStream_t s);

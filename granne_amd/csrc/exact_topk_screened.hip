@@ -49,7 +49,9 @@ struct EtsFloor {
 // COUNT: into the block's LDS histogram (hq: the query's column of it). COLLECT: into the query's candidate list.
 // ETS_BITS: `word` is the block's word of the query's bitmap -- rows e_blk .. e_blk + 31 are its bits 0 .. 31 -- and only
 // allowed rows are counted or collected. ETS_LIST: the rows are list positions; what is collected is the id at the position.
-template <int MODE, int SRC>
+// ROLLED (COLLECT): the hits are placed by one loop over the set bits, as ets_radius16 places its rows, not by sixteen
+// unrolled stores -- the 16 x 13 form over a list with its queries in the rows has no registers left for their addresses.
+template <int MODE, int SRC, bool ROLLED = false>
 __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
                                            bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq, uint32_t word) {
     const uint32_t wv = word >> (4u * h); // the lane's row v: bit 8 (v / 4) + v % 4 of it
@@ -78,6 +80,14 @@ __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F
         if (h == 0u && mine + other > 0u) base = atomicAdd(P.cnt + q, mine + other); // (hits: q is a live query)
         base = (uint32_t)__shfl((int)base, (int)col, 64);
         uint32_t pos = base + (h ? other : 0u); // the pair's lower lane first
+        if constexpr (ROLLED) {
+            static_assert(SRC == ETS_LIST, "the rolled placement reads the list");
+            for (uint32_t m = mask; m != 0u; m &= m - 1u, ++pos) {
+                const uint32_t v = (uint32_t)__builtin_ctz(m);
+                if (pos < ETS_CAP) P.cand[(size_t)q * ETS_CAP + pos] = P.list[e_blk + 8u * (v >> 2) + (v & 3u) + 4u * h];
+            }
+            return;
+        }
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             if (mask >> v & 1u) {
@@ -203,9 +213,11 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
     ets_b16x8 qh[KG], ql[KG]; // the lane's half of its query as bf16 pieces, in registers for the whole range
     {
         const float* qp;
-        if constexpr (QSRC == ETS_Q_ROWS)
-            qp = reinterpret_cast<const float*>(P.elements + (P.q_first + (qlive ? q : 0u)) * P.row_stride);
-        else
+        if constexpr (QSRC == ETS_Q_ROWS) { // ETS_LIST: P.q_first + q is a position of the list, as the scanned rows are
+            uint64_t id = P.q_first + (qlive ? q : 0u);
+            if constexpr (SRC == ETS_LIST) id = P.list[id];
+            qp = reinterpret_cast<const float*>(P.elements + id * P.row_stride);
+        } else
             qp = reinterpret_cast<const float*>(P.queries) + (size_t)(qlive ? q : 0u) * P.dim;
 #pragma unroll
         for (int g = 0; g < KG; ++g) {
@@ -312,7 +324,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
                 if constexpr (MODE == ETS_RADIUS)
                     ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
                 else
-                    ets_take16<MODE, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+                    ets_take16<MODE, SRC, MODE == ETS_COLLECT && SRC == ETS_LIST && QSRC == ETS_Q_ROWS && KG == 13>(
+                        P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
             }
         }
     }
@@ -353,7 +366,8 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
     ets_i32x4 qr[4]; // bytes 32 g + 16 h .. + 15 of the query (bf_i8_kernel's operand)
     float qinv = 0.0f;
     if constexpr (QSRC == ETS_Q_ROWS) {
-        const uint64_t id = P.q_first + (qlive ? q : 0u);
+        uint64_t id = P.q_first + (qlive ? q : 0u);
+        if constexpr (SRC == ETS_LIST) id = P.list[id]; // (a position of the list, as the scanned rows are)
         const uint8_t* qp = P.elements + id * P.row_stride;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -636,13 +650,21 @@ __global__ void ets_status_kernel(uint32_t* status, uint32_t routed, uint32_t fo
 }
 
 // ---- the handle's own rows as queries ----
-// ets_gather_kernel's sibling: the rows first + p, p = list[f] or p_base + f, dense for exact_topk's scan
+// ets_gather_kernel's sibling: the rows first + p, p = list[f] or p_base + f, dense for exact_topk's scan.
+// `allowed` (graph_filtered_host.h; null everywhere else, and in the three kernels below that take it): a filter's id list
+// -- first + p is then a POSITION of it, and the element is the id at that position.
+__device__ __forceinline__ uint64_t ets_element(const uint32_t* __restrict__ allowed, uint64_t x) { return allowed ? allowed[x] : x; }
 __global__ void ets_gather_rows_kernel(const uint8_t* __restrict__ elements, uint32_t row_stride, uint32_t qbytes, uint64_t first,
-                                       const uint32_t* __restrict__ list, uint32_t p_base, uint32_t m, uint8_t* __restrict__ out) {
+                                       const uint32_t* __restrict__ list, uint32_t p_base, uint32_t m, uint8_t* __restrict__ out,
+                                       const uint32_t* __restrict__ allowed) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)m * qbytes; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t f = (uint32_t)(i / qbytes), b = (uint32_t)(i - (uint64_t)f * qbytes);
-        out[i] = elements[(first + (list ? list[f] : p_base + f)) * row_stride + b];
+        out[i] = elements[ets_element(allowed, first + (list ? list[f] : p_base + f)) * row_stride + b];
     }
+}
+// the elements of the window [first, first + count) of a filter's id list, widened (granne_hip_*_graph_filtered's out_elements)
+__global__ void gf_elements_kernel(const uint32_t* __restrict__ allowed, uint64_t first, uint32_t count, uint64_t* __restrict__ out) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < count; p += gridDim.x * blockDim.x) out[p] = allowed[first + p];
 }
 // One block per row f of a scan with k + 1: element e = first + p among its own k + 1 nearest is dropped where it is listed
 // (at `at`, found by the block), the last entry where it is not (more than k bit-copies with smaller ids); the k entries,
@@ -650,11 +672,12 @@ __global__ void ets_gather_rows_kernel(const uint8_t* __restrict__ elements, uin
 __global__ __launch_bounds__(256) void kg_drop_self_kernel(uint64_t first, const uint32_t* __restrict__ list, uint32_t p_base, uint32_t k,
                                                            const uint64_t* __restrict__ ids, const float* __restrict__ dists,
                                                            const uint32_t* __restrict__ counts, uint64_t* __restrict__ out_ids,
-                                                           float* __restrict__ out_dists, uint32_t* __restrict__ out_counts) {
+                                                           float* __restrict__ out_dists, uint32_t* __restrict__ out_counts,
+                                                           const uint32_t* __restrict__ allowed) {
     __shared__ uint32_t at;
     const uint32_t f = blockIdx.x, tid = threadIdx.x;
     const size_t p = list ? list[f] : p_base + f;
-    const uint64_t e = first + p;
+    const uint64_t e = ets_element(allowed, first + p);
     const uint32_t c = counts[f] <= k + 1u ? counts[f] : k + 1u;
     const uint64_t* const in_ids = ids + (size_t)f * (k + 1u);
     const float* const in_dists = dists + (size_t)f * (k + 1u);
@@ -783,11 +806,11 @@ __global__ void ers_status_kernel(uint32_t* status, const uint32_t* xs, uint32_t
 // p_base + f, gets its id as the one candidate of dists_kernel -- d(e, e) in the reference's arithmetic -- and its radius
 // dense beside its gathered row.
 __global__ void rg_self_kernel(uint64_t first, const uint32_t* __restrict__ list, uint32_t p_base, uint32_t m, const float* __restrict__ radii,
-                               uint32_t* __restrict__ self_ids, float* __restrict__ out_radii) {
+                               uint32_t* __restrict__ self_ids, float* __restrict__ out_radii, const uint32_t* __restrict__ allowed) {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= m) return;
     const uint32_t p = list ? list[f] : p_base + f;
-    self_ids[f] = (uint32_t)(first + p);
+    self_ids[f] = (uint32_t)ets_element(allowed, first + p);
     out_radii[f] = radii[p];
 }
 // kg_drop_self_kernel's rule with a radius. One block per row f of exact_range's answer for cap + 1 ([m][cap + 1], counts,
@@ -800,11 +823,12 @@ __global__ __launch_bounds__(256) void rg_drop_self_kernel(uint64_t first, const
                                                            const uint32_t* __restrict__ counts, const uint32_t* __restrict__ totals,
                                                            const float* __restrict__ self, const float* __restrict__ radii,
                                                            uint64_t* __restrict__ out_ids, float* __restrict__ out_dists,
-                                                           uint32_t* __restrict__ out_counts, uint32_t* __restrict__ out_totals) {
+                                                           uint32_t* __restrict__ out_counts, uint32_t* __restrict__ out_totals,
+                                                           const uint32_t* __restrict__ allowed) {
     __shared__ uint32_t at;
     const uint32_t f = blockIdx.x, tid = threadIdx.x;
     const size_t p = list ? list[f] : p_base + f;
-    const uint64_t e = first + p;
+    const uint64_t e = ets_element(allowed, first + p);
     const uint32_t c = counts[f] <= cap + 1u ? counts[f] : cap + 1u;
     const uint64_t* const in_ids = ids + (size_t)f * (cap + 1u);
     const float* const in_dists = dists + (size_t)f * (cap + 1u);
@@ -828,15 +852,15 @@ __global__ __launch_bounds__(256) void rg_drop_self_kernel(uint64_t first, const
 
 // ---- launchers ----
 hipError_t rg_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, const float* radii, uint32_t* self_ids, float* out_radii,
-                   hipStream_t s) {
-    hipLaunchKernelGGL(rg_self_kernel, dim3((m + 255) / 256), dim3(256), 0, s, first, list, p_base, m, radii, self_ids, out_radii);
+                   hipStream_t s, const uint32_t* allowed) {
+    hipLaunchKernelGGL(rg_self_kernel, dim3((m + 255) / 256), dim3(256), 0, s, first, list, p_base, m, radii, self_ids, out_radii, allowed);
     return hipGetLastError();
 }
 hipError_t rg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t cap, const uint64_t* ids, const float* dists,
                         const uint32_t* counts, const uint32_t* totals, const float* self, const float* radii, uint64_t* out_ids, float* out_dists,
-                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s) {
+                        uint32_t* out_counts, uint32_t* out_totals, hipStream_t s, const uint32_t* allowed) {
     hipLaunchKernelGGL(rg_drop_self_kernel, dim3(m), dim3(256), 0, s, first, list, p_base, cap, ids, dists, counts, totals, self, radii, out_ids,
-                       out_dists, out_counts, out_totals);
+                       out_dists, out_counts, out_totals, allowed);
     return hipGetLastError();
 }
 hipError_t ers_radius(bool i8, const uint8_t* queries, const float* radii, uint32_t nq, uint32_t dim, float eps, float* lo, float* hi,
@@ -872,11 +896,11 @@ static uint32_t ets_grid(uint64_t work) {
 
 uint32_t ets_tile_rows(uint32_t form) { return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : ETS_I8_ROWS; }
 
-template <int MODE, int SRC>
+template <int MODE, int SRC, int QSRC = ETS_Q_DENSE>
 static EtsScanFn ets_scan_fn(uint32_t form, uint32_t* lds) {
-    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC>;
-    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC>;
-    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC>;
+    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC, QSRC>;
+    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC, QSRC>;
+    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC, QSRC>;
     return nullptr;
 }
 template <int MODE>
@@ -916,15 +940,27 @@ hipError_t ets_scan_rows(uint32_t form, bool collect, uint32_t tiles, uint32_t r
         lds = ets_i8_lds(mode), fn = collect ? ets_i8_kernel<ETS_COLLECT, ETS_ALL, ETS_Q_ROWS> : ets_i8_kernel<ETS_COUNT, ETS_ALL, ETS_Q_ROWS>;
     return ets_scan_launch(fn, lds, tiles, ranges, P, s);
 }
+// the nine instantiations of ETS_LIST with ETS_Q_ROWS (graph_filtered_host.h): the three forms here with
+// COUNT and COLLECT, with RADIUS in ets_scan_radius_rows_list
+hipError_t ets_scan_rows_list(uint32_t form, bool collect, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = collect ? ets_scan_fn<ETS_COLLECT, ETS_LIST, ETS_Q_ROWS>(form, &lds) : ets_scan_fn<ETS_COUNT, ETS_LIST, ETS_Q_ROWS>(form, &lds);
+    return P.list ? ets_scan_launch(fn, lds, tiles, ranges, P, s) : hipErrorInvalidValue;
+}
 hipError_t ets_gather_rows(const uint8_t* elements, uint32_t row_stride, uint32_t qbytes, uint64_t first, const uint32_t* list, uint32_t p_base,
-                           uint32_t m, uint8_t* out, hipStream_t s) {
+                           uint32_t m, uint8_t* out, hipStream_t s, const uint32_t* allowed) {
     hipLaunchKernelGGL(ets_gather_rows_kernel, dim3(ets_grid((uint64_t)m * qbytes)), dim3(256), 0, s, elements, row_stride, qbytes, first, list,
-                       p_base, m, out);
+                       p_base, m, out, allowed);
+    return hipGetLastError();
+}
+hipError_t gf_elements(const uint32_t* allowed, uint64_t first, uint32_t count, uint64_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(gf_elements_kernel, dim3(ets_grid(count)), dim3(256), 0, s, allowed, first, count, out);
     return hipGetLastError();
 }
 hipError_t kg_drop_self(uint64_t first, const uint32_t* list, uint32_t p_base, uint32_t m, uint32_t k, const uint64_t* ids, const float* dists,
-                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s) {
-    hipLaunchKernelGGL(kg_drop_self_kernel, dim3(m), dim3(256), 0, s, first, list, p_base, k, ids, dists, counts, out_ids, out_dists, out_counts);
+                        const uint32_t* counts, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, hipStream_t s, const uint32_t* allowed) {
+    hipLaunchKernelGGL(kg_drop_self_kernel, dim3(m), dim3(256), 0, s, first, list, p_base, k, ids, dists, counts, out_ids, out_dists, out_counts,
+                       allowed);
     return hipGetLastError();
 }
 hipError_t ets_scan_radius(uint32_t form, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
@@ -939,6 +975,11 @@ hipError_t ets_scan_radius_rows(uint32_t form, uint32_t tiles, uint32_t ranges, 
     else if (form == ETS_FORM_B16_13x2) lds = ets_b16_lds<13, 2>(ETS_RADIUS), fn = ets_b16_kernel<13, 2, ETS_RADIUS, ETS_ALL, ETS_Q_ROWS>;
     else if (form == ETS_FORM_I8) lds = ets_i8_lds(ETS_RADIUS), fn = ets_i8_kernel<ETS_RADIUS, ETS_ALL, ETS_Q_ROWS>;
     return ets_scan_launch(fn, lds, tiles, ranges, P, s);
+}
+hipError_t ets_scan_radius_rows_list(uint32_t form, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = ets_scan_fn<ETS_RADIUS, ETS_LIST, ETS_Q_ROWS>(form, &lds);
+    return P.list ? ets_scan_launch(fn, lds, tiles, ranges, P, s) : hipErrorInvalidValue;
 }
 hipError_t ets_clear(uint32_t* p, uint32_t n, hipStream_t s) {
     hipLaunchKernelGGL(ets_clear_kernel, dim3(1), dim3(64), 0, s, p, n);

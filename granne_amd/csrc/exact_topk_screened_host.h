@@ -74,7 +74,8 @@ static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_que
 // the handle's own rows first + p (p = d_list[f], or f where d_list is null; f < m) by exact_topk's scan with k + 1, the
 // row itself dropped (knn_graph_host.h)
 static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, uint32_t k, uint64_t* d_out_ids,
-                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_xs, hipStream_t s);
+                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_xs, hipStream_t s, const uint32_t* d_filter = nullptr,
+                      const uint32_t* d_allowed = nullptr);
 
 // The selection on stream s, arguments checked, nq > 0. Everything is ordered on s; the call waits on s once, after the
 // last round, for one word: the number of queries on the fallback list (and runs exact_topk's scan over them if any).
@@ -87,9 +88,15 @@ static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t
 // rows *own_first .. + nq - 1, d_queries and the filter are null, and the answer is every row's k nearest OTHER rows --
 // the scans read their queries where the rows lie and take the diagonal out (ETS_Q_ROWS), dists_kernel strides over the
 // rows, and what exact_topk's scan answers is asked for k + 1 and has the row itself dropped (kg_by_scan).
+// own_first WITH one shared bitmap (graph_filtered_host.h): the caller has compacted the bitmap already --
+// d_allowed is its id list of allowed_m >= 2 ids, nothing is compacted or read back here -- and the queries are the rows
+// at the list's POSITIONS *own_first .. + nq - 1 (within allowed_m): the scans run over the list with their queries read
+// through it (ETS_LIST with ETS_Q_ROWS, the diagonal a compare of positions), dists_kernel gets the round's query rows
+// gathered dense, and kg_by_scan runs under the filter and drops the id at the position.
 static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
                                    float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s,
-                                   const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0, const uint64_t* own_first = nullptr) {
+                                   const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0, const uint64_t* own_first = nullptr,
+                                   const uint32_t* d_allowed = nullptr, uint64_t allowed_m = 0) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
     if (const int rc = ets_form(ix, s, &form)) return rc;
@@ -108,7 +115,8 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     const size_t o_keys = o_dist + (size_t)qc_max * ET_CAP * 4;
     // ETS_LIST: the list's length (u64), the compaction's block counts, the list
     const size_t o_m = o_keys + (size_t)qc_max * ET_CAP * 8, o_blk = o_m + 256, o_list = o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
-    const size_t total = form == ETS_FORM_ROUTED ? 256 : list ? o_list + (size_t)n * 4 : o_m;
+    // (the caller's list: a round's query rows, dense for dists_kernel, where the compaction's words would be)
+    const size_t total = form == ETS_FORM_ROUTED ? 256 : d_allowed ? o_m + up((size_t)qc_max * qbytes) : list ? o_list + (size_t)n * 4 : o_m;
     uint8_t* scratch = nullptr;
     HIP_TRY(hipMallocAsync((void**)&scratch, total, s));
     struct Release {
@@ -122,13 +130,14 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     HIP_TRY(ets_clear(xs, 8u, s)); // words 0..3: xs; word 4 (o_fbn = 16 bytes): the fallback count
     if (form == ETS_FORM_ROUTED) {
         if (own_first) {
-            if (const int rc = kg_by_scan(ix, *own_first, nullptr, nq, k, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+            if (const int rc = kg_by_scan(ix, *own_first, nullptr, nq, k, d_out_ids, d_out_dists, d_out_counts, xs, s, d_filter, d_allowed)) return rc;
         } else if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s))
             return rc;
         if (d_status) HIP_TRY(ets_status(d_status, nq, (uint32_t)ETS_FORM_ROUTED, xs, s));
         return GRANNE_HIP_OK;
     }
-    if (list) {
+    if (d_allowed) n = allowed_m;
+    else if (list) {
         if (const int rc = filter_compact<uint32_t>(d_filter, n, (uint32_t*)(scratch + o_blk), (uint32_t*)(scratch + o_list),
                                                     (uint64_t*)(scratch + o_m), nullptr, s))
             return rc;
@@ -170,7 +179,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     P.cnt = (uint32_t*)(scratch + o_cnt);
     P.cand = (uint32_t*)(scratch + o_cand);
     P.eps2 = 2.0f * ets_epsilon(i8, ix->dim);
-    P.list = list ? (const uint32_t*)(scratch + o_list) : nullptr;
+    P.list = d_allowed ? d_allowed : list ? (const uint32_t*)(scratch + o_list) : nullptr;
     P.filter_stride = filter_stride_words;
     uint32_t* const fb_count = (uint32_t*)(scratch + o_fbn);
     uint32_t* const fb_list = (uint32_t*)(scratch + o_fbl);
@@ -191,7 +200,9 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
             if (G < 1) G = 1;
             P.n = rows;
             P.per_range = ((rows + G - 1) / G + tile - 1) / tile * tile;
-            HIP_TRY(own_first ? ets_scan_rows(form, collect, tiles, (uint32_t)G, P, s) : ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s));
+            HIP_TRY(!own_first  ? ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s)
+                    : d_allowed ? ets_scan_rows_list(form, collect, tiles, (uint32_t)G, P, s)
+                                : ets_scan_rows(form, collect, tiles, (uint32_t)G, P, s));
             return GRANNE_HIP_OK;
         };
         HIP_TRY(ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
@@ -202,9 +213,13 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
         if (const int rc = pass(true, n)) return rc;
         // the survivors' distances in the reference's arithmetic, then exact_topk's ranking by (distance bits, id)
         HIP_TRY(ets_pad(P.cand, P.cnt, P.lo, qc, c0, (uint32_t*)(scratch + o_sel), fb_count, fb_list, d_status, s));
-        const uint8_t* const dq = own_first ? P.elements + P.q_first * ix->row_stride : P.queries; // (a row is a prepared query)
+        const uint8_t* dq = own_first ? P.elements + P.q_first * ix->row_stride : P.queries; // (a row is a prepared query)
+        if (own_first && d_allowed) { // the rows at the round's positions lie apart: gathered, as kg_by_scan gathers them
+            HIP_TRY(ets_gather_rows(P.elements, ix->row_stride, (uint32_t)qbytes, P.q_first, nullptr, 0u, qc, scratch + o_m, s, d_allowed));
+            dq = scratch + o_m;
+        }
         if (const int rc = dists_launch(ix, dq, nullptr, ET_CAP, P.cand, (uint64_t)qc * ET_CAP, (float*)(scratch + o_dist), nullptr, s,
-                                        own_first ? ix->row_stride : 0u))
+                                        own_first && !d_allowed ? ix->row_stride : 0u))
             return rc;
         HIP_TRY(ets_keys(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, (uint64_t*)(scratch + o_keys), s));
         hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_keys), (const uint32_t*)P.cnt,
@@ -218,7 +233,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     HIP_TRY(hipStreamSynchronize(s));
     if (nfb == 0) return GRANNE_HIP_OK;
     if (own_first) {
-        if (const int rc = kg_by_scan(ix, *own_first, fb_list, nfb, k, d_out_ids, d_out_dists, d_out_counts, xs, s)) return rc;
+        if (const int rc = kg_by_scan(ix, *own_first, fb_list, nfb, k, d_out_ids, d_out_dists, d_out_counts, xs, s, d_filter, d_allowed)) return rc;
         if (d_status) HIP_TRY(ets_status(d_status, 0u, form, xs, s)); // (ETS_VOIDED where exact_topk voided one of them)
         return GRANNE_HIP_OK;
     }

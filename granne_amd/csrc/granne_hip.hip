@@ -2496,3 +2496,4 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 #include "exact_range_screened_host.h"
 #include "knn_graph_host.h"
 #include "range_graph_host.h"
+#include "graph_filtered_host.h"

@@ -22,9 +22,11 @@ static int knn_graph_args(const granne_hip_index* ix, uint64_t first, uint64_t c
 
 // The rows first + p (p = d_list[f], or f where d_list is null; f < m) answered by exact_topk's own scan: gathered as dense
 // queries a round of ET_CHUNK at a time, asked for k + 1, and the row itself dropped on the way to place p of the outputs
-// (kg_drop_self_kernel). d_xs: exact_topk's status words.
+// (kg_drop_self_kernel). d_xs: exact_topk's status words. d_filter with d_allowed, its id list (graph_filtered_host.h): the
+// rows are the ids at the list's positions first + p, and the scan runs under the filter.
 static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, uint32_t k, uint64_t* d_out_ids,
-                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_xs, hipStream_t s) {
+                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_xs, hipStream_t s, const uint32_t* d_filter,
+                      const uint32_t* d_allowed) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const uint32_t qbytes = ix->dim * query_elem_size(ix->dtype);
     const uint32_t mc_max = m < ET_CHUNK ? m : ET_CHUNK, k1 = k + 1u;
@@ -39,11 +41,11 @@ static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t
     for (uint32_t c0 = 0; c0 < m; c0 += ET_CHUNK) {
         const uint32_t mc = m - c0 < ET_CHUNK ? m - c0 : ET_CHUNK;
         const uint32_t* const list = d_list ? d_list + c0 : nullptr;
-        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, list, c0, mc, buf, s));
-        if (const int rc = exact_topk_run(ix, buf, mc, k1, nullptr, 0, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), d_xs, s))
+        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, list, c0, mc, buf, s, d_allowed));
+        if (const int rc = exact_topk_run(ix, buf, mc, k1, d_filter, 0, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), d_xs, s))
             return rc;
         HIP_TRY(kg_drop_self(first, list, c0, mc, k, (const uint64_t*)(buf + o_ids), (const float*)(buf + o_d), (const uint32_t*)(buf + o_c), d_out_ids,
-                             d_out_dists, d_out_counts, s));
+                             d_out_dists, d_out_counts, s, d_allowed));
     }
     return GRANNE_HIP_OK;
 }

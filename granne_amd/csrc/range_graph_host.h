@@ -37,9 +37,12 @@ static int range_graph_args(const granne_hip_index* ix, uint64_t first, uint64_t
 
 // Path C: the elements first + p (p = d_list[f], or f where d_list is null; f < m) by exact_range's own scan, a round of
 // ET_CHUNK at a time: rows and radii gathered, d(e, e) from dists_kernel, the answer for cap + 1, the element struck out on
-// the way to place p of the outputs. d_radii: the call's, by place. d_xs: exact_range's status words.
+// the way to place p of the outputs. d_radii: the call's, by place. d_xs: exact_range's status words. d_filter with
+// d_allowed, its id list (graph_filtered_host.h): the elements are the ids at the list's positions first + p, the scan runs
+// under the filter -- which allows the element, so it is counted exactly when d(e, e) <= r, as without one.
 static int rg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, const float* d_radii, uint32_t cap,
-                      uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_xs, hipStream_t s) {
+                      uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_xs, hipStream_t s,
+                      const uint32_t* d_filter = nullptr, const uint32_t* d_allowed = nullptr) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const uint32_t qbytes = ix->dim * query_elem_size(ix->dtype);
     const uint32_t mc_max = m < ET_CHUNK ? m : ET_CHUNK, cap1 = cap + 1u;
@@ -51,24 +54,26 @@ static int rg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t
     for (uint32_t c0 = 0; c0 < m; c0 += ET_CHUNK) {
         const uint32_t mc = m - c0 < ET_CHUNK ? m - c0 : ET_CHUNK;
         const uint32_t* const list = d_list ? d_list + c0 : nullptr;
-        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, list, c0, mc, buf, s));
-        HIP_TRY(rg_self(first, list, c0, mc, d_radii, (uint32_t*)(buf + o_sid), (float*)(buf + o_r), s));
+        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, list, c0, mc, buf, s, d_allowed));
+        HIP_TRY(rg_self(first, list, c0, mc, d_radii, (uint32_t*)(buf + o_sid), (float*)(buf + o_r), s, d_allowed));
         if (const int rc = dists_launch(ix, buf, nullptr, 1u, (const uint32_t*)(buf + o_sid), mc, (float*)(buf + o_self), nullptr, s)) return rc;
-        if (const int rc = exact_range_run(ix, buf, mc, (const float*)(buf + o_r), cap1, nullptr, 0, (uint64_t*)(buf + o_ids), (float*)(buf + o_d),
+        if (const int rc = exact_range_run(ix, buf, mc, (const float*)(buf + o_r), cap1, d_filter, 0, (uint64_t*)(buf + o_ids), (float*)(buf + o_d),
                                            (uint32_t*)(buf + o_c), (uint32_t*)(buf + o_t), d_xs, s))
             return rc;
         HIP_TRY(rg_drop_self(first, list, c0, mc, cap, (const uint64_t*)(buf + o_ids), (const float*)(buf + o_d), (const uint32_t*)(buf + o_c),
                              (const uint32_t*)(buf + o_t), (const float*)(buf + o_self), (const float*)(buf + o_r), d_out_ids, d_out_dists,
-                             d_out_counts, d_out_totals, s));
+                             d_out_counts, d_out_totals, s, d_allowed));
     }
     return GRANNE_HIP_OK;
 }
 
 // Path B: the elements first + d_list[f], f < m, whose totals the pass has made: their cap nearest others by the screened
 // selection over their gathered rows with k = cap + 1, the element dropped (kg_drop_self). An answer of count 0 is an
-// element voided by exact_topk's overflow.
+// element voided by exact_topk's overflow. d_filter, d_allowed: as rg_by_scan's -- the selection is then the screened
+// filtered one.
 static int rg_by_topk(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, uint32_t cap, uint64_t* d_out_ids,
-                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s) {
+                      float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s, const uint32_t* d_filter = nullptr,
+                      const uint32_t* d_allowed = nullptr) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const uint32_t qbytes = ix->dim * query_elem_size(ix->dtype);
     const uint32_t mc_max = m < ET_CHUNK ? m : ET_CHUNK, cap1 = cap + 1u;
@@ -78,19 +83,26 @@ static int rg_by_topk(const granne_hip_index* ix, uint64_t first, const uint32_t
     uint8_t* const buf = mem.as<uint8_t>();
     for (uint32_t c0 = 0; c0 < m; c0 += ET_CHUNK) {
         const uint32_t mc = m - c0 < ET_CHUNK ? m - c0 : ET_CHUNK;
-        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, d_list + c0, c0, mc, buf, s));
-        if (const int rc = exact_topk_screened_run(ix, buf, mc, cap1, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), nullptr, s))
+        HIP_TRY(ets_gather_rows(ix->d_elements.as<uint8_t>(), ix->row_stride, qbytes, first, d_list + c0, c0, mc, buf, s, d_allowed));
+        if (const int rc = exact_topk_screened_run(ix, buf, mc, cap1, (uint64_t*)(buf + o_ids), (float*)(buf + o_d), (uint32_t*)(buf + o_c), nullptr, s,
+                                                   d_filter))
             return rc;
         HIP_TRY(kg_drop_self(first, d_list + c0, c0, mc, cap, (const uint64_t*)(buf + o_ids), (const float*)(buf + o_d), (const uint32_t*)(buf + o_c),
-                             d_out_ids, d_out_dists, d_out_counts, s));
+                             d_out_ids, d_out_dists, d_out_counts, s, d_allowed));
         if (d_status) HIP_TRY(ers_voided((const uint32_t*)(buf + o_c), mc, d_status, s));
     }
     return GRANNE_HIP_OK;
 }
 
 // The call on stream s, arguments checked, nq = count > 0. d_radii: one per element of the window. d_status optional.
+// d_filter (graph_filtered_host.h; null: all rows, and nothing below differs): one shared bitmap that the
+// caller has compacted -- d_allowed is its id list of allowed_m >= 2 ids -- and the window is the list's POSITIONS first ..
+// first + nq - 1 (within allowed_m): the pass scans the list with its queries read through it (ETS_LIST with ETS_Q_ROWS,
+// the diagonal a compare of positions), the listed positions become ids in ers_pad, dists_kernel gets the round's query
+// rows gathered dense, and paths B and C run under the filter and strike out the id at the position.
 static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t nq, const float* d_radii, uint32_t cap, uint64_t* d_out_ids,
-                           float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_status, hipStream_t s) {
+                           float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_status, hipStream_t s,
+                           const uint32_t* d_filter = nullptr, const uint32_t* d_allowed = nullptr, uint64_t allowed_m = 0) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
     if (const int rc = ets_form(ix, s, &form)) return rc;
@@ -100,20 +112,23 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
         PfStreamMem xs;
         HIP_TRY(xs.alloc(16, s));
         HIP_TRY(ets_clear(xs.as<uint32_t>(), 4u, s));
-        if (const int rc = rg_by_scan(ix, first, nullptr, nq, d_radii, cap, d_out_ids, d_out_dists, d_out_counts, d_out_totals, xs.as<uint32_t>(), s))
+        if (const int rc = rg_by_scan(ix, first, nullptr, nq, d_radii, cap, d_out_ids, d_out_dists, d_out_counts, d_out_totals, xs.as<uint32_t>(), s,
+                                      d_filter, d_allowed))
             return rc;
         if (d_status) HIP_TRY(ers_status(d_status, xs.as<uint32_t>(), nq, (uint32_t)ETS_FORM_ROUTED, s));
         return GRANNE_HIP_OK;
     }
-    const uint64_t n = ix->n_elements;
+    const uint64_t n = d_allowed ? allowed_m : ix->n_elements; // the rows, or the list's positions, the pass scans
     const uint32_t qc_max = nq < ET_CHUNK ? nq : ET_CHUNK;
+    const uint32_t qbytes = ix->dim * query_elem_size(ix->dtype);
     // scratch as exact_range_screened_run's: the numbers of B and C elements and er_rank_kernel's bitmap over the window
     // (cleared together); the two lists; a round's thresholds, counters and totals, its id lists [qc][2][ET_CAP], their
     // distances, the keys
     const size_t o_n = 0, o_dense = 256, o_lb = o_dense + up((size_t)filter_words(nq) * 4), o_lc = o_lb + up((size_t)nq * 4);
     const size_t o_lo = o_lc + up((size_t)nq * 4), w = up((size_t)qc_max * 4), o_hi = o_lo + w, o_sure = o_hi + w, o_cnt = o_sure + w;
     const size_t o_bcnt = o_cnt + w, o_tot = o_bcnt + w, o_cand = o_tot + w, o_dist = o_cand + (size_t)qc_max * 2 * ET_CAP * 4;
-    const size_t o_keys = o_dist + (size_t)qc_max * 2 * ET_CAP * 4, total = o_keys + (size_t)qc_max * ET_CAP * 8;
+    const size_t o_keys = o_dist + (size_t)qc_max * 2 * ET_CAP * 4, o_q = o_keys + (size_t)qc_max * ET_CAP * 8;
+    const size_t total = o_q + (d_allowed ? (size_t)qc_max * qbytes : 0); // (a list: a round's query rows, dense)
     PfStreamMem mem;
     HIP_TRY(mem.alloc(total, s));
     uint8_t* const scratch = mem.as<uint8_t>();
@@ -129,7 +144,7 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
     P.dim = ix->dim;
     P.queries = nullptr;
     P.inv_norm = i8 ? ix->d_inv_norm.as<float>() : nullptr;
-    P.inv_gmax = i8 ? P.inv_norm + ((n + 31u) & ~31ull) : nullptr;
+    P.inv_gmax = i8 ? P.inv_norm + ((ix->n_elements + 31u) & ~31ull) : nullptr;
     P.lo = (const float*)(scratch + o_lo);
     P.hi = (const float*)(scratch + o_hi);
     P.hist = nullptr;
@@ -138,6 +153,7 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
     P.bcnt = (uint32_t*)(scratch + o_bcnt);
     P.cand = (uint32_t*)(scratch + o_cand);
     P.eps2 = 0.0f;
+    P.list = d_allowed;
     const ErsLists lists{(uint32_t*)(scratch + o_n), (uint32_t*)(scratch + o_lb), (uint32_t*)(scratch + o_lc)};
     float* const dist = (float*)(scratch + o_dist);
     uint64_t* const keys = (uint64_t*)(scratch + o_keys);
@@ -155,11 +171,17 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
         P.per_range = ((n + G - 1) / G + tile - 1) / tile * tile;
         HIP_TRY(ers_radius(i8, nullptr, d_radii + c0, qc, ix->dim, ets_epsilon(i8, ix->dim), (float*)(scratch + o_lo), (float*)(scratch + o_hi),
                            P.sure, P.cnt, P.bcnt, s));
-        HIP_TRY(ets_scan_radius_rows(form, tiles, (uint32_t)G, P, s));
-        HIP_TRY(ers_pad(P.cand, P.sure, P.bcnt, nullptr, qc, s));
-        // the listed rows' distances in the reference's arithmetic, the queries read where the rows lie
-        if (const int rc = dists_launch(ix, P.elements + P.q_first * ix->row_stride, nullptr, 2u * ET_CAP, P.cand, (uint64_t)qc * 2u * ET_CAP, dist,
-                                        nullptr, s, ix->row_stride))
+        HIP_TRY(d_allowed ? ets_scan_radius_rows_list(form, tiles, (uint32_t)G, P, s) : ets_scan_radius_rows(form, tiles, (uint32_t)G, P, s));
+        HIP_TRY(ers_pad(P.cand, P.sure, P.bcnt, P.list, qc, s));
+        // the listed rows' distances in the reference's arithmetic, the queries read where the rows lie (a list: they lie
+        // apart, and are gathered as rg_by_scan gathers them)
+        const uint8_t* dq = P.elements + P.q_first * ix->row_stride;
+        if (d_allowed) {
+            HIP_TRY(ets_gather_rows(P.elements, ix->row_stride, qbytes, P.q_first, nullptr, 0u, qc, scratch + o_q, s, d_allowed));
+            dq = scratch + o_q;
+        }
+        if (const int rc = dists_launch(ix, dq, nullptr, 2u * ET_CAP, P.cand, (uint64_t)qc * 2u * ET_CAP, dist, nullptr, s,
+                                        d_allowed ? 0u : ix->row_stride))
             return rc;
         HIP_TRY(ers_keys(P.cand, dist, d_radii + c0, P.lo, P.hi, P.sure, P.bcnt, qc, c0, keys, (uint32_t*)(scratch + o_tot), lists, d_status, s));
         hipLaunchKernelGGL(er_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)keys, (const uint32_t*)(scratch + o_tot), c0, cap,
@@ -171,11 +193,14 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
     HIP_TRY(hipMemcpyAsync(np, lists.n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s)); // the entry's one wait of its own
     if (np[0]) // path B; er_rank_kernel has written the totals
-        if (const int rc = rg_by_topk(ix, first, lists.b, np[0], cap, d_out_ids, d_out_dists, d_out_counts, d_status, s)) return rc;
+        if (const int rc = rg_by_topk(ix, first, lists.b, np[0], cap, d_out_ids, d_out_dists, d_out_counts, d_status, s, d_filter, d_allowed))
+            return rc;
     if (np[1]) { // path C, totals included
         uint32_t* const xs = (uint32_t*)(scratch + o_lo); // (the rounds are over: their thresholds' place)
         HIP_TRY(ets_clear(xs, 4u, s));
-        if (const int rc = rg_by_scan(ix, first, lists.c, np[1], d_radii, cap, d_out_ids, d_out_dists, d_out_counts, d_out_totals, xs, s)) return rc;
+        if (const int rc = rg_by_scan(ix, first, lists.c, np[1], d_radii, cap, d_out_ids, d_out_dists, d_out_counts, d_out_totals, xs, s, d_filter,
+                                      d_allowed))
+            return rc;
         if (d_status) HIP_TRY(ers_status(d_status, xs, 0u, 0u, s));
     }
     return GRANNE_HIP_OK;

@@ -814,6 +814,83 @@ class Granne:
             raise GranneHipError(ERR_OVERFLOW, "range_graph: exact_topk's selection overflowed for an element handed to it")
         return out
 
+    def knn_graph_filtered_device(self, d_filter, first, count, k, d_elements, d_ids, d_dists, d_counts, d_status=0, stream=0):
+        """knn_graph of the subset one shared bitmap allows, for the positions first .. first + count - 1 of its ascending id
+        list (granne_hip_knn_graph_filtered_device). Raw device pointers (int; d_filter e.g. a Filter's `ptr` over
+        num_elements() ids; d_elements: u64[count]; d_status: u32[4] zeroed by the caller, or 0); ordered on `stream`, which
+        the call waits on at its start and its end."""
+        check(lib().granne_hip_knn_graph_filtered_device(self._h, C.c_void_p(d_filter), int(first), int(count), int(k),
+                                                         C.c_void_p(d_elements), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                                         C.c_void_p(d_counts), C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def range_graph_filtered_device(self, d_filter, first, count, d_radii, cap, d_elements, d_ids, d_dists, d_counts, d_totals,
+                                    d_status=0, stream=0):
+        """range_graph of the subset one shared bitmap allows (granne_hip_range_graph_filtered_device); the window and the
+        pointers as knn_graph_filtered_device's, d_radii: f32[count]."""
+        check(lib().granne_hip_range_graph_filtered_device(self._h, C.c_void_p(d_filter), int(first), int(count), C.c_void_p(d_radii),
+                                                           int(cap), C.c_void_p(d_elements), C.c_void_p(d_ids), C.c_void_p(d_dists),
+                                                           C.c_void_p(d_counts), C.c_void_p(d_totals), C.c_void_p(d_status),
+                                                           C.c_void_p(stream)))
+
+    def _graph_filtered(self, allowed, first, count, width, radius):
+        """the two subset graphs' host convenience: (elements, ids, dists, counts[, totals]), the status words"""
+        import torch
+        owner, fptr, stride = self._filter_arg(allowed, 1, self.num_elements())
+        if stride:
+            raise ValueError("allowed: one shared filter")
+        first, width = int(first), int(width)
+        count = owner.count() - first if count is None else int(count)
+        shape = max(count, 0)
+        dev = torch.device("cuda", self.device)
+        el = torch.empty(shape, dtype=torch.int64, device=dev)
+        ids = torch.empty((shape, max(width, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((shape, max(width, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(shape, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        if radius is None:
+            tot = None
+            self.knn_graph_filtered_device(fptr, first, count, width, el.data_ptr(), ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(),
+                                           st.data_ptr(), stream)
+        else:
+            d_r = torch.from_numpy(np.array(np.broadcast_to(np.asarray(radius, dtype=np.float32), (shape,)))).to(dev)
+            tot = torch.empty(shape, dtype=torch.int32, device=dev)
+            self.range_graph_filtered_device(fptr, first, count, d_r.data_ptr(), width, el.data_ptr(), ids.data_ptr(), ds.data_ptr(),
+                                             cnt.data_ptr(), tot.data_ptr(), st.data_ptr(), stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        out = (el.cpu().numpy().astype(np.uint64), ids.cpu().numpy().astype(np.uint64), ds.cpu().numpy(),
+               cnt.cpu().numpy().astype(np.uint32))
+        if tot is not None:
+            out += (tot.cpu().numpy().astype(np.uint32),)
+        return out, st.cpu().numpy().astype(np.uint32)
+
+    def knn_graph_filtered(self, k, allowed, first=0, count=None, stats=False):
+        """`knn_graph` of a subset: `allowed` (whatever `exact_topk_screened_filtered` takes for one shared filter) has the
+        ascending id list A; for the positions first .. first + count - 1 of A (count=None: to its end) the first k of all
+        OTHER allowed elements by (distance bits, id) -- `exact_topk_filtered(get_element(e), k + 1, allowed)` with e left
+        out. Returns elements [count] u64 (A[first + p]), then `knn_graph`'s returns with counts min(k, len(A) - 1); ids
+        are the index's own. No copy of the subset's rows is made."""
+        out, status = self._graph_filtered(allowed, first, count, k, None)
+        if stats:
+            return out + (status,)
+        if status[3] & 0x80000000:
+            raise GranneHipError(ERR_OVERFLOW, "knn_graph_filtered: exact_topk's selection overflowed for an element handed to it")
+        return out
+
+    def range_graph_filtered(self, radius, allowed, max_results=1024, first=0, count=None, stats=False):
+        """`range_graph` of a subset, the window and `allowed` as `knn_graph_filtered`'s: for each element e = A[first + p] the
+        OTHER allowed elements within `radius` (a scalar, or one value per position of the window) --
+        `exact_range(get_element(e), r, max_results + 1, allowed)` with e struck out. Returns elements [count] u64, then
+        `range_graph`'s returns."""
+        out, status = self._graph_filtered(allowed, first, count, max_results, radius)
+        if stats:
+            return out + (status,)
+        if status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "range_graph_filtered: exact_topk's selection overflowed for an element handed to it")
+        return out
+
     def num_elements(self):
         """Rows of the element set (at least len()): what exact_topk and exact_topk_filtered scan."""
         return int(lib().granne_hip_index_num_elements(self._h))

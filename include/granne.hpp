@@ -432,6 +432,29 @@ public:
         return out;
     }
 
+    // The two graphs of a subset (granne_hip_knn_graph_filtered_device, granne_hip_range_graph_filtered_device): `allowed`
+    // (over num_elements() ids) has the ascending id list A; for the positions [first, first + count) of A, element
+    // A[first + p] -- written to `elements` -- gets its k nearest OTHER allowed elements, respectively the OTHER allowed
+    // elements within its radius, as knn_graph and range_graph give them for all elements. Ids are the index's own; no copy
+    // of the subset's rows is made. first + count beyond A throws.
+    std::vector<std::vector<std::pair<size_t, float>>> knn_graph_filtered(size_t k, const Filter& allowed, size_t first, size_t count,
+                                                                          std::vector<uint64_t>* elements = nullptr,
+                                                                          std::vector<uint32_t>* status = nullptr) const {
+        return graph_filtered(nullptr, k, allowed, first, count, elements, nullptr, status);
+    }
+    std::vector<std::vector<std::pair<size_t, float>>> range_graph_filtered(const std::vector<float>& radii, size_t max_results,
+                                                                            const Filter& allowed, size_t first, size_t count,
+                                                                            std::vector<uint64_t>* elements = nullptr,
+                                                                            std::vector<uint32_t>* totals = nullptr,
+                                                                            std::vector<uint32_t>* status = nullptr) const {
+        if (radii.size() != count && radii.size() != 1) throw std::invalid_argument("range_graph_filtered: one radius, or one per element");
+        const std::vector<float> r = radii.size() == count ? radii : std::vector<float>(count, radii[0]);
+        std::vector<uint32_t> tot;
+        auto out = graph_filtered(&r, max_results, allowed, first, count, elements, &tot, status);
+        if (totals) *totals = tot;
+        return out;
+    }
+
     // exact_topk among the ids `allowed` lets through (granne_hip_exact_topk_filtered_device; one bitmap for all queries,
     // over num_elements() ids): the scan walks the bitmap's id list -- the tool for a selective filter, where
     // search_filtered steps over many disallowed nodes per allowed one. A result holds fewer than k ids when fewer are allowed.
@@ -735,6 +758,46 @@ private:
         if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error(overflow);
         for (size_t i = 0; i < nq; ++i)
             for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * cap + j], ds[i * cap + j]);
+        return out;
+    }
+    // knn_graph_filtered (radii null: `width` is k) and range_graph_filtered (`width` is the cap) on device buffers
+    std::vector<std::vector<std::pair<size_t, float>>> graph_filtered(const std::vector<float>* radii, size_t width, const Filter& allowed,
+                                                                      size_t first, size_t count, std::vector<uint64_t>* elements,
+                                                                      std::vector<uint32_t>* totals, std::vector<uint32_t>* status) const {
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed.len() != num_elements() || allowed.device() != device)
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        const size_t o_ids = count * 8, o_d = o_ids + count * width * 8, o_c = o_d + count * width * 4, o_t = o_c + count * 4;
+        const size_t o_st = o_t + count * 4, total = o_st + 16;
+        detail::DeviceMem d_r(count * 4 + 16, device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        if (radii) d_r.upload(radii->data(), count * 4);
+        d_out.upload(host.data(), total);
+        char* const o = (char*)d_out.get();
+        const int rc =
+            radii ? granne_hip_range_graph_filtered_device(h_.get(), allowed.words(), first, count, (const float*)d_r.get(), (uint32_t)width,
+                                                           (uint64_t*)o, (uint64_t*)(o + o_ids), (float*)(o + o_d), (uint32_t*)(o + o_c),
+                                                           (uint32_t*)(o + o_t), (uint32_t*)(o + o_st), nullptr)
+                  : granne_hip_knn_graph_filtered_device(h_.get(), allowed.words(), first, count, (uint32_t)width, (uint64_t*)o,
+                                                         (uint64_t*)(o + o_ids), (float*)(o + o_d), (uint32_t*)(o + o_c), (uint32_t*)(o + o_st),
+                                                         nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(count);
+        if (count == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* el = (const uint64_t*)host.data();
+        const uint64_t* ids = (const uint64_t*)(host.data() + o_ids);
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        const uint32_t* st = (const uint32_t*)(host.data() + o_st);
+        if (elements) elements->assign(el, el + count);
+        if (totals) totals->assign((const uint32_t*)(host.data() + o_t), (const uint32_t*)(host.data() + o_t) + count);
+        if (status) status->assign(st, st + 4);
+        if (radii ? st[0] != 0u : (st[3] & 0x80000000u) != 0u)
+            throw std::runtime_error("graph of a subset: exact_topk's selection overflowed for an element handed to it");
+        for (size_t i = 0; i < count; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * width + j], ds[i * width + j]);
         return out;
     }
     std::shared_ptr<granne_hip_index> h_;

@@ -527,6 +527,52 @@ int granne_hip_range_graph(const granne_hip_index* index, uint64_t first, uint64
                            uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_totals,
                            uint32_t* out_status /* optional */);
 
+/* The two graphs of a SUBSET: every allowed element's exact neighbours among the allowed elements, under one shared id
+ * bitmap over the handle's ids (ceil(n_elements / 32) u32 words, bit i of word i / 32 for id i: a granne_hip_filter's).
+ * The model:
+ *   A          the ascending list of the allowed ids, m = |A|
+ *   window     a range of POSITIONS of A, [first, first + count); output row p belongs to element e = A[first + p], and
+ *              out_elements[p] = e
+ *   knn        row p: the first k of all allowed j != e by (distance bits of dist(element e, element j), j); counts[p] =
+ *              min(k, m - 1); unused places hold UINT64_MAX and +inf, as granne_hip_knn_graph pads them. Equivalently
+ *              granne_hip_exact_topk_filtered(row e, k + 1, the bitmap) with e dropped where it is listed and the last
+ *              entry dropped where it is not (more than k allowed bit-copies of e with smaller ids). k in [1, 1023].
+ *   range      row p, radius r = radii[p]: granne_hip_exact_range(row e, r, cap + 1, the bitmap) with e struck out --
+ *              totals[p] is one less exactly where dist(e, e) <= r in the reference's arithmetic, and exact however large;
+ *              the listing is the first min(total, cap) by (distance bits, id). cap in [1, GRANNE_HIP_RANGE_CAP_MAX].
+ * m is read back once, at the start of the call (the bitmap is compacted by granne_hip_filter_to_ids_device's kernels):
+ * first + count > m is refused, naming the three numbers; count == 0 does nothing; m == 1 gives count and total 0.
+ *   screened   handles that granne_hip_exact_topk_screened screens: its scans over the positions of A, the queries read
+ *              from the rows A[first + p] where they lie, the score of a row with itself found by comparing POSITIONS and
+ *              taken out before the floor, the histogram, the candidate list or a count sees it. No second
+ *              copy of the subset's rows is made, and the ids written are the handle's.
+ *   fallback   knn: an element with more than GRANNE_HIP_EXACT_TOPK_CAP survivors, or a routed handle (f32 beyond 208
+ *              components or off the proven norm bound, int8 beyond 128), by granne_hip_exact_topk_filtered_device with
+ *              k + 1 over the gathered rows. range: paths B and C of granne_hip_range_graph, under the bitmap.
+ *   d_status   u32[4], optional, zeroed by the caller: granne_hip_knn_graph's words, respectively granne_hip_range_graph's.
+ * Refused (GRANNE_HIP_ERR_INVALID, the message naming knn_graph_filtered or range_graph_filtered): a null index, null
+ * buffers or filter, k or cap out of range, a window beyond A, GRANNE_HIP_F16 and compact SumEmbeddings handles.
+ * Stream-ordered; the calls wait on `stream` as granne_hip_knn_graph and granne_hip_range_graph do, and once more at their
+ * start. Scratch from hipMallocAsync: theirs, and 4 bytes per element of the handle for A. */
+int granne_hip_knn_graph_filtered_device(const granne_hip_index* index, const uint32_t* d_filter, uint64_t first, uint64_t count,
+                                         uint32_t k, uint64_t* d_out_elements, uint64_t* d_out_ids, float* d_out_dists,
+                                         uint32_t* d_out_counts, uint32_t* d_status /* u32[4], optional, zeroed by the caller */,
+                                         void* stream);
+/* the same with host buffers in and out (synchronous). GRANNE_HIP_ERR_OVERFLOW when bit 31 of status[3] is set: the outputs
+ * (and out_status, optional) are still written. */
+int granne_hip_knn_graph_filtered(const granne_hip_index* index, const uint32_t* filter, uint64_t first, uint64_t count, uint32_t k,
+                                  uint64_t* out_elements, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                  uint32_t* out_status /* optional */);
+int granne_hip_range_graph_filtered_device(const granne_hip_index* index, const uint32_t* d_filter, uint64_t first, uint64_t count,
+                                           const float* d_radii, uint32_t cap, uint64_t* d_out_elements, uint64_t* d_out_ids,
+                                           float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_out_totals,
+                                           uint32_t* d_status /* u32[4], optional, zeroed by the caller */, void* stream);
+/* the same with host buffers in and out (synchronous); a NaN radius is refused. GRANNE_HIP_ERR_OVERFLOW when status[0] is
+ * not 0: the outputs (and out_status, optional) are still written. */
+int granne_hip_range_graph_filtered(const granne_hip_index* index, const uint32_t* filter, uint64_t first, uint64_t count,
+                                    const float* radii, uint32_t cap, uint64_t* out_elements, uint64_t* out_ids, float* out_dists,
+                                    uint32_t* out_counts, uint32_t* out_totals, uint32_t* out_status /* optional */);
+
 /* The per-shard top-k of one batch as ONE buffer -- what a rank contributes to the single exchange
  * step of the partitioned mode (one all-gather, or one peer copy):
  *   [nq*k u64 local ids][nq*k f32 dists][nq u32 counts], padded to 16 bytes.                      */

@@ -421,6 +421,19 @@ extern "C" {
         d_status: *mut u32, stream: *mut c_void) -> c_int;
     fn granne_hip_range_graph(index: *const granne_hip_index, first: u64, count: u64, radii: *const f32, cap: u32,
         out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_knn_graph_filtered_device(index: *const granne_hip_index, d_filter: *const u32, first: u64,
+        count: u64, k: u32, d_out_elements: *mut u64, d_out_ids: *mut u64, d_out_dists: *mut f32,
+        d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_knn_graph_filtered(index: *const granne_hip_index, filter: *const u32, first: u64, count: u64,
+        k: u32, out_elements: *mut u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
+        out_status: *mut u32) -> c_int;
+    fn granne_hip_range_graph_filtered_device(index: *const granne_hip_index, d_filter: *const u32, first: u64,
+        count: u64, d_radii: *const f32, cap: u32, d_out_elements: *mut u64, d_out_ids: *mut u64,
+        d_out_dists: *mut f32, d_out_counts: *mut u32, d_out_totals: *mut u32, d_status: *mut u32,
+        stream: *mut c_void) -> c_int;
+    fn granne_hip_range_graph_filtered(index: *const granne_hip_index, filter: *const u32, first: u64, count: u64,
+        radii: *const f32, cap: u32, out_elements: *mut u64, out_ids: *mut u64, out_dists: *mut f32,
+        out_counts: *mut u32, out_totals: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_merge_topk_device(d_ids: *const u64, d_dists: *const f32, d_counts: *const u32,
         shard_offsets: *const u64, n_shards: u32, nq: u32, k: u32, d_out_ids: *mut u64, d_out_dists: *mut f32,
         d_out_counts: *mut u32, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -659,6 +672,45 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_range_graph(self.handle, first as u64, count as u64, radii.as_ptr(), cap as u32,
             ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), totals.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok(((0..count).map(|i| (0..counts[i] as usize).map(|j| (ids[i * cap + j] as usize, ds[i * cap + j])).collect()).collect(), totals))
+    }
+    /// `granne_hip_knn_graph_filtered_device`: `knn_graph` of the subset `filter` allows. A is the filter's ascending id
+    /// list; for the positions `first .. first + count` of A, element `A[first + p]` (returned first) gets its exact `k`
+    /// nearest OTHER allowed elements by (distance bits, id). Ids are the index's own; no copy of the subset's rows is
+    /// made. An `Err` where the window reaches beyond A.
+    pub fn knn_graph_filtered(&self, k: usize, filter: &GpuFilter, first: usize, count: usize)
+                              -> std::io::Result<(Vec<u64>, Vec<Vec<(usize, f32)>>)> {
+        if count == 0 { return Ok((Vec::new(), Vec::new())); }
+        assert_eq!(filter.len(), self.num_elements());
+        let stream = Stream::new(self.device())?;
+        let out = DeviceResults::new(count, k, self.device())?;
+        let elements = DeviceBuffer::<u64>::new(count, self.device())?;
+        check(unsafe { granne_hip_knn_graph_filtered_device(self.handle, filter.words.ptr as *const u32, first as u64,
+            count as u64, k as u32, elements.ptr, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        let mut e = vec![0u64; count];
+        elements.copy_to(&mut e, &stream)?;
+        Ok((e, out.to_host(count, &stream)?))
+    }
+    /// `granne_hip_range_graph_filtered_device`: `range_graph` of the subset `filter` allows, the window as
+    /// `knn_graph_filtered`'s: the elements, their OTHER allowed elements within `radii[p]` (at most `cap` listed) and the
+    /// exact number of them.
+    pub fn range_graph_filtered(&self, radii: &[f32], cap: usize, filter: &GpuFilter, first: usize, count: usize)
+                                -> std::io::Result<(Vec<u64>, Vec<Vec<(usize, f32)>>, Vec<u32>)> {
+        assert_eq!(count, radii.len());
+        if count == 0 { return Ok((Vec::new(), Vec::new(), Vec::new())); }
+        assert_eq!(filter.len(), self.num_elements());
+        let stream = Stream::new(self.device())?;
+        let r = DeviceBuffer::<f32>::new(count, self.device())?;
+        r.copy_from(radii, &stream)?;
+        let out = DeviceResults::new(count, cap, self.device())?;
+        let elements = DeviceBuffer::<u64>::new(count, self.device())?;
+        let totals = DeviceBuffer::<u32>::new(count, self.device())?;
+        check(unsafe { granne_hip_range_graph_filtered_device(self.handle, filter.words.ptr as *const u32, first as u64,
+            count as u64, r.ptr as *const f32, cap as u32, elements.ptr, out.ids.ptr, out.dists.ptr, out.counts.ptr, totals.ptr,
+            std::ptr::null_mut(), stream.raw) })?;
+        let (mut e, mut t) = (vec![0u64; count], vec![0u32; count]);
+        elements.copy_to(&mut e, &stream)?;
+        totals.copy_to(&mut t, &stream)?;
+        Ok((e, out.to_host(count, &stream)?, t))
     }
     /// `granne_hip_exact_topk_filtered_device`: `exact_topk` among the ids `filter` allows (one bitmap for all queries,
     /// over `num_elements()` ids): the scan walks the bitmap's id list, exact by construction -- the tool for a selective
