@@ -258,6 +258,10 @@ SIGNATURES = {
     "granne_hip_exact_topk_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
     "granne_hip_exact_topk_screened_filtered_device": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_topk_screened_filtered": (i32, [vp, vp, u32, u32, vp, u64, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_after_device": (i32, [vp, vp, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_after": (i32, [vp, vp, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_screened_after_device": (i32, [vp, vp, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+    "granne_hip_exact_topk_screened_after": (i32, [vp, vp, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch_device": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp, vp]),
     "granne_hip_search_postfiltered_batch": (i32, [vp, vp, u32, u32, u32, vp, u32, i32, vp, u64, u64, vp, vp, vp, vp, vp]),
     "granne_hip_exact_range_device": (i32, [vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp]),

@@ -46,10 +46,15 @@
 //                      beside the row, the query loop reads it back by readlane. A query none of the wave's eight rows is
 //                      allowed for is skipped by that wave -- a wave-uniform skip: et_dist shuffles across the wave.
 //                      Priming: see et_select_kernel.
+//   cursor    granne_hip_exact_topk_after*: the k rows that FOLLOW a key of this order (exact_topk_cursor.h) -- one more
+//             admission rule in the three passes and ET_BITS' target rule for every source: et_scan_after_kernel and
+//             et_select_after_kernel, the second inclusion of exact_topk_kernels.inc. The kernels without a cursor keep
+//             their names and compile to the instructions they were.
 // Compiled with -ffp-contract=off: every fused operation is an explicit fmaf.
 #pragma once
 
 #include "dist.h"
+#include "exact_topk_cursor.h"
 #include "filter.h"
 #include "ordered_sum.h"
 
@@ -98,6 +103,7 @@ struct EtParams {
     uint64_t prev_rows;      // ET_LIST: p_{st-1}; 0: no predecessor (stage 0 and pass 3 are never idle)
     const uint32_t* filter;  // ET_BITS: the queries' bitmaps (this round's first)
     uint64_t filter_stride;  // ET_BITS: words from one query's bitmap to the next
+    EtCursor after = {nullptr, nullptr}; // et_scan_after_kernel: the queries' cursors (this round's). (Last: see `list`.)
 };
 
 // A group's row. NBLK > 0: its 128-byte blocks in registers, lane `sub` holding the 16-byte piece `sub` of each (pieces
@@ -226,203 +232,21 @@ __device__ __forceinline__ float et_dist(const EtRow<I8, NBLK>& R, const uint8_t
     }
 }
 
-// One pass over the rows (ET_LIST: the list's entries) [0, P.rows): grid = (query tiles of ET_QT, row ranges). PASS 1
-// counts first-level bins, PASS 2 the second-level bins inside sel.b1 of the queries that need them, PASS 3 collects the
-// keys at or below the bound. SRC: where a row index comes from, whether a pair is admitted, what the range is clipped to.
-template <bool I8, int NBLK, int PASS, EtSrc SRC>
-__global__ __launch_bounds__(ET_THREADS) void et_scan_kernel(const EtParams P) {
-    static_assert(ET_GROUPS == 32u && ET_QT <= 32u, "a step's rows share one filter word; a wave's lanes 0..31 hold a tile's words");
-    extern __shared__ __align__(16) uint8_t smem_et[];
-    __shared__ uint32_t s_bound[ET_QT], s_b1[ET_QT], s_on[ET_QT];
-    __shared__ int s_dy[ET_QT];
-    uint64_t rows = P.rows;
-    if constexpr (SRC == ET_LIST) {
-        const uint64_t m = *P.m;
-        if (P.prev_rows != 0 && P.prev_rows >= m) return; // an idle stage (the whole grid alike)
-        if (m < rows) rows = m;
-    }
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, sub = lane & 7u, grp = tid >> 3;
-    const uint32_t q0 = blockIdx.x * ET_QT;
-    const uint32_t qn = P.nq - q0 < ET_QT ? P.nq - q0 : ET_QT;
-    uint32_t on = 0;
-    if (tid < ET_QT) {
-        uint32_t b1 = 0, bound = 0;
-        if (tid < qn) {
-            bound = P.bound[q0 + tid];
-            on = 1;
-            if constexpr (PASS == 2) {
-                const EtSel s = P.sel[q0 + tid];
-                on = s.need2;
-                b1 = s.b1;
-            }
-            if constexpr (PASS == 3) on = P.sel[q0 + tid].over ? 0u : 1u;
-        }
-        s_bound[tid] = bound, s_b1[tid] = b1, s_on[tid] = on, s_dy[tid] = 0;
-    }
-    if (!__syncthreads_or((int)on)) return; // no query of the tile takes part in this pass
-    // The range of blockIdx.y, a multiple of ET_GROUPS rows: `rows` split over the G = gridDim.y ranges launched,
-    // ceil(ceil(rows / G) / 32) * 32. ET_ALL, ET_BITS: the host's P.per_range -- this expression over P.rows, raised to 32
-    // for rows == 0, where r1 = 0 and nothing runs whatever the value. ET_LIST: rows was clipped to *m, known here alone.
-    // (The other two could divide here too and drop the field; measured on the 10M-row f32 scan that costs ~0.15 %.)
-    uint64_t per_range = P.per_range;
-    if constexpr (SRC == ET_LIST) per_range = ((rows + gridDim.y - 1) / gridDim.y + ET_GROUPS - 1) / ET_GROUPS * ET_GROUPS;
-    const uint64_t r0 = (uint64_t)blockIdx.y * per_range;
-    const uint64_t r1 = r0 + per_range < rows ? r0 + per_range : rows;
-    if (r0 >= r1) return; // (the ranges past the last row; ET_LIST: past the m entries)
-    if constexpr (NBLK > 0) {
-        if constexpr (!I8) {
-            float* sq = reinterpret_cast<float*>(smem_et);
-            const float* gq = reinterpret_cast<const float*>(P.queries) + (size_t)q0 * P.dim;
-            const uint32_t qsf = P.q_lds / 4u;
-            for (uint32_t i = tid; i < qn * P.dim; i += ET_THREADS) {
-                const uint32_t qi = i / P.dim, c = i - qi * P.dim;
-                sq[qi * qsf + c] = gq[i];
-            }
-        } else {
-            const uint8_t* gq = P.queries + (size_t)q0 * P.dim;
-            for (uint32_t i = tid; i < qn * P.q_lds; i += ET_THREADS) {
-                const uint32_t qi = i / P.q_lds, c = i - qi * P.q_lds;
-                smem_et[i] = c < P.dim ? gq[(size_t)qi * P.dim + c] : (uint8_t)0;
-            }
-        }
-        __syncthreads();
-        if constexpr (I8) {
-            if (tid < qn) {
-                const uint32_t* w = reinterpret_cast<const uint32_t*>(smem_et + (size_t)tid * P.q_lds);
-                int dy = 0;
-                for (uint32_t i = 0; i < P.q_lds / 4u; ++i) dy = dot4_i8(w[i], w[i], dy);
-                s_dy[tid] = dy;
-            }
-            __syncthreads();
-        }
-    }
-    for (uint64_t e0 = r0; e0 < r1; e0 += ET_GROUPS) { // e0: a multiple of ET_GROUPS = 32 (per_range is one)
-        const uint64_t e = e0 + grp;
-        const bool live = e < r1;
-        uint64_t row = live ? e : r1 - 1;
-        if constexpr (SRC == ET_LIST) row = P.list[row];
-        uint32_t fw = 0; // ET_BITS: lane l & 31 holds the word of the tile's query l & 31 with this step's 32 rows
-        if constexpr (SRC == ET_BITS) {
-            if ((lane & 31u) < qn) fw = P.filter[(uint64_t)(q0 + (lane & 31u)) * P.filter_stride + (e0 >> 5)];
-        }
-        EtRow<I8, NBLK> R;
-        et_load_row<I8, NBLK>(R, P.elements + row * (uint64_t)P.row_stride, P.row_bytes, lane);
-        for (uint32_t qi = 0; qi < qn; ++qi) {
-            if (!s_on[qi]) continue;
-            bool allowed = true;
-            if constexpr (SRC == ET_BITS) {
-                const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)fw, (int)qi);
-                if (((w >> ((tid >> 6) * 8u)) & 0xFFu) == 0u) continue; // none of this wave's eight rows: the whole wave skips
-                allowed = (w >> grp) & 1u;
-            }
-            const uint8_t* qp = NBLK > 0 ? smem_et + (size_t)qi * P.q_lds
-                                         : P.queries + (size_t)(q0 + qi) * P.dim * (I8 ? 1u : 4u);
-            const float d = et_dist<I8, NBLK>(R, qp, s_dy[qi], P.dim, P.row_bytes, lane);
-            if (live && allowed && sub == 0u) {
-                const uint32_t key = et_key(d);
-                if (key <= s_bound[qi]) {
-                    const size_t q = q0 + qi;
-                    if constexpr (PASS == 1) {
-                        atomicAdd(P.hist + q * ET_BINS1 + (key >> 11), 1u);
-                    } else if constexpr (PASS == 2) {
-                        if ((key >> 11) == s_b1[qi]) atomicAdd(P.hist + q * ET_BINS2 + (key & 2047u), 1u);
-                    } else {
-                        const uint32_t pos = atomicAdd(P.cnt + q, 1u);
-                        if (pos < ET_CAP) P.cand[q * ET_CAP + pos] = (uint64_t)__float_as_uint(d) << 32 | (uint64_t)(uint32_t)(SRC == ET_LIST ? row : e);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// One block per query over the histogram of a counting pass: the first bin whose prefix reaches the target, and what
-// follows from it (the header's rule). `rows`: the stage's prefix p_st; `total`: what the pass counted at or below the
-// query's bound; `final`: the pass saw every row there is -- its verdicts go to the status words.
-//   ET_LIST  m (the list's length: *m_ptr; for ET_ALL, served by this instantiation with no m_ptr, m_all = n) and prev_rows
-//            decide whether the stage is idle (nothing is touched) and whether it is final (the header). The target is
-//            min(k, min(p_st, m)): every entry of the prefix is a row that counts.
-//   ET_BITS  `final` is the host's (the last stage scans all n rows). A prefix may hold fewer than k allowed rows of a
-//            query. A bound taken from those -- a key that min(k, allowed rows OF THE PREFIX) rows are at or below -- would
-//            be too tight for a longer prefix, which may hold allowed rows between it and the true k-th key. So a NON-FINAL
-//            stage narrows only on evidence that lasts: total >= k rows of the prefix at or below the new bound are k rows
-//            of every longer prefix too. With total < k it keeps the bound it has. Only the final stage, which has seen
-//            every row, uses target = min(k, total): a bound below all-ones already holds k allowed rows (total >= k), so
-//            total < k means the bound is all-ones and total is every allowed row of the query.
-// A target of 0 (no row that counts) stores an all-zero EtSel and leaves the bound: pass 3 collects nothing, the count is 0.
-// The second level is reached only past ET_CAP > ET_KMAX rows at or below B1: its target is k - below1 for every source.
-template <int LEVEL, EtSrc SRC>
-__global__ __launch_bounds__(256) void et_select_kernel(const uint32_t* hist, uint32_t k, uint64_t rows, uint64_t prev_rows, const uint64_t* m_ptr,
-                                                        uint64_t m_all, uint32_t* bound, EtSel* sel, uint32_t final, uint32_t* status) {
-    static_assert(SRC != ET_ALL, "all rows: the list rule with m = n by value");
-    constexpr uint32_t NB = LEVEL == 1 ? ET_BINS1 : ET_BINS2, PER = NB / 256u;
-    __shared__ uint32_t s_wave[4];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    if constexpr (SRC == ET_LIST) {
-        const uint64_t m = m_ptr ? *m_ptr : m_all;
-        if (prev_rows != 0 && prev_rows >= m) return; // idle: bound and sel stay the final stage's
-        final = rows >= m ? 1u : 0u;
-        if (m < rows) rows = m;
-    }
-    EtSel s = sel[q];
-    if constexpr (LEVEL == 2) {
-        if (!s.need2) return;
-    } else {
-        s.b1 = 0, s.below1 = 0, s.need2 = 0, s.over = 0;
-    }
-    uint32_t c[PER], mine = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < PER; ++i) {
-        c[i] = hist[(size_t)q * NB + tid * PER + i];
-        mine += c[i];
-    }
-    uint32_t total;
-    const uint32_t before = fl_block_exclusive<4>(mine, s_wave, &total);
-    uint32_t target;
-    if constexpr (LEVEL == 2) target = k - s.below1;
-    else if constexpr (SRC == ET_LIST) target = rows < k ? (uint32_t)rows : k;
-    else target = final && total < k ? total : k;
-    // nothing that counts, or (ET_BITS, not final) too few allowed rows yet: nothing is narrowed. (ET_LIST: total < target
-    // cannot happen for target > 0 -- the bound holds min(k, rows) entries.)
-    if (target == 0 || total < target) {
-        if (tid == 0) {
-            s.need2 = 0;
-            sel[q] = s;
-        }
-        return;
-    }
-    if (before < target && before + mine >= target) { // one thread's bins hold the target
-        uint32_t b = 0, below = before;
-#pragma unroll
-        for (uint32_t i = 0; i < PER; ++i) {
-            if (below < target && below + c[i] >= target) {
-                b = tid * PER + i;
-                break;
-            }
-            below += c[i];
-        }
-        const uint32_t pop = hist[(size_t)q * NB + b];
-        const uint32_t old = bound[q];
-        if constexpr (LEVEL == 1) {
-            s.b1 = b, s.below1 = below;
-            if (below + pop <= ET_CAP) {
-                const uint32_t nb = (b << 11) | 2047u;
-                bound[q] = nb < old ? nb : old;
-            } else {
-                s.need2 = 1;
-                if (final && status) atomicAdd(status + 1, 1u);
-            }
-        } else {
-            const uint32_t nb = (s.b1 << 11) | b;
-            bound[q] = nb < old ? nb : old; // holds k rows whether or not they fit
-            if (s.below1 + below + pop > ET_CAP) {
-                s.over = 1;
-                if (final && status) atomicAdd(status + 0, 1u);
-            }
-        }
-        sel[q] = s;
-    }
-}
+// The scan and the select (exact_topk_kernels.inc): without a cursor under the names they have always had, and with one.
+#define ET_SCAN_KERNEL et_scan_kernel
+#define ET_SELECT_KERNEL et_select_kernel
+#define ET_CURSOR false
+#include "exact_topk_kernels.inc"
+#undef ET_SCAN_KERNEL
+#undef ET_SELECT_KERNEL
+#undef ET_CURSOR
+#define ET_SCAN_KERNEL et_scan_after_kernel
+#define ET_SELECT_KERNEL et_select_after_kernel
+#define ET_CURSOR true
+#include "exact_topk_kernels.inc"
+#undef ET_SCAN_KERNEL
+#undef ET_SELECT_KERNEL
+#undef ET_CURSOR
 
 // The first m (<= ET_CAP) keys of `cand` into `keys` (LDS, ET_CAP entries), sorted ascending (bitonic, padded with all-ones
 // to a power of two); every thread of a block of ET_RANK_THREADS calls it, and the keys are in place when it returns.
@@ -468,29 +292,37 @@ __global__ __launch_bounds__(ET_RANK_THREADS) void et_rank_kernel(const uint64_t
 }
 
 typedef void (*EtScanFn)(const EtParams);
-template <bool I8, int NBLK, EtSrc SRC>
+template <bool I8, int NBLK, EtSrc SRC, bool AFTER>
 inline EtScanFn et_scan_pass(int pass) {
-    return pass == 1 ? et_scan_kernel<I8, NBLK, 1, SRC> : pass == 2 ? et_scan_kernel<I8, NBLK, 2, SRC> : et_scan_kernel<I8, NBLK, 3, SRC>;
+    if constexpr (AFTER)
+        return pass == 1 ? et_scan_after_kernel<I8, NBLK, 1, SRC> : pass == 2 ? et_scan_after_kernel<I8, NBLK, 2, SRC>
+                                                                              : et_scan_after_kernel<I8, NBLK, 3, SRC>;
+    else
+        return pass == 1 ? et_scan_kernel<I8, NBLK, 1, SRC> : pass == 2 ? et_scan_kernel<I8, NBLK, 2, SRC> : et_scan_kernel<I8, NBLK, 3, SRC>;
 }
-template <bool I8, EtSrc SRC>
+template <bool I8, EtSrc SRC, bool AFTER>
 inline EtScanFn et_scan_blocks(uint32_t nblk, int pass) {
-    return nblk <= 1 ? et_scan_pass<I8, 1, SRC>(pass) : nblk <= 2 ? et_scan_pass<I8, 2, SRC>(pass) : nblk <= 4 ? et_scan_pass<I8, 4, SRC>(pass)
-         : nblk <= 8 ? et_scan_pass<I8, 8, SRC>(pass) : et_scan_pass<I8, 0, SRC>(pass);
+    return nblk <= 1 ? et_scan_pass<I8, 1, SRC, AFTER>(pass) : nblk <= 2 ? et_scan_pass<I8, 2, SRC, AFTER>(pass)
+         : nblk <= 4 ? et_scan_pass<I8, 4, SRC, AFTER>(pass) : nblk <= 8 ? et_scan_pass<I8, 8, SRC, AFTER>(pass)
+                                                             : et_scan_pass<I8, 0, SRC, AFTER>(pass);
 }
-template <bool I8>
+template <bool I8, bool AFTER>
 inline EtScanFn et_scan_src(uint32_t nblk, int pass, EtSrc src) {
-    return src == ET_ALL ? et_scan_blocks<I8, ET_ALL>(nblk, pass) : src == ET_LIST ? et_scan_blocks<I8, ET_LIST>(nblk, pass)
-                                                                                    : et_scan_blocks<I8, ET_BITS>(nblk, pass);
+    return src == ET_ALL ? et_scan_blocks<I8, ET_ALL, AFTER>(nblk, pass) : src == ET_LIST ? et_scan_blocks<I8, ET_LIST, AFTER>(nblk, pass)
+                                                                                           : et_scan_blocks<I8, ET_BITS, AFTER>(nblk, pass);
 }
-// the pass's kernel for device rows of row_bytes: the fewest register blocks that hold the row, or the memory form
-inline EtScanFn et_scan_fn(bool i8, uint32_t row_bytes, int pass, EtSrc src) {
+// the pass's kernel for device rows of row_bytes: the fewest register blocks that hold the row, or the memory form;
+// after: the cursor form, which reads P.after
+inline EtScanFn et_scan_fn(bool i8, uint32_t row_bytes, int pass, EtSrc src, bool after = false) {
     const uint32_t nblk = (row_bytes + 127u) / 128u;
-    return i8 ? et_scan_src<true>(nblk, pass, src) : et_scan_src<false>(nblk, pass, src);
+    if (after) return i8 ? et_scan_src<true, true>(nblk, pass, src) : et_scan_src<false, true>(nblk, pass, src);
+    return i8 ? et_scan_src<true, false>(nblk, pass, src) : et_scan_src<false, false>(nblk, pass, src);
 }
 // the level's select for the source: ET_ALL is served by the list rule (et_select_kernel)
 typedef void (*EtSelectFn)(const uint32_t*, uint32_t, uint64_t, uint64_t, const uint64_t*, uint64_t, uint32_t*, EtSel*, uint32_t, uint32_t*);
-inline EtSelectFn et_select_fn(int level, EtSrc src) {
-    if (src == ET_BITS) return level == 1 ? et_select_kernel<1, ET_BITS> : et_select_kernel<2, ET_BITS>;
+inline EtSelectFn et_select_fn(int level, EtSrc src, bool after = false) {
+    if (src == ET_BITS) return level == 1 ? et_select_kernel<1, ET_BITS> : et_select_kernel<2, ET_BITS>; // (with a cursor too: the rule is its own)
+    if (after) return level == 1 ? et_select_after_kernel<1, ET_LIST> : et_select_after_kernel<2, ET_LIST>;
     return level == 1 ? et_select_kernel<1, ET_LIST> : et_select_kernel<2, ET_LIST>;
 }
 

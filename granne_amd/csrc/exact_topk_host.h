@@ -94,11 +94,16 @@ static EtScratch et_scratch(uint64_t n, uint32_t nq, bool list) {
 // one bitmap for every query, compacted here to its ids (ET_LIST); else one bitmap per query (ET_BITS). d_over (optional,
 // u32[nq]): 1 where the selection overflowed and the query was voided, else 0. d_scratch (optional): et_scratch(..).total
 // bytes of the caller's on the index's device, free for this call on s; null: taken from the stream-ordered allocator.
+// d_after_ids (exact_topk_after_host.h; null: no query has a cursor, and nothing below differs): with d_after_dists the
+// queries' cursors, f32 [nq] and u64 [nq] on the device -- the scans and the list rule's select run in their cursor forms
+// (exact_topk.h, AFTER), which read the two arrays where they lie (EtParams::after): no scratch of their own, no launch more.
 static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_filter,
                           uint64_t filter_stride_words, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status,
-                          hipStream_t s, uint32_t* d_over = nullptr, uint8_t* d_scratch = nullptr) {
+                          hipStream_t s, uint32_t* d_over = nullptr, uint8_t* d_scratch = nullptr, const float* d_after_dists = nullptr,
+                          const uint64_t* d_after_ids = nullptr) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     const uint64_t n = ix->n_elements;
+    const bool after = d_after_ids != nullptr;
     const bool i8 = ix->dtype == GRANNE_HIP_I8;
     const EtSrc src = !d_filter ? ET_ALL : filter_stride_words == 0 ? ET_LIST : ET_BITS;
     const bool list = src == ET_LIST;
@@ -156,6 +161,7 @@ static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uin
         P.queries = (const uint8_t*)d_queries + (size_t)c0 * qbytes;
         P.nq = qc;
         P.filter = src == ET_BITS ? d_filter + (size_t)c0 * filter_stride_words : nullptr;
+        P.after = EtCursor{after ? d_after_dists + c0 : nullptr, after ? d_after_ids + c0 : nullptr};
         // a counting pass (1, 2) and its select, or the collecting pass (3), over the prefix `rows` that follows `prev`
         auto pass = [&](int which, uint64_t rows, uint64_t prev, uint32_t final) -> int {
             uint64_t G = (rows + ET_GROUPS - 1) / ET_GROUPS;
@@ -167,10 +173,10 @@ static int exact_topk_run(const granne_hip_index* ix, const void* d_queries, uin
             if (P.per_range < ET_GROUPS) P.per_range = ET_GROUPS;
             P.prev_rows = prev;
             P.hist = which == 1 ? hist1 : hist2;
-            hipLaunchKernelGGL(et_scan_fn(i8, ix->row_bytes, which, src), dim3(tiles, (uint32_t)G), dim3(ET_THREADS), lds, s, P);
+            hipLaunchKernelGGL(et_scan_fn(i8, ix->row_bytes, which, src, after), dim3(tiles, (uint32_t)G), dim3(ET_THREADS), lds, s, P);
             HIP_TRY(hipGetLastError());
             if (which == 3) return GRANNE_HIP_OK;
-            hipLaunchKernelGGL(et_select_fn(which, src), dim3(qc), dim3(256), 0, s, (const uint32_t*)P.hist, k, rows, prev, P.m, n,
+            hipLaunchKernelGGL(et_select_fn(which, src, after), dim3(qc), dim3(256), 0, s, (const uint32_t*)P.hist, k, rows, prev, P.m, n,
                                (uint32_t*)(scratch + o_bound), (EtSel*)(scratch + o_sel), final, d_status);
             HIP_TRY(hipGetLastError());
             return GRANNE_HIP_OK;

@@ -95,6 +95,7 @@ struct EtsParams {
     uint64_t filter_stride = 0;       // ETS_BITS: in words
     uint64_t q_first = 0;             // ETS_Q_ROWS: the element that is this round's query 0 (queries is not read); with
                                       // ETS_LIST: its position in the list
+    const float* tops = nullptr;      // the cursor forms: [nq] the pass's upper threshold (COUNT: top_sure, COLLECT: top_any)
 };
 
 // the launchers (exact_topk_screened.hip); every one is ordered on s and returns what the launch left
@@ -115,6 +116,19 @@ hipError_t ets_gather(const uint8_t* queries, uint32_t qbytes, const uint32_t* f
 hipError_t ets_scatter(const uint32_t* fb_list, uint32_t nfb, uint32_t k, const uint64_t* ids, const float* dists, const uint32_t* counts,
                        const uint32_t* xs, uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* status, hipStream_t s);
 hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s);
+
+// ---- a cursor per query (exact_topk_after_host.h) ----
+// ets_init with the cursors: lo as ets_init makes it (+inf also for a cursor distance outside [0, 2]), and per query
+// top_sure (a score below it: surely after the cursor) and top_any (a score above it: surely before); +inf without one
+hipError_t ets_init_after(bool i8, const uint8_t* queries, uint32_t nq, uint32_t dim, float eps, const float* after_dists, const uint64_t* after_ids,
+                          float* lo, float* top_sure, float* top_any, uint32_t* hist, uint32_t* cnt, hipStream_t s);
+// ets_scan_src under P.tops: COUNT is given top_sure and counts lo <= s < top, COLLECT top_any and lists lo - 2 eps <= s <= top
+hipError_t ets_scan_after(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s);
+// ets_select over buckets that end at min(1, top_sure)
+hipError_t ets_select_after(uint32_t* hist, uint32_t nq, uint32_t k, float* lo, const float* top_sure, hipStream_t s);
+// ets_keys for the candidates beyond the cursor only, dense; cnt[q] becomes their number (et_rank_kernel's m)
+hipError_t ets_keys_after(const uint32_t* cand, const float* dists, uint32_t* cnt, uint32_t nq, const float* after_dists,
+                          const uint64_t* after_ids, uint64_t* keys, hipStream_t s);
 
 // ---- the handle's own rows as queries (knn_graph_host.h) ----
 // ets_scan over all rows with the queries of ETS_Q_ROWS: P.q_first, P.nq; ets_init with queries == nullptr starts them

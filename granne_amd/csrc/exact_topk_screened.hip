@@ -3,6 +3,7 @@
 // without the packed f32 instructions. It needs nothing of the library's other kernels but dist.h's dot4_i8.
 #include "exact_topk_screened.h"
 #include "dist.h"
+#include "exact_topk_cursor.h"
 
 namespace granne_hip {
 
@@ -32,14 +33,20 @@ __device__ __forceinline__ EtsBlock ets_block() {
 
 __device__ __forceinline__ float ets_width(float lo) { return (1.0f - lo) * (1.0f / (float)ETS_BUCKETS); }
 __device__ __forceinline__ float ets_edge(float lo, float w, int j) { return lo + w * (float)j; }
+// AFTER: the buckets end at the query's `top` where that is below 1 (no cursor: top = +inf, and this is ets_width(lo))
+__device__ __forceinline__ float ets_width_top(float lo, float top) { return (__builtin_fminf(1.0f, top) - lo) * (1.0f / (float)ETS_BUCKETS); }
 
 // A lane's view of its query's floor. ETS_RADIUS: thr = lo is the lower threshold; w and inv_w are not used.
+// AFTER (the cursor forms): `top` is the query's upper threshold, read from P.tops -- COUNT: top_sure, a row
+// counts with s < top; COLLECT: top_any, a row is listed with s <= top -- and the buckets lie between lo and min(1, top).
 struct EtsFloor {
-    float thr, lo, w, inv_w;
-    template <int MODE>
+    float thr, lo, w, inv_w, top;
+    template <int MODE, bool AFTER = false>
     __device__ __forceinline__ void init(const EtsParams& P, uint32_t q, bool qlive) {
         lo = qlive ? P.lo[q] : __builtin_inff();
-        w = ets_width(lo);
+        top = __builtin_inff();
+        if constexpr (AFTER) top = qlive ? P.tops[q] : __builtin_inff();
+        w = AFTER ? ets_width_top(lo, top) : ets_width(lo);
         inv_w = 1.0f / w;
         thr = MODE == ETS_COLLECT ? lo - P.eps2 : lo;
     }
@@ -51,11 +58,17 @@ struct EtsFloor {
 // allowed rows are counted or collected. ETS_LIST: the rows are list positions; what is collected is the id at the position.
 // ROLLED (COLLECT): the hits are placed by one loop over the set bits, as ets_radius16 places its rows, not by sixteen
 // unrolled stores -- the 16 x 13 form over a list with its queries in the rows has no registers left for their addresses.
-template <int MODE, int SRC, bool ROLLED = false>
+// AFTER: a row above the query's `top` takes no part (COUNT: at it neither): it is before the cursor, or not surely after it.
+template <int MODE, int SRC, bool ROLLED = false, bool AFTER = false>
 __device__ __forceinline__ void ets_take16(const EtsParams& P, const EtsFloor& F, const float (&sc)[16], uint64_t e_blk, uint64_t r1,
                                            bool whole, uint32_t q, uint32_t col, uint32_t h, uint32_t* hq, uint32_t word) {
     const uint32_t wv = word >> (4u * h); // the lane's row v: bit 8 (v / 4) + v % 4 of it
-    auto allowed = [&](int v) { return SRC != ETS_BITS || (wv >> (8 * (v / 4) + v % 4) & 1u) != 0u; };
+    auto allowed = [&](int v) {
+        if constexpr (AFTER) {
+            if (MODE == ETS_COUNT ? !(sc[v] < F.top) : !(sc[v] <= F.top)) return false;
+        }
+        return SRC != ETS_BITS || (wv >> (8 * (v / 4) + v % 4) & 1u) != 0u;
+    };
     if constexpr (MODE == ETS_COUNT) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -194,8 +207,10 @@ __device__ __forceinline__ uint32_t ets_diag(uint32_t qid, bool qlive, uint64_t 
 // f32 rows of up to 16 KG components. grid = (query tiles of ETS_QT, row ranges), bf_block's order. SRC: the rows are all
 // rows (ETS_ALL, ETS_BITS: P.n of them) or the rows at the positions [0, P.n) of P.list (ETS_LIST). QSRC: the queries are
 // the caller's dense ones, or the elements P.q_first + q (ETS_Q_ROWS), split into their pieces straight from their rows.
-template <int KG, int R, int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE>
+// AFTER: the cursor form -- P.tops [nq] is the pass's upper threshold per query (EtsFloor, ets_take16); nothing else differs.
+template <int KG, int R, int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE, bool AFTER = false>
 __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P) {
+    static_assert(!AFTER || (MODE != ETS_RADIUS && QSRC == ETS_Q_DENSE), "a cursor: top-k of dense queries");
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr uint32_t ET = 32u * R;                // rows per tile
     constexpr uint32_t COMPS = 16u * KG;            // components per (zero padded) row
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
         }
     }
     EtsFloor F;
-    F.init<MODE>(P, q, qlive);
+    F.init<MODE, AFTER>(P, q, qlive);
     if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
 
     const uint64_t r0 = (uint64_t)blk.range * P.per_range;
@@ -324,7 +339,7 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_b16_kernel(const EtsParams P)
                 if constexpr (MODE == ETS_RADIUS)
                     ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
                 else
-                    ets_take16<MODE, SRC, MODE == ETS_COLLECT && SRC == ETS_LIST && QSRC == ETS_Q_ROWS && KG == 13>(
+                    ets_take16<MODE, SRC, MODE == ETS_COLLECT && SRC == ETS_LIST && QSRC == ETS_Q_ROWS && KG == 13, AFTER>(
                         P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
             }
         }
@@ -344,8 +359,9 @@ constexpr uint32_t ETS_I8_R = 4, ETS_I8_ROWS = 32u * ETS_I8_R, ETS_I8_STRIDE = 1
 // LDS (gm, two copies by the tile's parity: one is read while the next tile's is being made).
 // ETS_Q_ROWS: the lane's 16-byte groups of element P.q_first + q are the operand as they lie (device rows are zero padded),
 // its 1 / |q| is the row's own P.inv_norm.
-template <int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE>
+template <int MODE, int SRC = ETS_ALL, int QSRC = ETS_Q_DENSE, bool AFTER = false>
 __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) {
+    static_assert(!AFTER || (MODE != ETS_RADIUS && QSRC == ETS_Q_DENSE), "a cursor: top-k of dense queries");
     extern __shared__ __align__(16) uint8_t smem_ets[];
     constexpr int R = (int)ETS_I8_R;
     constexpr uint32_t ET = ETS_I8_ROWS, STRIDE = ETS_I8_STRIDE;
@@ -400,7 +416,7 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
         qinv = dy > 0 ? 1.0f / __builtin_sqrtf((float)dy) : 0.0f;
     }
     EtsFloor F;
-    F.init<MODE>(P, q, qlive);
+    F.init<MODE, AFTER>(P, q, qlive);
     if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
 
     const uint64_t r0 = (uint64_t)blk.range * P.per_range;
@@ -507,7 +523,7 @@ __global__ __launch_bounds__(ETS_THREADS) void ets_i8_kernel(const EtsParams P) 
             if constexpr (MODE == ETS_RADIUS)
                 ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
             else
-                ets_take16<MODE, SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+                ets_take16<MODE, SRC, false, AFTER>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
         }
     }
     if constexpr (MODE == ETS_COUNT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
@@ -613,6 +629,88 @@ __global__ void ets_keys_kernel(const uint32_t* __restrict__ cand, const float* 
                                 uint32_t nq, uint64_t* __restrict__ keys) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nq * ETS_CAP; i += (uint64_t)gridDim.x * blockDim.x)
         if ((uint32_t)(i & (ETS_CAP - 1u)) < cnt[i / ETS_CAP]) keys[i] = (uint64_t)__float_as_uint(dists[i]) << 32 | (uint64_t)cand[i];
+}
+
+// ---- the cursor forms of the three small kernels (granne_hip_exact_topk_screened_after*) ----
+// ets_init_kernel with a cursor (after_dists[q], after_ids[q]; an id of all-ones: none). With the bound eps a score places
+// a row before any exact arithmetic:
+//   top_sure = 1 - d_after - eps rounded down: s < top_sure has d > d_after -- SURELY after the cursor, whatever its id;
+//   top_any  = 1 - d_after + eps rounded up:   s > top_any  has d < d_after -- surely before it, dropped;
+// what lies between is the band, which only dists_kernel and et_past decide. Both are made in double and rounded outward,
+// as ets_radius_kernel makes lo and hi. d_after = 0: the reference clamps its distances at 0, so a score above 1 + eps is
+// a row AT distance 0, not before it -- top_any = +inf, nothing is dropped. No cursor: both are +inf, and every kernel
+// computes what it computes without one. A cursor distance that is no distance of this metric (its bits above 2.0f's: a
+// sign, a NaN, +inf, beyond 2) gets no screen: lo = +inf, the query goes to exact_topk's scan, which compares bits.
+template <bool I8>
+__global__ void ets_init_after_kernel(const uint8_t* __restrict__ queries, uint32_t nq, uint32_t dim, float eps, const float* __restrict__ after_dists,
+                                      const uint64_t* __restrict__ after_ids, float* __restrict__ lo, float* __restrict__ top_sure,
+                                      float* __restrict__ top_any, uint32_t* __restrict__ hist, uint32_t* __restrict__ cnt) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    bool ok = true;
+    if constexpr (!I8) {
+        const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
+        float s = 0.0f;
+        for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
+        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+    }
+    float ts = __builtin_inff(), ta = __builtin_inff();
+    if (after_ids[q] != ~0ull) {
+        const float d = after_dists[q];
+        if (__float_as_uint(d) > __float_as_uint(2.0f)) ok = false;
+        else {
+            const double dl = 1.0 - (double)d - (double)eps, du = 1.0 - (double)d + (double)eps;
+            ts = (float)dl;
+            if ((double)ts > dl) ts = nextafterf(ts, -__builtin_inff());
+            if (d > 0.0f) {
+                ta = (float)du;
+                if ((double)ta < du) ta = nextafterf(ta, __builtin_inff());
+            }
+        }
+    }
+    lo[q] = ok ? ETS_LO0 : __builtin_inff();
+    top_sure[q] = ts, top_any[q] = ta;
+    for (uint32_t j = 0; j < ETS_BUCKETS; ++j) hist[(size_t)q * ETS_BUCKETS + j] = 0u;
+    cnt[q] = 0u;
+}
+// ets_select_kernel over buckets that end at min(1, top_sure): the histogram holds sure rows only, so the k witnesses of the
+// new floor are all beyond the cursor, whatever the band holds. The edge is ets_take16's expression.
+__global__ __launch_bounds__(64) void ets_select_after_kernel(uint32_t* __restrict__ hist, uint32_t k, float* __restrict__ lo,
+                                                              const float* __restrict__ top_sure) {
+    const uint32_t q = blockIdx.x, lane = threadIdx.x;
+    const uint32_t c = hist[(size_t)q * ETS_BUCKETS + lane];
+    hist[(size_t)q * ETS_BUCKETS + lane] = 0u;
+    uint32_t above = 0; // rows in the buckets lane .. 63
+    for (uint32_t j = 0; j < ETS_BUCKETS; ++j) {
+        const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)j);
+        above += j >= lane ? o : 0u;
+    }
+    const uint64_t have = __ballot(above >= k);
+    if (lane == 0u && have != 0ull) {
+        const float l = lo[q];
+        if (l < 1.0f) lo[q] = ets_edge(l, ets_width_top(l, top_sure[q]), 63 - __builtin_clzll(have));
+    }
+}
+// ets_keys_kernel with the cursor, one block per query: only the candidates BEYOND the cursor get a key -- a band row the
+// exact arithmetic puts at or before it gets none -- dense in keys[q] in any order (et_rank_kernel sorts them), as
+// ers_keys_kernel keeps the rows within a radius; cnt[q] becomes their number. A query on the fallback list (cnt beyond
+// ETS_CAP, or no screen: voided for et_rank_kernel) keeps its count.
+__global__ __launch_bounds__(256) void ets_keys_after_kernel(const uint32_t* __restrict__ cand, const float* __restrict__ dists, uint32_t* __restrict__ cnt,
+                                                             const float* __restrict__ after_dists, const uint64_t* __restrict__ after_ids,
+                                                             uint64_t* __restrict__ keys) {
+    __shared__ uint32_t n_keys;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t m = cnt[q];
+    const uint64_t from = et_from(after_dists[q], after_ids[q]);
+    if (tid == 0u) n_keys = 0u;
+    __syncthreads(); // (every thread has read cnt[q])
+    if (m > ETS_CAP) return;
+    for (uint32_t i = tid; i < m; i += 256u) {
+        const size_t at = (size_t)q * ETS_CAP + i;
+        if (et_past(dists[at], cand[at], from)) keys[(size_t)q * ETS_CAP + atomicAdd(&n_keys, 1u)] = (uint64_t)__float_as_uint(dists[at]) << 32 | (uint64_t)cand[at];
+    }
+    __syncthreads();
+    if (tid == 0u) cnt[q] = n_keys;
 }
 
 // the fallback: the listed queries, dense, for exact_topk's scan -- and its answers back into their places
@@ -1020,6 +1118,42 @@ hipError_t ets_empty(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dist
     hipLaunchKernelGGL(ets_empty_kernel, dim3(ets_grid((uint64_t)nq * k)), dim3(256), 0, s, nq, k, out_ids, out_dists, out_counts);
     return hipGetLastError();
 }
+// ---- the cursor forms: the three forms x the three row sources x COUNT and COLLECT, dense queries ----
+template <int MODE, int SRC>
+static EtsScanFn ets_scan_after_fn(uint32_t form, uint32_t* lds) {
+    if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC, ETS_Q_DENSE, true>;
+    if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC, ETS_Q_DENSE, true>;
+    if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC, ETS_Q_DENSE, true>;
+    return nullptr;
+}
+template <int MODE>
+static EtsScanFn ets_scan_after_mode(uint32_t form, int src, uint32_t* lds) {
+    return src == ETS_ALL    ? ets_scan_after_fn<MODE, ETS_ALL>(form, lds)
+           : src == ETS_LIST ? ets_scan_after_fn<MODE, ETS_LIST>(form, lds)
+           : src == ETS_BITS ? ets_scan_after_fn<MODE, ETS_BITS>(form, lds)
+                             : nullptr;
+}
+hipError_t ets_scan_after(uint32_t form, bool collect, int src, uint32_t tiles, uint32_t ranges, const EtsParams& P, hipStream_t s) {
+    uint32_t lds = 0;
+    const EtsScanFn fn = collect ? ets_scan_after_mode<ETS_COLLECT>(form, src, &lds) : ets_scan_after_mode<ETS_COUNT>(form, src, &lds);
+    return P.tops ? ets_scan_launch(fn, lds, tiles, ranges, P, s) : hipErrorInvalidValue;
+}
+hipError_t ets_init_after(bool i8, const uint8_t* queries, uint32_t nq, uint32_t dim, float eps, const float* after_dists, const uint64_t* after_ids,
+                          float* lo, float* top_sure, float* top_any, uint32_t* hist, uint32_t* cnt, hipStream_t s) {
+    hipLaunchKernelGGL(i8 ? ets_init_after_kernel<true> : ets_init_after_kernel<false>, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, dim,
+                       eps, after_dists, after_ids, lo, top_sure, top_any, hist, cnt);
+    return hipGetLastError();
+}
+hipError_t ets_select_after(uint32_t* hist, uint32_t nq, uint32_t k, float* lo, const float* top_sure, hipStream_t s) {
+    hipLaunchKernelGGL(ets_select_after_kernel, dim3(nq), dim3(64), 0, s, hist, k, lo, top_sure);
+    return hipGetLastError();
+}
+hipError_t ets_keys_after(const uint32_t* cand, const float* dists, uint32_t* cnt, uint32_t nq, const float* after_dists,
+                          const uint64_t* after_ids, uint64_t* keys, hipStream_t s) {
+    hipLaunchKernelGGL(ets_keys_after_kernel, dim3(nq), dim3(256), 0, s, cand, dists, cnt, after_dists, after_ids, keys);
+    return hipGetLastError();
+}
+
 hipError_t ets_status(uint32_t* status, uint32_t routed, uint32_t form, const uint32_t* xs, hipStream_t s) {
     hipLaunchKernelGGL(ets_status_kernel, dim3(1), dim3(1), 0, s, status, routed, form, xs);
     return hipGetLastError();

@@ -25,10 +25,10 @@ static int exact_topk_screened_filtered_args(const granne_hip_index* ix, uint32_
 
 // The nfb queries of the fallback list (dense at d_fb_queries, their places among the call's in d_fb_list) by
 // exact_topk_run, each under its own bitmap: the listed queries' bitmaps are gathered a bounded number (256 MiB) at a
-// time, as exact_range_run's phase B gathers them.
+// time, as exact_range_run's phase B gathers them. d_fb_after_*: the listed queries' cursors, dense like their queries (null: none).
 static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_queries, const uint32_t* d_fb_list, uint32_t nfb, uint32_t k,
                              const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
-                             uint32_t* d_xs, hipStream_t s) {
+                             uint32_t* d_xs, hipStream_t s, const float* d_fb_after_dists, const uint64_t* d_fb_after_ids) {
     const size_t qbytes = (size_t)ix->dim * query_elem_size(ix->dtype);
     const uint64_t words = filter_words(ix->n_elements);
     uint64_t chunk = (256ull << 20) / (words * 4u);
@@ -40,7 +40,8 @@ static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_que
         const uint32_t qc = nfb - c0 < chunk ? nfb - c0 : (uint32_t)chunk;
         if (const int rc = pf_gather_rows(d_filter, filter_stride_words * 4u, d_fb_list + c0, qc, words * 4u, maps.p, s)) return rc;
         if (const int rc = exact_topk_run(ix, d_fb_queries + (size_t)c0 * qbytes, qc, k, maps.as<uint32_t>(), words, d_ids + (size_t)c0 * k,
-                                          d_dists + (size_t)c0 * k, d_counts + c0, d_xs, s))
+                                          d_dists + (size_t)c0 * k, d_counts + c0, d_xs, s, nullptr, nullptr,
+                                          d_fb_after_ids ? d_fb_after_dists + c0 : nullptr, d_fb_after_ids ? d_fb_after_ids + c0 : nullptr))
             return rc;
     }
     return GRANNE_HIP_OK;

@@ -70,7 +70,7 @@ static int ets_scan_norms(const granne_hip_index* ix, hipStream_t s) {
 // the fallback list's queries under their own bitmaps (exact_topk_screened_filtered_host.h)
 static int ets_fallback_bits(const granne_hip_index* ix, const uint8_t* d_fb_queries, const uint32_t* d_fb_list, uint32_t nfb, uint32_t k,
                              const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
-                             uint32_t* d_xs, hipStream_t s);
+                             uint32_t* d_xs, hipStream_t s, const float* d_fb_after_dists = nullptr, const uint64_t* d_fb_after_ids = nullptr);
 // the handle's own rows first + p (p = d_list[f], or f where d_list is null; f < m) by exact_topk's scan with k + 1, the
 // row itself dropped (knn_graph_host.h)
 static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t* d_list, uint32_t m, uint32_t k, uint64_t* d_out_ids,
@@ -93,10 +93,16 @@ static int kg_by_scan(const granne_hip_index* ix, uint64_t first, const uint32_t
 // at the list's POSITIONS *own_first .. + nq - 1 (within allowed_m): the scans run over the list with their queries read
 // through it (ETS_LIST with ETS_Q_ROWS, the diagonal a compare of positions), dists_kernel gets the round's query rows
 // gathered dense, and kg_by_scan runs under the filter and drops the id at the position.
+// d_after_ids (exact_topk_after_host.h; null: no cursor, and nothing below differs; never with own_first):
+// with d_after_dists the queries' cursors. ets_init_after makes two more words per query, top_sure and top_any; the
+// counting passes histogram the rows surely beyond the cursor, the collecting pass lists up to top_any, ets_keys_after
+// keeps the candidates the exact arithmetic puts beyond the cursor, and whatever goes to exact_topk_run goes with its cursor.
 static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out_ids,
                                    float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, hipStream_t s,
                                    const uint32_t* d_filter = nullptr, uint64_t filter_stride_words = 0, const uint64_t* own_first = nullptr,
-                                   const uint32_t* d_allowed = nullptr, uint64_t allowed_m = 0) {
+                                   const uint32_t* d_allowed = nullptr, uint64_t allowed_m = 0, const float* d_after_dists = nullptr,
+                                   const uint64_t* d_after_ids = nullptr) {
+    const bool after = d_after_ids != nullptr;
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
     if (const int rc = ets_form(ix, s, &form)) return rc;
@@ -114,7 +120,8 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     const size_t o_cand = o_sel + up((size_t)qc_max * sizeof(EtSel)), o_dist = o_cand + (size_t)qc_max * ET_CAP * 4;
     const size_t o_keys = o_dist + (size_t)qc_max * ET_CAP * 4;
     // ETS_LIST: the list's length (u64), the compaction's block counts, the list
-    const size_t o_m = o_keys + (size_t)qc_max * ET_CAP * 8, o_blk = o_m + 256, o_list = o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
+    const size_t o_top = o_keys + (size_t)qc_max * ET_CAP * 8; // a cursor call: top_sure [qc], top_any [qc]
+    const size_t o_m = o_top + up(after ? (size_t)qc_max * 8 : 0), o_blk = o_m + 256, o_list = o_blk + up(list ? (size_t)fl_blocks(n) * 4 : 0);
     // (the caller's list: a round's query rows, dense for dists_kernel, where the compaction's words would be)
     const size_t total = form == ETS_FORM_ROUTED ? 256 : d_allowed ? o_m + up((size_t)qc_max * qbytes) : list ? o_list + (size_t)n * 4 : o_m;
     uint8_t* scratch = nullptr;
@@ -131,7 +138,8 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     if (form == ETS_FORM_ROUTED) {
         if (own_first) {
             if (const int rc = kg_by_scan(ix, *own_first, nullptr, nq, k, d_out_ids, d_out_dists, d_out_counts, xs, s, d_filter, d_allowed)) return rc;
-        } else if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s))
+        } else if (const int rc = exact_topk_run(ix, d_queries, nq, k, d_filter, filter_stride_words, d_out_ids, d_out_dists, d_out_counts, xs, s,
+                                                 nullptr, nullptr, d_after_dists, d_after_ids))
             return rc;
         if (d_status) HIP_TRY(ets_status(d_status, nq, (uint32_t)ETS_FORM_ROUTED, xs, s));
         return GRANNE_HIP_OK;
@@ -183,6 +191,9 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     P.filter_stride = filter_stride_words;
     uint32_t* const fb_count = (uint32_t*)(scratch + o_fbn);
     uint32_t* const fb_list = (uint32_t*)(scratch + o_fbl);
+    float* const top_sure = (float*)(scratch + o_top);
+    float* const top_any = top_sure + qc_max;
+    const float eps = ets_epsilon(i8, ix->dim);
     for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
         const uint32_t qc = nq - c0 < ET_CHUNK ? nq - c0 : ET_CHUNK;
         const uint32_t tiles = (qc + ETS_QT - 1) / ETS_QT;
@@ -200,15 +211,20 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
             if (G < 1) G = 1;
             P.n = rows;
             P.per_range = ((rows + G - 1) / G + tile - 1) / tile * tile;
-            HIP_TRY(!own_first  ? ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s)
+            P.tops = !after ? nullptr : collect ? top_any : top_sure;
+            HIP_TRY(after       ? ets_scan_after(form, collect, src, tiles, (uint32_t)G, P, s)
+                    : !own_first ? ets_scan_src(form, collect, src, tiles, (uint32_t)G, P, s)
                     : d_allowed ? ets_scan_rows_list(form, collect, tiles, (uint32_t)G, P, s)
                                 : ets_scan_rows(form, collect, tiles, (uint32_t)G, P, s));
             return GRANNE_HIP_OK;
         };
-        HIP_TRY(ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
+        HIP_TRY(after ? ets_init_after(i8, P.queries, qc, ix->dim, eps, d_after_dists + c0, d_after_ids + c0, (float*)(scratch + o_lo), top_sure,
+                                       top_any, P.hist, P.cnt, s)
+                      : ets_init(i8, P.queries, qc, ix->dim, (float*)(scratch + o_lo), P.hist, P.cnt, s));
         for (uint32_t st = 0; st < stages; ++st) {
             if (const int rc = pass(false, prefix[st])) return rc;
-            HIP_TRY(ets_select(P.hist, qc, k, (float*)(scratch + o_lo), s));
+            HIP_TRY(after ? ets_select_after(P.hist, qc, k, (float*)(scratch + o_lo), top_sure, s)
+                          : ets_select(P.hist, qc, k, (float*)(scratch + o_lo), s));
         }
         if (const int rc = pass(true, n)) return rc;
         // the survivors' distances in the reference's arithmetic, then exact_topk's ranking by (distance bits, id)
@@ -221,7 +237,9 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
         if (const int rc = dists_launch(ix, dq, nullptr, ET_CAP, P.cand, (uint64_t)qc * ET_CAP, (float*)(scratch + o_dist), nullptr, s,
                                         own_first && !d_allowed ? ix->row_stride : 0u))
             return rc;
-        HIP_TRY(ets_keys(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, (uint64_t*)(scratch + o_keys), s));
+        HIP_TRY(after ? ets_keys_after(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, d_after_dists + c0, d_after_ids + c0,
+                                       (uint64_t*)(scratch + o_keys), s)
+                      : ets_keys(P.cand, (const float*)(scratch + o_dist), P.cnt, qc, (uint64_t*)(scratch + o_keys), s));
         hipLaunchKernelGGL(et_rank_kernel, dim3(qc), dim3(ET_RANK_THREADS), 0, s, (const uint64_t*)(scratch + o_keys), (const uint32_t*)P.cnt,
                            (const EtSel*)(scratch + o_sel), k, d_out_ids + (size_t)c0 * k, d_out_dists + (size_t)c0 * k, d_out_counts + c0,
                            (uint32_t*)nullptr, (uint32_t*)nullptr);
@@ -239,15 +257,24 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     }
     // the fallback: the listed queries by exact_topk's own scan (under their filter), the answers into their places
     const size_t f_ids = up((size_t)nfb * qbytes), f_d = f_ids + (size_t)nfb * k * 8, f_c = f_d + up((size_t)nfb * k * 4);
+    const size_t f_ai = up(f_c + (size_t)nfb * 4), f_ad = f_ai + (size_t)nfb * 8; // their cursors, gathered alongside
     uint8_t* fb = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&fb, f_c + (size_t)nfb * 4, s));
+    HIP_TRY(hipMallocAsync((void**)&fb, after ? f_ad + (size_t)nfb * 4 : f_c + (size_t)nfb * 4, s));
     Release release_fb{fb, s};
     HIP_TRY(ets_gather((const uint8_t*)d_queries, (uint32_t)qbytes, fb_list, nfb, fb, s));
+    const float* fb_ad = nullptr;
+    const uint64_t* fb_ai = nullptr;
+    if (after) {
+        HIP_TRY(ets_gather((const uint8_t*)d_after_ids, 8u, fb_list, nfb, fb + f_ai, s));
+        HIP_TRY(ets_gather((const uint8_t*)d_after_dists, 4u, fb_list, nfb, fb + f_ad, s));
+        fb_ad = (const float*)(fb + f_ad), fb_ai = (const uint64_t*)(fb + f_ai);
+    }
     if (src != ETS_BITS) {
-        if (const int rc = exact_topk_run(ix, fb, nfb, k, d_filter, 0, (uint64_t*)(fb + f_ids), (float*)(fb + f_d), (uint32_t*)(fb + f_c), xs, s))
+        if (const int rc = exact_topk_run(ix, fb, nfb, k, d_filter, 0, (uint64_t*)(fb + f_ids), (float*)(fb + f_d), (uint32_t*)(fb + f_c), xs, s,
+                                          nullptr, nullptr, fb_ad, fb_ai))
             return rc;
     } else if (const int rc = ets_fallback_bits(ix, fb, fb_list, nfb, k, d_filter, filter_stride_words, (uint64_t*)(fb + f_ids), (float*)(fb + f_d),
-                                                (uint32_t*)(fb + f_c), xs, s))
+                                                (uint32_t*)(fb + f_c), xs, s, fb_ad, fb_ai))
         return rc;
     HIP_TRY(ets_scatter(fb_list, nfb, k, (const uint64_t*)(fb + f_ids), (const float*)(fb + f_d), (const uint32_t*)(fb + f_c), xs, d_out_ids,
                         d_out_dists, d_out_counts, d_status, s));

@@ -2493,6 +2493,7 @@ extern "C" int granne_hip_dist_pairs(const granne_hip_index* ix, const void* que
 // ------------------------------------------------------------------------------------------------
 #include "exact_topk_screened_host.h"
 #include "exact_topk_screened_filtered_host.h"
+#include "exact_topk_after_host.h"
 #include "exact_range_screened_host.h"
 #include "knn_graph_host.h"
 #include "range_graph_host.h"

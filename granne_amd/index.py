@@ -980,6 +980,80 @@ class Granne:
             raise GranneHipError(ERR_OVERFLOW, "exact_topk_screened_filtered: exact_topk's selection overflowed for a query handed to it")
         return out
 
+    # ---- the exact entries paged by a key cursor (include/granne_hip.h) -----
+    def exact_topk_after_device(self, d_queries, nq, k, d_after_dists, d_after_ids, d_filter, filter_stride_words, d_ids, d_dists,
+                                d_counts, d_status=0, stream=0):
+        """The k rows that follow each query's cursor in exact_topk's order (granne_hip_exact_topk_after_device): raw device
+        pointers (int); d_after_dists f32[nq], d_after_ids u64[nq] (UINT64_MAX: no cursor for that query; d_after_ids 0:
+        for none); d_filter 0 for all rows, or as exact_topk_filtered_device takes it. Asynchronous on `stream`."""
+        check(lib().granne_hip_exact_topk_after_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_after_dists),
+                                                       C.c_void_p(d_after_ids), C.c_void_p(d_filter), int(filter_stride_words),
+                                                       C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts), C.c_void_p(d_status),
+                                                       C.c_void_p(stream)))
+
+    def exact_topk_screened_after_device(self, d_queries, nq, k, d_after_dists, d_after_ids, d_filter, filter_stride_words, d_ids,
+                                         d_dists, d_counts, d_status=0, stream=0):
+        """exact_topk_after_device's answer with the matrix cores screening the rows first
+        (granne_hip_exact_topk_screened_after_device): the same arguments; d_status: exact_topk_screened's words. Ordered on
+        `stream`, which the call waits on where exact_topk_screened[_filtered]_device waits."""
+        check(lib().granne_hip_exact_topk_screened_after_device(self._h, C.c_void_p(d_queries), int(nq), int(k), C.c_void_p(d_after_dists),
+                                                                C.c_void_p(d_after_ids), C.c_void_p(d_filter), int(filter_stride_words),
+                                                                C.c_void_p(d_ids), C.c_void_p(d_dists), C.c_void_p(d_counts),
+                                                                C.c_void_p(d_status), C.c_void_p(stream)))
+
+    def _exact_topk_after(self, screened, queries, k, after, allowed, prepared, stats):
+        import torch
+        q = self._prepare(queries, prepared)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("queries must be [nq, %d]" % self.dim)
+        k, nq = int(k), q.shape[0]
+        dev = torch.device("cuda", self.device)
+        ad_ptr = ai_ptr = 0
+        if after is not None:
+            ad = np.array(np.broadcast_to(np.asarray(after[0], np.float32), (nq,)))  # (a scalar serves every query)
+            ai = np.array(np.broadcast_to(np.asarray(after[1], np.uint64), (nq,)))
+            tad, tai = torch.from_numpy(ad).to(dev), torch.from_numpy(ai.view(np.int64)).to(dev)
+            ad_ptr, ai_ptr = tad.data_ptr(), tai.data_ptr()
+        owner, fptr, stride = (None, 0, 0) if allowed is None else self._filter_arg(allowed, nq, self.num_elements())
+        tq = torch.from_numpy(q.view(np.uint8).reshape(nq, q.shape[1] * q.itemsize)).to(dev)
+        ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+        ds = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (the filter was made on the null stream)
+        entry = self.exact_topk_screened_after_device if screened else self.exact_topk_after_device
+        entry(tq.data_ptr(), nq, k, ad_ptr, ai_ptr, fptr, stride, ids.data_ptr(), ds.data_ptr(), cnt.data_ptr(), st.data_ptr(),
+              torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        del owner
+        status = st.cpu().numpy().view(np.uint32)
+        out = ids.cpu().numpy().view(np.uint64), ds.cpu().numpy(), cnt.cpu().numpy().view(np.uint32)
+        if stats:
+            return out + (status,)
+        if screened and status[3] & 0x80000000:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk_screened_after: exact_topk's selection overflowed for a query handed to it")
+        if not screened and status[0]:
+            raise GranneHipError(ERR_OVERFLOW, "exact_topk_after: %d queries have more than %d rows inside one second-level bin at "
+                                 "their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
+        return out
+
+    def exact_topk_after(self, queries, k, after=None, allowed=None, prepared=True, stats=False):
+        """The next page of `exact_topk` (of `exact_topk_filtered` with `allowed`): per query the k rows that FOLLOW the
+        cursor `after` = (dists, ids) -- one (distance, id) per query, usually the last entry of the page before -- in the
+        order (distance bits, id), strictly after it. An id of UINT64_MAX: that query has no cursor; after=None: none has,
+        and the call is `exact_topk`'s, the same bytes. Returns ids [nq, k] u64, dists [nq, k] f32, counts [nq] u32 =
+        min(k, rows after the cursor), the places past the count UINT64_MAX / +inf. Paging on from each page's last entry
+        lists the whole order exactly, past EXACT_TOPK_KMAX. Overflow and stats as `exact_topk`."""
+        return self._exact_topk_after(False, queries, k, after, allowed, prepared, stats)
+
+    def exact_topk_screened_after(self, queries, k, after=None, allowed=None, prepared=True, stats=False):
+        """`exact_topk_after`'s returns, the same bytes, with `exact_topk_screened`'s matrix-core screen in front: rows the
+        score puts before the cursor are dropped, rows it puts surely after it raise the floor, and only the band around
+        the cursor and the survivors get the reference's arithmetic. Status words and overflow as `exact_topk_screened`."""
+        return self._exact_topk_after(True, queries, k, after, allowed, prepared, stats)
+
     # ---- range search: all elements within a radius, by scan and by walk (include/granne_hip.h, DESIGN.md 3.10e) -----
     def _radii(self, radius, nq):
         """`radius` -- a scalar or one value per query -- as float32 [nq]; a NaN is refused here as by the host entries"""

@@ -533,6 +533,26 @@ public:
         return out;
     }
 
+    // The next page of exact_topk (granne_hip_exact_topk_after_device): per query the k rows that FOLLOW the cursor
+    // after[i] = (distance, id) -- usually the last entry of the page before -- in the order (distance bits, id), strictly
+    // after it. An id of UINT64_MAX: that query has no cursor; after == nullptr: none has. allowed (optional): one bitmap
+    // for all queries, as exact_topk_filtered takes it. Paging on from each page's last entry lists the whole order
+    // exactly, past k = 1024. Throws where exact_topk throws. `status` (optional): the four status words of the call.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_after(const Element* elements, size_t nq, size_t k,
+                                                                        const std::pair<float, uint64_t>* after,
+                                                                        const Filter* allowed = nullptr,
+                                                                        std::vector<uint32_t>* status = nullptr) const {
+        return exact_topk_after_by(false, elements, nq, k, after, allowed, status);
+    }
+    // exact_topk_after's answer, the same ids and distance bytes, with exact_topk_screened's matrix-core screen in front
+    // (granne_hip_exact_topk_screened_after_device). Throws where exact_topk_screened throws.
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_screened_after(const Element* elements, size_t nq, size_t k,
+                                                                                 const std::pair<float, uint64_t>* after,
+                                                                                 const Filter* allowed = nullptr,
+                                                                                 std::vector<uint32_t>* status = nullptr) const {
+        return exact_topk_after_by(true, elements, nq, k, after, allowed, status);
+    }
+
     // The num_neighbors nearest ALLOWED ids by the ordinary search with a long list and a filter of its result
     // (granne_hip.h, "post-filtered search"): a query's list of stages[s] entries answers it once it holds min_allowed
     // allowed ids or the walk ran out of graph, else the query goes on to the next stage; what no stage finishes gets the
@@ -758,6 +778,54 @@ private:
         if (*(const uint32_t*)(host.data() + o_st)) throw std::runtime_error(overflow);
         for (size_t i = 0; i < nq; ++i)
             for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * cap + j], ds[i * cap + j]);
+        return out;
+    }
+    // exact_topk_after and exact_topk_screened_after on device buffers
+    std::vector<std::vector<std::pair<size_t, float>>> exact_topk_after_by(bool screened, const Element* elements, size_t nq, size_t k,
+                                                                           const std::pair<float, uint64_t>* after, const Filter* allowed,
+                                                                           std::vector<uint32_t>* status) const {
+        const size_t dim = granne_hip_index_dim(h_.get());
+        const int device = granne_hip_index_device(h_.get());
+        if (allowed && (allowed->len() != num_elements() || allowed->device() != device))
+            throw std::runtime_error("the filter must cover the index's elements on its device");
+        std::vector<typename decltype(Element::data)::value_type> q(nq * dim);
+        for (size_t i = 0; i < nq; ++i) {
+            if (elements[i].len() != dim) throw std::runtime_error("query dimension mismatch");
+            std::memcpy(q.data() + i * dim, elements[i].as_slice(), dim * sizeof(q[0]));
+        }
+        const size_t qb = q.size() * sizeof(q[0]);
+        // the cursors: ids [nq] u64, then dists [nq] f32, in one block
+        std::vector<uint8_t> cur(nq * 12 + 16, 0);
+        for (size_t i = 0; after && i < nq; ++i) {
+            std::memcpy(cur.data() + i * 8, &after[i].second, 8);
+            std::memcpy(cur.data() + nq * 8 + i * 4, &after[i].first, 4);
+        }
+        const size_t o_d = nq * k * 8, o_c = o_d + nq * k * 4, o_st = o_c + nq * 4, total = o_st + 16;
+        detail::DeviceMem d_q(qb + 16, device), d_cur(cur.size(), device), d_out(total, device);
+        std::vector<uint8_t> host(total, 0);
+        d_q.upload(q.data(), qb);
+        d_cur.upload(cur.data(), cur.size());
+        d_out.upload(host.data(), total);
+        const float* d_ad = after ? (const float*)((const char*)d_cur.get() + nq * 8) : nullptr;
+        const uint64_t* d_ai = after ? (const uint64_t*)d_cur.get() : nullptr;
+        int rc = (screened ? granne_hip_exact_topk_screened_after_device : granne_hip_exact_topk_after_device)(
+            h_.get(), d_q.get(), (uint32_t)nq, (uint32_t)k, d_ad, d_ai, allowed ? allowed->words() : nullptr, 0, (uint64_t*)d_out.get(),
+            (float*)((char*)d_out.get() + o_d), (uint32_t*)((char*)d_out.get() + o_c), (uint32_t*)((char*)d_out.get() + o_st), nullptr);
+        check(granne_hip_stream_synchronize(nullptr, device));
+        check(rc);
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        if (nq == 0) return out;
+        d_out.download(host.data(), total);
+        const uint64_t* ids = (const uint64_t*)host.data();
+        const float* ds = (const float*)(host.data() + o_d);
+        const uint32_t* counts = (const uint32_t*)(host.data() + o_c);
+        const uint32_t* st = (const uint32_t*)(host.data() + o_st);
+        if (status) status->assign(st, st + 4);
+        if (screened && (st[3] & 0x80000000u))
+            throw std::runtime_error("exact_topk_screened_after: exact_topk's selection overflowed for a query handed to it");
+        if (!screened && st[0]) throw std::runtime_error("exact_topk_after: a query has too many rows inside one second-level bin at its k-th distance");
+        for (size_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back((size_t)ids[i * k + j], ds[i * k + j]);
         return out;
     }
     // knn_graph_filtered (radii null: `width` is k) and range_graph_filtered (`width` is the cap) on device buffers

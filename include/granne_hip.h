@@ -1091,6 +1091,56 @@ int granne_hip_exact_topk_screened_filtered(const granne_hip_index* index, const
                                             const uint32_t* filter, uint64_t filter_stride_words, uint64_t* out_ids,
                                             float* out_dists, uint32_t* out_counts, uint32_t* out_status);
 
+/* ---- the exact entries paged by a key cursor -----------------------------------
+ * Every exact entry lists at most GRANNE_HIP_EXACT_TOPK_KMAX rows per query. Their answer is ordered by one total key,
+ * distance bits << 32 | id, so "the next k after this key" is well defined and exact. Per query the caller names the last
+ * entry it has:
+ *   d_after_dists f32[nq], d_after_ids u64[nq]   the cursor (distance, id) of query q. d_after_ids[q] == UINT64_MAX (the
+ *              fill id of the outputs): query q has no cursor. d_after_ids == NULL: no query has one (d_after_dists is
+ *              then not read), and the call is the sibling's, bit for bit.
+ * The answer of query q is the first k rows of granne_hip_exact_topk's own order whose key is STRICTLY greater than
+ * bits(d_after_dists[q]) << 32 | d_after_ids[q], in that order: the ids, distance bytes and counts the tail of an unbounded
+ * exact scan would give. count = min(k, eligible rows); nothing eligible gives count 0; the places past the count are
+ * UINT64_MAX / +inf. Feeding a page's last (distance, id) back as the next cursor enumerates the whole order with no gaps
+ * and no repeats, through runs of rows with equal distance bits included -- the way past k = 1024, and the way to list
+ * what granne_hip_exact_range counted beyond its cap (page until the radius or its `total` is reached). The cursor is
+ * compared as bits: it need not be an entry of the answer, and a distance that no row can have (a sign bit, a NaN) simply
+ * sorts where its bits put it.
+ *   d_filter   optional. NULL: all rows. Otherwise granne_hip_exact_topk_filtered's convention: filter_stride_words == 0
+ *              is one bitmap for every query, anything else one bitmap per query at d_filter + q * filter_stride_words.
+ *   d_status   u32[4], optional, zeroed by the caller: the sibling's words (granne_hip_exact_topk / _filtered).
+ * Refusals, limits, stream ordering and scratch are granne_hip_exact_topk_device's / granne_hip_exact_topk_filtered_device's,
+ * with their messages; also refused: d_after_ids without d_after_dists. The options' LAST_SCAN word is not written. */
+int granne_hip_exact_topk_after_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                       const float* d_after_dists, const uint64_t* d_after_ids, const uint32_t* d_filter,
+                                       uint64_t filter_stride_words, uint64_t* d_out_ids, float* d_out_dists,
+                                       uint32_t* d_out_counts, uint32_t* d_status, void* stream);
+/* the same with host buffers in and out; synchronous; GRANNE_HIP_ERR_OVERFLOW as granne_hip_exact_topk */
+int granne_hip_exact_topk_after(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                                const float* after_dists, const uint64_t* after_ids, const uint32_t* filter,
+                                uint64_t filter_stride_words, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                uint32_t* out_status);
+/* The same answer with granne_hip_exact_topk_screened's matrix-core screen in front. The screen's bound eps places a row
+ * by its score s before any exact arithmetic: s > 1 - d_after + eps is before the cursor and dropped, s < 1 - d_after - eps
+ * is surely after it, and only the band between gets the reference's arithmetic to decide. The floor is raised on sure
+ * rows only, the survivors up to the band's top are ranked, the keys at or before the cursor voided.
+ *   routed     as granne_hip_exact_topk_screened[_filtered] routes; answered by granne_hip_exact_topk_after_device.
+ *   fallback   more than GRANNE_HIP_EXACT_TOPK_CAP survivors (a band swollen by thousands of rows at the cursor's distance
+ *              included), an f32 query outside the norm bound, or a cursor distance whose bits lie above 2.0f's: answered
+ *              by granne_hip_exact_topk_after_device with its cursor, after the screen.
+ *   d_status   granne_hip_exact_topk_screened's four words.
+ * Refusals and messages: granne_hip_exact_topk_screened's, or granne_hip_exact_topk_screened_filtered's with a filter.
+ * Scratch: the sibling's plus two words per query. One wait on `stream` where the sibling waits. */
+int granne_hip_exact_topk_screened_after_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, uint32_t k,
+                                                const float* d_after_dists, const uint64_t* d_after_ids,
+                                                const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,
+                                                float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_status, void* stream);
+/* host buffers in and out; synchronous; GRANNE_HIP_ERR_OVERFLOW as granne_hip_exact_topk_screened */
+int granne_hip_exact_topk_screened_after(const granne_hip_index* index, const void* queries, uint32_t nq, uint32_t k,
+                                         const float* after_dists, const uint64_t* after_ids, const uint32_t* filter,
+                                         uint64_t filter_stride_words, uint64_t* out_ids, float* out_dists,
+                                         uint32_t* out_counts, uint32_t* out_status);
+
 /* ---- post-filtered search: staged over-fetch on the ordinary search -----------
  * "The nearest neighbours among the ids this bitmap allows", answered by the ORDINARY search with a long list and a filter
  * of its result: no walker knows about the filter, so the register walkers serve it, and so do GRANNE_HIP_F16 and compact

@@ -233,6 +233,20 @@ extern "C" {
     fn granne_hip_exact_topk_screened_filtered(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         filter: *const u32, filter_stride_words: u64, out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32,
         out_status: *mut u32) -> c_int;
+    // the exact entries paged by a key cursor
+    fn granne_hip_exact_topk_after_device(index: *const granne_hip_index, d_queries: *const c_void, nq: u32,
+        k: u32, d_after_dists: *const f32, d_after_ids: *const u64, d_filter: *const u32, filter_stride_words: u64,
+        d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_topk_after(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
+        after_dists: *const f32, after_ids: *const u64, filter: *const u32, filter_stride_words: u64,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
+    fn granne_hip_exact_topk_screened_after_device(index: *const granne_hip_index, d_queries: *const c_void,
+        nq: u32, k: u32, d_after_dists: *const f32, d_after_ids: *const u64, d_filter: *const u32,
+        filter_stride_words: u64, d_out_ids: *mut u64, d_out_dists: *mut f32, d_out_counts: *mut u32,
+        d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn granne_hip_exact_topk_screened_after(index: *const granne_hip_index, queries: *const c_void, nq: u32,
+        k: u32, after_dists: *const f32, after_ids: *const u64, filter: *const u32, filter_stride_words: u64,
+        out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
     // partitioned indexes: the bitmap slice, filtered search and the exact selection over global ids
     fn granne_hip_filter_slice_device(d_filter: *const u32, n_bits: u64, filter_stride_words: u64, n_filters: u32,
         first_bit: u64, n_out_bits: u64, d_out: *mut u32, out_stride_words: u64, device_id: c_int, stream: *mut c_void) -> c_int;
@@ -738,6 +752,48 @@ impl<E: GpuElements> GpuGranne<E> {
         let out = DeviceResults::new(nq, k, self.device())?;
         check(unsafe { granne_hip_exact_topk_screened_filtered_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
             filter.words.ptr as *const u32, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr, std::ptr::null_mut(), stream.raw) })?;
+        out.to_host(nq, &stream)
+    }
+    /// `granne_hip_exact_topk_after_device`: the next page of `exact_topk` -- per query the `k` rows that follow the cursor
+    /// `after[i]` = (distance, id), usually the last entry of the page before, in the order (distance bits, id), strictly
+    /// after it. An id of `u64::MAX`: that query has no cursor. `filter`: `None` for all rows, else the rows one bitmap
+    /// allows. Paging on from each page's last entry lists the whole order exactly, past `k` = 1024.
+    pub fn exact_topk_after(&self, elements: &[E::Vector], k: usize, after: &[(f32, u64)], filter: Option<&GpuFilter>)
+                            -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        self.exact_topk_after_by(false, elements, k, after, filter)
+    }
+    /// `granne_hip_exact_topk_screened_after_device`: `exact_topk_after`'s answer, the same ids and distance bytes, with the
+    /// matrix cores screening the rows first: only the band around the cursor and the survivors get the exact arithmetic.
+    pub fn exact_topk_screened_after(&self, elements: &[E::Vector], k: usize, after: &[(f32, u64)], filter: Option<&GpuFilter>)
+                                     -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        self.exact_topk_after_by(true, elements, k, after, filter)
+    }
+    fn exact_topk_after_by(&self, screened: bool, elements: &[E::Vector], k: usize, after: &[(f32, u64)], filter: Option<&GpuFilter>)
+                           -> std::io::Result<Vec<Vec<(usize, f32)>>> {
+        let nq = elements.len();
+        assert_eq!(nq, after.len());
+        if nq == 0 { return Ok(Vec::new()); }
+        if let Some(f) = filter { assert_eq!(f.len(), self.num_elements()); }
+        let stream = Stream::new(self.device())?;
+        let q = self.upload_queries(elements, &stream)?;
+        let (ad, ai): (Vec<f32>, Vec<u64>) = after.iter().cloned().unzip();
+        let d_ad = DeviceBuffer::<f32>::new(nq, self.device())?;
+        let d_ai = DeviceBuffer::<u64>::new(nq, self.device())?;
+        d_ad.copy_from(&ad, &stream)?;
+        d_ai.copy_from(&ai, &stream)?;
+        let out = DeviceResults::new(nq, k, self.device())?;
+        let words = filter.map_or(std::ptr::null(), |f| f.words.ptr as *const u32);
+        check(unsafe {
+            if screened {
+                granne_hip_exact_topk_screened_after_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
+                    d_ad.ptr as *const f32, d_ai.ptr as *const u64, words, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr,
+                    std::ptr::null_mut(), stream.raw)
+            } else {
+                granne_hip_exact_topk_after_device(self.handle, q.ptr as *const c_void, nq as u32, k as u32,
+                    d_ad.ptr as *const f32, d_ai.ptr as *const u64, words, 0, out.ids.ptr, out.dists.ptr, out.counts.ptr,
+                    std::ptr::null_mut(), stream.raw)
+            }
+        })?;
         out.to_host(nq, &stream)
     }
     /// `granne_hip_search_postfiltered_batch_device`: the `num_neighbors` nearest ids `filter` allows, by the ordinary
