@@ -26,6 +26,7 @@ OPT_FORCE_GENERAL = 21  # 1: no register walker (tests and measurement: the unfi
 (SCAN_NONE, SCAN_RING, SCAN_I8, SCAN_I8_CHUNKED, SCAN_B16_7_4, SCAN_B16_13_2, SCAN_B16_16_1, SCAN_B16_CHUNKED, SCAN_F32_52_4,
  SCAN_F32_100_2, SCAN_F32_128_1) = range(11)
 EXACT_TOPK_KMAX = 1024  # GRANNE_HIP_EXACT_TOPK_KMAX
+ETS_FORM_B16_LONG, ETS_FORM_I8_LONG = 4, 5  # GRANNE_HIP_ETS_FORM_*_LONG: status[3] of a screened call over long rows
 EXACT_TOPK_CAP = 4096  # GRANNE_HIP_EXACT_TOPK_CAP: candidates ranked per query
 PF_MAX_STAGES = 8  # GRANNE_HIP_PF_MAX_STAGES: post-filtered search (Granne.search_postfiltered_batch)
 PF_FALLBACK_SHORT, PF_FALLBACK_EXACT = 0, 1  # GRANNE_HIP_PF_FALLBACK_*
@@ -155,6 +156,8 @@ SIGNATURES = {
     "granne_hip_exact_topk_screened_device": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp]),
     "granne_hip_exact_topk_screened": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
     "granne_hip_exact_topk_screen_epsilon": (C.c_float, [i32, u32]),
+    "granne_hip_exact_topk_screen_epsilon_long": (C.c_float, [i32, u32]),
+    "granne_hip_index_screen_long_rows": (i32, [vp, i32]),
     "granne_hip_knn_graph_device": (i32, [vp, u64, u64, u32, vp, vp, vp, vp, vp]),
     "granne_hip_knn_graph": (i32, [vp, u64, u64, u32, vp, vp, vp, vp]),
     "granne_hip_range_graph_device": (i32, [vp, u64, u64, vp, u32, vp, vp, vp, vp, vp, vp]),

@@ -16,7 +16,8 @@
 #include "exact_topk_screened_filtered_host.h"
 
 static_assert(GRANNE_HIP_ETS_FORM_ROUTED == ETS_FORM_ROUTED && GRANNE_HIP_ETS_FORM_B16_7x4 == ETS_FORM_B16_7x4 &&
-                  GRANNE_HIP_ETS_FORM_B16_13x2 == ETS_FORM_B16_13x2 && GRANNE_HIP_ETS_FORM_I8 == ETS_FORM_I8 && GRANNE_HIP_ETS_VOIDED == ETS_VOIDED,
+                  GRANNE_HIP_ETS_FORM_B16_13x2 == ETS_FORM_B16_13x2 && GRANNE_HIP_ETS_FORM_I8 == ETS_FORM_I8 && GRANNE_HIP_ETS_FORM_B16_LONG == ETS_FORM_B16_LONG &&
+                  GRANNE_HIP_ETS_FORM_I8_LONG == ETS_FORM_I8_LONG && GRANNE_HIP_ETS_VOIDED == ETS_VOIDED,
               "the status words granne_hip.h declares");
 
 // exact_range_args under this entry's name
@@ -73,7 +74,7 @@ static int exact_range_screened_run(const granne_hip_index* ix, const void* d_qu
                                     uint32_t* d_out_counts, uint32_t* d_out_totals, uint32_t* d_status, hipStream_t s) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
-    if (const int rc = ets_form(ix, s, &form)) return rc;
+    if (const int rc = ets_form(ix, s, &form, true)) return rc;
     const bool i8 = ix->dtype == GRANNE_HIP_I8;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (form == ETS_FORM_ROUTED) { // no screen for the handle: the whole call is exact_range's
@@ -153,7 +154,7 @@ static int exact_range_screened_run(const granne_hip_index* ix, const void* d_qu
         if (G >= 8) G &= ~7ull;
         if (G < 1) G = 1;
         P.per_range = ((n + G - 1) / G + tile - 1) / tile * tile;
-        HIP_TRY(ers_radius(i8, P.queries, d_radii + c0, qc, ix->dim, ets_epsilon(i8, ix->dim), (float*)(scratch + o_lo), (float*)(scratch + o_hi),
+        HIP_TRY(ers_radius(i8, P.queries, d_radii + c0, qc, ix->dim, ets_epsilon_of(form, i8, ix->dim), (float*)(scratch + o_lo), (float*)(scratch + o_hi),
                            P.sure, P.cnt, P.bcnt, s));
         HIP_TRY(ets_scan_radius(form, src, tiles, (uint32_t)G, P, s));
         HIP_TRY(ers_pad(P.cand, P.sure, P.bcnt, P.list, qc, s));

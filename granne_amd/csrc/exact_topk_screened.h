@@ -46,7 +46,17 @@ constexpr float ETS_LO0 = -1.25f;                   // below every screen score:
 constexpr float ETS_NORM2_MAX = 1.0f + 0x1p-10f;    // f32: the bound holds for |x|^2, |q|^2 up to here
 constexpr float ETS_NORM2_TEST = 1.0f + 0x1p-10f - 0x1p-14f; // what an f32 sum of <= 208 squares is held to (its own rounding: 208 x 2^-24)
 constexpr uint32_t ETS_F32_DIM_MAX = 208, ETS_I8_DIM_MAX = 128;
-enum { ETS_FORM_ROUTED = 0, ETS_FORM_B16_7x4 = 1, ETS_FORM_B16_13x2 = 2, ETS_FORM_I8 = 3 };
+enum { ETS_FORM_ROUTED = 0, ETS_FORM_B16_7x4 = 1, ETS_FORM_B16_13x2 = 2, ETS_FORM_I8 = 3, ETS_FORM_B16_LONG = 4, ETS_FORM_I8_LONG = 5 };
+// The long-row forms (granne_hip_index_screen_long_rows): rows beyond the register forms' lengths, walked in
+// chunks of ETS_LONG_CHUNK components with the tile's accumulators kept across the chunks. Dense queries only.
+constexpr uint32_t ETS_LONG_DIM_MAX = 2048, ETS_LONG_CHUNK = 128;
+constexpr bool ets_form_long(uint32_t form) { return form == ETS_FORM_B16_LONG || form == ETS_FORM_I8_LONG; }
+// What an f32 sum of `dim` squares is held to so that the true sum is at most ETS_NORM2_MAX: the sum's own rounding is at
+// most (dim + 4) 2^-24 of it (dim products, dim - 1 additions in any order, the lanes' three). Short rows: ETS_NORM2_TEST,
+// bit for bit; long rows: 1 + 2^-10 - dim 2^-23 (exact in f32: both are multiples of 2^-23 in [1, 2)).
+__host__ __device__ static inline float ets_norm2_test(uint32_t dim) {
+    return dim <= ETS_F32_DIM_MAX ? ETS_NORM2_TEST : (1.0f + 0x1p-10f) - (float)dim * 0x1p-23f;
+}
 constexpr uint32_t ETS_VOIDED = 0x80000000u; // status[3]: exact_topk's own selection overflowed for a query handed to it
 // What a scan runs over (granne_hip_exact_topk_screened_filtered*): all rows; the positions of the id list
 // one shared bitmap compacts to; or all rows under a bit test, one bitmap per query -- a 32-row result block is one word of
@@ -72,6 +82,25 @@ static inline float ets_epsilon(int i8, uint32_t dim) {
     const double ref = (double)dim * 0x1p-24 * 1.01;        // the reference's dim fused steps, 32 accumulators, ordered sum
     return (float)((split + mfma + ref) * (1.0 + 0x1p-10) + 0x1p-22); // |x||q| <= 1 + 2^-10; 1 - dot, lo - 2 eps rounded
 }
+
+// The bound of the long-row forms; 0: no long-row screen for the shape (the short forms' shapes included).
+// f32: ets_epsilon's terms with kpad = 128 ceil(dim / 128) -- the accumulator carried from chunk to chunk is one more
+// partial sum of the same 3 kpad terms, which the any-order bound covers. int8: up to 1040 components the dot and both
+// squared norms are below 2^24 and the short form's 11 roundings are all there are; beyond, four more conversions round
+// (the dot on both sides, |x|^2 and |q|^2 on both sides at half weight each: 15 x 2^-24) and lo - 2 eps rounds once: 16
+// units, each relative to a computed value that may exceed 1 by a few of them -- just above 2^-20; 2^-19 has the margin.
+static inline float ets_epsilon_long(int i8, uint32_t dim) {
+    if (dim > ETS_LONG_DIM_MAX) return 0.0f;
+    if (i8) return dim <= ETS_I8_DIM_MAX ? 0.0f : dim <= 1040u ? 0x1p-20f : 0x1p-19f;
+    if (dim <= ETS_F32_DIM_MAX) return 0.0f;
+    const double kpad = (double)ETS_LONG_CHUNK * (double)((dim + ETS_LONG_CHUNK - 1u) / ETS_LONG_CHUNK);
+    const double split = 3.1 * 0x1p-18;
+    const double mfma = 3.0 * kpad * 0x1p-23 * 1.02;
+    const double ref = (double)dim * 0x1p-24 * 1.01;
+    return (float)((split + mfma + ref) * (1.0 + 0x1p-10) + 0x1p-22);
+}
+// the bound a form's kernels are given
+static inline float ets_epsilon_of(uint32_t form, int i8, uint32_t dim) { return ets_form_long(form) ? ets_epsilon_long(i8, dim) : ets_epsilon(i8, dim); }
 
 struct EtsParams {
     const uint8_t* elements;

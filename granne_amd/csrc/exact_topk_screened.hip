@@ -535,6 +535,346 @@ constexpr uint32_t ets_i8_lds(int mode, bool list = false) {
            (list ? 4u * ETS_I8_R * 4u : 0u);
 }
 
+// ---- the long-row forms (granne_hip_index_screen_long_rows): dense queries, rows of up to ETS_LONG_DIM_MAX ----
+// f32 rows of any length up to ETS_LONG_DIM_MAX, walked in chunks of 128 components (brute_force.h's bf_b16_chunked_kernel
+// with the screen's epilogues): the accumulators of a tile of 32 R rows stay in registers across the chunks; a chunk of the
+// tile goes HBM -> registers -> the two bf16 pieces -> LDS, the next one (of this tile, or the first of the next) being
+// fetched before this one's matrix work; a lane reads its half of its query's chunk (64 components) from memory again for
+// every tile and splits it in registers -- from L2: 16 KB per wave and chunk against 12 R Mflop. What lies past a row's
+// or a query's end is zero by predicate: the last chunk of a dim that is no multiple of 128, the last float4 of a dim that
+// is no multiple of 4 (the device row is zero padded to 16 bytes), a query row that starts on no 16-byte boundary.
+template <int R, int MODE, int SRC = ETS_ALL, bool AFTER = false>
+__global__ __launch_bounds__(ETS_THREADS) void ets_b16_long_kernel(const EtsParams P) {
+    static_assert(!AFTER || MODE != ETS_RADIUS, "a cursor: top-k");
+    extern __shared__ __align__(16) uint8_t smem_ets[];
+    constexpr int KG = 8;                           // groups of 8 components per lane half and chunk
+    constexpr uint32_t ET = 32u * R;                // rows per tile
+    constexpr uint32_t COMPS = ETS_LONG_CHUNK;      // components per chunk
+    constexpr uint32_t STRIDE_B = 2u * COMPS + 16u; // bytes per LDS row of one piece: an odd number of 16-byte units
+    static_assert(COMPS == 16u * KG, "a lane half holds KG groups of 8");
+    uint8_t* tile_hi = smem_ets;
+    uint8_t* tile_lo = smem_ets + (size_t)ET * STRIDE_B;
+    uint32_t* lh = reinterpret_cast<uint32_t*>(smem_ets + 2u * (size_t)ET * STRIDE_B); // COUNT: [ETS_BUCKETS][ETS_QT]; RADIUS: [ETS_THREADS]
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t col = lane & 31u, h = lane >> 5;
+    const EtsBlock blk = ets_block();
+    const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
+    const bool qlive = q < P.nq;
+    if constexpr (MODE == ETS_COUNT) ets_hist_clear(lh, tid); // (the first chunk's barriers stand between this and the first count)
+    const float* qp = reinterpret_cast<const float*>(P.queries) + (size_t)(qlive ? q : 0u) * P.dim;
+    const uint32_t nchunks = (P.dim + COMPS - 1u) / COMPS;
+    const bool qvec_ok = (P.dim & 3u) == 0u && (reinterpret_cast<uintptr_t>(P.queries) & 15u) == 0u; // every query starts on 16 bytes
+    EtsFloor F;
+    F.init<MODE, AFTER>(P, q, qlive);
+    if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
+
+    const uint64_t r0 = (uint64_t)blk.range * P.per_range;
+    const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
+    const uint32_t row_f4 = P.row_bytes / 16u; // float4 units of a device row that hold data
+    constexpr uint32_t UNITS = COMPS / 4u;     // float4 units per row and chunk: a thread keeps its column, rows 16 apart
+    constexpr uint32_t NPF = ET * UNITS / ETS_THREADS;
+    static_assert(UNITS == 32u && ETS_THREADS % UNITS == 0u, "unit tid + 512 j: row tid / 32 + 16 j, column tid % 32");
+    const uint32_t my_row = tid / UNITS, my_c4 = tid % UNITS;
+    float4 pf[NPF]; // the next chunk, on its way from memory while this one is scored
+    auto fetch = [&](uint64_t e0, uint32_t c) {
+        const uint32_t c4 = c * UNITS + my_c4;
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) {
+            const uint64_t row = e0 + my_row + (ETS_THREADS / UNITS) * j;
+            pf[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (row < r1 && c4 < row_f4) {
+                uint64_t id = row;
+                if constexpr (SRC == ETS_LIST) id = P.list[id];
+                pf[j] = *reinterpret_cast<const float4*>(P.elements + id * P.row_stride + (size_t)c4 * 16u);
+            }
+        }
+    };
+    if (r0 < r1) fetch(r0, 0u);
+    for (uint64_t e0 = r0; e0 < r1; e0 += ET) {
+        ets_f32x16 acc[R]; // the tile's scores so far: carried from chunk to chunk
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[r][v] = 0.0f;
+#pragma unroll 1
+        for (uint32_t c = 0; c < nchunks; ++c) {
+            __syncthreads(); // the previous chunk has been consumed
+#pragma unroll
+            for (uint32_t j = 0; j < NPF; ++j) { // split into the two pieces on the way to LDS
+                const uint32_t row = my_row + (ETS_THREADS / UNITS) * j;
+                ets_b16x4 hi, lo;
+                const float v[4] = {pf[j].x, pf[j].y, pf[j].z, pf[j].w};
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    hi[t] = (__bf16)v[t];
+                    lo[t] = (__bf16)(v[t] - (float)hi[t]);
+                }
+                *reinterpret_cast<ets_b16x4*>(tile_hi + (size_t)row * STRIDE_B + my_c4 * 8u) = hi;
+                *reinterpret_cast<ets_b16x4*>(tile_lo + (size_t)row * STRIDE_B + my_c4 * 8u) = lo;
+            }
+            __syncthreads();
+            if (c + 1u < nchunks) fetch(e0, c + 1u);
+            else if (e0 + ET < r1) fetch(e0 + ET, 0u);
+            // the lane's half of its query's chunk as bf16 pieces
+            ets_b16x8 qh[KG], ql[KG];
+            const bool q_vec = qvec_ok && (c + 1u) * COMPS <= P.dim; // the whole chunk inside the vector, on 16 bytes: 16 loads for 64
+#pragma unroll
+            for (int g = 0; g < KG; ++g) {
+                const uint32_t c0 = c * COMPS + h * 8u * KG + (uint32_t)g * 8u;
+                float v8[8];
+                if (q_vec) {
+                    const float4 a = *reinterpret_cast<const float4*>(qp + c0), b = *reinterpret_cast<const float4*>(qp + c0 + 4u);
+                    v8[0] = a.x, v8[1] = a.y, v8[2] = a.z, v8[3] = a.w, v8[4] = b.x, v8[5] = b.y, v8[6] = b.z, v8[7] = b.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v8[j] = c0 + (uint32_t)j < P.dim ? qp[c0 + (uint32_t)j] : 0.0f;
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float v = qlive ? v8[j] : 0.0f;
+                    const __bf16 hi = (__bf16)v;
+                    qh[g][j] = hi;
+                    ql[g][j] = (__bf16)(v - (float)hi);
+                }
+            }
+            // the fragments of the next (step, block) are read while the matrix cores work on this one
+            const size_t off0 = (size_t)col * STRIDE_B + (size_t)h * 16u * KG;
+            constexpr int NF = KG * R;
+            ets_b16x8 ah[2], al[2];
+            ah[0] = *reinterpret_cast<const ets_b16x8*>(tile_hi + off0);
+            al[0] = *reinterpret_cast<const ets_b16x8*>(tile_lo + off0);
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                const int g = i / R, r = i % R;
+                if (i + 1 < NF) {
+                    const int gn = (i + 1) / R, rn = (i + 1) % R;
+                    ah[(i + 1) & 1] = *reinterpret_cast<const ets_b16x8*>(tile_hi + off0 + (size_t)rn * 32u * STRIDE_B + (size_t)gn * 16u);
+                    al[(i + 1) & 1] = *reinterpret_cast<const ets_b16x8*>(tile_lo + off0 + (size_t)rn * 32u * STRIDE_B + (size_t)gn * 16u);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], qh[g], acc[r], 0, 0, 0);
+                acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], ql[g], acc[r], 0, 0, 0);
+                acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i & 1], qh[g], acc[r], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // result block r as in ets_b16_kernel: one max over the block decides for the wave, then the form's epilogue
+        const bool whole = e0 + ET <= r1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float mx = acc[r][0];
+#pragma unroll
+            for (int v = 1; v < 16; ++v) mx = __builtin_fmaxf(mx, acc[r][v]);
+            if (__ballot(mx >= F.thr)) {
+                float sc[16];
+#pragma unroll
+                for (int v = 0; v < 16; ++v) sc[v] = acc[r][v];
+                const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && mx >= F.thr);
+                if constexpr (MODE == ETS_RADIUS)
+                    ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
+                else
+                    ets_take16<MODE, SRC, false, AFTER>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+            }
+        }
+    }
+    if constexpr (MODE == ETS_COUNT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_RADIUS) ets_sure_flush(P, q, h, lh[tid]);
+}
+
+constexpr int ETS_B16_LONG_R = 3;
+constexpr uint32_t ets_b16_long_lds(int mode) {
+    return 2u * (32u * ETS_B16_LONG_R) * (2u * ETS_LONG_CHUNK + 16u) + ets_mode_words(mode) * 4u; // tile_hi, tile_lo, the mode's words
+}
+
+// int8 rows of up to ETS_LONG_DIM_MAX bytes (device rows of more than 128 bytes are zero padded to a multiple of 128),
+// walked in chunks of 128 bytes: i32 accumulators carried across the chunks, the score ets_i8_kernel's expression. A chunk
+// of the tile is a plain staged copy, HBM -> registers -> LDS, into one of TWO chunk buffers: a chunk is a sixth of the
+// matrix work a barrier pair of ets_b16_long_kernel encloses, so the second barrier is spared -- the buffer written now was
+// last read two chunks ago, before the barrier every wave has passed since. The rows' 1 / |x| and the blocks' bounds travel
+// with a tile's first chunk into the copy of the tile's parity: the epilogue of the tile before may still be reading the other.
+// A lane reads its 16-byte groups of its query's chunk from memory for every tile; 1 / |q| is summed over all chunks first.
+template <int MODE, int SRC = ETS_ALL, bool AFTER = false>
+__global__ __launch_bounds__(ETS_THREADS) void ets_i8_long_kernel(const EtsParams P) {
+    static_assert(!AFTER || MODE != ETS_RADIUS, "a cursor: top-k");
+    extern __shared__ __align__(16) uint8_t smem_ets[];
+    constexpr int R = (int)ETS_I8_R;
+    constexpr uint32_t ET = ETS_I8_ROWS, STRIDE = ETS_I8_STRIDE, CHUNK = ETS_LONG_CHUNK;
+    uint8_t* tile = smem_ets;                                                    // [2][ET][STRIDE], by the chunk's parity
+    float* inv = reinterpret_cast<float*>(smem_ets + 2u * (size_t)ET * STRIDE); // [2][ET] 1 / |x|, by the tile's parity
+    float* gms = inv + 2u * ET;                                                  // [2][2][R] inv_gmax of the tile's blocks, by lane half
+    uint32_t* lh = reinterpret_cast<uint32_t*>(gms + 4 * R);                     // COUNT: [ETS_BUCKETS][ETS_QT]; RADIUS: [ETS_THREADS]
+    uint32_t* gml = lh + ets_mode_words(MODE);                                   // ETS_LIST: [2][2][R] float bits, by the tile's parity
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t col = lane & 31u, h = lane >> 5;
+    const EtsBlock blk = ets_block();
+    const uint32_t q = blk.qt * ETS_QT + wave * 32u + col;
+    const bool qlive = q < P.nq;
+    if constexpr (MODE == ETS_COUNT) ets_hist_clear(lh, tid);
+    if constexpr (SRC == ETS_LIST) {
+        if (tid < 4u * R) gml[tid] = 0u;
+    }
+    // A chunk has its one barrier AFTER its staging, so the first tile's maxima (atomicMax into gml, by every wave) are
+    // raised before any barrier of the loop: this one stands between the clearing above and them.
+    __syncthreads();
+    const uint8_t* qp = P.queries + (size_t)(qlive ? q : 0u) * P.dim;
+    const uint32_t nchunks = (P.dim + CHUNK - 1u) / CHUNK; // at least 2: the form is for rows of more than 128 bytes
+    const bool qvec_ok = (P.dim & 15u) == 0u && (reinterpret_cast<uintptr_t>(P.queries) & 15u) == 0u; // every group whole, on 16 bytes
+    // bytes 128 c + 32 g + 16 h .. + 15 of the query (ets_i8_kernel's operand), zero past its end
+    auto load_q = [&](uint32_t c, ets_i32x4 (&qr)[4]) {
+        if (qvec_ok) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t off = c * CHUNK + (uint32_t)g * 32u + h * 16u;
+                qr[g] = ets_i32x4{0, 0, 0, 0};
+                if (qlive && off < P.dim) qr[g] = *reinterpret_cast<const ets_i32x4*>(qp + off);
+            }
+        } else {
+            const uint32_t last = P.dim - 1u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const uint32_t cc = c * CHUNK + (uint32_t)g * 32u + h * 16u + (uint32_t)w * 4u + (uint32_t)b;
+                        const uint32_t raw = qp[cc < last ? cc : last];
+                        const uint32_t keep = (qlive && cc < P.dim) ? 0xFFu : 0u;
+                        v |= (raw & keep) << (8 * b);
+                    }
+                    qr[g][w] = (int)v;
+                }
+            }
+        }
+    };
+    float qinv = 0.0f;
+    {
+        int dy = 0;
+#pragma unroll 1
+        for (uint32_t c = 0; c < nchunks; ++c) {
+            ets_i32x4 qr[4];
+            load_q(c, qr);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) dy = dot4_i8((uint32_t)qr[g][w], (uint32_t)qr[g][w], dy);
+        }
+        dy += __shfl_xor(dy, 32, 64); // the other half of every chunk
+        qinv = dy > 0 ? 1.0f / __builtin_sqrtf((float)dy) : 0.0f;
+    }
+    EtsFloor F;
+    F.init<MODE, AFTER>(P, q, qlive);
+    if constexpr (MODE == ETS_RADIUS) lh[tid] = 0u; // the thread's rows with s >= hi over the whole range (and ETS_SURE_FULL)
+
+    const uint64_t r0 = (uint64_t)blk.range * P.per_range;
+    const uint64_t r1 = r0 + P.per_range < P.n ? r0 + P.per_range : P.n;
+    // 8 threads per row and chunk (16 bytes each): 64 rows per round
+    constexpr uint32_t NPF = ET * 8u / ETS_THREADS;
+    const uint32_t my_row = tid >> 3, my_c = tid & 7u;
+    uint4 pf[NPF];
+    float pfn[NPF], pfg = 0.0f; // (of a tile's first chunk)
+    auto fetch = [&](uint64_t e0, uint32_t c) {
+        const uint32_t off = c * CHUNK + my_c * 16u;
+        if constexpr (SRC != ETS_LIST) {
+            if (c == 0u && tid < 2u * R) pfg = e0 + 32u * (tid >> 1) < r1 ? P.inv_gmax[((e0 >> 5) + (tid >> 1)) * 2u + (tid & 1u)] : 0.0f;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < NPF; ++j) {
+            const uint64_t row = e0 + my_row + (ETS_THREADS / 8u) * j;
+            pf[j] = make_uint4(0, 0, 0, 0);
+            uint64_t id = row;
+            if constexpr (SRC == ETS_LIST) id = row < r1 ? P.list[row] : 0u;
+            if (row < r1 && off < P.row_bytes) pf[j] = *reinterpret_cast<const uint4*>(P.elements + id * P.row_stride + off);
+            if (c == 0u) pfn[j] = (row < r1 && my_c == 0u) ? P.inv_norm[id] : 0.0f;
+        }
+    };
+    if (r0 < r1) fetch(r0, 0u);
+    uint32_t par = 0, buf = 0; // the tile's parity (inv, gms, gml) and the chunk's (tile)
+    for (uint64_t e0 = r0; e0 < r1; e0 += ET, par ^= 1u) {
+        float* const inv_t = inv + par * ET;
+        const float* gm = gms + par * 2u * R;
+        ets_i32x16 acc[R]; // the tile's dots so far: carried from chunk to chunk
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[r][v] = 0;
+#pragma unroll 1
+        for (uint32_t c = 0; c < nchunks; ++c, buf ^= 1u) {
+            uint8_t* const t = tile + (size_t)buf * ET * STRIDE;
+#pragma unroll
+            for (uint32_t j = 0; j < NPF; ++j) {
+                const uint32_t row = my_row + (ETS_THREADS / 8u) * j;
+                *reinterpret_cast<uint4*>(t + (size_t)row * STRIDE + my_c * 16u) = pf[j];
+                if (c == 0u && my_c == 0u) {
+                    inv_t[row] = pfn[j];
+                    if constexpr (SRC == ETS_LIST) // row = 32 r + 8 g4 + 4 h + t: non-negative floats order as their bits
+                        atomicMax(gml + par * 2u * R + (row >> 2 & 1u) * R + (row >> 5), __float_as_uint(pfn[j]));
+                }
+            }
+            if constexpr (SRC != ETS_LIST) {
+                if (c == 0u && tid < 2u * R) gms[par * 2u * R + (tid & 1u) * R + (tid >> 1)] = pfg;
+            }
+            __syncthreads(); // the one barrier of a chunk
+            if constexpr (SRC == ETS_LIST) {
+                gm = reinterpret_cast<const float*>(gml + par * 2u * R);
+                // the next tile's copy: last read before this barrier, next raised after this tile's second one
+                if (c == 0u && tid < 2u * R) gml[(par ^ 1u) * 2u * R + tid] = 0u;
+            }
+            if (c + 1u < nchunks) fetch(e0, c + 1u);
+            else if (e0 + ET < r1) fetch(e0 + ET, 0u);
+            ets_i32x4 qr[4];
+            load_q(c, qr);
+            ets_i32x4 afrag[2][R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) afrag[0][r] = *reinterpret_cast<const ets_i32x4*>(t + (size_t)(r * 32 + col) * STRIDE + h * 16);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (g + 1 < 4) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        afrag[(g + 1) & 1][r] = *reinterpret_cast<const ets_i32x4*>(t + (size_t)(r * 32 + col) * STRIDE + (g + 1) * 32 + h * 16);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[g & 1][r], qr[g], acc[r], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ets_i8_kernel's block test and scores: the conversion of a dot beyond 2^24 rounds, monotonely, so the largest dot
+        // times the largest 1 / |x| still bounds the block's scores from above
+        const bool whole = e0 + ET <= r1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int im = 0;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) im = max(im, acc[r][v]);
+            const bool hit = ((float)im * gm[h * R + r]) * qinv >= F.thr;
+            if (!__ballot(hit)) continue;
+            float sc[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) { // rows r*32 + 8*g4 + 4*h + 0..3: their 1 / |x| in one read
+                const float4 iv = *reinterpret_cast<const float4*>(inv_t + r * 32 + 8 * g4 + 4 * h);
+                sc[g4 * 4 + 0] = ((float)acc[r][g4 * 4 + 0] * iv.x) * qinv;
+                sc[g4 * 4 + 1] = ((float)acc[r][g4 * 4 + 1] * iv.y) * qinv;
+                sc[g4 * 4 + 2] = ((float)acc[r][g4 * 4 + 2] * iv.z) * qinv;
+                sc[g4 * 4 + 3] = ((float)acc[r][g4 * 4 + 3] * iv.w) * qinv;
+            }
+            const uint32_t word = ets_word<SRC>(P, q, e0 + (uint32_t)(r * 32), r1, qlive && hit);
+            if constexpr (MODE == ETS_RADIUS)
+                ets_radius16<SRC>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, word, lh + tid);
+            else
+                ets_take16<MODE, SRC, false, AFTER>(P, F, sc, e0 + (uint32_t)(r * 32), r1, whole, q, col, h, lh + wave * 32u + col, word);
+        }
+    }
+    if constexpr (MODE == ETS_COUNT) ets_hist_flush(P, lh, blk.qt * ETS_QT, tid);
+    if constexpr (MODE == ETS_RADIUS) ets_sure_flush(P, q, h, lh[tid]);
+}
+
+constexpr uint32_t ets_i8_long_lds(int mode, bool list = false) {
+    return 2u * ETS_I8_ROWS * ETS_I8_STRIDE + 2u * ETS_I8_ROWS * 4u + 4u * ETS_I8_R * 4u + ets_mode_words(mode) * 4u +
+           (list ? 4u * ETS_I8_R * 4u : 0u);
+}
+
 __global__ void ets_clear_kernel(uint32_t* p, uint32_t n) {
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
 }
@@ -575,7 +915,7 @@ __global__ void ets_init_kernel(const uint8_t* __restrict__ queries, uint32_t nq
             const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
             float s = 0.0f;
             for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
-            ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+            ok = s <= ets_norm2_test(dim); // (false for a NaN)
         }
     }
     lo[q] = ok ? ETS_LO0 : __builtin_inff();
@@ -652,7 +992,7 @@ __global__ void ets_init_after_kernel(const uint8_t* __restrict__ queries, uint3
         const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
         float s = 0.0f;
         for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
-        ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+        ok = s <= ets_norm2_test(dim); // (false for a NaN)
     }
     float ts = __builtin_inff(), ta = __builtin_inff();
     if (after_ids[q] != ~0ull) {
@@ -811,7 +1151,7 @@ __global__ void ets_radius_kernel(const uint8_t* __restrict__ queries, const flo
             const float* qp = reinterpret_cast<const float*>(queries) + (size_t)q * dim;
             float s = 0.0f;
             for (uint32_t c = 0; c < dim; ++c) s += qp[c] * qp[c];
-            ok = s <= ETS_NORM2_TEST; // (false for a NaN)
+            ok = s <= ets_norm2_test(dim); // (false for a NaN)
         }
     }
     const float r = radii[q];
@@ -992,13 +1332,19 @@ static uint32_t ets_grid(uint64_t work) {
     return (uint32_t)(g > 8192 ? 8192 : g < 1 ? 1 : g);
 }
 
-uint32_t ets_tile_rows(uint32_t form) { return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : ETS_I8_ROWS; }
+uint32_t ets_tile_rows(uint32_t form) {
+    return form == ETS_FORM_B16_7x4 ? 128u : form == ETS_FORM_B16_13x2 ? 64u : form == ETS_FORM_B16_LONG ? 32u * ETS_B16_LONG_R : ETS_I8_ROWS;
+}
 
 template <int MODE, int SRC, int QSRC = ETS_Q_DENSE>
 static EtsScanFn ets_scan_fn(uint32_t form, uint32_t* lds) {
     if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC, QSRC>;
     if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC, QSRC>;
     if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC, QSRC>;
+    if constexpr (QSRC == ETS_Q_DENSE) { // the long-row forms: dense queries only
+        if (form == ETS_FORM_B16_LONG) return *lds = ets_b16_long_lds(MODE), ets_b16_long_kernel<ETS_B16_LONG_R, MODE, SRC>;
+        if (form == ETS_FORM_I8_LONG) return *lds = ets_i8_long_lds(MODE, SRC == ETS_LIST), ets_i8_long_kernel<MODE, SRC>;
+    }
     return nullptr;
 }
 template <int MODE>
@@ -1118,12 +1464,14 @@ hipError_t ets_empty(uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dist
     hipLaunchKernelGGL(ets_empty_kernel, dim3(ets_grid((uint64_t)nq * k)), dim3(256), 0, s, nq, k, out_ids, out_dists, out_counts);
     return hipGetLastError();
 }
-// ---- the cursor forms: the three forms x the three row sources x COUNT and COLLECT, dense queries ----
+// ---- the cursor forms: the five forms x the three row sources x COUNT and COLLECT, dense queries ----
 template <int MODE, int SRC>
 static EtsScanFn ets_scan_after_fn(uint32_t form, uint32_t* lds) {
     if (form == ETS_FORM_B16_7x4) return *lds = ets_b16_lds<7, 4>(MODE), ets_b16_kernel<7, 4, MODE, SRC, ETS_Q_DENSE, true>;
     if (form == ETS_FORM_B16_13x2) return *lds = ets_b16_lds<13, 2>(MODE), ets_b16_kernel<13, 2, MODE, SRC, ETS_Q_DENSE, true>;
     if (form == ETS_FORM_I8) return *lds = ets_i8_lds(MODE, SRC == ETS_LIST), ets_i8_kernel<MODE, SRC, ETS_Q_DENSE, true>;
+    if (form == ETS_FORM_B16_LONG) return *lds = ets_b16_long_lds(MODE), ets_b16_long_kernel<ETS_B16_LONG_R, MODE, SRC, true>;
+    if (form == ETS_FORM_I8_LONG) return *lds = ets_i8_long_lds(MODE, SRC == ETS_LIST), ets_i8_long_kernel<MODE, SRC, true>;
     return nullptr;
 }
 template <int MODE>

@@ -1,5 +1,6 @@
 // exact_topk_screened_host.h -- host side of the screened exact selection (included by granne_hip.hip after
-// exact_topk_host.h): granne_hip_exact_topk_screened*, granne_hip_exact_topk_screen_epsilon. The kernels and the method:
+// exact_topk_host.h): granne_hip_exact_topk_screened*, granne_hip_exact_topk_screen_epsilon[_long],
+// granne_hip_index_screen_long_rows. The kernels and the method:
 // exact_topk_screened.h; DESIGN.md 3.7b.
 #pragma once
 
@@ -10,6 +11,18 @@ static_assert(ETS_CAP == ET_CAP && sizeof(EtSel) == 16 && offsetof(EtSel, over) 
 extern "C" float granne_hip_exact_topk_screen_epsilon(int dtype, uint32_t dim) {
     if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return 0.0f;
     return ets_epsilon(dtype == GRANNE_HIP_I8, dim);
+}
+
+extern "C" float granne_hip_exact_topk_screen_epsilon_long(int dtype, uint32_t dim) {
+    if (dtype != GRANNE_HIP_F32 && dtype != GRANNE_HIP_I8) return 0.0f;
+    return ets_epsilon_long(dtype == GRANNE_HIP_I8, dim);
+}
+
+// the handle's dense-query screened entries screen long rows too (ets_form); a handle without such rows: accepted, no effect
+extern "C" int granne_hip_index_screen_long_rows(granne_hip_index* ix, int on) {
+    if (!ix) return fail(GRANNE_HIP_ERR_INVALID, "screen_long_rows: index is null");
+    ix->screen_long.store(on ? 1 : 0);
+    return GRANNE_HIP_OK;
 }
 
 static int exact_topk_screened_args(const granne_hip_index* ix, uint32_t nq, uint32_t k, bool buffers) {
@@ -26,13 +39,18 @@ static int exact_topk_screened_args(const granne_hip_index* ix, uint32_t nq, uin
 // The form that screens the handle's rows, or ETS_FORM_ROUTED: rows too long for the register forms, or f32 rows beyond
 // the norm the bound is proven for. The largest squared norm is looked up once per handle (one pass over the rows and one
 // wait on s, under norm_mu); every later call reads the verdict.
-static int ets_form(const granne_hip_index* ix, hipStream_t s, uint32_t* form) {
+// Rows beyond the register forms: the long-row forms where the handle has asked for them
+// (granne_hip_index_screen_long_rows) and the call's queries are dense (`dense_queries`; the graphs have no long-row form
+// yet: they pass false and stay routed); ETS_FORM_ROUTED otherwise, as before.
+static int ets_form(const granne_hip_index* ix, hipStream_t s, uint32_t* form, bool dense_queries) {
     *form = ETS_FORM_ROUTED;
+    const bool long_ok = dense_queries && ix->screen_long.load() != 0 && ix->dim <= ETS_LONG_DIM_MAX;
     if (ix->dtype == GRANNE_HIP_I8) {
         if (ix->dim <= ETS_I8_DIM_MAX && ix->row_bytes <= 128u) *form = ETS_FORM_I8;
+        else if (long_ok && ix->dim > ETS_I8_DIM_MAX && ix->row_bytes % ETS_LONG_CHUNK == 0u) *form = ETS_FORM_I8_LONG;
         return GRANNE_HIP_OK;
     }
-    if (ix->dim > ETS_F32_DIM_MAX) return GRANNE_HIP_OK;
+    if (ix->dim > ETS_F32_DIM_MAX && !long_ok) return GRANNE_HIP_OK;
     granne_hip_index* mix = const_cast<granne_hip_index*>(ix);
     int verdict = mix->screen_rows.load();
     if (verdict == 0) {
@@ -50,11 +68,11 @@ static int ets_form(const granne_hip_index* ix, hipStream_t s, uint32_t* form) {
             HIP_TRY(e);
             float worst;
             memcpy(&worst, &bits, 4);
-            verdict = worst <= ETS_NORM2_TEST ? 1 : 2; // (a NaN compares false)
+            verdict = worst <= ets_norm2_test(ix->dim) ? 1 : 2; // (a NaN compares false)
             mix->screen_rows.store(verdict);
         }
     }
-    if (verdict == 1) *form = ix->dim <= 112u ? ETS_FORM_B16_7x4 : ETS_FORM_B16_13x2;
+    if (verdict == 1) *form = ix->dim <= 112u ? ETS_FORM_B16_7x4 : ix->dim <= ETS_F32_DIM_MAX ? ETS_FORM_B16_13x2 : ETS_FORM_B16_LONG;
     return GRANNE_HIP_OK;
 }
 
@@ -105,7 +123,7 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     const bool after = d_after_ids != nullptr;
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
-    if (const int rc = ets_form(ix, s, &form)) return rc;
+    if (const int rc = ets_form(ix, s, &form, !own_first)) return rc;
     const int src = !d_filter ? ETS_ALL : filter_stride_words == 0 ? ETS_LIST : ETS_BITS;
     const bool list = src == ETS_LIST && form != ETS_FORM_ROUTED;
     uint64_t n = ix->n_elements; // ETS_LIST: the list's length, once it is known
@@ -186,14 +204,14 @@ static int exact_topk_screened_run(const granne_hip_index* ix, const void* d_que
     P.hist = (uint32_t*)(scratch + o_hist);
     P.cnt = (uint32_t*)(scratch + o_cnt);
     P.cand = (uint32_t*)(scratch + o_cand);
-    P.eps2 = 2.0f * ets_epsilon(i8, ix->dim);
+    P.eps2 = 2.0f * ets_epsilon_of(form, i8, ix->dim);
     P.list = d_allowed ? d_allowed : list ? (const uint32_t*)(scratch + o_list) : nullptr;
     P.filter_stride = filter_stride_words;
     uint32_t* const fb_count = (uint32_t*)(scratch + o_fbn);
     uint32_t* const fb_list = (uint32_t*)(scratch + o_fbl);
     float* const top_sure = (float*)(scratch + o_top);
     float* const top_any = top_sure + qc_max;
-    const float eps = ets_epsilon(i8, ix->dim);
+    const float eps = ets_epsilon_of(form, i8, ix->dim);
     for (uint32_t c0 = 0; c0 < nq; c0 += ET_CHUNK) {
         const uint32_t qc = nq - c0 < ET_CHUNK ? nq - c0 : ET_CHUNK;
         const uint32_t tiles = (qc + ETS_QT - 1) / ETS_QT;

@@ -196,6 +196,8 @@ struct granne_hip_index {
     DevBuf d_inv_norm;
     // exact_topk_screened over f32 rows: 0 not looked yet, 1 every row's squared norm is within the screen's bound, 2 not
     std::atomic<int> screen_rows{0};
+    // granne_hip_index_screen_long_rows: the dense-query screened entries screen rows beyond the register forms too
+    std::atomic<int> screen_long{0};
     // f32 rows of the sketched shapes: one SKETCH_LINE per row (search_kernel.h), made with the index, or null
     DevBuf d_sketch;
     // host-pointer searches (granne_hip_search / _search_batch): a stream, a device buffer and a pinned

@@ -66,7 +66,7 @@ static int gf_compact(const granne_hip_index* ix, const char* what, const uint32
 static int gf_alone(const granne_hip_index* ix, uint32_t width, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                     uint32_t* d_out_totals, uint32_t* d_status, hipStream_t s) {
     uint32_t form = ETS_FORM_ROUTED;
-    if (const int rc = ets_form(ix, s, &form)) return rc;
+    if (const int rc = ets_form(ix, s, &form, false)) return rc;
     HIP_TRY(ets_empty(1u, width, d_out_ids, d_out_dists, d_out_counts, s));
     if (d_out_totals) HIP_TRY(ets_clear(d_out_totals, 1u, s));
     if (d_status) HIP_TRY(ers_status(d_status, nullptr, 0u, form, s));

@@ -105,7 +105,7 @@ static int range_graph_run(const granne_hip_index* ix, uint64_t first, uint32_t 
                            const uint32_t* d_filter = nullptr, const uint32_t* d_allowed = nullptr, uint64_t allowed_m = 0) {
     GRANNE_HIP_ON_DEVICE(ix->device);
     uint32_t form = ETS_FORM_ROUTED;
-    if (const int rc = ets_form(ix, s, &form)) return rc;
+    if (const int rc = ets_form(ix, s, &form, false)) return rc;
     const bool i8 = ix->dtype == GRANNE_HIP_I8;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (form == ETS_FORM_ROUTED) { // no screen for the handle: every element is path C's

@@ -705,6 +705,13 @@ class Granne:
                                  "at their k-th distance" % (int(status[0]), EXACT_TOPK_CAP))
         return out
 
+    def screen_long_rows(self, on=True):
+        """granne_hip_index_screen_long_rows: the dense-query screened entries of this index (`exact_topk_screened`,
+        `_filtered`, `_after`, `exact_range_screened`) screen rows beyond 208 (f32) / 128 (int8) components too, up to 2048
+        -- status[3] is then 4 (f32) or 5 (int8) -- instead of handing the whole call to `exact_topk`'s scan. Off by
+        default; the answers are the same bytes either way. The graphs have no long-row form yet: they stay routed."""
+        check(lib().granne_hip_index_screen_long_rows(self._h, 1 if on else 0))
+
     def exact_topk_screened_device(self, d_queries, nq, k, d_ids, d_dists, d_counts, d_status=0, stream=0):
         """exact_topk's answer with the matrix cores screening the rows first (granne_hip_exact_topk_screened_device). Raw
         device pointers (int; d_status: u32[4] zeroed by the caller, or 0); ordered on `stream`, which the call waits on

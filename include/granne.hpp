@@ -392,6 +392,12 @@ public:
         return out;
     }
 
+    // granne_hip_index_screen_long_rows: the dense-query screened entries of this index (exact_topk_screened, _filtered,
+    // _after, exact_range_screened) screen rows beyond 208 (f32) / 128 (int8) components too, up to 2048, instead of handing
+    // the call to exact_topk's scan. Off by default; the answers are the same bytes either way. The graphs have no
+    // long-row form yet.
+    void screen_long_rows(bool on = true) { check(granne_hip_index_screen_long_rows(h_.get(), on ? 1 : 0)); }
+
     // The exact k-NN graph of the index's own elements (granne_hip_knn_graph): for every element of [first, first + count)
     // its k (up to 1023) nearest OTHER elements by (distance bits, id) -- exact_topk of the element's own row with the
     // element left out, the matrix cores screening the rows first. Throws where exact_topk throws. `status` (optional):

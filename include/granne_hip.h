@@ -452,7 +452,8 @@ int granne_hip_exact_topk(const granne_hip_index* index, const void* queries, ui
  *              query's row is voided as it voids it (count 0).
  *   d_status   u32[4], optional, zeroed by the caller: [0] queries answered by the fallback, [1] queries routed by the
  *              handle's shape (0 or nq), [2] the largest number of survivors of one query (it counts on past the cap),
- *              [3] the form that ran (0 routed, 1 and 2 the f32 forms for up to 112 and 208 components, 3 int8), bit 31
+ *              [3] the form that ran (0 routed, 1 and 2 the f32 forms for up to 112 and 208 components, 3 int8, 4 and 5 the f32 and
+ *              int8 long-row forms of granne_hip_index_screen_long_rows), bit 31
  *              set where exact_topk voided a query handed to it.
  * Stream-ordered; the call waits on `stream` once, at its end, for one word (the length of the fallback list). Scratch
  * from hipMallocAsync, about 64 MB for a round of 1024 queries (candidates 16 MB, their distances 16 MB, keys 32 MB) plus, where
@@ -466,6 +467,18 @@ int granne_hip_exact_topk_screened(const granne_hip_index* index, const void* qu
                                    uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status /* optional */);
 /* the screen's bound for rows of `dtype` and `dim` components -- the number the kernels are given; 0: no screen for the shape */
 float granne_hip_exact_topk_screen_epsilon(int dtype, uint32_t dim);
+/* Rows beyond those lengths -- the 384, 768, 1024, 1536 components of today's embeddings -- have forms of their own, which
+ * walk a row in chunks of 128 components and keep the tile's accumulators in registers from chunk to chunk (DESIGN.md 3.7i;
+ * status[3] = GRANNE_HIP_ETS_FORM_B16_LONG / _I8_LONG). They are asked for per handle:
+ * 1: the dense-query screened entries of this handle screen long rows too (f32 of 209..2048 components, int8 of
+ * 129..2048); 0 [default]: such handles are routed, as before. Handles the short forms serve, F16 and compact
+ * handles: accepted, no effect. The entries this reaches are granne_hip_exact_topk_screened[_filtered][_after] and
+ * granne_hip_exact_range_screened; the graphs have no long-row form yet: granne_hip_knn_graph*, granne_hip_range_graph* stay
+ * routed for such rows. f32 rows are still held to the norm test (here 1 + 2^-10 - dim 2^-23 for the computed sum of
+ * squares), looked up once per handle. May be called at any time; a call in flight uses the value it read at its start. */
+int granne_hip_index_screen_long_rows(granne_hip_index* index, int on);
+/* the bound the long-row forms are given; 0: no long-row screen for the shape */
+float granne_hip_exact_topk_screen_epsilon_long(int dtype, uint32_t dim);
 
 /* The exact k-NN graph of the handle's own elements: for every e in [first, first + count), all elements j != e are
  * ranked by (distance bits of dist(element e, element j), j) and the first k are written to row e - first of the outputs.
@@ -1294,6 +1307,8 @@ int granne_hip_exact_range(const granne_hip_index* index, const void* queries, u
 #define GRANNE_HIP_ETS_FORM_B16_7x4 1u
 #define GRANNE_HIP_ETS_FORM_B16_13x2 2u
 #define GRANNE_HIP_ETS_FORM_I8 3u
+#define GRANNE_HIP_ETS_FORM_B16_LONG 4u
+#define GRANNE_HIP_ETS_FORM_I8_LONG 5u
 #define GRANNE_HIP_ETS_VOIDED 0x80000000u
 int granne_hip_exact_range_screened_device(const granne_hip_index* index, const void* d_queries, uint32_t nq, const float* d_radii,
                                            uint32_t cap, const uint32_t* d_filter, uint64_t filter_stride_words, uint64_t* d_out_ids,

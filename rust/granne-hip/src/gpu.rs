@@ -332,6 +332,9 @@ pub const GRANNE_HIP_SHARDED_OPT_DEPTH: c_int = 1;
 pub const GRANNE_HIP_SHARDED_OPT_EXCHANGE: c_int = 2;
 pub const GRANNE_HIP_SHARDED_EXCHANGE_PEER: u64 = 0;
 pub const GRANNE_HIP_SHARDED_EXCHANGE_RCCL: u64 = 1;
+/// status[3] of a screened call that ran a long-row form (`GpuGranne::screen_long_rows`)
+pub const GRANNE_HIP_ETS_FORM_B16_LONG: u32 = 4;
+pub const GRANNE_HIP_ETS_FORM_I8_LONG: u32 = 5;
 
 // The rest of the C ABI (include/granne_hip.h), not used by the wrappers below: generated from the header by
 // tools/gen_rust_sys.py; tests/test_abi.py checks that every entry point is declared here exactly as the header has it.
@@ -426,6 +429,8 @@ extern "C" {
     fn granne_hip_exact_topk_screened(index: *const granne_hip_index, queries: *const c_void, nq: u32, k: u32,
         out_ids: *mut u64, out_dists: *mut f32, out_counts: *mut u32, out_status: *mut u32) -> c_int;
     fn granne_hip_exact_topk_screen_epsilon(dtype: c_int, dim: u32) -> f32;
+    fn granne_hip_index_screen_long_rows(index: *mut granne_hip_index, on: c_int) -> c_int;
+    fn granne_hip_exact_topk_screen_epsilon_long(dtype: c_int, dim: u32) -> f32;
     fn granne_hip_knn_graph_device(index: *const granne_hip_index, first: u64, count: u64, k: u32, d_out_ids: *mut u64,
         d_out_dists: *mut f32, d_out_counts: *mut u32, d_status: *mut u32, stream: *mut c_void) -> c_int;
     fn granne_hip_knn_graph(index: *const granne_hip_index, first: u64, count: u64, k: u32, out_ids: *mut u64,
@@ -664,6 +669,13 @@ impl<E: GpuElements> GpuGranne<E> {
         check(unsafe { granne_hip_exact_topk_screened(self.handle, q.as_ptr() as *const c_void, nq as u32, k as u32,
             ids.as_mut_ptr(), ds.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j] as usize, ds[i * k + j])).collect()).collect())
+    }
+    /// `granne_hip_index_screen_long_rows`: the dense-query screened entries of this handle (`exact_topk_screened`,
+    /// `_filtered`, `_after`, `exact_range_screened`) screen rows beyond 208 (f32) / 128 (int8) components too, up to 2048,
+    /// instead of handing the call to `exact_topk`'s scan. Off by default; the answers are the same bytes either way. The
+    /// graphs have no long-row form yet.
+    pub fn screen_long_rows(&mut self, on: bool) -> std::io::Result<()> {
+        check(unsafe { granne_hip_index_screen_long_rows(self.handle, on as c_int) })
     }
     /// `granne_hip_knn_graph`: for every element of `first .. first + count` its exact `k` (up to 1023) nearest OTHER
     /// elements by (distance bits, id) -- `exact_topk` of the element's own row with the element left out, the matrix
